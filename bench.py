@@ -14,9 +14,24 @@ The work is FIXED as N grows (strong scaling): rank r computes cells x in [r*512
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  `roofline` is the dominant kernel (k_packet, nearest triangle +
-fused sign) timed with HIP events on the stream it is launched on; `cpu_baseline` is the CPU
-oracle's multi-threaded restatement of the reference algorithm (oracle/, kind "port": the Rust
-reference cannot be built in this image) on a bounded sample, N=1 only.
+fused sign) timed with HIP events on the stream it is launched on.  A plain run does only what
+that line's headline needs: set-up, warm-up, the timed steps, the line (N > 1: the check of the
+delivered grid, whose failure switches the measured exchange).  Everything measured or checked
+beside it runs with --full:
+  - `roofline` priced with a rocprofv3 --kernel-trace child run, `traffic` from --pmc child runs;
+  - `phases_ms` of one extra one-shot call (sign planes, seed passes, device total);
+  - `cpu_baseline`, the CPU oracle's multi-threaded restatement of the reference algorithm
+    (oracle/, kind "port": the Rust reference is not part of the build) on a bounded sample, N=1 only,
+    with `reference_parity` (config 3: `oracle_check`) and `host_pointer_call_ms` beside it;
+  - N > 1: `per_rank` and `link_probe`.
+--no-cpu-baseline and --no-live-pmc leave parts of --full out.
+
+    python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs DIR
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32): the whole
+output where it is at most 32 MB, else the values at a fixed, seeded sample of up to 2^22 positions
+(<name>_sample.npy) and those positions (<name>_sample_index.npy, float64).  The inputs are
+deterministic, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -53,7 +68,14 @@ def parse():
     ap.add_argument("--config", type=int, default=0, choices=[0, 2, 3, 4, 5],
                     help="another BASELINE.json config on ONE GPU instead of the headline (0): 2 = 256^3 blob-100k Raycast, 3 = 10 M queries "
                          "RtreeBvh, 4 = 512^3 blob-1M Raycast, 5 = 1024^3 sheet-100k Normal; same JSON line with that config's roofline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what is beside the headline (CPU baseline, reference parity, rocprofv3 child runs, one-shot "
+                         "phases, host-pointer call, per-rank lines and link probe); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; a fixed, seeded sample of outputs above 32 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config in (2, 4, 5):
         args.mesh, args.grid, args.sign = {2: ("blob-100k", 256, "Raycast"), 4: ("blob-1M", 512, "Raycast"), 5: ("sheet-100k", 1024, "Normal")}[args.config]
         args.cpu_seconds = min(args.cpu_seconds, 45.0)   # a bounded sample (<= 384^3) of the config's own mesh / sign rule beside its line
@@ -82,16 +104,19 @@ def bench_queries(args):
     t0 = time.perf_counter()
     for _ in range(args.steps):
         t = M2STimings()
-        generate_sdf(dv, topo, dq, AccelerationMethod.RtreeBvh, timings=t)
+        last = generate_sdf(dv, topo, dq, AccelerationMethod.RtreeBvh, timings=t)
         tims.append(t)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "sdf", last)
+    del last
     dist_ms = float(np.mean([t.distance_ms for t in tims]))      # Morton sort + seed lattice + k_packet<LIST, UNSIGNED, RAYS3>
     b_alg = 16.0 * nq + 12.0 * v.shape[0] + 12.0 * int(tims[0].n_triangles)   # 16 B per query + the mesh once
     achieved = b_alg / (dist_ms * 1e-3) / 1e9
     traffic = traffic_src = None
-    if not args.no_live_pmc:
-        live, why_not = live_pmc(["--config", "3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-live-pmc"])
+    if args.full and not args.no_live_pmc:
+        live, why_not = live_pmc(["--config", "3", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-live-pmc"])
         if live is not None:
             traffic = 2.0 * live["FETCH_SIZE"] * 1024.0 + live["WRITE_SIZE"] * 1024.0
             traffic_src = (f"live: rocprofv3 --pmc child runs of this command after the timed region, k_packet only (the query sort and seed lattice in front "
@@ -100,7 +125,7 @@ def bench_queries(args):
         elif why_not != "child run":
             traffic_src = f"live measurement unavailable ({why_not})"
     extra = {}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # "CPU BVH nearest + 3-ray sign" beside the 10 M-query run (generic/rtree_bvh.rs:79-174): the oracle's
         # BVH-accelerated exact search + best-of-three rays, all host threads, on the first 1 M queries of the same set; the same
         # sample also checks the GPU result bit for bit
@@ -271,6 +296,28 @@ def emit(line: str):
     os.write(_JSON_FD if _JSON_FD is not None else 1, (line + "\n").encode())
 
 
+DUMP_WHOLE_MAX = 8 << 20      # values: 32 MB of float32 written whole
+DUMP_SAMPLE = 1 << 22         # above that: at most 16 MB of values + 32 MB of float64 positions
+
+
+def dump_outputs(d, name, t, shape=None):
+    """--dump-outputs: the device tensor `t`, one output of the timed path's last step, as d/<name>.npy in float32 (reshaped to `shape`),
+    or, when larger than DUMP_WHOLE_MAX values, its values at the positions of DUMP_SAMPLE seeded draws (sorted, repeats dropped; the
+    same for the same output size in every run) as d/<name>_sample.npy and the positions as d/<name>_sample_index.npy."""
+    import torch
+
+    os.makedirs(d, exist_ok=True)
+    flat = t.reshape(-1)
+    if flat.numel() <= DUMP_WHOLE_MAX:
+        a = flat.float().cpu().numpy()
+        np.save(os.path.join(d, f"{name}.npy"), a.reshape(shape) if shape is not None else a)
+        return
+    pos = np.unique(np.random.default_rng(0x5DF0).integers(0, flat.numel(), DUMP_SAMPLE, dtype=np.int64))
+    vals = flat[torch.as_tensor(pos, device=flat.device)].float().cpu().numpy()
+    np.save(os.path.join(d, f"{name}_sample.npy"), vals)
+    np.save(os.path.join(d, f"{name}_sample_index.npy"), pos.astype(np.float64))
+
+
 def main():
     args = parse()
     _stdout_is_for_the_json_line_only()
@@ -403,10 +450,14 @@ def main():
             verified = all_agree(bool(torch.equal(out.view(torch.int32), ref.view(torch.int32))))
         del ref
 
+    # the whole grid of the last timed step (every rank holds it: rank 0 writes it), before anything below writes into `out` again
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "grid_sdf", outs[0] if in_process else out, (n, n, n))
+
     # N > 1: what every rank spent where (means over the timed steps), and what its links give — so that ONE run on a multi-GPU
     # node says which delivery (push / store / trail, peer vs RCCL) to choose instead of a bare number
     per_rank = link_probe = None
-    if sharded or in_process:
+    if args.full and (sharded or in_process):
         def rank_line(ts, wall_ms):
             dev_total = float(np.mean([t.total_ms for t in ts]))
             return {"accel_build_ms": round(float(np.mean([t.accel_build_ms for t in ts])), 4), "seeds_and_cut_ms": round(float(np.mean([t.seed_ms for t in ts])), 4),
@@ -449,11 +500,13 @@ def main():
             dist.all_gather_object(link_probe, mine)
 
     # phase breakdown of one extra, untimed, synchronous one-shot call on this rank's whole slab
-    ph = M2STimings()
-    scratch_out = out if pg is None else torch.empty(n ** 3, dtype=torch.float32, device=dev)
-    xs = slab_bounds(n, n_gpus, 0) if in_process else (x0, x1)
-    generate_grid_sdf(dv, topo, grid, sign, x_slab=xs, out=scratch_out, timings=ph)
-    del scratch_out
+    ph = None
+    if args.full:
+        ph = M2STimings()
+        scratch_out = out if pg is None else torch.empty(n ** 3, dtype=torch.float32, device=dev)
+        xs = slab_bounds(n, n_gpus, 0) if in_process else (x0, x1)
+        generate_grid_sdf(dv, topo, grid, sign, x_slab=xs, out=scratch_out, timings=ph)
+        del scratch_out
     world_label = n_gpus
 
     if rank == 0:
@@ -463,7 +516,6 @@ def main():
         launches = int(sum(t.distance_launches for t in tims))
         dist_ms = float(sum(t.distance_ms for t in tims)) / max(launches, 1)   # average launch of the dominant kernel
         build_ms = float(np.mean([t.accel_build_ms for t in tims]))
-        sign_ms, seed_ms, total_ms = float(ph.sign_ms), float(ph.seed_ms), float(ph.total_ms)
         n_tris = int(tims[0].n_triangles)
         slab_voxels = float(sum(t.n_units for t in tims)) / max(launches, 1)      # voxels one launch processes
         # algorithmic bytes of one launch of the dominant kernel:
@@ -476,8 +528,9 @@ def main():
         valu_frac = None
         pmc_src = None
         pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if world_label == 1 and launches == args.steps and not args.no_live_pmc:
-            child = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-live-pmc", "--grid", str(n), "--mesh", args.mesh, "--sign", args.sign]
+        if args.full and world_label == 1 and launches == args.steps and not args.no_live_pmc:
+            child = ["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-live-pmc", "--grid", str(n), "--mesh", args.mesh,
+                     "--sign", args.sign]
             live, why_not = live_pmc(child)
             if live is not None and live.get("rocprof_avg_ms"):
                 # the roofline is priced with the profiler's average launch duration; the event time stays beside it
@@ -537,9 +590,7 @@ def main():
                 # overlap and their individual durations (roofline.avg_launch_ms) are longer than when run alone
                 "piece_streams": (int(os.environ.get("M2S_PIECE_STREAMS", "2")) if exchange == "rccl" and chunks > 1 else 1),
             },
-            "phases_ms": {"accel_build": round(build_ms, 4), "sign_planes": round(sign_ms, 4), "seed_passes": round(seed_ms, 4),
-                          "distance_per_launch": round(dist_ms, 4), "launches_per_step": launches // max(args.steps, 1),
-                          "one_shot_device_total": round(total_ms, 4)},
+            "phases_ms": {"accel_build": round(build_ms, 4), "distance_per_launch": round(dist_ms, 4), "launches_per_step": launches // max(args.steps, 1)},
             "roofline": {
                 "bound": "hbm",
                 "kernel": ("k_packet<GRID, MODE_UNSIGNED, SIGN_GRID_PLANE>" if args.sign == "Raycast" else "k_packet<GRID, MODE_NORMAL_FOLD, SIGN_NONE>"),
@@ -564,11 +615,14 @@ def main():
                 "valu_issue_frac_pmc": valu_frac,
             },
         }
+        if ph is not None:
+            res["phases_ms"].update(sign_planes=round(float(ph.sign_ms), 4), seed_passes=round(float(ph.seed_ms), 4),
+                                    one_shot_device_total=round(float(ph.total_ms), 4))
         if per_rank is not None:
             res["per_rank"] = per_rank
             res["config"]["exchange_ran"] = exchange_ran
             res["link_probe"] = link_probe
-        if world_label == 1 and not args.no_cpu_baseline:
+        if args.full and world_label == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"], rn, ref = cpu_baseline(v, idx, lo, hi, int(sign), args.cpu_seconds, n)
             # What a user switching from the reference sees (SURVEY.md header fact 2, §8c): this library's exact minimum
             # against the reference's propagation semantics (the CPU run above, kept) on the same grid.
@@ -579,7 +633,7 @@ def main():
                                        "reference": f"oracle PROPAGATE (generate/grid.rs:383-558 restated), {res['cpu_baseline']['cores']} heaps",
                                        **reference_parity(ours, ref, normal_sign=(args.sign == "Normal"))}
             del ours, ref
-        if world_label == 1 and not args.no_cpu_baseline and args.config == 0:
+        if args.full and world_label == 1 and not args.no_cpu_baseline and args.config == 0:
             # the PCIe-inclusive drop-in call (host pointers in/out), reported for DESIGN.md; never `value`
             host_out = np.empty(n ** 3, np.float32)
             times = []

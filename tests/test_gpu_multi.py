@@ -448,7 +448,7 @@ def _bench(args, env=None, launcher=None):
 def test_bench_contract_single_line_json_in_every_mode():
     """bench.py prints ONE JSON line on stdout whatever runs underneath (RCCL prints a banner on stdout when a communicator is
     created), carries `roofline`, and the multi-shard modes verify the delivered grid against the single-GPU result."""
-    small = ["--grid", "128", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    small = ["--grid", "128", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     d = _bench(small)
     assert d["n_gpus"] == 1 and d["unit"] == "Mvoxels/s" and d["roofline"]["bound"] == "hbm" and d["roofline"]["frac"] > 0
     d = _bench(small + ["--gpus", "3"], {"M2S_BENCH_DEVICES": "0,0,0"})                       # one process, three shards on this GPU
@@ -466,3 +466,42 @@ def test_bench_contract_single_line_json_in_every_mode():
     d = _bench(small, {"M2S_FORCE_COLLECTIVES": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(29900 + os.getpid() % 90), "RANK": "0",
                        "WORLD_SIZE": "1", "M2S_EXCHANGE": "rccl"})                              # 1-rank nccl group: the banner case
     assert d["config"]["exchange"] == "rccl" and d["config"]["gather_verified"] is True
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) prints the headline line for exactly --steps timed steps and measures nothing beside it;
+    --dump-outputs writes the grid of the last step: whole while small, as a seeded sample of positions when large, the same bits in
+    two runs and the same bits as the call itself."""
+    v, idx = meshes.named("blob-100k")
+    lo, hi = meshes.extended_bbox(v, 0.1)
+    small = ["--grid", "96", "--steps", "3", "--warmup", "1"]
+    d = _bench(small + ["--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "Mvoxels/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["value"] == pytest.approx(96 ** 3 / d["ms_per_step"] / 1e3, rel=1e-2)
+    assert not {"cpu_baseline", "reference_parity", "host_pointer_call_ms", "per_rank", "link_probe"} & set(d)
+    assert d["roofline"]["achieved_basis"] == "avg_launch_ms" and "one_shot_device_total" not in d["phases_ms"]
+    _bench(small + ["--dump-outputs", str(tmp_path / "b")])
+    a, b = np.load(tmp_path / "a" / "grid_sdf.npy"), np.load(tmp_path / "b" / "grid_sdf.npy")
+    assert a.dtype == np.float32 and a.shape == (96, 96, 96) and a.tobytes() == b.tobytes()
+    want = generate_grid_sdf(v, Topology.TriangleList(idx), Grid.from_bounding_box(lo, hi, [96, 96, 96]), SignMethod.Raycast)
+    assert np.array_equal(a.reshape(-1).view(np.uint32), want.reshape(-1).view(np.uint32))
+    # the multi-shard forms dump the delivered whole grid: one process with three shards, and two ranks (rank 0 writes)
+    d = _bench(small + ["--gpus", "3", "--dump-outputs", str(tmp_path / "m")], {"M2S_BENCH_DEVICES": "0,0,0"})
+    assert d["n_gpus"] == 3 and d["steps"] == 3 and "per_rank" not in d
+    launch = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+              "--master-port", str(29700 + os.getpid() % 200)]
+    d = _bench(small + ["--gpus", "2", "--dump-outputs", str(tmp_path / "r")], {"M2S_DIST_BACKEND": "gloo", "M2S_EXCHANGE": "peer"}, launch)
+    assert d["n_gpus"] == 2 and d["config"]["gather_verified"] is True and "per_rank" not in d
+    for sub in ("m", "r"):
+        assert np.load(tmp_path / sub / "grid_sdf.npy").tobytes() == a.tobytes(), sub
+
+    _bench(["--grid", "256", "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "c")])
+    files = sorted(os.listdir(tmp_path / "c"))
+    assert files == ["grid_sdf_sample.npy", "grid_sdf_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "c" / f) for f in files) <= 64 << 20
+    vals, pos = np.load(tmp_path / "c" / files[0]), np.load(tmp_path / "c" / files[1])
+    assert vals.dtype == np.float32 and pos.dtype == np.float64 and vals.shape == pos.shape and pos.size > 3_000_000
+    p = pos.astype(np.int64)
+    assert np.array_equal(p, pos) and np.all(np.diff(p) > 0) and p[0] >= 0 and p[-1] < 256 ** 3
+    want = generate_grid_sdf(v, Topology.TriangleList(idx), Grid.from_bounding_box(lo, hi, [256, 256, 256]), SignMethod.Raycast)
+    assert np.array_equal(vals.view(np.uint32), want.reshape(-1)[p].view(np.uint32))

@@ -10,8 +10,8 @@ PY
 for rep in 1 2 3; do
   for cfg in 0 3 2 4 5; do
     a="--config $cfg"; [ $cfg = 0 ] && a=""
-    M2S_LIB=$R05 python bench.py $a --steps 20 --warmup 3 --no-cpu-baseline --no-live-pmc > $O/tmp.json 2>/dev/null; echo "config $cfg round-5 library: $(line $O/tmp.json)"
-    python bench.py $a --steps 20 --warmup 3 --no-cpu-baseline --no-live-pmc > $O/tmp.json 2>/dev/null; echo "config $cfg this tree      : $(line $O/tmp.json)"
+    M2S_LIB=$R05 python bench.py $a --steps 20 --warmup 3 --full --no-cpu-baseline --no-live-pmc > $O/tmp.json 2>/dev/null; echo "config $cfg round-5 library: $(line $O/tmp.json)"
+    python bench.py $a --steps 20 --warmup 3 --full --no-cpu-baseline --no-live-pmc > $O/tmp.json 2>/dev/null; echo "config $cfg this tree      : $(line $O/tmp.json)"
   done
 done > $O/ab.txt 2>&1
 cat $O/ab.txt

@@ -6,5 +6,5 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do VALS+=("$1"); shift; done
 [ "$1" == "--" ] && shift
 for v in "${VALS[@]}"; do
   echo -n "$VAR=$v $* : "
-  env $VAR=$v "$@" python bench.py --no-cpu-baseline --steps 10 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['phases_ms'])"
+  env $VAR=$v "$@" python bench.py --full --no-cpu-baseline --steps 10 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['phases_ms'])"
 done

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 for C in $CFGS; do
   OUT=$PWD/gpurun_out/$TAG/cfg$C
   mkdir -p $OUT
-  python bench.py --config $C --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+  python bench.py --config $C --steps 10 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err
   BENCH="python $PWD/bench.py --config $C --steps 4 --warmup 1 --no-cpu-baseline --no-live-pmc"
   ( cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- $BENCH > $OUT/trace.log 2>&1 )
   DB=$(find $OUT/trace -name "*.db" | head -1)
