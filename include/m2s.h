@@ -100,7 +100,8 @@ typedef struct m2s_timings {
   float distance_ms;     /* nearest-triangle search (+ fused sign resolve) — the dominant kernel's launch */
   float total_ms;        /* first kernel to last kernel, device side */
   float seed_ms;         /* grid path: what precedes the dominant launch besides the build — jump-flooding seed lattice
-                            (one triangle per packet brick) and the cut lists (k_cut) */
+                            (one triangle per packet brick) and the cut lists (k_cut).  Closest-point calls: the first pass (the
+                            distance walk whose results seed k_closest), included in their distance_ms */
   float reserved_f;
   uint64_t n_triangles;
   uint64_t n_units;      /* voxels or queries produced by this call */
@@ -292,6 +293,38 @@ int m2s_mesh_generate_sdf(m2s_mesh* mesh, const float* queries, size_t n_queries
  * Asynchronous calls also DEFER their device-side error report to this call: M2S_ERR_NAN if any of them met a
  * NaN distance in SignMethod::Normal (the reference panics, lib.rs:257). */
 int m2s_mesh_drain_timings(m2s_mesh* mesh, m2s_timings* timings);
+
+/* ---- closest points: which triangle is nearest, and where on it -------------------------------------
+ * What libigl signed_distance (I, C), trimesh closest_point or Open3D compute_closest_points return beside the distance, for the
+ * SDF gradient sign * (p - c) / |d|, attribute transfer from the nearest face and snapping points onto the surface.  Per point p:
+ *   triangle_out[i]        the t minimising point_triangle_distance2(p, T_t) (geo.rs:33-37,70-138, f32, no FMA), t in the caller's
+ *                          triangle order (Topology::get_triangles, lib.rs:175-193); on exact ties of d2 the lowest t; a NaN d2 is never
+ *                          nearest; UINT32_MAX when no triangle has a comparable distance.
+ *   point_out[3i .. 3i+2]  closest_point_triangle(p, a, b, c) of that triangle (geo.rs:70-138), bit for bit; NaN x 3 under UINT32_MAX.
+ *   distance_out[i]        its unsigned distance sqrt(d2): bit-equal to |m2s_generate_sdf(.., M2S_ACCEL_RTREE_BVH, ..)| and to
+ *                          |m2s_generate_grid_sdf(.., M2S_SIGN_RAYCAST, ..)| at the same point (f32::MAX where those give it).
+ * Any of the three outputs may be NULL, not all of them (M2S_ERR_BAD_ARG).  A mesh without triangles: M2S_ERR_EMPTY_MESH.
+ * Two passes on the call's stream: the unsigned distance walk of the generate call, then a walk that finds the triangle attaining each
+ * distance.  m2s_opts as for the generate calls — device, stream / stream_mode, mem_kind (ALL data pointers on one side),
+ * synchronous, lane; timings: accel_build_ms = the build, distance_ms = both passes, seed_ms = the first pass alone (the distances that
+ * seed the second), total_ms = the whole device time; algorithm = 1: every triangle for every point (validation).  Host-memory indices are range-checked before any device work (M2S_ERR_BAD_ARG).
+ *
+ * m2s_closest_points — queries: n_queries packed xyz (NULL only with n_queries == 0); outputs n_queries entries (x 3 for point_out). */
+int m2s_closest_points(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes,
+                       int topology, const float* queries, size_t n_queries,
+                       uint32_t* triangle_out, float* point_out, float* distance_out, const m2s_opts* opts);
+/* m2s_grid_closest_points — the grid's cell centres (grid.rs:135-141, as the grid path computes them) in its output layout
+ * z + y*nz + x*ny*nz; the outputs address the whole grid (3 floats per cell for point_out).  opts->x_begin / x_end select an x-slab as for
+ * m2s_generate_grid_sdf: only the slab is written.  A grid without cells, x_period or peer_out: M2S_ERR_BAD_ARG. */
+int m2s_grid_closest_points(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes,
+                            int topology, const m2s_grid* grid,
+                            uint32_t* triangle_out, float* point_out, float* distance_out, const m2s_opts* opts);
+/* The same on a persistent mesh (below): its resident tree, no build; results identical to the one-shot calls.  The tree is walked as it
+ * is (no re-marking of its leaves), so later generate calls on the mesh are unaffected. */
+int m2s_mesh_closest_points(m2s_mesh* mesh, const float* queries, size_t n_queries,
+                            uint32_t* triangle_out, float* point_out, float* distance_out, const m2s_opts* opts);
+int m2s_mesh_grid_closest_points(m2s_mesh* mesh, const m2s_grid* grid,
+                                 uint32_t* triangle_out, float* point_out, float* distance_out, const m2s_opts* opts);
 
 /* Grid helpers with the reference's exact f32 arithmetic (so callers need not re-derive it).
  * m2s_grid_from_bounding_box — Grid::from_bounding_box, grid.rs:59-74.

@@ -10,6 +10,7 @@
 //   generate_sdf           lib.rs:291-311
 //   Grid<V>                grid.rs:30-170                      new_ / from_bounding_box / getters / snap_point_to_grid
 //   generate_grid_sdf      generate/grid.rs:265-378
+//   closest_points / grid_closest_points                       nearest triangle + closest point (no reference counterpart; m2s.h)
 //   serde::*               serde.rs:75-221                     SerializeSdf / DeserializeSdf / save_to_file / read_from_file
 //
 // V is any point type with x(), y(), z() | .x .y .z | operator[] (the reference's `Point` trait adapters,
@@ -243,6 +244,49 @@ template <class V, class I = uint32_t>
 std::vector<float> generate_grid_sdf(const std::vector<V>& vertices, const Topology<I>& indices, const Grid<V>& grid,
                                      SignMethod sign_method = SignMethod::Raycast) {
   return generate_grid_sdf(vertices.data(), vertices.size(), indices, grid, sign_method);
+}
+
+// ---- closest points (m2s_closest_points, m2s_grid_closest_points) --------------------------------------------------------
+// Nearest triangle (Topology order, lowest index on ties, UINT32_MAX if none is comparable), the closest point on it and the unsigned
+// distance, per query point or per grid cell (grid order).  The distances are bit-equal to |generate_sdf(.., RtreeBvh)|.
+struct ClosestPoints {
+  std::vector<uint32_t> triangle;
+  std::vector<std::array<float, 3>> point;
+  std::vector<float> distance;
+};
+template <class V, class I = uint32_t>
+ClosestPoints closest_points(const V* vertices, size_t n_vertices, const Topology<I>& indices, const V* query_points, size_t n_queries) {
+  detail::Packed<V> v(vertices, n_vertices), q(query_points, n_queries);
+  detail::IndexArg<I> ia(indices);
+  ClosestPoints r;
+  r.triangle.resize(n_queries);
+  r.point.resize(n_queries);
+  r.distance.resize(n_queries);
+  static_assert(sizeof(std::array<float, 3>) == 12, "packed xyz");
+  detail::check(m2s_closest_points(v.ptr, n_vertices, ia.ptr, indices.count, ia.bytes, indices.kind, q.ptr, n_queries, r.triangle.data(),
+                                   reinterpret_cast<float*>(r.point.data()), r.distance.data(), nullptr));
+  return r;
+}
+template <class V, class I = uint32_t>
+ClosestPoints closest_points(const std::vector<V>& vertices, const Topology<I>& indices, const std::vector<V>& query_points) {
+  return closest_points(vertices.data(), vertices.size(), indices, query_points.data(), query_points.size());
+}
+template <class V, class I = uint32_t>
+ClosestPoints grid_closest_points(const V* vertices, size_t n_vertices, const Topology<I>& indices, const Grid<V>& grid) {
+  detail::Packed<V> v(vertices, n_vertices);
+  detail::IndexArg<I> ia(indices);
+  const size_t n = grid.get_total_cell_count();
+  ClosestPoints r;
+  r.triangle.resize(n);
+  r.point.resize(n);
+  r.distance.resize(n);
+  detail::check(m2s_grid_closest_points(v.ptr, n_vertices, ia.ptr, indices.count, ia.bytes, indices.kind, &grid.raw(), r.triangle.data(),
+                                        reinterpret_cast<float*>(r.point.data()), r.distance.data(), nullptr));
+  return r;
+}
+template <class V, class I = uint32_t>
+ClosestPoints grid_closest_points(const std::vector<V>& vertices, const Topology<I>& indices, const Grid<V>& grid) {
+  return grid_closest_points(vertices.data(), vertices.size(), indices, grid);
 }
 
 // ---- serde (serde.rs:75-221) ----------------------------------------------------------------------------------------------

@@ -135,6 +135,10 @@ EXPORTS = [
     "m2s_mesh_generate_grid_sdf",
     "m2s_mesh_generate_sdf",
     "m2s_mesh_drain_timings",
+    "m2s_closest_points",
+    "m2s_grid_closest_points",
+    "m2s_mesh_closest_points",
+    "m2s_mesh_grid_closest_points",
     "m2s_sdf_grid_encoded_size",
     "m2s_sdf_generic_encoded_size",
     "m2s_sdf_encode_grid",
@@ -195,6 +199,10 @@ def _prototypes():
         "m2s_mesh_generate_grid_sdf": (C.c_int, [C.c_void_p, C.POINTER(M2SGrid), C.c_int, C.c_void_p, C.POINTER(M2SOpts)]),
         "m2s_mesh_generate_sdf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(M2SOpts)]),
         "m2s_mesh_drain_timings": (C.c_int, [C.c_void_p, C.POINTER(M2STimings)]),
+        "m2s_closest_points": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
+        "m2s_grid_closest_points": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(M2SGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
+        "m2s_mesh_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
+        "m2s_mesh_grid_closest_points": (C.c_int, [C.c_void_p, C.POINTER(M2SGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
         "m2s_sdf_grid_encoded_size": (C.c_size_t, [C.POINTER(M2SGrid), C.c_size_t]),
         "m2s_sdf_generic_encoded_size": (C.c_size_t, [C.c_size_t, C.c_size_t]),
         "m2s_sdf_encode_grid": (C.c_int, [C.POINTER(M2SGrid), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(M2SOpts)]),

@@ -277,6 +277,64 @@ def generate_sdf(vertices, indices: Topology, query_points, acceleration_method:
     return out[: n_out.value]
 
 
+def _closest_buffers(a, n):
+    """(triangles uint32[n], points f32[n, 3], distances f32[n]) on the call's side, and their raw pointers."""
+    if a.device:
+        t = a.torch
+        tri = t.empty(n, dtype=t.int32, device=a.dev)   # bit pattern == u32; handed out as uint32 where torch has it
+        pts = t.empty((n, 3), dtype=t.float32, device=a.dev)
+        dist = t.empty(n, dtype=t.float32, device=a.dev)
+        ptrs = [x.data_ptr() if n else None for x in (tri, pts, dist)]
+    else:
+        tri, pts, dist = np.empty(n, np.uint32), np.empty((n, 3), np.float32), np.empty(n, np.float32)
+        ptrs = [x.ctypes.data if n else None for x in (tri, pts, dist)]
+    return (tri, pts, dist), ptrs
+
+
+def _closest_result(a, bufs):
+    tri, pts, dist = bufs
+    if a.device and hasattr(a.torch, "uint32"):
+        tri = tri.view(a.torch.uint32)
+    return tri, pts, dist
+
+
+def closest_points(vertices, indices: Topology, query_points, *, timings: M2STimings = None, algorithm: int = 0):
+    """Nearest triangle, closest point on it and unsigned distance of every query (include/m2s.h m2s_closest_points): returns
+    (triangles uint32[n], points f32[n, 3], distances f32[n]).  The triangle index is in Topology order (lowest index on ties,
+    0xFFFFFFFF where no distance is comparable); distances are bit-equal to |generate_sdf(.., RtreeBvh)|."""
+    a = _Args(vertices, indices, query_points)
+    bufs, (pt, pp, pd) = _closest_buffers(a, a.n_q)
+    o = a.opts(timings, algorithm)
+    rc = _lib.lib().m2s_closest_points(a.p_verts, a.n_verts, a.p_idx, a.n_idx, a.index_bytes, a.topology, a.p_q, a.n_q, pt, pp, pd,
+                                       C.byref(o))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    return _closest_result(a, bufs)
+
+
+def grid_closest_points(vertices, indices: Topology, grid: "Grid", *, timings: M2STimings = None, algorithm: int = 0,
+                        x_slab: Sequence[int] = None, out=None):
+    """closest_points for the cell centres of `grid`, flattened in grid order (z + y * nz + x * ny * nz).  `x_slab=(x0, x1)`
+    computes only the cells with x0 <= x < x1; `out` = (triangles, points, distances) of the whole grid to write into (the rest is
+    left untouched)."""
+    a = _Args(vertices, indices)
+    total = grid.get_total_cell_count()
+    if out is None:
+        bufs, ptrs = _closest_buffers(a, total)
+    else:
+        bufs = tuple(out)
+        ptrs = [(x.data_ptr() if a.device else x.ctypes.data) if total else None for x in bufs]
+    xb, xe = (0, 0) if x_slab is None else (int(x_slab[0]), int(x_slab[1]))
+    if x_slab is not None and xb == xe:
+        return _closest_result(a, bufs)
+    o = a.opts(timings, algorithm, xb, xe)
+    rc = _lib.lib().m2s_grid_closest_points(a.p_verts, a.n_verts, a.p_idx, a.n_idx, a.index_bytes, a.topology, C.byref(grid._g),
+                                            *ptrs, C.byref(o))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    return _closest_result(a, bufs)
+
+
 class PeerMode(enum.IntEnum):
     """include/m2s.h `m2s_peer_mode`: how a slab reaches the peers' whole-grid buffers."""
     Push = 0    # one wide copy kernel per slab piece, overlapped with the next piece's walk
@@ -627,6 +685,42 @@ class Mesh:
         if rc != _lib.M2S_OK:
             _raise(rc)
         return out[: n_out.value]
+
+    def closest_points(self, query_points, *, timings: M2STimings = None, algorithm: int = 0):
+        """closest_points on the resident tree: same results as the one-shot function."""
+        a = self._a
+        if a.device:
+            q = query_points if _is_torch(query_points) else a.torch.as_tensor(np.asarray(query_points, np.float32), device=a.dev)
+            q = q.detach().to(device=a.dev, dtype=a.torch.float32).contiguous().reshape(-1, 3)
+            n_q, p_q = q.shape[0], (q.data_ptr() if q.numel() else None)
+        else:
+            q = np.ascontiguousarray(np.asarray(query_points, np.float32)).reshape(-1, 3)
+            n_q, p_q = q.shape[0], (q.ctypes.data if q.size else None)
+        bufs, ptrs = _closest_buffers(a, n_q)
+        o = a.opts(timings, algorithm)
+        rc = _lib.lib().m2s_mesh_closest_points(self._h, p_q, n_q, *ptrs, C.byref(o))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        return _closest_result(a, bufs)
+
+    def grid_closest_points(self, grid: Grid, *, timings: M2STimings = None, algorithm: int = 0, x_slab: Sequence[int] = None,
+                            out=None):
+        """grid_closest_points on the resident tree: same results as the one-shot function."""
+        a = self._a
+        total = grid.get_total_cell_count()
+        if out is None:
+            bufs, ptrs = _closest_buffers(a, total)
+        else:
+            bufs = tuple(out)
+            ptrs = [(x.data_ptr() if a.device else x.ctypes.data) if total else None for x in bufs]
+        xb, xe = (0, 0) if x_slab is None else (int(x_slab[0]), int(x_slab[1]))
+        if x_slab is not None and xb == xe:
+            return _closest_result(a, bufs)
+        o = a.opts(timings, algorithm, xb, xe)
+        rc = _lib.lib().m2s_mesh_grid_closest_points(self._h, C.byref(grid._g), *ptrs, C.byref(o))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        return _closest_result(a, bufs)
 
     def debug_digest(self):
         """FNV-1a digests of the resident arrays (test hook `m2s_debug_mesh_digest`): triangle records, pre-test planes, box nodes,

@@ -269,10 +269,17 @@ __global__ __launch_bounds__(256) void k_emit(int n, const int2* __restrict__ ra
       const f3 v[3] = {a, bq, cq};
       const f3 e[3] = {mk3(r.abx, r.aby, r.abz), mk3(r.bcx, r.bcy, r.bcz), mk3(a.x - cq.x, a.y - cq.y, a.z - cq.z)};  // ab, bc, ca
       float m[3][4];
-      bool ok = true;
       const float vmax = fmaxf(fmaxf(fabsf(a.x), fmaxf(fabsf(a.y), fabsf(a.z))),
                                fmaxf(fmaxf(fabsf(bq.x), fmaxf(fabsf(bq.y), fabsf(bq.z))), fmaxf(fabsf(cq.x), fmaxf(fabsf(cq.y), fabsf(cq.z)))));
-      for (int k = 0; k < 3; ++k) {
+      // The face plane must hold all three vertices, or (n.p - dn)^2 is no lower bound: for a sliver (distinct, nearly collinear
+      // vertices) cross(ab, ac) is mostly rounding noise and b, c can lie far off the plane through a (a vertex then gets a positive
+      // bound although its distance is 0, and the walks pruned the nearest triangle).  |n.b - dn|, |n.c - dn| <= 8 ulps of the largest
+      // coordinate: the plane term is then off by at most ~1e-6 x that, inside the walks' absolute slack.  (Well-shaped triangles stay
+      // below 6 ulps: blob-100k, sheet-100k, suzanne, the build-digest meshes; slivers reach millions.)
+      const float dn = nu.x * a.x + nu.y * a.y + nu.z * a.z;
+      const float hb = nu.x * bq.x + nu.y * bq.y + nu.z * bq.z - dn, hc = nu.x * cq.x + nu.y * cq.y + nu.z * cq.z - dn;
+      bool ok = fmaxf(fabsf(hb), fabsf(hc)) <= 9.5367431640625e-07f * vmax;   // 8 x 2^-23; NaN fails
+      for (int k = 0; ok && k < 3; ++k) {
         f3 mk = cross3(e[k], nu);                                   // in the plane, perpendicular to edge k
         const float ml = sqrtf(mk.x * mk.x + mk.y * mk.y + mk.z * mk.z);
         if (!(ml > 1.0e-30f) || !(ml < 3.0e38f)) { ok = false; break; }
@@ -286,7 +293,7 @@ __global__ __launch_bounds__(256) void k_emit(int n, const int2* __restrict__ ra
         m[k][3] = o + 8.0e-6f * vmax + 1.0e-30f;                     // outward: makes the bound smaller
       }
       if (ok) {
-        pl.nx = nu.x; pl.ny = nu.y; pl.nz = nu.z; pl.dn = nu.x * a.x + nu.y * a.y + nu.z * a.z;
+        pl.nx = nu.x; pl.ny = nu.y; pl.nz = nu.z; pl.dn = dn;
         pl.m0x = m[0][0]; pl.m0y = m[0][1]; pl.m0z = m[0][2]; pl.o0 = m[0][3];
         pl.m1x = m[1][0]; pl.m1y = m[1][1]; pl.m1z = m[1][2]; pl.o1 = m[1][3];
         pl.m2x = m[2][0]; pl.m2y = m[2][1]; pl.m2z = m[2][2]; pl.o2 = m[2][3];

@@ -887,6 +887,138 @@ static void reap_pending(m2s_mesh* m, bool wait) {
   m->pending.resize(keep);
 }
 
+// ---- closest points (m2s_closest_points and its three siblings) ---------------------------------------------------------------
+// Two passes on the call's stream: the unsigned distance walk of the matching m2s_generate_* call, unchanged, into a workspace buffer,
+// then k_closest (closest.hip), which finds the triangle that attains each distance.  ev[0] .. ev[1] is the build (one-shot calls),
+// ev[2] .. ev[3] both passes, so finish_call reports them as accel_build_ms and distance_ms.
+namespace {
+
+using namespace m2s;
+
+struct ClosestArgs {
+  uint32_t* tri;
+  float* point;
+  float* dist;
+};
+
+int check_closest_outputs(const ClosestArgs& o) {
+  if (!o.tri && !o.point && !o.dist) return fail(M2S_ERR_BAD_ARG, "triangle_out, point_out and distance_out are all NULL");
+  return 0;
+}
+
+// Host-memory indices are range-checked before the device is touched (device-memory calls: by the build, as in every call).
+int check_host_indices(const void* indices, size_t n_indices, int index_bytes, int topology, size_t n_vertices, size_t n_tris) {
+  if (!indices || n_tris == 0) return 0;
+  const size_t used = topology == M2S_TRIANGLE_LIST ? 3 * n_tris : n_indices;   // a trailing partial triple is never read
+  for (size_t i = 0; i < used; ++i) {
+    const uint64_t v = index_bytes == 2 ? static_cast<const uint16_t*>(indices)[i] : static_cast<const uint32_t*>(indices)[i];
+    if (v >= n_vertices)
+      return fail(M2S_ERR_BAD_ARG, "vertex index %llu out of range (%zu vertices; the reference panics indexing `vertices`)", (unsigned long long)v, n_vertices);
+  }
+  return 0;
+}
+
+// Grid parameters of a closest-point call: an x-slab as for m2s_generate_grid_sdf; x_period and peer_out are grid-distance features only.
+int closest_grid_params(const m2s_grid* grid, const m2s_opts* opts, GridParams* g, size_t* slab_cells) {
+  if (!grid) return fail(M2S_ERR_BAD_ARG, "grid is NULL");
+  if (grid->cell_count[0] == 0 || grid->cell_count[1] == 0 || grid->cell_count[2] == 0) return fail(M2S_ERR_BAD_ARG, "grid without cells");
+  if (opts && opts->struct_size >= sizeof(m2s_opts) && (opts->x_period != 0 || opts->n_peer_out != 0))
+    return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_period / peer_out do not apply to closest-point calls");
+  return fill_grid_params(grid, opts, g, slab_cells);
+}
+
+// Device-side outputs of a call: the caller's arrays (device memory) or workspace slabs copied out afterwards (host memory).
+int closest_outputs(Arena& ws, const CallCtx& c, const ClosestArgs& o, size_t n, uint64_t first, ClosestOut* d) {
+  *d = ClosestOut{o.tri, o.point, o.dist, 0};
+  if (c.mem_kind == M2S_MEM_DEVICE) return 0;
+  d->tri = o.tri ? ws.take<uint32_t>(n) : nullptr;
+  d->point = o.point ? ws.take<float>(3 * n) : nullptr;
+  d->dist = o.dist ? ws.take<float>(n) : nullptr;
+  d->off = first;
+  if ((o.tri && !d->tri) || (o.point && !d->point) || (o.dist && !d->dist)) return fail(M2S_ERR_HIP, "internal: workspace");
+  return 0;
+}
+int closest_copy_out(DeviceState& st, const CallCtx& c, const ClosestArgs& o, const ClosestOut& d, size_t n, uint64_t first) {
+  if (c.mem_kind == M2S_MEM_DEVICE) return 0;
+  int rc = 0;
+  if (o.tri && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.tri + first), reinterpret_cast<const char*>(d.tri), n * 4))) return rc;
+  if (o.point && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.point + 3 * first), reinterpret_cast<const char*>(d.point), n * 12))) return rc;
+  if (o.dist && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.dist + first), reinterpret_cast<const char*>(d.dist), n * 4))) return rc;
+  return 0;
+}
+size_t closest_workspace_bytes(const CallCtx& c, size_t n) {
+  return align_up(n * 4) + (c.mem_kind == M2S_MEM_HOST ? align_up(n * 4) + align_up(n * 12) + align_up(n * 4) : 0) + 1024;
+}
+
+// Both passes over the slab of g on a built mesh.
+int run_grid_closest(Arena& ws, const CallCtx& c, DeviceState& st, const DeviceMesh& mesh, const GridParams& g, size_t slab_cells,
+                     const ClosestArgs& o, int* d_err) {
+  const uint64_t first = (uint64_t)g.xb * g.n[1] * g.n[2];
+  float* d_dist = ws.take<float>(slab_cells);
+  ClosestOut d;
+  if (!d_dist) return fail(M2S_ERR_HIP, "internal: workspace");
+  int rc = closest_outputs(ws, c, o, slab_cells, first, &d);
+  if (rc) return rc;
+  GridParams gd = g;
+  gd.out_off = first;                                  // the first pass writes the slab into d_dist
+  rc = launch_grid_distance(ws, c.stream, mesh, gd, MODE_UNSIGNED, nullptr, c.algorithm, d_dist, d_err, nullptr, nullptr, !c.sync);
+  if (rc) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st.ev[4], c.stream));
+  rc = launch_closest_grid(c.stream, mesh, g, d_dist, first, c.algorithm, d);
+  if (rc) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st.ev[3], c.stream));
+  return closest_copy_out(st, c, o, d, slab_cells, first);
+}
+
+// Both passes over a query set on a built mesh; d_q on the device.
+int run_query_closest(Arena& ws, const CallCtx& c, DeviceState& st, const DeviceMesh& mesh, const float* d_q, size_t n_q,
+                      const ClosestArgs& o, int* d_err) {
+  float* d_dist = ws.take<float>(n_q);
+  ClosestOut d;
+  if (!d_dist) return fail(M2S_ERR_HIP, "internal: workspace");
+  int rc = closest_outputs(ws, c, o, n_q, 0, &d);
+  if (rc) return rc;
+  QueryPlan plan;   // the Morton order (perm) serves the second pass too; algorithm 1 has none (input order)
+  rc = prepare_query_walk(ws, c.stream, d_q, n_q, mesh.n_tris, SIGN_NONE, c.algorithm, &plan);
+  if (rc) return rc;
+  if (query_is_tiny(n_q, mesh.n_tris, c.algorithm, SIGN_NONE))
+    rc = launch_query_brute_split(ws, c.stream, mesh, d_q, n_q, MODE_UNSIGNED, SIGN_NONE, d_dist, d_err);
+  else
+    rc = launch_query_walk(ws, c.stream, mesh, d_q, plan, MODE_UNSIGNED, SIGN_NONE, c.algorithm, d_dist, d_err);
+  if (rc) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st.ev[4], c.stream));
+  rc = launch_closest_queries(c.stream, mesh, d_q, plan.perm, n_q, d_dist, c.algorithm, d);
+  if (rc) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st.ev[3], c.stream));
+  return closest_copy_out(st, c, o, d, n_q, 0);
+}
+
+// finish_call for a closest-point call: distance_ms = both passes (ev[2] .. ev[3]); seed_ms = the first pass alone (ev[2] .. ev[4]), the
+// exact distances that seed k_closest.
+int finish_closest(const CallCtx& c, DeviceState& st, int* d_err, size_t n_tris, size_t n_units) {
+  const int rc = finish_call(c, st, d_err, c.timings, n_tris, n_units, false);
+  if (rc == M2S_OK && c.sync && c.timings) {
+    float first = 0.0f;
+    (void)hipEventElapsedTime(&first, st.ev[2], st.ev[4]);
+    c.timings->seed_ms = first;
+    c.timings->distance_launches = 2;
+  }
+  return rc;
+}
+
+// Options of a call on a persistent mesh: its device unless the caller names the same one.
+int mesh_call_opts(const m2s_mesh* m, const m2s_opts* opts, m2s_opts* o) {
+  *o = m2s_opts{};
+  if (opts) memcpy(o, opts, (opts->struct_size >= sizeof(m2s_opts)) ? sizeof(m2s_opts) : (size_t)M2S_OPTS_V1_SIZE);
+  else o->device = -1;
+  if (o->device < 0) o->device = m->device;
+  if (o->device != m->device) return fail(M2S_ERR_BAD_ARG, "mesh lives on device %d, call asked for %d", m->device, o->device);
+  if (!opts) o->synchronous = 1;
+  return 0;
+}
+
+}  // namespace
+
 using namespace m2s;
 
 extern "C" {
@@ -1610,6 +1742,163 @@ int m2s_mesh_generate_sdf(m2s_mesh* m, const float* queries, size_t n_queries, i
   }
   if (n_out) *n_out = n_queries;
   return finish_call(c, *st, d_err, c.timings, m->n_tris, n_queries, false);
+}
+
+int m2s_closest_points(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology,
+                       const float* queries, size_t n_queries, uint32_t* triangle_out, float* point_out, float* distance_out,
+                       const m2s_opts* opts) {
+  g_err[0] = 0;
+  const ClosestArgs o{triangle_out, point_out, distance_out};
+  int rc = check_mesh_args(vertices, n_vertices, indices, n_indices, index_bytes, topology);
+  if (rc) return rc;
+  if ((rc = check_closest_outputs(o))) return rc;
+  if (n_queries && !queries) return fail(M2S_ERR_BAD_ARG, "queries is NULL");
+  if (n_queries >= 0xffffffc0ull) return fail(M2S_ERR_BAD_ARG, "too many queries for one call");
+  const size_t n_tris = m2s_triangle_count(n_vertices, n_indices, indices != nullptr, topology);
+  if (n_tris == 0) return fail(M2S_ERR_EMPTY_MESH, "closest points on a mesh without triangles");
+  if (!opts || opts->mem_kind == M2S_MEM_HOST) {
+    if ((rc = check_host_indices(indices, n_indices, index_bytes, topology, n_vertices, n_tris))) return rc;
+  }
+  if (n_queries == 0) return M2S_OK;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(opts, &c, &st))) return rc;
+  size_t need = bvh_workspace_bytes(n_tris) + query_workspace_bytes(n_queries) + align_up(n_queries * 16) + closest_workspace_bytes(c, n_queries) + 4096;
+  if (c.mem_kind == M2S_MEM_HOST)
+    need += align_up(n_vertices * 12) + align_up(n_indices * (size_t)(indices ? index_bytes : 0)) + align_up(n_queries * 12) + 1024;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  StagedMesh sm;
+  if ((rc = stage_mesh(ws, c, vertices, n_vertices, indices, n_indices, index_bytes, &sm))) return rc;
+  const float* d_q = queries;
+  if (c.mem_kind == M2S_MEM_HOST) {
+    float* dq = ws.take<float>(n_queries * 3);
+    if (!dq) return fail(M2S_ERR_HIP, "internal: workspace");
+    if ((rc = staged_h2d(*st, c.stream, reinterpret_cast<char*>(dq), reinterpret_cast<const char*>(queries), n_queries * 12))) return rc;
+    d_q = dq;
+  }
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  DeviceMesh mesh;
+  rc = build_device_mesh(ws, c.stream, sm.d_verts, n_vertices, sm.d_indices, n_indices, index_bytes, topology, n_tris, d_err, &mesh,
+                         nullptr, false, query_leaf_max(n_queries, n_tris, SIGN_NONE));
+  if (rc) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  if ((rc = run_query_closest(ws, c, *st, mesh, d_q, n_queries, o, d_err))) return rc;
+  return finish_closest(c, *st, d_err, n_tris, n_queries);
+}
+
+int m2s_grid_closest_points(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology,
+                            const m2s_grid* grid, uint32_t* triangle_out, float* point_out, float* distance_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  const ClosestArgs o{triangle_out, point_out, distance_out};
+  int rc = check_mesh_args(vertices, n_vertices, indices, n_indices, index_bytes, topology);
+  if (rc) return rc;
+  if ((rc = check_closest_outputs(o))) return rc;
+  GridParams g;
+  size_t slab_cells = 0;
+  if ((rc = closest_grid_params(grid, opts, &g, &slab_cells))) return rc;
+  const size_t n_tris = m2s_triangle_count(n_vertices, n_indices, indices != nullptr, topology);
+  if (n_tris == 0) return fail(M2S_ERR_EMPTY_MESH, "closest points on a mesh without triangles");
+  if (!opts || opts->mem_kind == M2S_MEM_HOST) {
+    if ((rc = check_host_indices(indices, n_indices, index_bytes, topology, n_vertices, n_tris))) return rc;
+  }
+  if (slab_cells == 0) return M2S_OK;   // an empty slab [x, x)
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(opts, &c, &st))) return rc;
+  size_t need = bvh_workspace_bytes(n_tris) + grid_distance_workspace_bytes(g, n_tris) + closest_workspace_bytes(c, slab_cells) + 4096;
+  if (c.mem_kind == M2S_MEM_HOST) need += align_up(n_vertices * 12) + align_up(n_indices * (size_t)(indices ? index_bytes : 0)) + 1024;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  StagedMesh sm;
+  if ((rc = stage_mesh(ws, c, vertices, n_vertices, indices, n_indices, index_bytes, &sm))) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  DeviceMesh mesh;
+  rc = build_device_mesh(ws, c.stream, sm.d_verts, n_vertices, sm.d_indices, n_indices, index_bytes, topology, n_tris, d_err, &mesh,
+                         nullptr, false, grid_leaf_max(g, n_tris), (uint64_t)slab_cells);
+  if (rc) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  st->planes_done = nullptr;
+  st->have_raw_seeds = false;
+  if ((rc = run_grid_closest(ws, c, *st, mesh, g, slab_cells, o, d_err))) return rc;
+  return finish_closest(c, *st, d_err, n_tris, slab_cells);
+}
+
+int m2s_mesh_closest_points(m2s_mesh* m, const float* queries, size_t n_queries, uint32_t* triangle_out, float* point_out,
+                            float* distance_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  if (!m) return fail(M2S_ERR_BAD_ARG, "mesh is NULL");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  const ClosestArgs o{triangle_out, point_out, distance_out};
+  int rc = check_closest_outputs(o);
+  if (rc) return rc;
+  if (n_queries && !queries) return fail(M2S_ERR_BAD_ARG, "queries is NULL");
+  if (n_queries >= 0xffffffc0ull) return fail(M2S_ERR_BAD_ARG, "too many queries for one call");
+  if (m->n_tris == 0) return fail(M2S_ERR_EMPTY_MESH, "closest points on a mesh without triangles");
+  if (n_queries == 0) return M2S_OK;
+  m2s_opts mo;
+  if ((rc = mesh_call_opts(m, opts, &mo))) return rc;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(&mo, &c, &st))) return rc;
+  size_t need = query_workspace_bytes(n_queries) + align_up(n_queries * 16) + closest_workspace_bytes(c, n_queries) + 8192;
+  if (c.mem_kind == M2S_MEM_HOST) need += align_up(n_queries * 12) + 1024;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  const float* d_q = queries;
+  if (c.mem_kind == M2S_MEM_HOST) {
+    float* dq = ws.take<float>(n_queries * 3);
+    if (!dq) return fail(M2S_ERR_HIP, "internal: workspace");
+    if ((rc = staged_h2d(*st, c.stream, reinterpret_cast<char*>(dq), reinterpret_cast<const char*>(queries), n_queries * 12))) return rc;
+    d_q = dq;
+  }
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  if ((rc = remark_leaves(m, c, m->dm.leaf_max))) return rc;   // the tree as it is (any leaf size serves); keeps the mesh's stream bookkeeping
+  if ((rc = run_query_closest(ws, c, *st, m->dm, d_q, n_queries, o, d_err))) return rc;
+  return finish_closest(c, *st, d_err, m->n_tris, n_queries);
+}
+
+int m2s_mesh_grid_closest_points(m2s_mesh* m, const m2s_grid* grid, uint32_t* triangle_out, float* point_out, float* distance_out,
+                                 const m2s_opts* opts) {
+  g_err[0] = 0;
+  if (!m) return fail(M2S_ERR_BAD_ARG, "mesh is NULL");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  const ClosestArgs o{triangle_out, point_out, distance_out};
+  int rc = check_closest_outputs(o);
+  if (rc) return rc;
+  GridParams g;
+  size_t slab_cells = 0;
+  if ((rc = closest_grid_params(grid, opts, &g, &slab_cells))) return rc;
+  if (m->n_tris == 0) return fail(M2S_ERR_EMPTY_MESH, "closest points on a mesh without triangles");
+  if (slab_cells == 0) return M2S_OK;
+  m2s_opts mo;
+  if ((rc = mesh_call_opts(m, opts, &mo))) return rc;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(&mo, &c, &st))) return rc;
+  size_t need = grid_distance_workspace_bytes(g, m->n_tris) + closest_workspace_bytes(c, slab_cells) + 8192;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  st->planes_done = nullptr;
+  st->have_raw_seeds = false;
+  if ((rc = remark_leaves(m, c, m->dm.leaf_max))) return rc;
+  if ((rc = run_grid_closest(ws, c, *st, m->dm, g, slab_cells, o, d_err))) return rc;
+  return finish_closest(c, *st, d_err, m->n_tris, slab_cells);
 }
 
 // Peer-write bandwidth probe (include/m2s.h): the copy kernel of M2S_PEER_PUSH, timed with HIP events on a stream of its own.

@@ -346,6 +346,21 @@ int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const f
 int launch_query_distance(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const float* d_queries, size_t n_q,
                           int mode, int sign_src, int algorithm, float* d_out, int* d_err);
 
+// closest.hip: nearest triangle + closest point of every point, seeded by the exact distances of a first pass (d_dist).
+// Each output may be nullptr; a point's entry is its output index - off.
+struct ClosestOut {
+  uint32_t* tri;    // input triangle index (Topology::get_triangles order), 0xffffffff: none comparable
+  float* point;     // 3 per point
+  float* dist;
+  uint64_t off;
+};
+// Grid: the cells of the slab of g; d_dist holds the slab's unsigned distances at (cell index - dist_off).  algorithm 1: all pairs.
+int launch_closest_grid(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, const float* d_dist, uint64_t dist_off, int algorithm,
+                        const ClosestOut& out);
+// Queries: packets of 64 consecutive entries of perm (sorted position -> query; nullptr = input order); d_dist indexed by query.
+int launch_closest_queries(hipStream_t st, const DeviceMesh& mesh, const float* d_queries, const uint32_t* perm, size_t n_q, const float* d_dist,
+                           int algorithm, const ClosestOut& out);
+
 
 // serde.hip: payload arrays of the V1 container (fixed-width MessagePack records), any byte alignment.
 struct wire_bytes { uint8_t b[120]; uint32_t n; };   // envelope bytes passed by value to a 1-block kernel

@@ -16,6 +16,11 @@ float probe_dist2_signed(const float* p, const float* a, const float* b, const f
   *positive = pos ? 1 : 0;
   return d2;
 }
+void probe_closest_point(const float* p, const float* a, const float* b, const float* c, float* out) {
+  f3 A = mk3(a[0], a[1], a[2]), B = mk3(b[0], b[1], b[2]), Cc = mk3(c[0], c[1], c[2]);
+  const f3 q = closest_point_triangle(mk3(p[0], p[1], p[2]), A, B, Cc, tri_edges(A, B, Cc), tri_class(A, B, Cc));
+  out[0] = q.x; out[1] = q.y; out[2] = q.z;
+}
 int probe_ray(int axis, const float* o, const float* a, const float* b, const float* c, float* t) {
   return ray_triangle_aligned_rt(axis, mk3(o[0], o[1], o[2]), mk3(a[0], a[1], a[2]), mk3(b[0], b[1], b[2]),
                                  mk3(c[0], c[1], c[2]), t) ? 1 : 0;

@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""Compares the per-kernel gfx950 instruction streams of two hipcc -S listings of one translation unit.
+
+usage: tools/isa_kernel_diff.py <before.s> <after.s>
+
+A kernel's body is every instruction from its symbol to its .Lfunc_end label, with comments removed and
+local labels (.LBB*, .Ltmp*) renamed by order of appearance, so that code that only moved inside the file
+compares equal; its .amdhsa_* descriptor (registers, LDS, scratch) is compared as well.  Prints one line per
+kernel that differs, one per kernel present on one side only, and a summary; exit status 1 when anything
+differs.  Listings are made with the Makefile's FLAGS, e.g.
+
+  hipcc $(FLAGS) --cuda-device-only -S distance.hip -o distance.s
+"""
+import re
+import sys
+
+LABEL = re.compile(r"\.L(BB|tmp)[0-9_]+")
+
+
+def kernels(path):
+    lines = open(path).read().split("\n")
+    names = [m.group(1) for l in lines for m in [re.match(r"\s*\.amdhsa_kernel\s+(\S+)", l)] if m]
+    out = {}
+    for name in names:
+        start = next(i for i, l in enumerate(lines) if l.split(";", 1)[0].strip() == name + ":")
+        body, labels = [], {}
+        for l in lines[start + 1:]:
+            if l.startswith(".Lfunc_end"):
+                break
+            t = l.split(";", 1)[0].rstrip()
+            if not t.strip() or re.match(r"^\.L\w+:", t) or t.strip().startswith("."):
+                continue
+            body.append(LABEL.sub(lambda m: labels.setdefault(m.group(0), "L%d" % len(labels)), t.strip()))
+        k = lines.index("\t.amdhsa_kernel " + name)
+        desc = []
+        for l in lines[k + 1:]:
+            if ".end_amdhsa_kernel" in l:
+                break
+            desc.append(l.strip())
+        out[name] = (body, desc)
+    return out
+
+
+def main():
+    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    differ = 0
+    for name in sorted(set(a) | set(b)):
+        if name not in a or name not in b:
+            print("only in %s: %s" % ("after" if name in b else "before", name))
+            differ += 1
+        elif a[name] != b[name]:
+            print("differs (%d / %d instructions): %s" % (len(a[name][0]), len(b[name][0]), name))
+            differ += 1
+    same = len(set(a) & set(b)) - sum(1 for n in set(a) & set(b) if a[n] != b[n])
+    print("%d kernels before, %d after: %d identical, %d differ or are missing" % (len(a), len(b), same, differ))
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
