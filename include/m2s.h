@@ -422,6 +422,54 @@ typedef struct m2s_instance {
 int m2s_merge_instances(const m2s_instance* instances, size_t n_instances, float* vertices_out, uint32_t* indices_out,
                         float* bbox, const m2s_opts* opts);
 
+/* ---- queries on a finished grid SDF: sampling and ray marching ------------------------------------------------------
+ * What the reference client does with a generated grid on the GPU (mesh_to_sdf_client/shaders/draw_raymarching.wgsl), over a
+ * grid that stays where it is: sdf_grid (:118-200), estimate_normal (:202-209), sdf_3d with intersectAABB (:245-287) and
+ * compute_tetrahedral_barycenter (:585-640).  IEEE binary32 in the shader's operation order, no FMA.
+ * The grid: `grid` and its cell_count[0]*[1]*[2] distances in the library's layout z + y*nz + x*ny*nz (= the shader's get_distance,
+ * :92-99), with the client's uniforms (sdf.rs:74-81): start = first_cell, end = first_cell + (float)cell_count * cell_size
+ * (Grid::get_last_cell, grid.rs:82-88: one cell past the last centre), cell_size, cell_count.
+ * Sampling a point p at `iso`:
+ *   any(p < start) || any(p > end)  ->  `outside` (the shader's 100.0).
+ *   SNAP         idx = floor((p - (start - cell_size * 0.5)) / cell_size);  d[idx] - iso                        (:128-135)
+ *   TRILINEAR    c = (p - start) / cell_size, f = c - floor(c), idx = floor(c); the 8 corners (each - iso) interpolated
+ *                along x, then y, then z as a * (1 - f) + b * f                                                       (:137-175)
+ *   TETRAHEDRAL  the same idx and f; the six cases of compute_tetrahedral_barycenter in the shader's order (the LAST matching
+ *                case wins: all three fractions equal is case 6); dot(bary, samples) left to right                 (:177-197)
+ *   Every cell read clamps each index to [0, count - 1], so points between the last centre and `end` read the boundary cells twice.
+ * Normal (estimate_normal): eps = 0.01f * max(cs.x, max(cs.y, cs.z)); central differences of six samples (x, y, z order, each with its
+ *   own box test); v / sqrtf(v.x*v.x + v.y*v.y + v.z*v.z), and (0, 0, 0) where that length is 0 (WGSL leaves it undefined).  SNAP gives
+ *   zero normals almost everywhere, as the shader says.
+ * Ray marching (o, dir) (sdf_3d, `iso` for surface_iso, max_steps for MAX_STEPS): o outside the box enters it through intersectAABB with
+ *   fminf / fmaxf semantics (the non-NaN operand wins, so zero direction components are well defined); tNear > tFar is a miss:
+ *   (0, 0, 0, 1) and 0 steps; otherwise the march starts at o + (tNear + eps) * dir, as the shader writes it (also when the box lies
+ *   behind o).  Then up to max_steps times: dist = sample(pos); break if dist < eps; pos += dir * dist.  hit_out[4i..4i+3] = (pos, dist),
+ *   steps_out[i] = the advances made; a ray is a HIT when it entered the box and dist < eps; normal_out = estimate_normal(pos) for hits,
+ *   (0, 0, 0) otherwise.  `dir` is used as given, not normalised (the client normalises its camera rays).
+ * Defined where the shader is not: a point with a NaN coordinate samples as NaN with a NaN normal; a ray with a NaN in its origin or
+ *   direction gives NaN x 4, 0 steps and no hit; +-inf coordinates follow the box test (`outside`).
+ * Errors (M2S_ERR_BAD_ARG, before any device work): NULL grid or distances; a grid with a zero cell count, a cell size <= 0 or not finite,
+ *   or a start / end that is not finite (the shader's box would be empty or undefined); a bad mode; max_steps == 0 (ray march);
+ *   every output NULL; NULL inputs with n > 0; m2s_opts.algorithm, x_begin, x_end, x_period or peer_out not zero.  n == 0: M2S_OK.
+ * m2s_opts: device, stream / stream_mode, lane, synchronous; mem_kind covers EVERY data pointer (grid distances included).  Host memory
+ *   works but copies the whole grid over PCIe in every call: keep the grid on the device (M2S_MEM_DEVICE) for repeated queries.
+ *   timings: distance_ms = the kernel, n_units = points or rays. */
+enum m2s_sample_mode { M2S_SAMPLE_SNAP = 0, M2S_SAMPLE_TRILINEAR = 1, M2S_SAMPLE_TETRAHEDRAL = 2 };   /* = the shader's MODE_* (:43-45) */
+typedef struct m2s_sample_opts {
+  uint32_t struct_size;  /* sizeof(m2s_sample_opts) */
+  int32_t mode;          /* enum m2s_sample_mode; NULL opts: TRILINEAR, the client's default (sdf_program.rs:264) */
+  float iso;             /* NULL opts: 0 */
+  float outside;         /* value outside the box; NULL opts: 100.0f */
+  uint32_t max_steps;    /* ray march only, >= 1; NULL opts: 100 */
+} m2s_sample_opts;
+/* points: n_points packed xyz.  value_out: n_points floats; normal_out: 3 per point; either may be NULL, not both. */
+int m2s_sample_grid(const m2s_grid* grid, const float* distances, const float* points, size_t n_points, const m2s_sample_opts* sopts,
+                    float* value_out, float* normal_out, const m2s_opts* opts);
+/* origins, directions: n_rays packed xyz.  hit_out: 4 floats per ray; steps_out: 1 per ray; normal_out: 3 per ray; any may be NULL,
+ * not all. */
+int m2s_raymarch_grid(const m2s_grid* grid, const float* distances, const float* origins, const float* directions, size_t n_rays,
+                      const m2s_sample_opts* sopts, float* hit_out, uint32_t* steps_out, float* normal_out, const m2s_opts* opts);
+
 /* glTF 2.0 / GLB ingestion (host side) — what the reference client extracts from a file before the merge:
  * mesh_to_sdf_client/src/gltf/mod.rs:56-174 (models keyed by mesh index, one primitive per mesh survives;
  * POSITION + indices, sparse accessors and byteStride honoured; missing indices = 0..n, pbr/model.rs:29-32),

@@ -11,6 +11,7 @@
 //   Grid<V>                grid.rs:30-170                      new_ / from_bounding_box / getters / snap_point_to_grid
 //   generate_grid_sdf      generate/grid.rs:265-378
 //   closest_points / grid_closest_points                       nearest triangle + closest point (no reference counterpart; m2s.h)
+//   sample_grid / raymarch_grid  client draw_raymarching.wgsl  sdf_grid / estimate_normal / sdf_3d on a finished grid (m2s.h)
 //   serde::*               serde.rs:75-221                     SerializeSdf / DeserializeSdf / save_to_file / read_from_file
 //
 // V is any point type with x(), y(), z() | .x .y .z | operator[] (the reference's `Point` trait adapters,
@@ -287,6 +288,69 @@ ClosestPoints grid_closest_points(const V* vertices, size_t n_vertices, const To
 template <class V, class I = uint32_t>
 ClosestPoints grid_closest_points(const std::vector<V>& vertices, const Topology<I>& indices, const Grid<V>& grid) {
   return grid_closest_points(vertices.data(), vertices.size(), indices, grid);
+}
+
+// ---- queries on a finished grid (m2s_sample_grid, m2s_raymarch_grid) ------------------------------------------------------
+// The reference client's shader (draw_raymarching.wgsl: sdf_grid, estimate_normal, sdf_3d) over `distances`, the grid's cells in grid
+// order (what generate_grid_sdf returns).  Host memory: every call copies the grid to the device (m2s.h says when that matters).
+enum class SampleMode : int32_t { Snap = M2S_SAMPLE_SNAP, Trilinear = M2S_SAMPLE_TRILINEAR, Tetrahedral = M2S_SAMPLE_TETRAHEDRAL };
+struct SampleOptions {
+  SampleMode mode = SampleMode::Trilinear;
+  float iso = 0.0f;
+  float outside = 100.0f;
+  uint32_t max_steps = 100;   // raymarch_grid only
+};
+struct GridSamples {
+  std::vector<float> value;
+  std::vector<std::array<float, 3>> normal;   // empty unless asked for
+};
+struct RayMarch {
+  std::vector<std::array<float, 4>> hit;      // position, distance
+  std::vector<uint32_t> steps;
+  std::vector<std::array<float, 3>> normal;   // empty unless asked for
+};
+namespace detail {
+template <class V>
+void check_cells(const Grid<V>& grid, size_t n) {
+  if (n != grid.get_total_cell_count()) throw Panic(M2S_ERR_BAD_ARG, "distances do not match the grid's cell count");
+}
+inline m2s_sample_opts sample_opts(const SampleOptions& o) {
+  m2s_sample_opts s{};
+  s.struct_size = sizeof(s);
+  s.mode = (int32_t)o.mode;
+  s.iso = o.iso;
+  s.outside = o.outside;
+  s.max_steps = o.max_steps;
+  return s;
+}
+}  // namespace detail
+template <class V>
+GridSamples sample_grid(const Grid<V>& grid, const std::vector<float>& distances, const std::vector<V>& points, const SampleOptions& options = {},
+                        bool normals = false) {
+  detail::check_cells(grid, distances.size());
+  detail::Packed<V> p(points.data(), points.size());
+  const m2s_sample_opts so = detail::sample_opts(options);
+  GridSamples r;
+  r.value.resize(points.size());
+  if (normals) r.normal.resize(points.size());
+  detail::check(m2s_sample_grid(&grid.raw(), distances.data(), p.ptr, points.size(), &so, r.value.data(),
+                                normals ? reinterpret_cast<float*>(r.normal.data()) : nullptr, nullptr));
+  return r;
+}
+template <class V>
+RayMarch raymarch_grid(const Grid<V>& grid, const std::vector<float>& distances, const std::vector<V>& origins, const std::vector<V>& directions,
+                       const SampleOptions& options = {}, bool normals = false) {
+  detail::check_cells(grid, distances.size());
+  if (origins.size() != directions.size()) throw Panic(M2S_ERR_BAD_ARG, "origins and directions differ in length");
+  detail::Packed<V> o(origins.data(), origins.size()), d(directions.data(), directions.size());
+  const m2s_sample_opts so = detail::sample_opts(options);
+  RayMarch r;
+  r.hit.resize(origins.size());
+  r.steps.resize(origins.size());
+  if (normals) r.normal.resize(origins.size());
+  detail::check(m2s_raymarch_grid(&grid.raw(), distances.data(), o.ptr, d.ptr, origins.size(), &so, reinterpret_cast<float*>(r.hit.data()), r.steps.data(),
+                                  normals ? reinterpret_cast<float*>(r.normal.data()) : nullptr, nullptr));
+  return r;
 }
 
 // ---- serde (serde.rs:75-221) ----------------------------------------------------------------------------------------------

@@ -116,6 +116,10 @@ class M2SGltfInfo(C.Structure):
                 ("n_vertices", C.c_uint64), ("n_indices", C.c_uint64)]
 
 
+class M2SSampleOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("iso", C.c_float), ("outside", C.c_float), ("max_steps", C.c_uint32)]
+
+
 # every symbol include/m2s.h declares
 EXPORTS = [
     "m2s_generate_sdf",
@@ -150,6 +154,8 @@ EXPORTS = [
     "m2s_sdf_probe_file",
     "m2s_sdf_read_file",
     "m2s_order_cells_by_distance",
+    "m2s_sample_grid",
+    "m2s_raymarch_grid",
     "m2s_merge_instances",
     "m2s_gltf_open",
     "m2s_gltf_instances",
@@ -214,6 +220,10 @@ def _prototypes():
         "m2s_sdf_probe_file": (C.c_int, [C.c_char_p, C.POINTER(M2SSdfInfo)]),
         "m2s_sdf_read_file": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
         "m2s_order_cells_by_distance": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_float), C.POINTER(M2SOpts)]),
+        "m2s_sample_grid": (C.c_int, [C.POINTER(M2SGrid), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(M2SSampleOpts), C.c_void_p, C.c_void_p,
+                                      C.POINTER(M2SOpts)]),
+        "m2s_raymarch_grid": (C.c_int, [C.POINTER(M2SGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(M2SSampleOpts), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
         "m2s_merge_instances": (C.c_int, [C.POINTER(M2SInstance), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(M2SOpts)]),
         "m2s_gltf_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(M2SGltfInfo)]),
         "m2s_gltf_instances": (C.c_int, [C.c_void_p, C.POINTER(M2SInstance), C.c_size_t]),

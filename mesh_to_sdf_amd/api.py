@@ -335,6 +335,127 @@ def grid_closest_points(vertices, indices: Topology, grid: "Grid", *, timings: M
     return _closest_result(a, bufs)
 
 
+class SampleMode(enum.IntEnum):
+    """How a grid is read between cell centres (include/m2s.h m2s_sample_mode = the client shader's MODE_*)."""
+    Snap = 0
+    Trilinear = 1
+    Tetrahedral = 2
+
+
+class _GridQuery:
+    """The grid's distances and the per-point arrays of one grid query, on the side of `distances`: a CUDA tensor keeps everything on
+    its device (torch's current stream), anything else goes through host memory."""
+
+    def __init__(self, distances, timings=None, synchronous=True):
+        self.keep = []
+        self.device = _is_torch(distances) and distances.is_cuda
+        if self.device:
+            import torch
+
+            self.torch = torch
+            self.dev = distances.device
+            d = distances.detach().to(torch.float32).contiguous().reshape(-1)
+        else:
+            d = np.ascontiguousarray(np.asarray(distances, np.float32)).reshape(-1)
+        self.n_cells = d.numel() if self.device else d.size
+        self.p_d = self.ptr(d)
+        o = M2SOpts()
+        o.struct_size = C.sizeof(M2SOpts)
+        o.synchronous = 1 if synchronous else 0
+        if timings is not None:
+            o.timings = C.pointer(timings)
+        if self.device:
+            o.device = self.dev.index if self.dev.index is not None else self.torch.cuda.current_device()
+            o.stream = self.torch.cuda.current_stream(self.dev).cuda_stream
+            o.stream_mode = 1
+            o.mem_kind = _lib.MEM_DEVICE
+        else:
+            o.device = -1
+            o.mem_kind = _lib.MEM_HOST
+        self.opts = o
+
+    def ptr(self, x):
+        self.keep.append(x)
+        n = x.numel() if self.device else x.size
+        return (x.data_ptr() if self.device else x.ctypes.data) if n else None
+
+    def points(self, x):
+        """(n, 3) float32 on this call's side -> (pointer, n)."""
+        if self.device:
+            t = x if _is_torch(x) else self.torch.as_tensor(np.asarray(x, np.float32))
+            t = t.detach().to(device=self.dev, dtype=self.torch.float32).contiguous().reshape(-1, 3)
+            return self.ptr(t), t.shape[0]
+        if _is_torch(x):
+            x = x.detach().cpu().numpy()
+        a = np.ascontiguousarray(np.asarray(x, np.float32)).reshape(-1, 3)
+        return self.ptr(a), a.shape[0]
+
+    def empty(self, shape, dtype=np.float32):
+        if self.device:
+            t = self.torch.empty(shape, dtype=self.torch.int32 if dtype == np.uint32 else self.torch.float32, device=self.dev)
+            return t, self.ptr(t)
+        a = np.empty(shape, dtype)
+        return a, self.ptr(a)
+
+    def check_cells(self, grid):
+        if self.n_cells != grid.get_total_cell_count():
+            raise M2SPanic(_lib.ERR_BAD_ARG, f"distances hold {self.n_cells} values, the grid has {grid.get_total_cell_count()} cells")
+
+
+def _sample_opts(mode, iso, outside, max_steps):
+    so = _lib.M2SSampleOpts()
+    so.struct_size = C.sizeof(_lib.M2SSampleOpts)
+    so.mode, so.iso, so.outside, so.max_steps = int(mode), float(np.float32(iso)), float(np.float32(outside)), int(max_steps)
+    return so
+
+
+def sample_grid(grid: Grid, distances, points, *, mode: SampleMode = SampleMode.Trilinear, iso: float = 0.0, outside: float = 100.0,
+                normals: bool = False, timings: M2STimings = None):
+    """Samples a grid SDF at arbitrary points as the reference client's shader does (sdf_grid / estimate_normal of
+    draw_raymarching.wgsl; include/m2s.h m2s_sample_grid): `outside` beyond the grid box, else the snapped, trilinear or tetrahedral
+    value minus `iso`.  distances: the grid's cells in grid order (generate_grid_sdf's output).  Returns values f32[n], or
+    (values, normals f32[n, 3]) with normals=True.  A CUDA tensor `distances` keeps the call on its device."""
+    q = _GridQuery(distances, timings)
+    q.check_cells(grid)
+    p_pts, n = q.points(points)
+    values, p_v = q.empty(n)
+    nrm, p_n = q.empty((n, 3)) if normals else (None, None)
+    so = _sample_opts(mode, iso, outside, 100)
+    rc = _lib.lib().m2s_sample_grid(C.byref(grid._g), q.p_d, p_pts, n, C.byref(so), p_v, p_n, C.byref(q.opts))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    return (values, nrm) if normals else values
+
+
+def raymarch_grid(grid: Grid, distances, origins, directions, *, mode: SampleMode = SampleMode.Trilinear, iso: float = 0.0,
+                  outside: float = 100.0, max_steps: int = 100, normals: bool = False, timings: M2STimings = None):
+    """Sphere-traces rays through a grid SDF as the reference client's shader does (sdf_3d of draw_raymarching.wgsl; include/m2s.h
+    m2s_raymarch_grid).  Directions are used as given (not normalised).  Returns (positions f32[n, 3], dist f32[n], steps u32[n],
+    hit bool[n][, normals f32[n, 3]]): a hit is a ray that entered the grid box and ended closer than 0.01 * the largest cell size."""
+    q = _GridQuery(distances, timings)
+    q.check_cells(grid)
+    p_o, n = q.points(origins)
+    p_d, n_d = q.points(directions)
+    if n != n_d:
+        raise M2SPanic(_lib.ERR_BAD_ARG, f"{n} origins but {n_d} directions")
+    out, p_out = q.empty((n, 4))
+    steps, p_s = q.empty(n, np.uint32)
+    nrm, p_n = q.empty((n, 3)) if normals else (None, None)
+    so = _sample_opts(mode, iso, outside, max_steps)
+    rc = _lib.lib().m2s_raymarch_grid(C.byref(grid._g), q.p_d, p_o, p_d, n, C.byref(so), p_out, p_s, p_n, C.byref(q.opts))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    eps = np.float32(0.01) * np.float32(max(grid.get_cell_size()))
+    pos, dist = out[:, :3], out[:, 3]
+    # the miss output (0, 0, 0, 1) with no step is not a hit even where 1 < eps (cells larger than 100)
+    miss = (steps == 0) & (dist == 1.0) & (pos == 0).all(1)
+    hit = (dist < float(eps)) & ~miss
+    if q.device and hasattr(q.torch, "uint32"):
+        steps = steps.view(q.torch.uint32)
+    res = (pos, dist, steps, hit)
+    return res + (nrm,) if normals else res
+
+
 class PeerMode(enum.IntEnum):
     """include/m2s.h `m2s_peer_mode`: how a slab reaches the peers' whole-grid buffers."""
     Push = 0    # one wide copy kernel per slab piece, overlapped with the next piece's walk

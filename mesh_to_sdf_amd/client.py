@@ -3,6 +3,7 @@
   merge_instances          mesh_to_sdf_client/src/sdf_program.rs:597-641 (load_gltf's merge + bounding box)
   order_cells_by_distance  mesh_to_sdf_client/src/sdf.rs:62-72, :120     (voxel order + iso limits)
   Sdf.new                  mesh_to_sdf_client/src/sdf.rs:32-137          (generate, order, limits — without wgpu)
+  Sdf.sample / raymarch    mesh_to_sdf_client/shaders/draw_raymarching.wgsl (sdf_grid, estimate_normal, sdf_3d)
 
 numpy in -> numpy out (host pointers, staged inside the call); torch CUDA tensors in -> CUDA tensors out.
 """
@@ -14,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import M2SGltfInfo, M2SInstance, M2SOpts
-from .api import Grid, M2SError, SignMethod, Topology, _is_torch, generate_grid_sdf
+from .api import Grid, M2SError, SignMethod, Topology, _is_torch, generate_grid_sdf, raymarch_grid, sample_grid
 from .serde import _opts
 
 
@@ -173,6 +174,14 @@ class Sdf:
         dt = time.perf_counter() - t0
         ordered, limits = order_cells_by_distance(data)   # sdf.rs:62-68, :120
         return Sdf(data, ordered, grid, limits, dt)
+
+    def sample(self, points, **kw):
+        """sample_grid over this SDF's own grid and data (the shader's sdf_grid / estimate_normal, draw_raymarching.wgsl:118-209)."""
+        return sample_grid(self.grid, self.data, points, **kw)
+
+    def raymarch(self, origins, directions, **kw):
+        """raymarch_grid over this SDF's own grid and data (the shader's sdf_3d, draw_raymarching.wgsl:265-287)."""
+        return raymarch_grid(self.grid, self.data, origins, directions, **kw)
 
     def get_cell_count(self):   # sdf.rs:139-141
         c = self.grid.get_cell_count()

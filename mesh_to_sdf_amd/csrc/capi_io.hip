@@ -6,7 +6,9 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <stdexcept>
@@ -305,6 +307,105 @@ int save_impl(const char* path, const Layout& L, const float* queries, uint64_t 
   return rc;
 }
 
+// grid queries (m2s_sample_grid, m2s_raymarch_grid)
+// The grid, the sample options and the m2s_opts fields these calls do not take; everything the header lists as M2S_ERR_BAD_ARG
+// that needs no device.
+int query_args(const m2s_grid* grid, const float* distances, const m2s_sample_opts* so, bool ray, const m2s_opts* opts, GridQuery* q,
+               int* mode) {
+  if (!grid || !distances) return fail(M2S_ERR_BAD_ARG, "grid / distances is NULL");
+  if (opts) {
+    if (opts->algorithm != 0 || opts->x_begin != 0 || opts->x_end != 0)
+      return fail(M2S_ERR_BAD_ARG, "m2s_opts.algorithm / x_begin / x_end must be 0 for grid queries");
+    if (opts->struct_size >= sizeof(m2s_opts) && (opts->x_period != 0 || opts->n_peer_out != 0 || opts->peer_out))
+      return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_period / peer_out must be 0 for grid queries");
+  }
+  float cs_max = 0.0f;
+  for (int k = 0; k < 3; ++k) {
+    const uint64_t n = grid->cell_count[k];
+    const float cs = grid->cell_size[k];
+    if (n == 0 || n > (uint64_t)INT64_MAX) return fail(M2S_ERR_BAD_ARG, "cell_count[%d] = %llu", k, (unsigned long long)n);
+    if (!(cs > 0.0f) || !std::isfinite(cs)) return fail(M2S_ERR_BAD_ARG, "cell_size[%d] = %g must be > 0 and finite", k, (double)cs);
+    q->start[k] = grid->first_cell[k];
+    q->end[k] = grid->first_cell[k] + (float)n * cs;   // Grid::get_last_cell (grid.rs:82-88), f32
+    q->cs[k] = cs;
+    q->n[k] = (int64_t)n;
+    if (!std::isfinite(q->start[k]) || !std::isfinite(q->end[k])) return fail(M2S_ERR_BAD_ARG, "the grid box is not finite on axis %d", k);
+  }
+  q->nyz = grid->cell_count[1] * grid->cell_count[2];
+  cs_max = std::max(q->cs[0], std::max(q->cs[1], q->cs[2]));   // :203 max(x, max(y, z))
+  q->eps = 0.01f * cs_max;
+  *mode = M2S_SAMPLE_TRILINEAR;
+  q->iso = 0.0f;
+  q->outside = 100.0f;
+  q->max_steps = 100;
+  if (so) {
+    if (so->struct_size < sizeof(m2s_sample_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_sample_opts.struct_size too small");
+    if (so->mode != M2S_SAMPLE_SNAP && so->mode != M2S_SAMPLE_TRILINEAR && so->mode != M2S_SAMPLE_TETRAHEDRAL)
+      return fail(M2S_ERR_BAD_ARG, "bad sample mode %d", so->mode);
+    if (ray && so->max_steps == 0) return fail(M2S_ERR_BAD_ARG, "max_steps must be >= 1");
+    *mode = so->mode;
+    q->iso = so->iso;
+    q->outside = so->outside;
+    q->max_steps = so->max_steps;
+  }
+  return 0;
+}
+
+uint64_t grid_cells(const m2s_grid* g) { return g->cell_count[0] * g->cell_count[1] * g->cell_count[2]; }
+
+// Runs `launch(d_grid, d_in0, d_in1, d_out...)` with every pointer on the device: host data is staged through the workspace.
+struct QueryIo {
+  const float* src;     // caller's pointer
+  size_t bytes;
+  bool output;
+  char* dev = nullptr;  // what the kernel sees
+};
+
+int run_query(const m2s_opts* opts, QueryIo* io, int n_io, uint64_t n_units, const std::function<int(hipStream_t)>& launch) {
+  CallCtx c;
+  DeviceState* st = nullptr;
+  int rc = resolve_ctx(opts, &c, &st);
+  if (rc) return rc;
+  const bool host = c.mem_kind == M2S_MEM_HOST;
+  size_t need = 4096;
+  if (host)
+    for (int i = 0; i < n_io; ++i) need += align_up(io[i].bytes ? io[i].bytes : 1);
+  rc = ensure_capacity(*st, need);
+  if (rc) return rc;
+  Arena ws{st->base, st->cap, 0};
+  for (int i = 0; i < n_io; ++i) {
+    io[i].dev = const_cast<char*>(reinterpret_cast<const char*>(io[i].src));
+    if (!host || !io[i].src) continue;
+    io[i].dev = ws.take<char>(io[i].bytes ? io[i].bytes : 1);
+    if (!io[i].dev) return fail(M2S_ERR_HIP, "internal: workspace");
+    if (!io[i].output && io[i].bytes) {
+      rc = staged_h2d(*st, c.stream, io[i].dev, reinterpret_cast<const char*>(io[i].src), io[i].bytes);
+      if (rc) return rc;
+    }
+  }
+  if (c.timings) M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  rc = launch(c.stream);
+  if (rc) return rc;
+  if (c.timings) M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  if (host)
+    for (int i = 0; i < n_io; ++i)
+      if (io[i].output && io[i].src && io[i].bytes) {
+        rc = staged_d2h(*st, c.stream, const_cast<char*>(reinterpret_cast<const char*>(io[i].src)), io[i].dev, io[i].bytes);
+        if (rc) return rc;
+      }
+  if (c.sync) M2S_HIP_CHECK(hipStreamSynchronize(c.stream));
+  if (c.timings) {
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, st->ev[0], st->ev[1]);
+    memset(c.timings, 0, sizeof(*c.timings));
+    c.timings->distance_ms = ms;
+    c.timings->total_ms = ms;
+    c.timings->n_units = n_units;
+    c.timings->distance_launches = 1;
+  }
+  return M2S_OK;
+}
+
 }  // namespace
 }  // namespace m2s
 
@@ -457,6 +558,53 @@ int m2s_order_cells_by_distance(const float* distances, size_t n, uint32_t* orde
   if (c.sync || iso_limits || c.mem_kind == M2S_MEM_HOST) M2S_HIP_CHECK(hipStreamSynchronize(c.stream));
   if (iso_limits) memcpy(iso_limits, st->h_err + 4, 8);
   return M2S_OK;
+}
+
+// ---- sampling and ray marching a finished grid (grid_query.hip) ----------------------------------------------------------
+int m2s_sample_grid(const m2s_grid* grid, const float* distances, const float* points, size_t n_points, const m2s_sample_opts* sopts,
+                    float* value_out, float* normal_out, const m2s_opts* opts) {
+  clear_error();
+  GridQuery q;
+  int mode = 0;
+  int rc = query_args(grid, distances, sopts, false, opts, &q, &mode);
+  if (rc) return rc;
+  if (!value_out && !normal_out) return fail(M2S_ERR_BAD_ARG, "no output requested");
+  if (n_points && !points) return fail(M2S_ERR_BAD_ARG, "points is NULL");
+  if (n_points == 0) {
+    if (opts && opts->timings) memset(opts->timings, 0, sizeof(*opts->timings));
+    return M2S_OK;
+  }
+  QueryIo io[4] = {{distances, grid_cells(grid) * 4, false}, {points, n_points * 12, false}, {value_out, value_out ? n_points * 4 : 0, true},
+                   {normal_out, normal_out ? n_points * 12 : 0, true}};
+  return run_query(opts, io, 4, n_points, [&](hipStream_t s) {
+    return launch_sample_grid(s, q, mode, reinterpret_cast<const float*>(io[0].dev), reinterpret_cast<const float*>(io[1].dev), n_points,
+                              value_out ? reinterpret_cast<float*>(io[2].dev) : nullptr,
+                              normal_out ? reinterpret_cast<float*>(io[3].dev) : nullptr);
+  });
+}
+
+int m2s_raymarch_grid(const m2s_grid* grid, const float* distances, const float* origins, const float* directions, size_t n_rays,
+                      const m2s_sample_opts* sopts, float* hit_out, uint32_t* steps_out, float* normal_out, const m2s_opts* opts) {
+  clear_error();
+  GridQuery q;
+  int mode = 0;
+  int rc = query_args(grid, distances, sopts, true, opts, &q, &mode);
+  if (rc) return rc;
+  if (!hit_out && !steps_out && !normal_out) return fail(M2S_ERR_BAD_ARG, "no output requested");
+  if (n_rays && (!origins || !directions)) return fail(M2S_ERR_BAD_ARG, "origins / directions is NULL");
+  if (n_rays == 0) {
+    if (opts && opts->timings) memset(opts->timings, 0, sizeof(*opts->timings));
+    return M2S_OK;
+  }
+  QueryIo io[6] = {{distances, grid_cells(grid) * 4, false}, {origins, n_rays * 12, false}, {directions, n_rays * 12, false},
+                   {hit_out, hit_out ? n_rays * 16 : 0, true}, {reinterpret_cast<const float*>(steps_out), steps_out ? n_rays * 4 : 0, true},
+                   {normal_out, normal_out ? n_rays * 12 : 0, true}};
+  return run_query(opts, io, 6, n_rays, [&](hipStream_t s) {
+    return launch_raymarch_grid(s, q, mode, reinterpret_cast<const float*>(io[0].dev), reinterpret_cast<const float*>(io[1].dev),
+                                reinterpret_cast<const float*>(io[2].dev), n_rays, hit_out ? reinterpret_cast<float*>(io[3].dev) : nullptr,
+                                steps_out ? reinterpret_cast<uint32_t*>(io[4].dev) : nullptr,
+                                normal_out ? reinterpret_cast<float*>(io[5].dev) : nullptr);
+  });
 }
 
 int m2s_merge_instances(const m2s_instance* instances, size_t n_instances, float* vertices_out, uint32_t* indices_out,

@@ -229,6 +229,7 @@ void warm_serde(hipStream_t st);
 void warm_client(hipStream_t st);
 void warm_sortlib(hipStream_t st);
 void warm_sortlib_query(hipStream_t st);
+void warm_grid_query(hipStream_t st);
 // bvh.hip: flatten topology, build triangle records + LBVH in pre-order layout.
 size_t bvh_workspace_bytes(size_t n_tris);
 // `after_setup` (optional) is called twice with the input-order centroid array and triangle records: with phase 0 once the kernels that fill
@@ -360,6 +361,23 @@ int launch_closest_grid(hipStream_t st, const DeviceMesh& mesh, const GridParams
 // Queries: packets of 64 consecutive entries of perm (sorted position -> query; nullptr = input order); d_dist indexed by query.
 int launch_closest_queries(hipStream_t st, const DeviceMesh& mesh, const float* d_queries, const uint32_t* perm, size_t n_q, const float* d_dist,
                            int algorithm, const ClosestOut& out);
+
+
+// grid_query.hip: sampling and ray-marching a finished grid SDF (the client's draw_raymarching.wgsl).  The grid's scalars travel as a
+// kernel argument; start / end are the shader's uniforms (first_cell, Grid::get_last_cell), n[] >= 1, cs[] > 0 and finite.
+struct GridQuery {
+  float start[3], end[3], cs[3];
+  int64_t n[3];
+  uint64_t nyz;        // n[1] * n[2]
+  float iso, outside;
+  float eps;           // 0.01 * max(cs): the normal's step and the march's hit threshold
+  uint32_t max_steps;
+};
+// mode: enum m2s_sample_mode.  Any output may be nullptr.  hit_out: 4 floats per ray (position, distance).
+int launch_sample_grid(hipStream_t st, const GridQuery& q, int mode, const float* d, const float* pts, uint64_t n, float* value_out,
+                       float* normal_out);
+int launch_raymarch_grid(hipStream_t st, const GridQuery& q, int mode, const float* d, const float* org, const float* dir, uint64_t n,
+                         float* hit_out, uint32_t* steps_out, float* normal_out);
 
 
 // serde.hip: payload arrays of the V1 container (fixed-width MessagePack records), any byte alignment.
