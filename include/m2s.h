@@ -55,7 +55,7 @@ extern "C" {
  * turns a negative code back into panic!(m2s_last_error()). */
 #define M2S_OK 0
 #define M2S_ERR_BAD_ARG (-1)     /* null pointer / bad enum / vertex index out of range (reference: index panic) */
-#define M2S_ERR_NAN (-2)         /* "NaN distance" — lib.rs:257 expect(), Normal sign only */
+#define M2S_ERR_NAN (-2)         /* "NaN distance" — lib.rs:257 expect(), Normal sign only; m2s_grid_isosurface: a NaN or +-inf grid value */
 #define M2S_ERR_EMPTY_MESH (-3)  /* AccelerationMethod::Rtree on a mesh with no triangle — generic/rtree.rs:117 unwrap() */
 #define M2S_ERR_HIP (-4)         /* HIP runtime failure, or no HIP device / kernels not loadable */
 
@@ -469,6 +469,40 @@ int m2s_sample_grid(const m2s_grid* grid, const float* distances, const float* p
  * not all. */
 int m2s_raymarch_grid(const m2s_grid* grid, const float* distances, const float* origins, const float* directions, size_t n_rays,
                       const m2s_sample_opts* sopts, float* hit_out, uint32_t* steps_out, float* normal_out, const m2s_opts* opts);
+
+/* ---- isosurface of a finished grid SDF: marching cubes (no reference counterpart) -----------------------------------------------
+ * m2s_grid_isosurface extracts the level set d = iso of `distances` (the grid's cells in the library's layout) as a welded, indexed
+ * triangle mesh.  The output is exact: tests/isosurface_model.py reproduces it bit for bit.  IEEE binary32, no FMA.
+ * Grid points: the cell centres, pos(i,j,k) = m2s_grid_cell_center = first_cell + (float)i * cell_size per axis; the value at a point
+ *   is d[L], L = k + j*nz + i*ny*nz.  A point is INSIDE iff d[L] < iso (a value equal to iso is outside).
+ * Vertices: the edge (P, a), a in {x, y, z}, joins P and P + e_a and crosses iff exactly one end is inside.  Each crossing edge gives
+ *   exactly one vertex: t = (iso - d0) / (d1 - d0) with d0 the value at P; the axis-a coordinate is p0 + t * (p1 - p0), the other two
+ *   are pos(P)'s.  Vertices are ordered by ascending 3*L + a.
+ * Triangles: a cell has its lowest corner at P with i < nx-1, j < ny-1, k < nz-1; its case is
+ *   sum inside(P + (dx,dy,dz)) << (4*dx + 2*dy + dz).  Triangles are ordered by the lowest corner's L, then by the table's order within
+ *   the cell.  The table (mesh_to_sdf_amd/csrc/isosurface_table.h, generated by tools/gen_isosurface_table.py, which states the rule):
+ *   on every cube face the crossing edges are paired into segments, and an ambiguous face (two inside corners on a diagonal) keeps
+ *   the inside corners SEPARATED, a decision that depends on that face's four signs only, so neighbouring cells agree.  Each cell's
+ *   segments form disjoint closed loops; each loop is fanned from its lowest local edge id, loops in order of that id.  At most
+ *   5 triangles per cell.
+ * Winding: the right-hand normal (v1-v0) x (v2-v0) points from inside to outside (towards increasing d): for an SDF that is negative
+ *   inside, outwards, as M2S_SIGN_NORMAL expects of an input mesh.
+ * The mesh is closed except where the level set meets the grid boundary: every interior mesh edge is used by as many triangles in one
+ *   direction as in the other.  That is one each, except that the fan diagonals of the two cells beside an ambiguous face can join the
+ *   same two vertices of that face, so such an edge has two triangles each way.  A value exactly equal to iso can give zero-area
+ *   triangles; they are kept.
+ * Counting and capacity: vertices_out == indices_out == NULL only counts; exactly one of them NULL is M2S_ERR_BAD_ARG.  counts (host,
+ *   2 x uint64 = { n_vertices, n_triangles }) is always written when the arguments are valid ({0, 0} with M2S_ERR_NAN).  A capacity
+ *   (3 floats per vertex, 3 uint32 per triangle) below its count is M2S_ERR_BAD_ARG with counts written, and nothing is written
+ *   past either capacity; n_vertices >= 2^32 is M2S_ERR_BAD_ARG with counts written (the indices are u32).  Always synchronous.
+ * Errors before any device work (M2S_ERR_BAD_ARG): NULL grid, distances or counts; a zero cell count; a cell size <= 0 or not finite;
+ *   a non-finite first_cell; a non-finite iso; m2s_opts.algorithm, x_begin, x_end, x_period or peer_out not zero.
+ * A count of 1 on some axis: no cells, M2S_OK with zero triangles (crossing edges along the other axes still give vertices).
+ * A NaN or +-inf distance anywhere: M2S_ERR_NAN, and no output is written.
+ * m2s_opts: device, stream / stream_mode, lane; mem_kind covers the grid and both outputs (host memory copies the grid over PCIe in
+ *   every call).  timings: distance_ms = the call's kernels, n_units = grid points. */
+int m2s_grid_isosurface(const m2s_grid* grid, const float* distances, float iso, float* vertices_out, uint64_t vertex_capacity,
+                        uint32_t* indices_out, uint64_t triangle_capacity, uint64_t* counts, const m2s_opts* opts);
 
 /* glTF 2.0 / GLB ingestion (host side) — what the reference client extracts from a file before the merge:
  * mesh_to_sdf_client/src/gltf/mod.rs:56-174 (models keyed by mesh index, one primitive per mesh survives;

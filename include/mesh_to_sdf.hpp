@@ -12,6 +12,7 @@
 //   generate_grid_sdf      generate/grid.rs:265-378
 //   closest_points / grid_closest_points                       nearest triangle + closest point (no reference counterpart; m2s.h)
 //   sample_grid / raymarch_grid  client draw_raymarching.wgsl  sdf_grid / estimate_normal / sdf_3d on a finished grid (m2s.h)
+//   grid_isosurface                                            marching-cubes mesh of a level set of a finished grid (no reference counterpart; m2s.h)
 //   serde::*               serde.rs:75-221                     SerializeSdf / DeserializeSdf / save_to_file / read_from_file
 //
 // V is any point type with x(), y(), z() | .x .y .z | operator[] (the reference's `Point` trait adapters,
@@ -350,6 +351,29 @@ RayMarch raymarch_grid(const Grid<V>& grid, const std::vector<float>& distances,
   if (normals) r.normal.resize(origins.size());
   detail::check(m2s_raymarch_grid(&grid.raw(), distances.data(), o.ptr, d.ptr, origins.size(), &so, reinterpret_cast<float*>(r.hit.data()), r.steps.data(),
                                   normals ? reinterpret_cast<float*>(r.normal.data()) : nullptr, nullptr));
+  return r;
+}
+
+// ---- isosurface of a finished grid (m2s_grid_isosurface) ------------------------------------------------------------------
+// The level set d = iso of `distances` (the grid's cells in grid order) as a welded, indexed mesh: indices are 3 per triangle,
+// wound outwards (towards increasing d).  m2s.h states the exact contract.
+template <class V>
+struct Isosurface {
+  std::vector<V> vertices;
+  std::vector<uint32_t> indices;
+};
+template <class V>
+Isosurface<V> grid_isosurface(const Grid<V>& grid, const std::vector<float>& distances, float iso = 0.0f) {
+  detail::check_cells(grid, distances.size());
+  uint64_t counts[2] = {0, 0};
+  detail::check(m2s_grid_isosurface(&grid.raw(), distances.data(), iso, nullptr, 0, nullptr, 0, counts, nullptr));
+  std::vector<float> v(3 * counts[0] + 3);   // never empty: two NULL outputs would mean "count only"
+  Isosurface<V> r;
+  r.indices.resize(3 * counts[1] + 3);
+  detail::check(m2s_grid_isosurface(&grid.raw(), distances.data(), iso, v.data(), counts[0], r.indices.data(), counts[1], counts, nullptr));
+  r.indices.resize(3 * counts[1]);
+  r.vertices.reserve(counts[0]);
+  for (uint64_t i = 0; i < counts[0]; ++i) r.vertices.push_back(detail::make_point<V>(v[3 * i], v[3 * i + 1], v[3 * i + 2]));
   return r;
 }
 

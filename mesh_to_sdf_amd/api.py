@@ -456,6 +456,30 @@ def raymarch_grid(grid: Grid, distances, origins, directions, *, mode: SampleMod
     return res + (nrm,) if normals else res
 
 
+def grid_isosurface(grid: Grid, distances, *, iso: float = 0.0, timings: M2STimings = None):
+    """Extracts the level set d = iso of a grid SDF as a welded, indexed triangle mesh (marching cubes over the cell centres;
+    include/m2s.h m2s_grid_isosurface states the exact contract).  Triangles wind outwards (towards increasing d).  Returns
+    (vertices f32[n, 3], indices u32[m, 3]).  A CUDA tensor `distances` keeps the call on its device and returns tensors."""
+    q = _GridQuery(distances, timings)
+    q.check_cells(grid)
+    L = _lib.lib()
+    counts = (C.c_uint64 * 2)()
+    it = float(np.float32(iso))
+    rc = L.m2s_grid_isosurface(C.byref(grid._g), q.p_d, it, None, 0, None, 0, counts, C.byref(q.opts))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    nv, nt = int(counts[0]), int(counts[1])
+    verts, p_v = q.empty((max(nv, 1), 3))          # never NULL: NULL for both outputs means "count only"
+    idx, p_i = q.empty((max(nt, 1), 3), np.uint32)
+    rc = L.m2s_grid_isosurface(C.byref(grid._g), q.p_d, it, p_v, nv, p_i, nt, counts, C.byref(q.opts))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    verts, idx = verts[:nv], idx[:nt]
+    if q.device and hasattr(q.torch, "uint32"):
+        idx = idx.view(q.torch.uint32)
+    return verts, idx
+
+
 class PeerMode(enum.IntEnum):
     """include/m2s.h `m2s_peer_mode`: how a slab reaches the peers' whole-grid buffers."""
     Push = 0    # one wide copy kernel per slab piece, overlapped with the next piece's walk
