@@ -429,7 +429,7 @@ int run_grid_distance_push(Arena& ws, const CallCtx& c, DeviceState& st, const D
     gp.xe = gp.xb + (uint32_t)std::min<uint64_t>(lpp, layers - i * lpp);
     gp.chunk_log = 31;
     gp.period = 0;
-    rc = launch_grid_walk(c.stream, mesh, gp, mode, plane, c.algorithm, plan, (uint32_t)((i * lpp) >> g.bl[0]), d_out, d_err);
+    rc = launch_grid_walk(c.stream, mesh, gp, mode, plane, plan, (uint32_t)((i * lpp) >> g.bl[0]), d_out, d_err);
     if (rc) return rc;
     if (i + 1 == pieces) M2S_HIP_CHECK(hipEventRecord(st.ev[3], c.stream));
     M2S_HIP_CHECK(hipEventRecord(st.piece_events[i], c.stream));
@@ -465,7 +465,7 @@ int run_grid_distance_trail(Arena& ws, const CallCtx& c, DeviceState& st, const 
   st.have_raw_seeds = false;
   if (rc) return rc;
   const uint64_t row = (uint64_t)g.n[1] * g.n[2];
-  const bool trailing = !plan.lane_walk && plan.brute_acc == nullptr && c.algorithm == 0 && mesh.n_nodes != 0 && g.chunk_log >= 31u;   // k_packet counts its packets; the other walks do not
+  const bool trailing = plan.choice.path != GridWalkChoice::LANE && plan.choice.path != GridWalkChoice::ALL_PAIRS_SPLIT && c.algorithm == 0 && mesh.n_nodes != 0 && g.chunk_log >= 31u;   // k_packet counts its packets; the other walks do not
   PeerOut walk_peers{};
   if (trailing) {
     const size_t counters = (size_t)trail_units(g) * (trail_rows(g) + 1u);
@@ -480,7 +480,7 @@ int run_grid_distance_trail(Arena& ws, const CallCtx& c, DeviceState& st, const 
   if (st.planes_done) M2S_HIP_CHECK(hipStreamWaitEvent(c.stream, st.planes_done, 0));
   M2S_HIP_CHECK(hipEventRecord(st.piece_events[0], c.stream));          // counters are zero, inputs are ready
   M2S_HIP_CHECK(hipEventRecord(st.ev[4], c.stream));
-  rc = launch_grid_walk(c.stream, mesh, g, mode, plane, c.algorithm, plan, 0, d_out, d_err, trailing ? &walk_peers : nullptr);
+  rc = launch_grid_walk(c.stream, mesh, g, mode, plane, plan, 0, d_out, d_err, trailing ? &walk_peers : nullptr);
   if (rc) return rc;
   M2S_HIP_CHECK(hipEventRecord(st.ev[3], c.stream));
   if (trailing) {
@@ -654,7 +654,7 @@ int run_grid_distance_to_host(Arena& ws, const CallCtx& c, DeviceState& st, cons
     GridParams gp = g;
     gp.xb = g.xb + (uint32_t)(i * lpp);
     gp.xe = (uint32_t)std::min<uint64_t>(g.xe, gp.xb + lpp);
-    rc = launch_grid_walk(c.stream, mesh, gp, mode, plane, c.algorithm, plan, (uint32_t)((i * lpp) >> g.bl[0]), d_slab, d_err);
+    rc = launch_grid_walk(c.stream, mesh, gp, mode, plane, plan, (uint32_t)((i * lpp) >> g.bl[0]), d_slab, d_err);
     if (rc) { cleanup(); return rc; }
     if (hipEventRecord(done[i], c.stream) != hipSuccess) { cleanup(); return fail(M2S_ERR_HIP, "hipEventRecord failed"); }
   }
@@ -2022,6 +2022,33 @@ int m2s_debug_leaf_sizes(const m2s_grid* grid, size_t n_tris, size_t n_queries, 
   out[1] = query_leaf_max(n_queries, n_tris, SIGN_RAYS3);
   out[2] = query_walk_is_lane(n_queries, n_tris, SIGN_RAYS3) ? 1u : 0u;
   return M2S_OK;
+}
+
+// Test hooks (not part of include/m2s.h): the path a grid call over `grid` takes for a mesh of n_tris triangles whose tree has n_nodes records (0: triangle
+// records only) and leaves of leaf_max, under the current knobs (distance.hip choose_grid_walk).  out[0] GridWalkChoice::Path, [1] seeds, [2] cut-list
+// levels, [3] waves per packet group, [4] split walk, [5] ... forced, [6] leaf-work form, [7] 1 if the workspace block is sized for a split walk
+// (choose_grid_walk_for_sizing).  Host arithmetic only; tests/test_capi_cpu.py pins the crossovers DESIGN.md section 9 states.  The _slab form takes the x-slab
+// (x_begin, x_end, x_period) of `opts` as a grid call does.
+int m2s_debug_grid_walk_choice_slab(const m2s_grid* grid, const m2s_opts* opts, size_t n_tris, size_t n_nodes, uint32_t leaf_max, int algorithm, uint32_t out[8]) {
+  g_err[0] = 0;
+  if (!grid || !out) return fail(M2S_ERR_BAD_ARG, "NULL argument");
+  GridParams g;
+  size_t slab_cells = 0;
+  const int rc = fill_grid_params(grid, opts, &g, &slab_cells);
+  if (rc) return rc;
+  const GridWalkChoice ch = choose_grid_walk(g, n_tris, n_nodes, leaf_max, false, algorithm, tuning());
+  out[0] = (uint32_t)ch.path;
+  out[1] = ch.seeds ? 1u : 0u;
+  out[2] = (uint32_t)ch.cut_levels;
+  out[3] = ch.group_waves;
+  out[4] = ch.split ? 1u : 0u;
+  out[5] = ch.split_forced ? 1u : 0u;
+  out[6] = (uint32_t)ch.defer;
+  out[7] = choose_grid_walk_for_sizing(g, n_tris).split ? 1u : 0u;
+  return M2S_OK;
+}
+int m2s_debug_grid_walk_choice(const m2s_grid* grid, size_t n_tris, size_t n_nodes, uint32_t leaf_max, int algorithm, uint32_t out[8]) {
+  return m2s_debug_grid_walk_choice_slab(grid, nullptr, n_tris, n_nodes, leaf_max, algorithm, out);
 }
 
 }  // extern "C"

@@ -271,19 +271,30 @@ struct SplitCtl {
   uint32_t emit_min = 0, emit_max = 0;   // bytes of records: a suspended walk hands over the surviving subtrees of this size range
   uint32_t rounds = 3;              // follow-up launches; the last one walks to the end
 };
-// What a grid walk needs besides the mesh: the seed lattice and the cut lists of a slab (device pointers into the call's arena).
+// Which path the walk of a slab takes (distance.hip choose_grid_walk: every crossover of DESIGN.md section 9 in one pure host function).
+struct Tuning;
+struct GridWalkChoice {
+  enum Path { NOTHING, ALL_PAIRS_SPLIT /* tiny: k_brute_split */, ALL_PAIRS /* algorithm 1 */, LANE, GROUP, PACKET };
+  Path path = NOTHING;             // NOTHING: an empty slab
+  bool seeds = false;              // a seed lattice (grid_walk_wants_seeds)
+  int cut_levels = 0;              // cut lists: 0 none, 1 k_cut<true, 0>, 2 k_cut<true, 1> + <true, 2>
+  uint32_t group_waves = 0;        // GROUP: waves per packet (2 or 4)
+  bool split = false;              // PACKET: split walk ...
+  bool split_forced = false;       // ... M2S_SPLIT=2: the flags start raised (tests)
+  int defer = 0;                   // PACKET: 1 exact evaluations queued and run densely, 2 + direct where most lanes are reached, 3 the pre-tests queued too (distance.hip DeferQueue)
+};
+GridWalkChoice choose_grid_walk(const GridParams& g, size_t n_tris, size_t n_nodes, uint32_t leaf_max, bool counting, int algorithm, const Tuning& tn);
+GridWalkChoice choose_grid_walk_for_sizing(const GridParams& g, size_t n_tris);   // before the mesh exists: splits wherever a real mesh's choice can
+// What a grid walk needs besides the mesh: the choice, and the seed lattice, cut lists and scratch it asks for (device pointers into the call's arena).
 struct GridWalkPlan {
+  GridWalkChoice choice;
   const uint32_t* seeds = nullptr;
   uint32_t seed_shift = 0, seed_ny = 0, seed_nz = 0;
   const uint32_t* cut_lists = nullptr;
   uint32_t cut_log = 0, cut_ny = 0, cut_nz = 0;
-  bool lane_walk = false;
-  SplitCtl split;                  // packet walk only
-  bool split_forced = false;       // M2S_SPLIT=2: the flags start raised (tests)
-  int defer = 0;                   // packet walk: 1 exact evaluations queued and run densely, 2 + direct where most lanes are reached (distance.hip DeferQueue)
-  const uint2* group_top = nullptr;   // packet groups (k_packet_group): the tree's top subtrees (k_tree_top); nullptr: one wave per packet
-  uint32_t group_waves = 0;           // ... waves per packet (2, 4, 8 or 16)
-  uint32_t* brute_acc = nullptr;   // tiny problems (grid_is_tiny): per-voxel minima of k_brute_split; no seeds, no lists, no tree
+  SplitCtl split;                     // choice.split
+  const uint2* group_top = nullptr;   // GROUP: the tree's top subtrees (k_tree_top)
+  uint32_t* brute_acc = nullptr;      // ALL_PAIRS_SPLIT: per-voxel minima of k_brute_split; no seeds, no lists, no tree
 };
 bool grid_is_tiny(const GridParams& g, size_t n_tris, int algorithm, bool raycast);   // raycast: the call's sign rule (the limits differ)
 // Seed lattice of a slab: one triangle id per packet brick (ids index the centroid array it was computed from).
@@ -301,8 +312,7 @@ int prepare_grid_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const G
 // `g` may be an x-piece of the slab the plan was prepared for, starting bx_off bricks into it (a multiple of 2 bricks).
 // `peers` (optional): buffers that receive the same values in the walk's epilogue (M2S_PEER_STORE).
 int launch_grid_walk(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, int mode, const uint32_t* d_inside_plane,
-                     int algorithm, const GridWalkPlan& plan, uint32_t bx_off, float* d_out, int* d_err,
-                     const PeerOut* peers = nullptr);
+                     const GridWalkPlan& plan, uint32_t bx_off, float* d_out, int* d_err, const PeerOut* peers = nullptr);
 // M2S_PEER_PUSH: copies the cells [first, first + count) of the whole-grid buffer `src` to the same range of every peer
 // (16 B per lane where the range allows).
 int launch_push_cells(hipStream_t st, const float* src, const PeerOut& peers, uint64_t first, uint64_t count);

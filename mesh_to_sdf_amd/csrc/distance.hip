@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "common.h"
 #include "geo.hip.h"
@@ -2231,52 +2232,58 @@ __global__ __launch_bounds__(256) void k_qpacket_bounds(float4* __restrict__ sor
   centres[packet] = make_float4(c[0], c[1], c[2], r);
 }
 
-template <bool GRID, int MODE, int SIGN>
-void launch_packet(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, const float4* qs, const uint32_t* perm,
-                   uint32_t n_q, const uint32_t* plane, float* out, int* err, uint32_t n_packets,
-                   const uint32_t* seed_in = nullptr, uint32_t seed_shift = 0, uint32_t seed_ny = 0,
-                   uint32_t seed_nz = 0, const GridParams* seed_lattice = nullptr, CutList cut = {nullptr, 0, 0, 0, 0, nullptr},
-                   const PeerOut* peers_in = nullptr, const SplitCtl* split_in = nullptr, int defer = 0) {
+// ---- host part: which path a call takes (choose_grid_walk), then the launches -------------------------------------------------
+
+// k_packet's parameter list by name.  A call site assigns what it has: the grid path the planes, the seed lattice's shape, the peers and the
+// split walk; the query path the sorted queries, their packet table (in `plane`'s place) and the lattice's description.
+struct PacketArgs {
+  DeviceMesh mesh{};
+  GridParams g{};
+  const float4* qsorted = nullptr;
+  const uint32_t *perm = nullptr, *plane = nullptr;
+  uint32_t n_q = 0, n_packets = 0;
+  float* out = nullptr;
+  int* err = nullptr;
+  const uint32_t* seed_in = nullptr;
+  uint32_t seed_shift = 0, seed_ny = 0, seed_nz = 0;
+  const GridParams* seed_lattice = nullptr;
+  CutList cut = {nullptr, 0, 0, 0, 0, nullptr};
   PeerOut peers{};
-  if (peers_in) peers = *peers_in;
   SplitCtl split{};
-  if (split_in) split = *split_in;
+};
+// `defer`: the leaf-work form asked for (GridWalkChoice::defer, M2S_DEFER).  Form 2 exists for grids only, and a split walk (grids; a.split.cnt
+// set) always queues its evaluations — the follow-up rounds do —: DEFER 3 if asked for, else 1.
+template <bool GRID, int MODE, int SIGN>
+void launch_packet(hipStream_t st, const PacketArgs& a, int defer) {
   const uint32_t per = 8u << XCD_RUN_LOG;                              // one run on each of the eight XCDs
-  const uint32_t grid_blocks = ((n_packets + per - 1) / per) * per;    // a whole number of runs per XCD (xcd_remap)
+  const uint32_t grid_blocks = ((a.n_packets + per - 1) / per) * per;  // a whole number of runs per XCD (xcd_remap)
+  const auto launch = [&](auto stats, auto split, auto form) {
+    hipLaunchKernelGGL((k_packet<GRID, MODE, SIGN, decltype(stats)::value, decltype(split)::value, decltype(form)::value>), dim3(grid_blocks), dim3(64), 0, st,
+                       a.mesh, a.g, a.qsorted, a.perm, a.n_q, a.plane, a.out, a.err, a.n_packets, a.seed_in, a.seed_shift, a.seed_ny, a.seed_nz, a.seed_lattice,
+                       a.cut, a.peers, a.split);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  constexpr std::integral_constant<int, 0> f0{};
+  constexpr std::integral_constant<int, 1> f1{};
+  constexpr std::integral_constant<int, 2> f2{};
+  constexpr std::integral_constant<int, 3> f3{};
 #ifdef M2S_STATS_BUILD
   // M2S_STATS: the counting variant (a few SALU ops more per node); never suspended, so that a packet's counters are whole.  Only the
   // side library libm2s_stats.so (make stats; tools/exp_stats.py loads it through M2S_LIB) carries these instantiations: the product
   // library's code object is seven k_packet variants smaller.
-  if (mesh.stats != nullptr)
-    hipLaunchKernelGGL((k_packet<GRID, MODE, SIGN, true, false>), dim3(grid_blocks), dim3(64), 0, st, mesh, g,
-                       qs, perm, n_q, plane, out, err, n_packets, seed_in, seed_shift, seed_ny, seed_nz, seed_lattice, cut, peers, split);
-  else
+  if (a.mesh.stats != nullptr) return launch(yes, no, f0);
 #endif
-  if (defer == 3 && GRID && MODE != MODE_NEAREST_NORMAL && split.cnt != nullptr)
-    hipLaunchKernelGGL((k_packet<GRID, MODE == MODE_NEAREST_NORMAL ? MODE_UNSIGNED : MODE, SIGN, false, GRID, GRID ? 3 : 1>), dim3(grid_blocks), dim3(64), 0, st, mesh, g,
-                       qs, perm, n_q, plane, out, err, n_packets, seed_in, seed_shift, seed_ny, seed_nz, seed_lattice, cut, peers, split);
-  else if (defer == 3)
-    hipLaunchKernelGGL((k_packet<GRID, MODE, SIGN, false, false, 3>), dim3(grid_blocks), dim3(64), 0, st, mesh, g,
-                       qs, perm, n_q, plane, out, err, n_packets, seed_in, seed_shift, seed_ny, seed_nz, seed_lattice, cut, peers, split);
-  else if (GRID && MODE != MODE_NEAREST_NORMAL && split.cnt != nullptr)   // (a split walk always queues its evaluations: the follow-up rounds do)
-    hipLaunchKernelGGL((k_packet<GRID, MODE == MODE_NEAREST_NORMAL ? MODE_UNSIGNED : MODE, SIGN, false, GRID, 1>), dim3(grid_blocks), dim3(64), 0, st, mesh, g,
-                       qs, perm, n_q, plane, out, err, n_packets, seed_in, seed_shift, seed_ny, seed_nz, seed_lattice, cut, peers, split);
-  else if (defer == 2 && GRID)
-    hipLaunchKernelGGL((k_packet<GRID, MODE, SIGN, false, false, GRID ? 2 : 1>), dim3(grid_blocks), dim3(64), 0, st, mesh, g,
-                       qs, perm, n_q, plane, out, err, n_packets, seed_in, seed_shift, seed_ny, seed_nz, seed_lattice, cut, peers, split);
-  else if (defer)
-    hipLaunchKernelGGL((k_packet<GRID, MODE, SIGN, false, false, 1>), dim3(grid_blocks), dim3(64), 0, st, mesh, g,
-                       qs, perm, n_q, plane, out, err, n_packets, seed_in, seed_shift, seed_ny, seed_nz, seed_lattice, cut, peers, split);
-  else
-    hipLaunchKernelGGL((k_packet<GRID, MODE, SIGN, false, false>), dim3(grid_blocks), dim3(64), 0, st, mesh, g,
-                       qs, perm, n_q, plane, out, err, n_packets, seed_in, seed_shift, seed_ny, seed_nz, seed_lattice, cut, peers, split);
+  if constexpr (GRID && MODE != MODE_NEAREST_NORMAL)
+    if (a.split.cnt != nullptr) return defer == 3 ? launch(no, yes, f3) : launch(no, yes, f1);
+  if constexpr (GRID)
+    if (defer == 2) return launch(no, no, f2);
+  return defer == 3 ? launch(no, no, f3) : defer ? launch(no, no, f1) : launch(no, no, f0);
 }
 // The follow-up rounds and the finish of a split grid walk (after launch_packet on the same stream).
 template <int MODE, int SIGN>
 void launch_split_rounds(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, const uint32_t* plane, float* out, int* err,
-                         const SplitCtl& split, const CutList& cut, const PeerOut* peers_in) {
-  PeerOut peers{};
-  if (peers_in) peers = *peers_in;
+                         const SplitCtl& split, const CutList& cut, const PeerOut& peers) {
   // as many single-wave workgroups as two rounds of the chip's wave slots: enough to fill it whatever the items' lengths, few enough
   // that a wave gets several items of a long list
   constexpr unsigned waves = 16384;
@@ -2291,18 +2298,44 @@ void launch_split_rounds(hipStream_t st, const DeviceMesh& mesh, const GridParam
 }
 template <bool GRID, int MODE, int SIGN>
 void launch_brute(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, const float* q, uint32_t n_q,
-                  const uint32_t* plane, float* out, int* err, uint32_t n_packets, const PeerOut* peers_in = nullptr) {
-  PeerOut peers{};
-  if (peers_in) peers = *peers_in;
+                  const uint32_t* plane, float* out, int* err, uint32_t n_packets, const PeerOut& peers = PeerOut{}) {
   hipLaunchKernelGGL((k_brute<GRID, MODE, SIGN>), dim3((n_packets + 3) / 4), dim3(256), 0, st, mesh, g, q, n_q, plane,
                      out, err, n_packets, peers);
 }
 
-uint32_t host_brick_count(const GridParams& g) {   // padded to whole super-bricks
-  const uint32_t nbx = bricks_along(g.xe - g.xb, g.bl[0]), nby = bricks_along(g.n[1], g.bl[1]), nbz = bricks_along(g.n[2], g.bl[2]);
-  const uint32_t xl = super_brick_xlog(nbx, g.xl_cap);
-  return ((nbx + (1u << xl) - 1u) >> xl) * ((nby + 7) >> 3) * ((nbz + 7) >> 3) * (64u << xl);
+// The (mode, sign) of a call as compile-time constants for a generic lambda: f(WalkForm<MODE, SIGN>{}).  The grid walks exist in three forms,
+// the query walks in four — every kernel of this file that takes <MODE, SIGN> is instantiated for these and no others (launch_brute<false>
+// alone has a fifth, SIGN_XRAY_ALL: launch_query_walk).  The Normal fold and the nearest normal carry their own sign: no planes, no rays.
+template <int M, int S>
+struct WalkForm { static constexpr int MODE = M, SIGN = S; };
+template <class F>
+void for_grid_form(int mode, bool planes, F&& f) {
+  if (mode == MODE_UNSIGNED && planes) f(WalkForm<MODE_UNSIGNED, SIGN_GRID_PLANE>{});
+  else if (mode == MODE_UNSIGNED) f(WalkForm<MODE_UNSIGNED, SIGN_NONE>{});
+  else f(WalkForm<MODE_NORMAL_FOLD, SIGN_NONE>{});
 }
+template <class F>
+void for_query_form(int mode, int sign_src, F&& f) {
+  if (mode == MODE_UNSIGNED && sign_src == SIGN_RAYS3) f(WalkForm<MODE_UNSIGNED, SIGN_RAYS3>{});
+  else if (mode == MODE_UNSIGNED) f(WalkForm<MODE_UNSIGNED, SIGN_NONE>{});
+  else if (mode == MODE_NORMAL_FOLD) f(WalkForm<MODE_NORMAL_FOLD, SIGN_NONE>{});
+  else f(WalkForm<MODE_NEAREST_NORMAL, SIGN_NONE>{});
+}
+
+// Packet bricks of the slab [g.xb, g.xe) per axis and in all: the real ones, those of the whole grid (all g.n[0] layers; the crossovers
+// that must not depend on how a caller cuts the grid into slabs count these) and the launch's — padded to whole super-bricks.
+struct BrickCounts { uint32_t nb[3]; uint64_t real, grid; uint32_t padded; };
+static bool slab_is_empty(const GridParams& g) { return g.xe <= g.xb || g.n[1] == 0 || g.n[2] == 0; }
+BrickCounts brick_counts(const GridParams& g) {
+  BrickCounts c;
+  c.nb[0] = bricks_along(g.xe - g.xb, g.bl[0]), c.nb[1] = bricks_along(g.n[1], g.bl[1]), c.nb[2] = bricks_along(g.n[2], g.bl[2]);
+  c.real = (uint64_t)c.nb[0] * c.nb[1] * c.nb[2];
+  c.grid = (uint64_t)bricks_along(g.n[0], g.bl[0]) * c.nb[1] * c.nb[2];
+  const uint32_t xl = super_brick_xlog(c.nb[0], g.xl_cap);
+  c.padded = ((c.nb[0] + (1u << xl) - 1u) >> xl) * ((c.nb[1] + 7) >> 3) * ((c.nb[2] + 7) >> 3) * (64u << xl);
+  return c;
+}
+uint32_t host_brick_count(const GridParams& g) { return brick_counts(g).padded; }
 
 }  // namespace
 
@@ -2327,8 +2360,20 @@ static GridParams coarse_level(const GridParams& fine, const uint32_t log2_strid
 }
 
 static size_t cut_blocks(const GridParams& g, uint32_t log) {
-  const uint32_t nbx = bricks_along(g.xe - g.xb, g.bl[0]), nby = bricks_along(g.n[1], g.bl[1]), nbz = bricks_along(g.n[2], g.bl[2]);
-  return (size_t)bricks_along(nbx, log) * bricks_along(nby, log) * bricks_along(nbz, log);
+  const BrickCounts bc = brick_counts(g);
+  return (size_t)bricks_along(bc.nb[0], log) * bricks_along(bc.nb[1], log) * bricks_along(bc.nb[2], log);
+}
+
+// Split walk: accumulator slots for up to SPLIT_CAP_SLOTS suspended packets, lists of SPLIT_ITEMS_PER_SLOT items per slot and round.
+// A launch of more packets than SPLIT_MAX_PACKETS is not split at all: it is hundreds of rounds of the chip's wave slots deep, its tail a
+// percent or two of it.  Below that every packet has a slot (a suspended packet can always hand over: no path back into the walk).
+constexpr uint32_t SPLIT_MAX_PACKETS = 1u << 19, SPLIT_ITEMS_PER_SLOT = 8;
+static uint32_t split_cap_slots(size_t packets) { return (uint32_t)std::min<size_t>(std::max<size_t>(packets, 64), SPLIT_MAX_PACKETS); }
+// patience, in ordinary packet times: the launch is packets / slots rounds of the chip's 8 192 wave slots deep, the flag goes up
+// when all but the last round have been handed out
+static uint32_t split_patience_q8(uint32_t packets, const Tuning& tn) {
+  const double rounds_before = std::max(1.0, (double)packets / 8192.0 - 1.0);
+  return (uint32_t)std::min(65535.0 * 256.0, 256.0 * tn.split_patience / rounds_before);
 }
 
 // Tiny problems take k_brute_split: at most 2^22 cells and cells x triangles <= 1e8 + 3000 x triangles (M2S_BRUTE_MAX overrides the
@@ -2336,46 +2381,135 @@ static size_t cut_blocks(const GridParams& g, uint32_t log) {
 // 0.34 / 0.92 ms, 20^3 0.58 / 0.96, 24^3 0.92 / 0.83; blob-100k 8^3 0.41 / 2.21, 12^3 1.08 / 2.55, 16^3 2.21 / 2.22; blob-6k 16^3 0.20 / 0.74,
 // 32^3 1.10 / 0.61 — brute force runs at 178 G point-triangle pairs per second (half the chip's fp32 issue rate), the walks of such
 // grids as long as their slowest lane's chain of dependent loads, which grows with the mesh.
-// Split walk: accumulator slots for up to SPLIT_CAP_SLOTS suspended packets, lists of SPLIT_ITEMS_PER_SLOT items per slot and round.
-// A launch of more packets than SPLIT_MAX_PACKETS is not split at all: it is hundreds of rounds of the chip's wave slots deep, its tail a
-// percent or two of it.  Below that every packet has a slot (a suspended packet can always hand over: no path back into the walk).
-constexpr uint32_t SPLIT_MAX_PACKETS = 1u << 19, SPLIT_ITEMS_PER_SLOT = 8;
-static uint32_t split_cap_slots(size_t packets) { return (uint32_t)std::min<size_t>(std::max<size_t>(packets, 64), SPLIT_MAX_PACKETS); }
-// The same conditions prepare_grid_walk applies (those it adds — lane walk, tree-less path, counters — only switch the split walk off).
-static bool split_may_run(const GridParams& g, size_t n_tris, size_t packets) {
-  const Tuning& tn = tuning();
-  if (tn.split == 0 || packets > SPLIT_MAX_PACKETS) return false;
-  if (tn.split > 0) return true;
-  const double real_bricks = (double)bricks_along(g.xe - g.xb, g.bl[0]) * bricks_along(g.n[1], g.bl[1]) * bricks_along(g.n[2], g.bl[2]);
-  const double grid_bricks = (double)bricks_along(g.n[0], g.bl[0]) * bricks_along(g.n[1], g.bl[1]) * bricks_along(g.n[2], g.bl[2]);
-  return real_bricks >= 10240.0 && n_tris >= 300000u && (double)n_tris >= 5.0 * grid_bricks;
-}
-// Nothing where the split walk cannot run (it was ~235 MB of every 256^3 call's block, ~370 MB from 2^19 packets on), the item lists by the
-// rounds in use.
-static size_t split_workspace_bytes(const GridParams& g, size_t n_tris, size_t packets) {
-  if (!split_may_run(g, n_tris, packets)) return 0;
-  const size_t cap = split_cap_slots(packets);
-  const size_t items = std::max<size_t>(cap, std::min<size_t>(cap * SPLIT_ITEMS_PER_SLOT, 1u << 20));
-  const size_t rounds = std::min(tuning().split_rounds, SPLIT_MAX_ROUNDS);
-  return 256 + SPLIT_CNT_WORDS * 4 + cap * 4 + 256 + cap * 128 * 4 + 256 + rounds * items * 16 + 256;
-}
 // Round 6 (packet groups, one-workgroup seed flood: the walks of small problems got faster), whole one-shot calls, brute / build + walk
 // (tools/exp_tiny.py, profiles/r06_tiny.txt): suzanne (968 triangles) 16^3 Raycast 0.120 / 0.125 ms, 24^3 0.151 / 0.127, Normal 24^3 0.097 / 0.132, 32^3
 // 0.136 / 0.128; blob-11k 12^3 Raycast 0.190 / 0.276, 16^3 0.323 / 0.232, Normal 16^3 0.204 / 0.231, 20^3 0.347 / 0.252; blob-100k 8^3 0.40 / 1.17,
 // 12^3 Raycast 1.05 / 0.94, Normal 0.66 / 0.93.  Brute force costs 0.08 ms + pairs / 1.9e11 per s with the Raycast planes (0.06 + pairs / 3e11 for
 // Normal), the walk 0.12 ms + 1e-5 ms per triangle: the limits below are where they cross (rounds 2 - 5: 1e8 + 3 000 per triangle for both).
-bool grid_is_tiny(const GridParams& g, size_t n_tris, int algorithm, bool raycast) {
-  if (algorithm != 0 || n_tris == 0 || g.xe <= g.xb || g.n[1] == 0 || g.n[2] == 0 || g.chunk_log < 31u) return false;
+static bool grid_is_tiny(const GridParams& g, size_t n_tris, int algorithm, bool raycast, const Tuning& tn) {
+  if (algorithm != 0 || n_tris == 0 || slab_is_empty(g) || g.chunk_log < 31u) return false;
   const double automatic = raycast ? 7.6e6 + 1.9e3 * (double)n_tris : 1.8e7 + 3.0e3 * (double)n_tris;
-  const double limit = tuning().brute_max >= 0.0 ? tuning().brute_max : automatic;
+  const double limit = tn.brute_max >= 0.0 ? tn.brute_max : automatic;
   const double cells = (double)(g.xe - g.xb) * g.n[1] * g.n[2];
   return cells <= 4194304.0 && cells * (double)n_tris <= limit;
 }
+bool grid_is_tiny(const GridParams& g, size_t n_tris, int algorithm, bool raycast) { return grid_is_tiny(g, n_tris, algorithm, raycast, tuning()); }
+
+// Which path the walk of the slab [g.xb, g.xe) takes, with every crossover of DESIGN.md §9 — the ONE place where they live.  Pure: no HIP call,
+// no arena memory, nothing read but the arguments (tests/test_capi_cpu.py pins the defaults through m2s_debug_grid_walk_choice).  `n_nodes`,
+// `leaf_max`, `counting`: the mesh's tree (0 nodes: a one-shot call built the triangle records only), its leaf size and whether it carries
+// the M2S_STATS counters.  An interleaved slab (g.chunk_log < 31) switches off the tiny path (grid_is_tiny) and the packet groups and
+// constrains the two-level cut lists: see `interleaved` below.
+GridWalkChoice choose_grid_walk(const GridParams& g, size_t n_tris, size_t n_nodes, uint32_t leaf_max, bool counting, int algorithm, const Tuning& tn) {
+  GridWalkChoice ch;
+  if (slab_is_empty(g)) return ch;
+  const BrickCounts bc = brick_counts(g);
+  const uint32_t packets = bc.padded;
+  const bool interleaved = g.chunk_log < 31u;
+  // a one-shot call that found its problem tiny built the triangle records only (no tree: n_nodes == 0); a resident mesh decides here, by the
+  // smaller (Raycast) limit: it has its tree already
+  if ((n_nodes == 0 && n_tris != 0 && algorithm == 0) || grid_is_tiny(g, n_tris, algorithm, true, tn)) {
+    ch.path = GridWalkChoice::ALL_PAIRS_SPLIT;
+    return ch;
+  }
+  const bool brute = algorithm == 1;
+  ch.seeds = grid_walk_wants_seeds(g, n_tris, algorithm);
+  // Walk flavour: bricks that each meet MANY triangles (triangles much smaller than voxels) are better served by
+  // independent per-lane walks.  Estimate: triangles per surface brick ~ T / (6 * bricks^(2/3)).
+  const int lane_env = tn.lane_walk;   // -1 auto, 0 never, 1 always
+  // measured crossover with the work-sharing lane walk (lane / packet walk, whole call, Raycast): blob-11k 32^3 0.77 / 0.86 ms, 48^3
+  // 0.80 / 0.71; blob-100k 64^3 1.71 / 2.85, 96^3 2.19 / 2.12; blob-1M 128^3 8.8 / 12.1, 256^3 32.7 / 14.3: the lane walk wins while
+  // there are more than ~8 triangles per brick.  (Round 4, with the packets' exact evaluations run densely — DeferQueue — the
+  // crossover is ~18: blob-100k 64^3, 24 per brick, 1.60 / 2.04; 80^3, 12.5, 1.79 / 1.67; blob-11k 32^3, 22, 0.73 / 0.67.)  That is the
+  // packet walk WITHOUT the split walk (below), whose launch lasts as long as its heaviest packets; where those can be split — the
+  // launch must be deeper than the chip's wave slots for that — the packets win beyond 70 triangles per brick (lane walk / packets /
+  // packets split, whole call, tools/exp_lane_vs_split.py, profiles/r04_lane_vs_split.txt): blob-100k 88^3 1.99 / 1.61 / 1.14 ms;
+  // blob-1M 96^3 (72 per brick) 5.44 / 8.41 / 4.68, 128^3 7.53 / 9.43 / 4.95, 192^3 15.1 / 8.49 / 6.39.
+  const double real_bricks = (double)bc.real, grid_bricks = (double)bc.grid;
+  const bool split_possible = !brute && n_nodes != 0 && tn.split != 0 && !counting && packets <= SPLIT_MAX_PACKETS;
+  // (automatic: a launch at least 1.25 x the chip's 8 192 wave slots deep, padding of the launch order not counted — the patience is measured from the time it takes to hand
+  // the packets out, and a launch that is resident at once has none: blob-100k 80^3, 8 000 packets, 2.33 -> 3.77 ms, blob-11k 64^3
+  // 0.54 -> 1.46)
+  // With the leaf work queued and leaves of 4 - 8 triangles on coarse grids (end of round 4) the walks are two to three times shorter and
+  // their tails with them, and the follow-up rounds' ~0.1 ms only pay on large meshes in coarse grids (walk without / with: blob-1M 112^3 2.80 /
+  // 2.55 ms, 128^3 2.72 / 2.12, 160^3 2.54 / 2.40, 192^3 3.16 / 3.06, 256^3 4.79 / 4.98; blob-100k 96^3 0.57 / 0.55, 112^3 0.59 / 0.75, 128^3
+  // 0.55 / 0.63, 160^3 0.86 / 0.80, 256^3 1.59 / 1.55; the 64-layer slabs of 512^3 x blob-1M 2.44 ... 2.99 / 2.57 ... 2.89): automatic from
+  // 300 000 triangles and 5 per brick of the whole grid on.
+  const bool split_auto = split_possible && tn.split < 0 && real_bricks >= 10240.0 && n_tris >= 300000u && (double)n_tris >= 5.0 * grid_bricks;
+  const double lane_ratio = split_auto ? tn.lane_ratio_split : tn.lane_ratio;
+  // (a tree with larger leaves — a one-shot call over a coarse grid, grid_leaf_max — is built for the packets: blob-100k 32^3, 195 triangles per
+  // brick, lane walk over leaves of 2 / packets over leaves of 8: 1.68 / 1.67 ms, 48^3 1.74 / 1.18; blob-1M 48^3 5.23 / 4.83, 80^3 5.41 / 4.62)
+  const bool lane_walk = !brute && n_tris && (lane_env >= 0 ? lane_env == 1 : (leaf_max <= 2u && (double)n_tris > lane_ratio * real_bricks));
+  // cut lists: the top of the tree is walked once per block of 2^log bricks per axis (k_cut)
+  // k_cut costs about 0.25 us per brick plus a latency floor of ~0.1 ms; measured crossover (blob-100k / blob-6k,
+  // tools/exp_cutmin.py): 192^3 = 110 592 packets loses 0.1-0.2 ms with the lists, 256^3 = 262 144 packets breaks even or
+  // gains, 512^3 gains 1.3 ms.  The tests lower it to cover small grids.
+  // (asynchronous calls are the pieces of a caller who pipelines them on two streams: k_cut then runs under the previous
+  // piece's walk and pays from about half that size)
+  const uint32_t cut_min_packets = tn.cut_min_packets;   // 100 000 (round 2: 200 000 for synchronous calls; re-measured with the 64-byte lists: 224^3 2.88 -> 2.75 ms, 192^3 2.41 -> 2.38, 160^3 2.04 -> 2.07)
+  if (!brute && !lane_walk && ch.seeds && packets >= cut_min_packets) {
+    // two levels (k_cut LEVEL 1 + 2; M2S_CUT_COARSE: -1 automatic, 0 never, 1 always).  The coarse launch is waves / 8 waves of its own whose longest
+    // chain (the subtree next to its region, up to the visit cap) is ~0.14 ms whatever the grid: 1024^3 (262 144 fine waves) seed + cut 5.98 -> 4.9 ms and
+    // the call 83.2 -> 81.9 ms (sheet-100k, Normal) / 40.8 -> 39.9 (blob-100k); 512^3 (32 768) 0.72 -> 0.67 + 0.14 ms with a walk 0.08 ms shorter — a wash;
+    // a 64-layer slab of 512^3 (4 096) 0.20 -> 0.34 ms.  Automatic from M2S_CUT_COARSE_MIN_WAVES = 40 000 fine waves on (profiles/r06_cut_coarse.txt; the
+    // tests force it on small grids).  A block must lie inside one chunk of an interleaved slab.  (The seed lattice has one point per brick — shift 0
+    // —, which the coarse level relies on.)
+    const int cc = tn.cut_coarse;
+    const size_t waves = cut_blocks(g, 2);   // blocks of 4 x 4 x 4 bricks = fine waves
+    const bool blocks_ok = !interleaved || g.chunk_log >= g.bl[0] + 2u;
+    const bool two_level = blocks_ok && (cc > 0 || (cc < 0 && waves >= tn.cut_coarse_min_waves));
+    ch.cut_levels = two_level ? 2 : 1;
+  }
+  // packet groups (k_packet_group; M2S_GROUP: -1 automatic, 0 never, 1 always): launches of at most M2S_GROUP_MAX_PACKETS packets without
+  // cut lists where the bricks meet several triangles each (the chains are long there: 64^3 ... 128^3 over 100 k triangles)
+  const int gk = tn.group;
+  // (not where the split walk is the automatic choice — large meshes in launches deeper than the chip: blob-1M 96^3 Raycast 1.88 ms split, 2.48 in groups)
+  const bool can = !brute && !lane_walk && ch.cut_levels == 0 && n_nodes != 0 && !counting && tn.split <= 0 && !split_auto && tn.defer < 0 && !interleaved;
+  const bool want = gk > 0 || (gk < 0 && (double)n_tris >= tn.group_min_ratio * real_bricks);
+  if (can && want) {
+    // as many waves per packet (a power of two, four at most) as keep the launch within M2S_GROUP_TARGET_WAVES waves
+    uint32_t w = 1;
+    while (w < GROUP_MAX_WAVES && (double)(2u * w) * real_bricks <= (double)tn.group_target_waves) w *= 2;
+    if (gk > 0 && w < 2u) w = GROUP_MAX_WAVES;                      // forced (tests)
+    if (w >= 2u) ch.group_waves = w;
+  }
+  // split walk (packet walk only; M2S_SPLIT: -1 / 1 on, 0 off, 2 on with the flags raised from the start)
+  // Where it pays (tools/exp_split.py, exp_split_rank.py; walk with / without): the stragglers are the packets deep inside a body
+  // whose voxels see many triangles at (nearly) the same distance, and they weigh the more the finer the mesh is against the grid —
+  // blob-100k in 96^3 ... 192^3 1.79 -> 1.07, 1.57 -> 1.28, 1.81 -> 1.63 ms, in 256^3 2.25 -> 2.34 (a wash), the 64-layer slabs of
+  // 512^3 1.21 -> 1.26 (a loss: no tail to speak of, three more launches); blob-1M in 256^3 12.8 -> 9.5 ms, its slowest 8-GPU slab of
+  // 512^3 5.05 -> 4.05, its fastest 3.14 -> 3.16.  Automatic: split_auto above (>= 300 000 triangles, >= 5 per packet brick of the WHOLE grid, >= 10 240 bricks).
+  ch.split = !lane_walk && split_possible && ch.group_waves == 0 && (tn.split > 0 || split_auto);
+  ch.split_forced = ch.split && tn.split == 2;
+  // The packet walk's leaf work (DeferQueue; M2S_DEFER forces a form): 0 wave-wide at once, 1 the exact evaluations queued per (voxel, triangle) pair,
+  // 2: queued, but at once where most of the wave is reached (grids much finer than the mesh: see DEFER_DIRECT_LANES),
+  // 3: the pre-tests queued too (defer_pretest) — from 0.045 triangles per brick on: walk, queued evaluations / + queued pre-tests, blob-100k
+  // 128^3 1.02 / 0.83 ms, 256^3 1.74 / 1.48, 512^3 (0.048 per brick) 6.85 / 6.54, 768^3 (0.014) 16.9 / 17.7; blob-1M 512^3 21.9 / 18.2; blob-11k
+  // 256^3 (0.04) 0.60 / 0.63; sheet-100k 512^3 (0.05) 13.2 / 12.0.  (Both forms of pre-test in one kernel, chosen per leaf by the number of lanes that
+  // want it, cost the dense regime what they gained the sparse one: 128^3 0.83 -> 0.92, 768^3 17.7 -> 16.9.)
+  ch.defer = tn.defer == 0 ? 0 : tn.defer > 0 ? tn.defer : ((double)n_tris < 0.02 * grid_bricks ? 2 : (double)n_tris < 0.045 * grid_bricks ? 1 : 3);
+  ch.path = lane_walk ? GridWalkChoice::LANE : ch.group_waves ? GridWalkChoice::GROUP : brute ? GridWalkChoice::ALL_PAIRS : GridWalkChoice::PACKET;
+  return ch;
+}
+// What a call knows before its mesh exists (it sizes its workspace block then): the most permissive mesh — a tree, leaves too large for the lane
+// walk, no counters.  Whatever choose_grid_walk splits for a real mesh over (g, n_tris), this splits too (tests/test_capi_cpu.py sweeps it).
+GridWalkChoice choose_grid_walk_for_sizing(const GridParams& g, size_t n_tris) { return choose_grid_walk(g, n_tris, 1, ~0u, false, 0, tuning()); }
+
+// Nothing where the split walk cannot run (it was ~235 MB of every 256^3 call's block, ~370 MB from 2^19 packets on), the item lists by the
+// rounds in use.
+static size_t split_workspace_bytes(const GridParams& g, size_t n_tris, size_t packets) {
+  if (!choose_grid_walk_for_sizing(g, n_tris).split) return 0;
+  const size_t cap = split_cap_slots(packets);
+  const size_t items = std::max<size_t>(cap, std::min<size_t>(cap * SPLIT_ITEMS_PER_SLOT, 1u << 20));
+  const size_t rounds = std::min(tuning().split_rounds, SPLIT_MAX_ROUNDS);
+  return 256 + SPLIT_CNT_WORDS * 4 + cap * 4 + 256 + cap * 128 * 4 + 256 + rounds * items * 16 + 256;
+}
 size_t grid_distance_workspace_bytes(const GridParams& g, size_t n_tris) {
-  const size_t bricks = (size_t)host_brick_count(g);
+  const BrickCounts bc = brick_counts(g);
+  const size_t bricks = (size_t)bc.padded;
   if ((double)(g.xe - g.xb) * g.n[1] * g.n[2] <= 4194304.0)   // room for k_brute_split's per-voxel words
     return bricks * 44 + bricks + 16384 + cut_blocks(g, 0) * CUT_WORDS * 4 + cut_blocks(g, 2) * CUTC_S * CUTC_WORDS * 4 + 512 + TOP_SUBTREES * 8 + 256 + bricks * 64 * 8 + 4096 + split_workspace_bytes(g, n_tris, bricks);
-  const size_t trail_counters = (size_t)bricks_along(g.xe - g.xb, g.bl[0]) * (bricks_along(g.n[1], g.bl[1]) + 1) * 4;   // M2S_PEER_TRAIL progress
+  const size_t trail_counters = (size_t)bc.nb[0] * (bc.nb[1] + 1) * 4;   // M2S_PEER_TRAIL progress
   return bricks * 44 + bricks + 16384 + cut_blocks(g, 0) * CUT_WORDS * 4 + cut_blocks(g, 2) * CUTC_S * CUTC_WORDS * 4 + 512 + TOP_SUBTREES * 8 + 256 + trail_counters + 1024 + split_workspace_bytes(g, n_tris, bricks);   // seeds + cut lists (one per brick) + split walk
 }
 
@@ -2386,12 +2520,8 @@ __global__ __launch_bounds__(256) void k_seed_remap(uint32_t* __restrict__ ids, 
   ids[i] = t < n_tris ? slot_of[t] : 0xffffffffu;
 }
 
-uint32_t host_packet_bricks(const GridParams& g) { return (g.xe <= g.xb || g.n[1] == 0 || g.n[2] == 0) ? 0u : host_brick_count(g); }
-
-bool grid_walk_wants_seeds(const GridParams& g, size_t n_tris, int algorithm) {
-  if (g.xe <= g.xb || g.n[1] == 0 || g.n[2] == 0) return false;
-  return algorithm != 1 && n_tris && host_brick_count(g) >= 8;
-}
+uint32_t host_packet_bricks(const GridParams& g) { return slab_is_empty(g) ? 0u : host_brick_count(g); }
+bool grid_walk_wants_seeds(const GridParams& g, size_t n_tris, int algorithm) { return algorithm != 1 && n_tris && host_packet_bricks(g) >= 8; }
 
 // Seeding: every 4^3 brick starts its walk from a triangle near its own centre (jump flooding over the lattice of brick
 // centres); that halves the nodes visited compared with a greedy descent.  `cen` are the triangle centroids the ids of
@@ -2413,21 +2543,14 @@ int launch_grid_seeds(Arena& ws, hipStream_t st, const float4* cen, uint32_t n_t
   const unsigned nb1 = (unsigned)((points1 + 255) / 256);
   if (points1 <= JFA_SMALL_MAX) {                               // the whole flood in one workgroup
     hipLaunchKernelGGL(k_jfa_small, dim3(1), dim3(JFA_SMALL_THREADS), 0, st, mesh, g1, ids);
-    out->ids = ids;
-    out->ny = g1.n[1];
-    out->nz = g1.n[2];
-    out->points = points1;
-    out->shift = seed_shift;
-    return 0;
-  }
-  M2S_HIP_CHECK(hipMemsetAsync(keys, 0xff, points1 * 8, st));
-  hipLaunchKernelGGL(k_jfa_splat, dim3((mesh.n_tris + 255) / 256), dim3(256), 0, st, mesh, g1, nullptr, keys);
-  // (Round 6, measured and not kept: the flood's long steps on a lattice of half the resolution + a refinement pass — the seeds get worse by
-  // a few hundredths of a cell far from the surface, where a packet's candidate set grows with the square root of exactly that: the
-  // headline walk 6.44 -> 7.00 ms with every step but the last two at half resolution, 6.76 -> 7.16 with only the steps >= 16 there;
-  // profiles/r06_seed_coarse_*.txt.  A bound from the lanes' FINAL minima would take 1.5 % of the node tests, 12 % of the pre-tests and
-  // 18 % of the exact evaluations: profiles/r06_stats2_headline.txt.)
-  {
+  } else {
+    M2S_HIP_CHECK(hipMemsetAsync(keys, 0xff, points1 * 8, st));
+    hipLaunchKernelGGL(k_jfa_splat, dim3((mesh.n_tris + 255) / 256), dim3(256), 0, st, mesh, g1, nullptr, keys);
+    // (Round 6, measured and not kept: the flood's long steps on a lattice of half the resolution + a refinement pass — the seeds get worse by
+    // a few hundredths of a cell far from the surface, where a packet's candidate set grows with the square root of exactly that: the
+    // headline walk 6.44 -> 7.00 ms with every step but the last two at half resolution, 6.76 -> 7.16 with only the steps >= 16 there;
+    // profiles/r06_seed_coarse_*.txt.  A bound from the lanes' FINAL minima would take 1.5 % of the node tests, 12 % of the pre-tests and
+    // 18 % of the exact evaluations: profiles/r06_stats2_headline.txt.)
     const uint32_t maxdim = max(g1.n[0], max(g1.n[1], g1.n[2]));
     hipLaunchKernelGGL(k_jfa_load, dim3(nb1), dim3(256), 0, st, mesh, keys, points1, la);
     int step = 1;
@@ -2439,8 +2562,7 @@ int launch_grid_seeds(Arena& ws, hipStream_t st, const float4* cen, uint32_t n_t
     }
     launch_jfa_pass(st, g1, src, dst, 1, ids);   // "JFA+1": one more unit pass; leaves the ids
   }
-  uint32_t* dst_ids = ids;
-  out->ids = dst_ids;
+  out->ids = ids;
   out->ny = g1.n[1];
   out->nz = g1.n[2];
   out->points = points1;
@@ -2448,25 +2570,37 @@ int launch_grid_seeds(Arena& ws, hipStream_t st, const float4* cen, uint32_t n_t
   return 0;
 }
 
-// Seeds and cut lists for the slab [g.xb, g.xe) (everything a walk needs besides the mesh); `launch_grid_walk` then
-// walks the slab, or any x-piece of it that starts on a block boundary.  `raw_seeds` (optional): a seed lattice computed
-// from the input-order centroids while the mesh was being built; its ids are translated to sorted slots here.
+// What k_cut is launched with, for grids and for queries.
+struct CutParams { float emit_near, emit_far; uint32_t budget, wave_cap; };   // emission radius of a list entry: emit_near brick radii next to the surface, emit_far of the distance far from it
+static CutParams cut_params(uint32_t n_tris, const Tuning& tn) {
+  // A wave that has visited wave_cap nodes lets its bricks emit whatever they meet next: the long union walks of the
+  // regions with many near-ties (deep inside a round body) are the tail of the launch — on the 64-layer slab of an 8-GPU
+  // rank, 4 waves per SIMD, they WERE its duration (0.39 -> 0.19 ms; 512^3: flat between 300 and 450, 200 costs the
+  // packets 0.5 ms) — and what they still decide so deep in the tree the packets decide almost as cheaply.
+  uint32_t depth = 1;
+  while ((1ull << depth) < (unsigned long long)n_tris + 1ull) ++depth;
+  // (emit_far 1/32: re-tuned at the end of round 3 (1/16 before): headline 9.19 -> 9.11 ms, 1024^3 x sheet-100k 92.95 -> 89.33 ms)
+  return {tn.cut_near, tn.cut_far, 100000u, tn.cut_wave_cap ? tn.cut_wave_cap : std::max(120u, 20u * depth)};
+}
+
+// Seeds and cut lists for the slab [g.xb, g.xe) (everything a walk needs besides the mesh) — what choose_grid_walk says the walk takes;
+// `launch_grid_walk` then walks the slab, or any x-piece of it that starts on a block boundary.  `raw_seeds` (optional): a seed lattice
+// computed from the input-order centroids while the mesh was being built; its ids are translated to sorted slots here.
 int prepare_grid_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const GridParams& g, int algorithm, bool pipelined,
                       GridWalkPlan* plan, const SeedLattice* raw_seeds) {
   *plan = GridWalkPlan{};
-  if (g.xe <= g.xb || g.n[1] == 0 || g.n[2] == 0) return 0;
-  const uint32_t packets = host_brick_count(g);
-  // a one-shot call that found its problem tiny built the triangle records only (no tree: n_nodes == 0); a resident mesh decides here, by the
-  // smaller (Raycast) limit: it has its tree already
-  if ((mesh.n_nodes == 0 && mesh.n_tris != 0 && algorithm == 0) || grid_is_tiny(g, mesh.n_tris, algorithm, true)) {
+  const Tuning& tn = tuning();
+  const GridWalkChoice ch = choose_grid_walk(g, mesh.n_tris, mesh.n_nodes, mesh.leaf_max, mesh.stats != nullptr, algorithm, tn);
+  plan->choice = ch;
+  if (ch.path == GridWalkChoice::NOTHING) return 0;
+  const BrickCounts bc = brick_counts(g);
+  const uint32_t packets = bc.padded;
+  if (ch.path == GridWalkChoice::ALL_PAIRS_SPLIT) {
     plan->brute_acc = ws.take<uint32_t>((size_t)packets * 64 * 2);
     if (!plan->brute_acc) { set_error("internal: brute-force workspace too small"); return M2S_ERR_HIP_INTERNAL; }
     return 0;
   }
-  const bool brute = algorithm == 1;
-  const uint32_t* seed1 = nullptr;
-  uint32_t sh1 = 0, s1ny = 0, s1nz = 0;
-  if (grid_walk_wants_seeds(g, mesh.n_tris, algorithm)) {
+  if (ch.seeds) {
     SeedLattice lat;
     if (raw_seeds && raw_seeds->ids) {
       lat = *raw_seeds;
@@ -2475,118 +2609,37 @@ int prepare_grid_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const G
       const int rc = launch_grid_seeds(ws, st, mesh.cen, mesh.n_tris, g, &lat);
       if (rc) return rc;
     }
-    seed1 = lat.ids;
-    s1ny = lat.ny;
-    s1nz = lat.nz;
-    sh1 = lat.shift;
+    plan->seeds = lat.ids; plan->seed_shift = lat.shift; plan->seed_ny = lat.ny; plan->seed_nz = lat.nz;
   }
-  // Walk flavour: bricks that each meet MANY triangles (triangles much smaller than voxels) are better served by
-  // independent per-lane walks.  Estimate: triangles per surface brick ~ T / (6 * bricks^(2/3)).
-  const int lane_env = tuning().lane_walk;   // -1 auto, 0 never, 1 always
-  // measured crossover with the work-sharing lane walk (lane / packet walk, whole call, Raycast): blob-11k 32^3 0.77 / 0.86 ms, 48^3
-  // 0.80 / 0.71; blob-100k 64^3 1.71 / 2.85, 96^3 2.19 / 2.12; blob-1M 128^3 8.8 / 12.1, 256^3 32.7 / 14.3: the lane walk wins while
-  // there are more than ~8 triangles per brick.  (Round 4, with the packets' exact evaluations run densely — DeferQueue — the
-  // crossover is ~18: blob-100k 64^3, 24 per brick, 1.60 / 2.04; 80^3, 12.5, 1.79 / 1.67; blob-11k 32^3, 22, 0.73 / 0.67.)  That is the
-  // packet walk WITHOUT the split walk (below), whose launch lasts as long as its heaviest packets; where those can be split — the
-  // launch must be deeper than the chip's wave slots for that — the packets win beyond 70 triangles per brick (lane walk / packets /
-  // packets split, whole call, tools/exp_lane_vs_split.py, profiles/r04_lane_vs_split.txt): blob-100k 88^3 1.99 / 1.61 / 1.14 ms;
-  // blob-1M 96^3 (72 per brick) 5.44 / 8.41 / 4.68, 128^3 7.53 / 9.43 / 4.95, 192^3 15.1 / 8.49 / 6.39.
-  const Tuning& tn = tuning();
-  const double real_bricks = (double)bricks_along(g.xe - g.xb, g.bl[0]) * bricks_along(g.n[1], g.bl[1]) * bricks_along(g.n[2], g.bl[2]);
-  const double grid_bricks = (double)bricks_along(g.n[0], g.bl[0]) * bricks_along(g.n[1], g.bl[1]) * bricks_along(g.n[2], g.bl[2]);
-  const bool split_possible = !brute && mesh.n_nodes != 0 && tn.split != 0 && mesh.stats == nullptr && packets <= SPLIT_MAX_PACKETS;
-  // (automatic: a launch at least 1.25 x the chip's 8 192 wave slots deep, padding of the launch order not counted — the patience is measured from the time it takes to hand
-  // the packets out, and a launch that is resident at once has none: blob-100k 80^3, 8 000 packets, 2.33 -> 3.77 ms, blob-11k 64^3
-  // 0.54 -> 1.46)
-  // With the leaf work queued and leaves of 4 - 8 triangles on coarse grids (end of round 4) the walks are two to three times shorter and
-  // their tails with them, and the follow-up rounds' ~0.1 ms only pay on large meshes in coarse grids (walk without / with: blob-1M 112^3 2.80 /
-  // 2.55 ms, 128^3 2.72 / 2.12, 160^3 2.54 / 2.40, 192^3 3.16 / 3.06, 256^3 4.79 / 4.98; blob-100k 96^3 0.57 / 0.55, 112^3 0.59 / 0.75, 128^3
-  // 0.55 / 0.63, 160^3 0.86 / 0.80, 256^3 1.59 / 1.55; the 64-layer slabs of 512^3 x blob-1M 2.44 ... 2.99 / 2.57 ... 2.89): automatic from
-  // 300 000 triangles and 5 per brick of the whole grid on.
-  const bool split_auto = split_possible && tn.split < 0 && real_bricks >= 10240.0 && mesh.n_tris >= 300000u && (double)mesh.n_tris >= 5.0 * grid_bricks;
-  const double lane_ratio = split_auto ? tn.lane_ratio_split : tn.lane_ratio;
-  // (a tree with larger leaves — a one-shot call over a coarse grid, grid_leaf_max — is built for the packets: blob-100k 32^3, 195 triangles per
-  // brick, lane walk over leaves of 2 / packets over leaves of 8: 1.68 / 1.67 ms, 48^3 1.74 / 1.18; blob-1M 48^3 5.23 / 4.83, 80^3 5.41 / 4.62)
-  const bool lane_walk = !brute && mesh.n_tris && (lane_env >= 0 ? lane_env == 1 : (mesh.leaf_max <= 2u && (double)mesh.n_tris > lane_ratio * real_bricks));
-  // cut lists: the top of the tree is walked once per block of 2^log bricks per axis (k_cut)
-  CutList cut = {nullptr, 0, 0, 0, 0, nullptr};
-  // k_cut costs about 0.25 us per brick plus a latency floor of ~0.1 ms; measured crossover (blob-100k / blob-6k,
-  // tools/exp_cutmin.py): 192^3 = 110 592 packets loses 0.1-0.2 ms with the lists, 256^3 = 262 144 packets breaks even or
-  // gains, 512^3 gains 1.3 ms.  The tests lower it to cover small grids.
-  // (asynchronous calls are the pieces of a caller who pipelines them on two streams: k_cut then runs under the previous
-  // piece's walk and pays from about half that size)
-  const uint32_t cut_min_packets = tuning().cut_min_packets;   // 100 000 (round 2: 200 000 for synchronous calls; re-measured with the 64-byte lists: 224^3 2.88 -> 2.75 ms, 192^3 2.41 -> 2.38, 160^3 2.04 -> 2.07)
-  if (!brute && !lane_walk && seed1 != nullptr && packets >= cut_min_packets) {
-    // emission radius of a list entry: emit_near brick radii next to the surface, emit_far of the distance far from it
-    const float emit_near = tuning().cut_near;
-    const float emit_far = tuning().cut_far;   // 1/32: re-tuned at the end of round 3 (1/16 before): headline 9.19 -> 9.11 ms, 1024^3 x sheet-100k 92.95 -> 89.33 ms
-    // A wave that has visited this many nodes lets its bricks emit whatever they meet next: the long union walks of the
-    // regions with many near-ties (deep inside a round body) are the tail of the launch — on the 64-layer slab of an 8-GPU
-    // rank, 4 waves per SIMD, they WERE its duration (0.39 -> 0.19 ms; 512^3: flat between 300 and 450, 200 costs the
-    // packets 0.5 ms) — and what they still decide so deep in the tree the packets decide almost as cheaply.
-    uint32_t depth = 1;
-    while ((1ull << depth) < (unsigned long long)mesh.n_tris + 1ull) ++depth;
-    const uint32_t wave_cap = tuning().cut_wave_cap ? tuning().cut_wave_cap : std::max(120u, 20u * depth);
-    const uint32_t budget = 100000u;
-    const uint32_t nbx = bricks_along(g.xe - g.xb, g.bl[0]), nby = bricks_along(g.n[1], g.bl[1]), nbz = bricks_along(g.n[2], g.bl[2]);
-    const size_t bricks = (size_t)nbx * nby * nbz;
-    uint32_t* lists = ws.take<uint32_t>(bricks * CUT_WORDS);
+  if (ch.cut_levels) {   // the top of the tree is walked once per block of 4 x 4 x 4 bricks (k_cut), in one level or two
+    const CutParams cp = cut_params(mesh.n_tris, tn);
+    const uint32_t nbx = bc.nb[0], nby = bc.nb[1], nbz = bc.nb[2], sh1 = plan->seed_shift, s1ny = plan->seed_ny, s1nz = plan->seed_nz;
+    const uint32_t* seed1 = plan->seeds;
+    uint32_t* lists = ws.take<uint32_t>((size_t)bc.real * CUT_WORDS);
     if (!lists) { set_error("internal: cut-list workspace too small"); return M2S_ERR_HIP_INTERNAL; }
     const uint32_t cbx = bricks_along(nbx, 2), cby = bricks_along(nby, 2), cbz = bricks_along(nbz, 2);   // blocks of 4 x 4 x 4 bricks = fine waves
-    const size_t waves = (size_t)cbx * cby * cbz;
-    // two levels (k_cut LEVEL 1 + 2; M2S_CUT_COARSE: -1 automatic, 0 never, 1 always).  The coarse launch is waves / 8 waves of its own whose longest
-    // chain (the subtree next to its region, up to the visit cap) is ~0.14 ms whatever the grid: 1024^3 (262 144 fine waves) seed + cut 5.98 -> 4.9 ms and
-    // the call 83.2 -> 81.9 ms (sheet-100k, Normal) / 40.8 -> 39.9 (blob-100k); 512^3 (32 768) 0.72 -> 0.67 + 0.14 ms with a walk 0.08 ms shorter — a wash;
-    // a 64-layer slab of 512^3 (4 096) 0.20 -> 0.34 ms.  Automatic from M2S_CUT_COARSE_MIN_WAVES = 40 000 fine waves on (profiles/r06_cut_coarse.txt; the
-    // tests force it on small grids).  A block must lie inside one chunk of an interleaved slab.
-    const int cc = tuning().cut_coarse;
-    const bool blocks_ok = sh1 == 0u && (g.chunk_log >= 31u || g.chunk_log >= g.bl[0] + 2u);
-    const bool two_level = blocks_ok && (cc > 0 || (cc < 0 && waves >= tuning().cut_coarse_min_waves));
-    if (two_level) {
+    const size_t waves = cut_blocks(g, 2);
+    if (ch.cut_levels == 2) {
       uint32_t* coarse = ws.take<uint32_t>(waves * CUTC_S * CUTC_WORDS);
       if (!coarse) { set_error("internal: cut-list workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-      const size_t groups = (size_t)bricks_along(cbx, 2) * bricks_along(cby, 2) * bricks_along(cbz, 2);
-      const uint32_t coarse_cap = tuning().cut_coarse_cap ? tuning().cut_coarse_cap : wave_cap;
-      hipLaunchKernelGGL((k_cut<true, 1>), dim3((unsigned)(groups * CUTC_S)), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, cbx, cby, cbz, coarse, 1.0f, emit_far, budget,
+      const size_t groups = cut_blocks(g, 4);   // 4 x 4 x 4 blocks
+      const uint32_t coarse_cap = tn.cut_coarse_cap ? tn.cut_coarse_cap : cp.wave_cap;
+      hipLaunchKernelGGL((k_cut<true, 1>), dim3((unsigned)(groups * CUTC_S)), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, cbx, cby, cbz, coarse, 1.0f, cp.emit_far, cp.budget,
                          coarse_cap, (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, (const uint32_t*)nullptr);
-      hipLaunchKernelGGL((k_cut<true, 2>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, emit_near, emit_far, budget, wave_cap,
+      hipLaunchKernelGGL((k_cut<true, 2>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap,
                          (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, (const uint32_t*)coarse);
     } else
-    hipLaunchKernelGGL((k_cut<true, 0>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, emit_near, emit_far, budget, wave_cap,
+    hipLaunchKernelGGL((k_cut<true, 0>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap,
                        (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, (const uint32_t*)nullptr);
-    cut = {lists, 0, nby, nbz, 0, nullptr};
+    plan->cut_lists = lists; plan->cut_log = 0; plan->cut_ny = nby; plan->cut_nz = nbz;
   }
-  // packet groups (k_packet_group; M2S_GROUP: -1 automatic, 0 never, 1 always): launches of at most M2S_GROUP_MAX_PACKETS packets without
-  // cut lists where the bricks meet several triangles each (the chains are long there: 64^3 ... 128^3 over 100 k triangles)
-  {
-    const int gk = tn.group;
-    // (not where the split walk is the automatic choice — large meshes in launches deeper than the chip: blob-1M 96^3 Raycast 1.88 ms split, 2.48 in groups)
-    const bool can = !brute && !lane_walk && cut.lists == nullptr && mesh.n_nodes != 0 && mesh.stats == nullptr && tn.split <= 0 && !split_auto && tn.defer < 0 && g.chunk_log >= 31u;
-    const bool want = gk > 0 || (gk < 0 && (double)mesh.n_tris >= tn.group_min_ratio * real_bricks);
-    if (can && want) {
-      // as many waves per packet (a power of two, four at most) as keep the launch within M2S_GROUP_TARGET_WAVES waves
-      uint32_t w = 1;
-      while (w < GROUP_MAX_WAVES && (double)(2u * w) * real_bricks <= (double)tn.group_target_waves) w *= 2;
-      if (gk > 0 && w < 2u) w = GROUP_MAX_WAVES;                      // forced (tests)
-      if (w >= 2u) {
-        uint2* top = ws.take<uint2>(TOP_SUBTREES);
-        if (!top) { set_error("internal: workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-        hipLaunchKernelGGL(k_tree_top, dim3(1), dim3(TOP_SUBTREES), 0, st, mesh, top);
-        plan->group_top = top;
-        plan->group_waves = w;
-      }
-    }
+  if (ch.path == GridWalkChoice::GROUP) {
+    uint2* top = ws.take<uint2>(TOP_SUBTREES);
+    if (!top) { set_error("internal: workspace too small"); return M2S_ERR_HIP_INTERNAL; }
+    hipLaunchKernelGGL(k_tree_top, dim3(1), dim3(TOP_SUBTREES), 0, st, mesh, top);
+    plan->group_top = top;
   }
-  plan->seeds = seed1; plan->seed_shift = sh1; plan->seed_ny = s1ny; plan->seed_nz = s1nz;
-  plan->cut_lists = cut.lists; plan->cut_log = cut.log; plan->cut_ny = cut.ny; plan->cut_nz = cut.nz;
-  plan->lane_walk = lane_walk;
-  // split walk (packet walk only; M2S_SPLIT: -1 / 1 on, 0 off, 2 on with the flags raised from the start)
-  // Where it pays (tools/exp_split.py, exp_split_rank.py; walk with / without): the stragglers are the packets deep inside a body
-  // whose voxels see many triangles at (nearly) the same distance, and they weigh the more the finer the mesh is against the grid —
-  // blob-100k in 96^3 ... 192^3 1.79 -> 1.07, 1.57 -> 1.28, 1.81 -> 1.63 ms, in 256^3 2.25 -> 2.34 (a wash), the 64-layer slabs of
-  // 512^3 1.21 -> 1.26 (a loss: no tail to speak of, three more launches); blob-1M in 256^3 12.8 -> 9.5 ms, its slowest 8-GPU slab of
-  // 512^3 5.05 -> 4.05, its fastest 3.14 -> 3.16.  Automatic: split_auto above (>= 300 000 triangles, >= 5 per packet brick of the WHOLE grid, >= 10 240 bricks).
-  if (!lane_walk && split_possible && plan->group_top == nullptr && (tn.split > 0 || split_auto)) {
+  if (ch.split) {
     SplitCtl sc;
     sc.cap_slots = split_cap_slots(packets);
     sc.cap_items = std::max(sc.cap_slots, std::min(sc.cap_slots * SPLIT_ITEMS_PER_SLOT, 1u << 20));
@@ -2594,26 +2647,15 @@ int prepare_grid_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const G
     sc.emit_min = std::max(2u, tn.split_min_records) * (uint32_t)sizeof(NodeExt);
     sc.emit_max = std::max(std::max(2u, tn.split_min_records), tn.split_max_records) * (uint32_t)sizeof(NodeExt);
     sc.grace = tn.split_budget ? tn.split_budget : 128u;
-    sc.idle_below = tn.split == 2 ? 1u : 0u;                               // forced (tests): every stamp is time 0 — all flags up, no patience
-    // patience, in ordinary packet times: the launch is packets / slots rounds of the chip's 8 192 wave slots deep, the flag goes up
-    // when all but the last round have been handed out
-    const double rounds_before = std::max(1.0, (double)packets / 8192.0 - 1.0);
-    sc.patience_q8 = (uint32_t)std::min(65535.0 * 256.0, 256.0 * tn.split_patience / rounds_before);
+    sc.idle_below = ch.split_forced ? 1u : 0u;                             // forced (tests): every stamp is time 0 — all flags up, no patience
+    sc.patience_q8 = split_patience_q8(packets, tn);
     sc.cnt = ws.take<uint32_t>(SPLIT_CNT_WORDS);
     sc.slot_packet = ws.take<uint32_t>(sc.cap_slots);
     sc.acc = ws.take<uint32_t>((size_t)sc.cap_slots * 128);
     sc.items = ws.take<uint4>((size_t)sc.rounds * sc.cap_items);
     if (!sc.cnt || !sc.slot_packet || !sc.acc || !sc.items) { set_error("internal: split-walk workspace too small"); return M2S_ERR_HIP_INTERNAL; }
     plan->split = sc;
-    plan->split_forced = tn.split == 2;
   }
-  // The packet walk's leaf work (DeferQueue; M2S_DEFER forces a form): 0 wave-wide at once, 1 the exact evaluations queued per (voxel, triangle) pair,
-  // 2: queued, but at once where most of the wave is reached (grids much finer than the mesh: see DEFER_DIRECT_LANES),
-  // 3: the pre-tests queued too (defer_pretest) — from 0.045 triangles per brick on: walk, queued evaluations / + queued pre-tests, blob-100k
-  // 128^3 1.02 / 0.83 ms, 256^3 1.74 / 1.48, 512^3 (0.048 per brick) 6.85 / 6.54, 768^3 (0.014) 16.9 / 17.7; blob-1M 512^3 21.9 / 18.2; blob-11k
-  // 256^3 (0.04) 0.60 / 0.63; sheet-100k 512^3 (0.05) 13.2 / 12.0.  (Both forms of pre-test in one kernel, chosen per leaf by the number of lanes that
-  // want it, cost the dense regime what they gained the sparse one: 128^3 0.83 -> 0.92, 768^3 17.7 -> 16.9.)
-  plan->defer = tn.defer == 0 ? 0 : tn.defer > 0 ? tn.defer : ((double)mesh.n_tris < 0.02 * grid_bricks ? 2 : (double)mesh.n_tris < 0.045 * grid_bricks ? 1 : 3);
   return 0;
 }
 
@@ -2650,96 +2692,70 @@ int launch_push_trailing(hipStream_t st, const float* src, const PeerOut& peers,
 }
 
 int launch_grid_walk(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, int mode, const uint32_t* d_inside_plane,
-                     int algorithm, const GridWalkPlan& plan, uint32_t bx_off, float* d_out, int* d_err, const PeerOut* peers) {
-  if (g.xe <= g.xb || g.n[1] == 0 || g.n[2] == 0) return 0;
+                     const GridWalkPlan& plan, uint32_t bx_off, float* d_out, int* d_err, const PeerOut* peers) {
+  const GridWalkChoice& ch = plan.choice;
+  if (slab_is_empty(g) || ch.path == GridWalkChoice::NOTHING) return 0;
   PeerOut pz{};
   if (peers) pz = *peers;
-  const uint32_t packets = host_brick_count(g);
-  const bool brute = algorithm == 1;
-  const uint32_t* seed1 = plan.seeds;
-  const uint32_t sh1 = plan.seed_shift, s1ny = plan.seed_ny, s1nz = plan.seed_nz;
+  const BrickCounts bc = brick_counts(g);
+  const uint32_t packets = bc.padded, real = (uint32_t)bc.real;   // (no super-brick padding for k_brute_split)
+  const uint32_t* plane = mode == MODE_UNSIGNED ? d_inside_plane : nullptr;   // the Normal fold carries its own sign
   const CutList cut = {plan.cut_lists, plan.cut_log, plan.cut_ny, plan.cut_nz, bx_off, nullptr};
-  if (plan.brute_acc != nullptr) {
-    // ~4 blocks per CU over (voxel blocks x triangle chunks); a chunk is a whole number of 128-triangle tiles
-    const uint32_t real = bricks_along(g.xe - g.xb, g.bl[0]) * bricks_along(g.n[1], g.bl[1]) * bricks_along(g.n[2], g.bl[2]);   // no super-brick padding here
-    const uint32_t vblocks = (real + 3) / 4, tiles = (mesh.n_tris + TILE - 1) / TILE;
-    const uint32_t chunks = std::max(1u, std::min(tiles, (1024u + vblocks - 1) / vblocks));
-    const uint32_t tiles_per_chunk = (tiles + chunks - 1) / chunks;
-    const uint32_t ychunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
+  if (ch.path == GridWalkChoice::ALL_PAIRS_SPLIT)
     M2S_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)plan.brute_acc, 0x7f800000, (size_t)packets * 64 * 2, st));   // +inf: where every search starts (Best<>)
-    if (mode == MODE_UNSIGNED) {
-      hipLaunchKernelGGL((k_brute_split<MODE_UNSIGNED>), dim3(vblocks, ychunks), dim3(256), 0, st, mesh, g, plan.brute_acc, d_err, real, tiles_per_chunk);
-      if (d_inside_plane) hipLaunchKernelGGL((k_brute_finish<MODE_UNSIGNED, SIGN_GRID_PLANE>), dim3(vblocks), dim3(256), 0, st, g, d_inside_plane, (const uint32_t*)plan.brute_acc, d_out, real, pz);
-      else hipLaunchKernelGGL((k_brute_finish<MODE_UNSIGNED, SIGN_NONE>), dim3(vblocks), dim3(256), 0, st, g, (const uint32_t*)nullptr, (const uint32_t*)plan.brute_acc, d_out, real, pz);
-    } else {
-      hipLaunchKernelGGL((k_brute_split<MODE_NORMAL_FOLD>), dim3(vblocks, ychunks), dim3(256), 0, st, mesh, g, plan.brute_acc, d_err, real, tiles_per_chunk);
-      hipLaunchKernelGGL((k_brute_finish<MODE_NORMAL_FOLD, SIGN_NONE>), dim3(vblocks), dim3(256), 0, st, g, (const uint32_t*)nullptr, (const uint32_t*)plan.brute_acc, d_out, real, pz);
-    }
-    M2S_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  if (plan.lane_walk) {
-    const unsigned blocks = (packets + 3) / 4;
-    if (mode == MODE_UNSIGNED && d_inside_plane)
-      hipLaunchKernelGGL((k_lane<MODE_UNSIGNED, SIGN_GRID_PLANE>), dim3(blocks), dim3(256), 0, st, mesh, g, d_inside_plane, d_out, d_err, packets, seed1, sh1, s1ny, s1nz, bx_off, pz);
-    else if (mode == MODE_UNSIGNED)
-      hipLaunchKernelGGL((k_lane<MODE_UNSIGNED, SIGN_NONE>), dim3(blocks), dim3(256), 0, st, mesh, g, nullptr, d_out, d_err, packets, seed1, sh1, s1ny, s1nz, bx_off, pz);
-    else
-      hipLaunchKernelGGL((k_lane<MODE_NORMAL_FOLD, SIGN_NONE>), dim3(blocks), dim3(256), 0, st, mesh, g, nullptr, d_out, d_err, packets, seed1, sh1, s1ny, s1nz, bx_off, pz);
-    M2S_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  if (plan.group_top != nullptr && !brute) {
-    const uint32_t per = 8u << XCD_RUN_LOG;
-    const uint32_t grid_blocks = ((packets + per - 1) / per) * per;        // as launch_packet: whole runs per XCD (xcd_remap)
-    const uint32_t gw = plan.group_waves;
-    const size_t lds_u = ((size_t)gw * 256u + DeferLayout<MODE_UNSIGNED>::SLOT_WORDS) * 4u, lds_n = ((size_t)gw * 256u + DeferLayout<MODE_NORMAL_FOLD>::SLOT_WORDS) * 4u;
-    if (mode == MODE_UNSIGNED && d_inside_plane)
-      hipLaunchKernelGGL((k_packet_group<MODE_UNSIGNED, SIGN_GRID_PLANE>), dim3(grid_blocks), dim3(64 * gw), lds_u, st, mesh, g, d_inside_plane, d_out, d_err, packets,
-                         seed1, sh1, s1ny, s1nz, bx_off, plan.group_top, pz);
-    else if (mode == MODE_UNSIGNED)
-      hipLaunchKernelGGL((k_packet_group<MODE_UNSIGNED, SIGN_NONE>), dim3(grid_blocks), dim3(64 * gw), lds_u, st, mesh, g, (const uint32_t*)nullptr, d_out, d_err, packets,
-                         seed1, sh1, s1ny, s1nz, bx_off, plan.group_top, pz);
-    else
-      hipLaunchKernelGGL((k_packet_group<MODE_NORMAL_FOLD, SIGN_NONE>), dim3(grid_blocks), dim3(64 * gw), lds_n, st, mesh, g, (const uint32_t*)nullptr, d_out, d_err, packets,
-                         seed1, sh1, s1ny, s1nz, bx_off, plan.group_top, pz);
-    M2S_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
   // (the Normal fold's split variants — k_packet<GRID, NORMAL_FOLD, ..., SPLIT, {1, 3}>, k_split_round<NORMAL_FOLD> — need 9 - 11 registers
   // more than eight waves per SIMD leave and spill them to scratch, the very thing that costs this kernel 10 - 40 %: the automatic choice
   // leaves the Normal sign to the plain walk; M2S_SPLIT=1 / 2 still runs them — the tests do)
-  const bool split_ok = mode != MODE_NORMAL_FOLD || tuning().split > 0;
-  SplitCtl piece_split = plan.split;
-  if (piece_split.cnt != nullptr && !plan.split_forced) {
+  const bool split = ch.path == GridWalkChoice::PACKET && ch.split && (mode != MODE_NORMAL_FOLD || tuning().split > 0);
+  PacketArgs a;
+  a.mesh = mesh; a.g = g; a.plane = plane; a.out = d_out; a.err = d_err; a.n_packets = packets;
+  a.seed_in = plan.seeds; a.seed_shift = plan.seed_shift; a.seed_ny = plan.seed_ny; a.seed_nz = plan.seed_nz; a.cut = cut; a.peers = pz;
+  if (split) {
+    a.split = plan.split;
     // the patience is measured in hand-out rounds of THIS launch (an x-piece of the slab is shallower than the slab the plan was made for)
-    const double rounds_before = std::max(1.0, (double)packets / 8192.0 - 1.0);
-    piece_split.patience_q8 = (uint32_t)std::min(65535.0 * 256.0, 256.0 * tuning().split_patience / rounds_before);
+    if (!ch.split_forced) a.split.patience_q8 = split_patience_q8(packets, tuning());
+    hipLaunchKernelGGL(k_split_init, dim3(1), dim3(64), 0, st, a.split.cnt, ch.split_forced ? 1u : 0u);
   }
-  const SplitCtl* split = (!brute && plan.split.cnt != nullptr && mesh.stats == nullptr && split_ok) ? &piece_split : nullptr;
-  if (split) hipLaunchKernelGGL(k_split_init, dim3(1), dim3(64), 0, st, split->cnt, plan.split_forced ? 1u : 0u);
-  if (mode == MODE_UNSIGNED && d_inside_plane) {
-    if (brute) launch_brute<true, MODE_UNSIGNED, SIGN_GRID_PLANE>(st, mesh, g, nullptr, 0, d_inside_plane, d_out, d_err, packets, peers);
-    else launch_packet<true, MODE_UNSIGNED, SIGN_GRID_PLANE>(st, mesh, g, nullptr, nullptr, 0, d_inside_plane, d_out, d_err, packets, seed1, sh1, s1ny, s1nz, nullptr, cut, peers, split, plan.defer);
-    if (split) launch_split_rounds<MODE_UNSIGNED, SIGN_GRID_PLANE>(st, mesh, g, d_inside_plane, d_out, d_err, *split, cut, peers);
-  } else if (mode == MODE_UNSIGNED) {
-    if (brute) launch_brute<true, MODE_UNSIGNED, SIGN_NONE>(st, mesh, g, nullptr, 0, nullptr, d_out, d_err, packets, peers);
-    else launch_packet<true, MODE_UNSIGNED, SIGN_NONE>(st, mesh, g, nullptr, nullptr, 0, nullptr, d_out, d_err, packets, seed1, sh1, s1ny, s1nz, nullptr, cut, peers, split, plan.defer);
-    if (split) launch_split_rounds<MODE_UNSIGNED, SIGN_NONE>(st, mesh, g, nullptr, d_out, d_err, *split, cut, peers);
-  } else {
-    if (brute) launch_brute<true, MODE_NORMAL_FOLD, SIGN_NONE>(st, mesh, g, nullptr, 0, nullptr, d_out, d_err, packets, peers);
-    else launch_packet<true, MODE_NORMAL_FOLD, SIGN_NONE>(st, mesh, g, nullptr, nullptr, 0, nullptr, d_out, d_err, packets, seed1, sh1, s1ny, s1nz, nullptr, cut, peers, split, plan.defer);
-    if (split) launch_split_rounds<MODE_NORMAL_FOLD, SIGN_NONE>(st, mesh, g, nullptr, d_out, d_err, *split, cut, peers);
-  }
+  for_grid_form(mode, plane != nullptr, [&](auto form) {
+    constexpr int MODE = decltype(form)::MODE, SIGN = decltype(form)::SIGN;
+    switch (ch.path) {
+      case GridWalkChoice::NOTHING: break;
+      case GridWalkChoice::ALL_PAIRS_SPLIT: {
+        // ~4 blocks per CU over (voxel blocks x triangle chunks); a chunk is a whole number of 128-triangle tiles
+        const uint32_t vblocks = (real + 3) / 4, tiles = (mesh.n_tris + TILE - 1) / TILE;
+        const uint32_t chunks = std::max(1u, std::min(tiles, (1024u + vblocks - 1) / vblocks));
+        const uint32_t tiles_per_chunk = (tiles + chunks - 1) / chunks, ychunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
+        hipLaunchKernelGGL((k_brute_split<MODE>), dim3(vblocks, ychunks), dim3(256), 0, st, mesh, g, plan.brute_acc, d_err, real, tiles_per_chunk);
+        hipLaunchKernelGGL((k_brute_finish<MODE, SIGN>), dim3(vblocks), dim3(256), 0, st, g, plane, (const uint32_t*)plan.brute_acc, d_out, real, pz);
+        break;
+      }
+      case GridWalkChoice::ALL_PAIRS: launch_brute<true, MODE, SIGN>(st, mesh, g, nullptr, 0, plane, d_out, d_err, packets, pz); break;
+      case GridWalkChoice::LANE:
+        hipLaunchKernelGGL((k_lane<MODE, SIGN>), dim3((packets + 3) / 4), dim3(256), 0, st, mesh, g, plane, d_out, d_err, packets, a.seed_in, a.seed_shift, a.seed_ny, a.seed_nz, bx_off, pz);
+        break;
+      case GridWalkChoice::GROUP: {
+        const uint32_t per = 8u << XCD_RUN_LOG, grid_blocks = ((packets + per - 1) / per) * per;        // as launch_packet: whole runs per XCD (xcd_remap)
+        const size_t lds = ((size_t)ch.group_waves * 256u + DeferLayout<MODE>::SLOT_WORDS) * 4u;
+        hipLaunchKernelGGL((k_packet_group<MODE, SIGN>), dim3(grid_blocks), dim3(64 * ch.group_waves), lds, st, mesh, g, plane, d_out, d_err, packets,
+                           a.seed_in, a.seed_shift, a.seed_ny, a.seed_nz, bx_off, plan.group_top, pz);
+        break;
+      }
+      case GridWalkChoice::PACKET:
+        launch_packet<true, MODE, SIGN>(st, a, ch.defer);
+        if (split) launch_split_rounds<MODE, SIGN>(st, mesh, g, plane, d_out, d_err, a.split, cut, pz);
+        break;
+    }
+  });
   M2S_HIP_CHECK(hipGetLastError());
   if (split && tuning().split_report) {
+    const SplitCtl& sc = a.split;
     uint32_t h[SPLIT_CNT_WORDS];
     M2S_HIP_CHECK(hipStreamSynchronize(st));
-    M2S_HIP_CHECK(hipMemcpy(h, split->cnt, sizeof(h), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[m2s split] %u packets: %u suspended (room for %u); items per round:", packets, h[0], split->cap_slots);
-    for (uint32_t r = 1; r <= split->rounds; ++r) fprintf(stderr, " %u", h[1 + r]);
+    M2S_HIP_CHECK(hipMemcpy(h, sc.cnt, sizeof(h), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[m2s split] %u packets: %u suspended (room for %u); items per round:", packets, h[0], sc.cap_slots);
+    for (uint32_t r = 1; r <= sc.rounds; ++r) fprintf(stderr, " %u", h[1 + r]);
     fprintf(stderr, " (room for %u each, reserved in blocks of 64); first look after %u units, patience %.2f of the time to the flag, subtrees of %u .. %u records; XCD 0: handed out in %.1f us\n",
-            split->cap_items, split->grace, split->patience_q8 / 256.0, split->emit_min / (uint32_t)sizeof(NodeExt), split->emit_max / (uint32_t)sizeof(NodeExt),
+            sc.cap_items, sc.grace, sc.patience_q8 / 256.0, sc.emit_min / (uint32_t)sizeof(NodeExt), sc.emit_max / (uint32_t)sizeof(NodeExt),
             h[16] ? ((h[16] & ~1u) - h[24]) * 0.01 : 0.0);
   }
   return 0;
@@ -2756,7 +2772,7 @@ int launch_grid_distance(Arena& ws, hipStream_t st, const DeviceMesh& mesh, cons
   // the sign planes may have been built beside the seed passes, on another stream (capi.hip): the walk needs them
   if (wait_before_final) M2S_HIP_CHECK(hipStreamWaitEvent(st, wait_before_final, 0));
   if (ev_before_final) M2S_HIP_CHECK(hipEventRecord(ev_before_final, st));
-  return launch_grid_walk(st, mesh, g, mode, d_inside_plane, algorithm, plan, 0, d_out, d_err, peers);
+  return launch_grid_walk(st, mesh, g, mode, d_inside_plane, plan, 0, d_out, d_err, peers);
 }
 
 // Test hook (capi.hip m2s_debug_cut_code): the list word k_cut writes for the range [start, start + len) of a tree of n_nodes records,
@@ -2801,8 +2817,7 @@ uint32_t query_leaf_max(size_t n_q, size_t n_tris, int sign_src) {
 uint32_t grid_leaf_max(const GridParams& g, size_t n_tris) {
   const Tuning& tn = tuning();
   if (tn.leaf_max != 0) return tn.leaf_max;
-  const double bricks = (double)bricks_along(g.n[0], g.bl[0]) * bricks_along(g.n[1], g.bl[1]) * bricks_along(g.n[2], g.bl[2]);
-  const double per_brick = (double)n_tris / std::max(1.0, bricks);
+  const double per_brick = (double)n_tris / std::max(1.0, (double)brick_counts(g).grid);
   return per_brick >= 40.0 ? 16u : per_brick >= 3.0 ? 8u : per_brick >= 0.6 ? 4u : 2u;   // (16: blob-100k 32^3, 195 per brick, 1.31 -> 1.11 ms; blob-1M 80^3 3.14 -> 2.53)
 }
 
@@ -2822,19 +2837,11 @@ int launch_query_brute_split(Arena& ws, hipStream_t st, const DeviceMesh& mesh, 
   const uint32_t tiles_per_chunk = (tiles + chunks - 1) / chunks, ychunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
   const dim3 grid(qblocks, ychunks);
   hipLaunchKernelGGL(k_brute_q_init, dim3(qblocks), dim3(256), 0, st, acc, nq, mode == MODE_NORMAL_FOLD ? 0x7f800000u : 0u);
-  if (mode == MODE_UNSIGNED && sign_src == SIGN_RAYS3) {
-    hipLaunchKernelGGL((k_brute_split_q<MODE_UNSIGNED, SIGN_RAYS3>), grid, dim3(256), 0, st, mesh, d_queries, nq, acc, d_err, tiles_per_chunk);
-    hipLaunchKernelGGL((k_brute_finish_q<MODE_UNSIGNED, SIGN_RAYS3>), dim3(qblocks), dim3(256), 0, st, (const uint32_t*)acc, nq, d_out);
-  } else if (mode == MODE_UNSIGNED) {
-    hipLaunchKernelGGL((k_brute_split_q<MODE_UNSIGNED, SIGN_NONE>), grid, dim3(256), 0, st, mesh, d_queries, nq, acc, d_err, tiles_per_chunk);
-    hipLaunchKernelGGL((k_brute_finish_q<MODE_UNSIGNED, SIGN_NONE>), dim3(qblocks), dim3(256), 0, st, (const uint32_t*)acc, nq, d_out);
-  } else if (mode == MODE_NORMAL_FOLD) {
-    hipLaunchKernelGGL((k_brute_split_q<MODE_NORMAL_FOLD, SIGN_NONE>), grid, dim3(256), 0, st, mesh, d_queries, nq, acc, d_err, tiles_per_chunk);
-    hipLaunchKernelGGL((k_brute_finish_q<MODE_NORMAL_FOLD, SIGN_NONE>), dim3(qblocks), dim3(256), 0, st, (const uint32_t*)acc, nq, d_out);
-  } else {
-    hipLaunchKernelGGL((k_brute_split_q<MODE_NEAREST_NORMAL, SIGN_NONE>), grid, dim3(256), 0, st, mesh, d_queries, nq, acc, d_err, tiles_per_chunk);
-    hipLaunchKernelGGL((k_brute_finish_q<MODE_NEAREST_NORMAL, SIGN_NONE>), dim3(qblocks), dim3(256), 0, st, (const uint32_t*)acc, nq, d_out);
-  }
+  for_query_form(mode, sign_src, [&](auto form) {
+    constexpr int MODE = decltype(form)::MODE, SIGN = decltype(form)::SIGN;
+    hipLaunchKernelGGL((k_brute_split_q<MODE, SIGN>), grid, dim3(256), 0, st, mesh, d_queries, nq, acc, d_err, tiles_per_chunk);
+    hipLaunchKernelGGL((k_brute_finish_q<MODE, SIGN>), dim3(qblocks), dim3(256), 0, st, (const uint32_t*)acc, nq, d_out);
+  });
   M2S_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -2974,18 +2981,13 @@ int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const f
   const uint32_t packets = (nq + 63) / 64;
   if (algorithm == 1) {
     if (mode == MODE_UNSIGNED && sign_src == SIGN_XRAY_ALL) launch_brute<false, MODE_UNSIGNED, SIGN_XRAY_ALL>(st, mesh, g, d_queries, nq, nullptr, d_out, d_err, packets);
-    else if (mode == MODE_UNSIGNED && sign_src == SIGN_RAYS3) launch_brute<false, MODE_UNSIGNED, SIGN_RAYS3>(st, mesh, g, d_queries, nq, nullptr, d_out, d_err, packets);
-    else if (mode == MODE_UNSIGNED) launch_brute<false, MODE_UNSIGNED, SIGN_NONE>(st, mesh, g, d_queries, nq, nullptr, d_out, d_err, packets);
-    else if (mode == MODE_NORMAL_FOLD) launch_brute<false, MODE_NORMAL_FOLD, SIGN_NONE>(st, mesh, g, d_queries, nq, nullptr, d_out, d_err, packets);
-    else launch_brute<false, MODE_NEAREST_NORMAL, SIGN_NONE>(st, mesh, g, d_queries, nq, nullptr, d_out, d_err, packets);
+    else for_query_form(mode, sign_src, [&](auto form) {
+      launch_brute<false, decltype(form)::MODE, decltype(form)::SIGN>(st, mesh, g, d_queries, nq, nullptr, d_out, d_err, packets);
+    });
     M2S_HIP_CHECK(hipGetLastError());
     return 0;
   }
-  const uint32_t* perm = plan.perm;
-  const float4* sorted = plan.sorted;
-  const uint32_t* table = plan.table;
   const uint32_t launched = plan.launched;
-  const bool lane_walk = plan.lane_walk;
   // seeds: jump flooding over a QL^3 lattice on the query bounding box (as for the grid path) — here, or beside the build (`pre`)
   const uint32_t* seeds = nullptr;
   const GridParams* d_lat = nullptr;
@@ -3006,28 +3008,20 @@ int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const f
   if (plan.centres != nullptr && seeds != nullptr) {
     uint32_t* lists = ws.take<uint32_t>((size_t)launched * CUT_WORDS);
     if (!lists) { set_error("internal: query workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-    const float emit_near = tuning().cut_near;
-    const float emit_far = tuning().cut_far;   // 1/32: re-tuned at the end of round 3 (1/16 before): headline 9.19 -> 9.11 ms, 1024^3 x sheet-100k 92.95 -> 89.33 ms
-    uint32_t depth = 1;
-    while ((1ull << depth) < (unsigned long long)mesh.n_tris + 1ull) ++depth;
-    const uint32_t wave_cap = tuning().cut_wave_cap ? tuning().cut_wave_cap : std::max(120u, 20u * depth);
+    const CutParams cp = cut_params(mesh.n_tris, tuning());
     hipLaunchKernelGGL((k_cut<false, 0>), dim3((launched + 63) / 64), dim3(64), 0, st, mesh, g, seeds, 0u, 0u, 0u, launched, 1u, 1u, lists,
-                       emit_near, emit_far, 100000u, wave_cap, (const float4*)plan.centres, table, d_lat);
+                       cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap, (const float4*)plan.centres, plan.table, d_lat);
     cut = {lists, 0, 0, 0, 0, plan.centres};
   }
-  if (lane_walk) {
-    const unsigned lb = (nq + 255u) / 256u;
-    if (mode == MODE_UNSIGNED && sign_src == SIGN_RAYS3) hipLaunchKernelGGL((k_lane_q<MODE_UNSIGNED, SIGN_RAYS3>), dim3(lb), dim3(256), 0, st, mesh, (const float4*)sorted, (const uint32_t*)perm, nq, d_out, d_err, seeds, d_lat);
-    else if (mode == MODE_UNSIGNED) hipLaunchKernelGGL((k_lane_q<MODE_UNSIGNED, SIGN_NONE>), dim3(lb), dim3(256), 0, st, mesh, (const float4*)sorted, (const uint32_t*)perm, nq, d_out, d_err, seeds, d_lat);
-    else if (mode == MODE_NORMAL_FOLD) hipLaunchKernelGGL((k_lane_q<MODE_NORMAL_FOLD, SIGN_NONE>), dim3(lb), dim3(256), 0, st, mesh, (const float4*)sorted, (const uint32_t*)perm, nq, d_out, d_err, seeds, d_lat);
-    else hipLaunchKernelGGL((k_lane_q<MODE_NEAREST_NORMAL, SIGN_NONE>), dim3(lb), dim3(256), 0, st, mesh, (const float4*)sorted, (const uint32_t*)perm, nq, d_out, d_err, seeds, d_lat);
-    M2S_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  if (mode == MODE_UNSIGNED && sign_src == SIGN_RAYS3) launch_packet<false, MODE_UNSIGNED, SIGN_RAYS3>(st, mesh, g, sorted, perm, nq, table, d_out, d_err, launched, seeds, 0, 0, 0, d_lat, cut, nullptr, nullptr, tuning().defer == 0 ? 0 : tuning().defer == 1 ? 1 : 3);
-  else if (mode == MODE_UNSIGNED) launch_packet<false, MODE_UNSIGNED, SIGN_NONE>(st, mesh, g, sorted, perm, nq, table, d_out, d_err, launched, seeds, 0, 0, 0, d_lat, cut, nullptr, nullptr, tuning().defer == 0 ? 0 : tuning().defer == 1 ? 1 : 3);
-  else if (mode == MODE_NORMAL_FOLD) launch_packet<false, MODE_NORMAL_FOLD, SIGN_NONE>(st, mesh, g, sorted, perm, nq, table, d_out, d_err, launched, seeds, 0, 0, 0, d_lat, cut, nullptr, nullptr, tuning().defer == 0 ? 0 : tuning().defer == 1 ? 1 : 3);
-  else launch_packet<false, MODE_NEAREST_NORMAL, SIGN_NONE>(st, mesh, g, sorted, perm, nq, table, d_out, d_err, launched, seeds, 0, 0, 0, d_lat, cut, nullptr, nullptr, tuning().defer == 0 ? 0 : tuning().defer == 1 ? 1 : 3);
+  PacketArgs a;
+  a.mesh = mesh; a.g = g; a.qsorted = plan.sorted; a.perm = plan.perm; a.n_q = nq; a.plane = plan.table; a.out = d_out; a.err = d_err; a.n_packets = launched;
+  a.seed_in = seeds; a.seed_lattice = d_lat; a.cut = cut;
+  const int defer = tuning().defer == 0 ? 0 : tuning().defer == 1 ? 1 : 3;
+  for_query_form(mode, sign_src, [&](auto form) {
+    constexpr int MODE = decltype(form)::MODE, SIGN = decltype(form)::SIGN;
+    if (plan.lane_walk) hipLaunchKernelGGL((k_lane_q<MODE, SIGN>), dim3((nq + 255u) / 256u), dim3(256), 0, st, mesh, a.qsorted, a.perm, nq, d_out, d_err, seeds, d_lat);
+    else launch_packet<false, MODE, SIGN>(st, a, defer);
+  });
   M2S_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -164,6 +164,127 @@ def test_leaf_size_rules(lib):
     assert ask(64, 11200, 10000000)[1:] == (2, 0)
 
 
+def test_grid_walk_choice_rules(lib):
+    """Which path a grid call takes under the default knobs (distance.hip choose_grid_walk; DESIGN.md sections 4.3 - 4.5 and 9): host arithmetic of
+    the library itself through the test hook m2s_debug_grid_walk_choice.  Every expectation is worked out from the rules as DESIGN.md states them:
+    cubic grids over the unit box have bricks of 4^3 cells; a launch's packets are the bricks padded to super-bricks (8 in y and z; 8, 4, 2 or 1 in x)."""
+    from mesh_to_sdf_amd import Grid, interleaved_slab
+
+    NOTHING, ALL_PAIRS_SPLIT, ALL_PAIRS, LANE, GROUP, PACKET = range(6)
+    fn = lib.m2s_debug_grid_walk_choice
+    fn.restype = C.c_int
+    slab_fn = lib.m2s_debug_grid_walk_choice_slab
+    slab_fn.restype = C.c_int
+    leaf_fn = lib.m2s_debug_leaf_sizes
+    leaf_fn.restype = C.c_int
+    out = (C.c_uint32 * 8)()
+    TREE = 199999   # any number of node records but 0: the mesh has its tree
+
+    def ask(n, n_tris, n_nodes=TREE, leaf_max=None, algorithm=0):
+        """(path, seeds, cut levels, group waves, split, split forced, defer, block sized for a split)"""
+        n = (n, n, n) if isinstance(n, int) else n
+        g = Grid.from_bounding_box([0.0, 0.0, 0.0], [1.0, 1.0, 1.0], list(n)) if all(n) else Grid.new([0.0, 0.0, 0.0], [1.0, 1.0, 1.0], list(n))
+        if leaf_max is None:   # as grid_leaf_max gives it (test_leaf_size_rules pins that rule)
+            leaves = (C.c_uint32 * 3)()
+            assert leaf_fn(C.byref(g._g), C.c_size_t(n_tris), C.c_size_t(0), leaves) == 0
+            leaf_max = leaves[0]
+        assert fn(C.byref(g._g), C.c_size_t(n_tris), C.c_size_t(n_nodes), C.c_uint32(leaf_max), C.c_int(algorithm), out) == 0
+        return tuple(out)
+
+    # 512^3 x 100 k (headline): 128^3 = 2 097 152 bricks, 0.0477 triangles per brick (leaves of 2).  Not the lane walk (far below 60 per brick);
+    # cut lists (>= 100 000 packets) in one level (32^3 = 32 768 fine waves < 40 000); no split (> 2^19 packets); defer 3 (0.0477 >= 0.045)
+    assert ask(512, 100000) == (PACKET, 1, 1, 0, 0, 0, 3, 0)
+    # 1024^3: 256^3 bricks, 64^3 = 262 144 fine waves >= 40 000: two levels; 0.006 per brick < 0.02: defer 2
+    assert ask(1024, 100000) == (PACKET, 1, 2, 0, 0, 0, 2, 0)
+    # 256^3: 64^3 = 262 144 packets >= 100 000: lists, 16^3 = 4 096 fine waves: one level; <= 2^19 packets but < 300 000 triangles: no split; 0.38: defer 3
+    assert ask(256, 100000) == (PACKET, 1, 1, 0, 0, 0, 3, 0)
+    # 128^3: 32 768 packets: no lists; 3.05 per brick (leaves of 8) >= 1, but two waves per packet would be 65 536 > 32 768 waves: no groups
+    assert ask(128, 100000) == (PACKET, 1, 0, 0, 0, 0, 3, 0)
+    # 96^3: 24^3 = 13 824: 2 x 13 824 = 27 648 <= 32 768 < 4 x 13 824: groups of 2 waves
+    assert ask(96, 100000) == (GROUP, 1, 0, 2, 0, 0, 3, 0)
+    # 64^3: 4 096 bricks, 24.4 per brick: leaves of 8, so not the lane walk; 4 x 4 096 <= 32 768: groups of 4 (the most)
+    assert ask(64, 100000) == (GROUP, 1, 0, 4, 0, 0, 3, 0)
+    # 128^3 x 1 M: >= 300 000 triangles, 30.5 >= 5 per brick, 32 768 >= 10 240 bricks, <= 2^19 packets: split walk, hence no groups; leaves of 8: no lane walk
+    assert ask(128, 1000000) == (PACKET, 1, 0, 0, 1, 0, 3, 1)
+    # 40^3 x 100 k over leaves of 2: 10^3 = 1 000 bricks, 100 per brick > 60: lane walk (no lists, no groups, no split)
+    assert ask(40, 100000, leaf_max=2)[:6] == (LANE, 1, 0, 0, 0, 0)
+    # 48^3: 12^3 = 1 728 bricks, 57.9 per brick <= 60: packets, in groups of 4 (4 x 1 728 <= 32 768)
+    assert ask(48, 100000, leaf_max=2) == (GROUP, 1, 0, 4, 0, 0, 3, 0)
+    # the same two over the leaves a one-shot call builds (16: >= 40 per brick): the lane walk needs leaves of 2
+    assert ask(40, 100000)[0] == GROUP and ask(48, 100000)[0] == GROUP
+    # 16^3 x 11 200, triangle records only (a one-shot call found its problem tiny and built no tree): all pairs; no seeds, no lists
+    assert ask(16, 11200, n_nodes=0) == (ALL_PAIRS_SPLIT, 0, 0, 0, 0, 0, 0, 0)
+    # ... with a resident tree the Raycast limit decides: 4 096 cells x 11 200 = 4.6e7 > 7.6e6 + 1 900 x 11 200 = 2.9e7: a walk — 64 bricks, 175 per
+    # brick (leaves of 16: not the lane walk), groups of 4; 8^3 = 512 cells x 11 200 = 5.7e6 is within the limit
+    assert ask(16, 11200) == (GROUP, 1, 0, 4, 0, 0, 3, 0)
+    assert ask(8, 11200)[0] == ALL_PAIRS_SPLIT
+    # algorithm 1: every triangle for every voxel, whatever the sizes; no seeds
+    for n, t in ((16, 11200), (64, 100000), (512, 100000), (128, 1000000)):
+        assert ask(n, t, algorithm=1)[:6] == (ALL_PAIRS, 0, 0, 0, 0, 0)
+        assert ask(n, t, n_nodes=0, algorithm=1)[0] == ALL_PAIRS
+    # an empty slab: nothing; no triangles: the packet walk of an empty tree, no seeds
+    assert ask((0, 4, 4), 100000) == (NOTHING, 0, 0, 0, 0, 0, 0, 0) and ask((4, 0, 4), 100000)[0] == NOTHING
+    assert ask(64, 0, n_nodes=0)[:6] == (PACKET, 0, 0, 0, 0, 0)
+
+    # knobs (DESIGN.md section 9), each against the default choice of a grid where it flips one field
+    base = ask(128, 100000)                              # (PACKET, 1, 0, 0, 0, 0, 3, 0)
+    big = ask(128, 1000000)                              # (PACKET, 1, 0, 0, 1, 0, 3, 1)
+    with _lib.knobs(M2S_SPLIT=0):                        # never — and no room for it in the block (two waves per packet are still too many for groups)
+        assert ask(128, 1000000) == big[:4] + (0, 0, 3, 0)
+    with _lib.knobs(M2S_SPLIT=1):                        # on wherever the walk form allows it (<= 2^19 packets)
+        assert ask(128, 100000) == base[:4] + (1, 0, 3, 1) and ask(128, 1000000) == big
+        assert ask(512, 100000) == (PACKET, 1, 1, 0, 0, 0, 3, 0)
+        assert ask(96, 100000) == (PACKET, 1, 0, 0, 1, 0, 3, 1)      # ... which excludes the groups
+    with _lib.knobs(M2S_SPLIT=2):                        # ... with the flags raised from the start
+        assert ask(128, 100000) == base[:4] + (1, 1, 3, 1) and ask(128, 1000000) == big[:5] + (1, 3, 1)
+    with _lib.knobs(M2S_GROUP=0):
+        assert ask(96, 100000) == (PACKET, 1, 0, 0, 0, 0, 3, 0)
+    with _lib.knobs(M2S_GROUP=1):                        # always, four waves where the automatic count would be one
+        assert ask(128, 100000) == (GROUP, 1, 0, 4) + base[4:] and ask(96, 100000) == (GROUP, 1, 0, 2, 0, 0, 3, 0)
+    with _lib.knobs(M2S_CUT_COARSE=0):
+        assert ask(1024, 100000) == (PACKET, 1, 1, 0, 0, 0, 2, 0)
+    with _lib.knobs(M2S_CUT_COARSE=1):
+        assert ask(512, 100000) == (PACKET, 1, 2, 0, 0, 0, 3, 0) and ask(128, 100000) == base   # (no lists: no levels)
+    with _lib.knobs(M2S_LANE_WALK=1):
+        assert ask(128, 100000) == (LANE,) + base[1:]
+    with _lib.knobs(M2S_LANE_WALK=0):
+        assert ask(40, 100000, leaf_max=2) == (GROUP, 1, 0, 4, 0, 0, 3, 0)   # 4 x 1 000 bricks <= 32 768
+    for form in range(4):
+        with _lib.knobs(M2S_DEFER=form):
+            assert ask(128, 100000) == base[:6] + (form, 0)
+    with _lib.knobs(M2S_DEFER=1):                        # a forced leaf-work form is a packet walk's: no groups
+        assert ask(96, 100000) == (PACKET, 1, 0, 0, 0, 0, 1, 0)
+    with _lib.knobs(M2S_CUT_MIN_PACKETS=1000):           # 8^3 = 512 fine waves: one level
+        assert ask(128, 100000) == (PACKET, 1, 1) + base[3:]
+    assert ask(128, 100000) == base and ask(128, 1000000) == big   # the defaults are back
+
+    # The workspace block is sized before the mesh exists: whatever mesh turns up — with or without a tree, any leaf size, either algorithm —,
+    # a walk that is split must find the block sized for it.  Whole grids, x-slabs and interleaved slabs.
+    sizes = (8, 24, 40, 96, 128, 200, 256, 1024)
+    dims = [(a, a, a) for a in sizes] + [(a, b, c) for a in sizes[::2] for b in (16, 100, 512) for c in (12, 256)]
+    tris = [1, 30, 1000, 11200, 99999, 300000, 1 << 20, 1 << 23, 1 << 25]
+    checked = splits = 0
+    for knobs in ({}, {"M2S_SPLIT": 1}, {"M2S_SPLIT": 2}, {"M2S_LANE_WALK": 0}, {"M2S_BRUTE_MAX": 0}):
+        with _lib.knobs(**knobs):
+            for d in dims:
+                g = Grid.from_bounding_box([0.0, 0.0, 0.0], [1.0, 1.0, 1.0], list(d))
+                slabs = [(0, 0, 0), (0, max(1, d[0] // 2), 0), (d[0] // 4, d[0], 0)]
+                slabs += [s for s in (interleaved_slab(g, 4, 1), interleaved_slab(g, 8, 5)) if s[2]]
+                for xb, xe, period in slabs:
+                    o = _lib.M2SOpts()
+                    o.struct_size, o.x_begin, o.x_end, o.x_period = C.sizeof(_lib.M2SOpts), xb, xe, period
+                    for t in tris:
+                        for n_nodes in (0, 2 * t - 1):
+                            for leaf_max in (2, 8, 16):
+                                for algorithm in (0, 1):
+                                    assert slab_fn(C.byref(g._g), C.byref(o), C.c_size_t(t), C.c_size_t(n_nodes), C.c_uint32(leaf_max), C.c_int(algorithm), out) == 0
+                                    checked += 1
+                                    splits += out[4]
+                                    assert out[4] <= out[7], (knobs, d, (xb, xe, period), t, n_nodes, leaf_max, algorithm, tuple(out))
+                                    assert out[5] <= out[4] and (out[3] == 0 or out[0] == GROUP) and (out[4] == 0 or out[0] == PACKET)
+    assert checked > 50000 and splits > 1000
+
+
 def test_cut_list_words_are_supersets_for_every_tree_size(lib):
     """distance.hip CutList: a list word carries a range's start exactly and its length as a small float rounded UP — the walk may take a
     superset of a subtree range, never less.  Host arithmetic of the library itself (test hook m2s_debug_cut_code), every width of the
