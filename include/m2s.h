@@ -326,6 +326,50 @@ int m2s_mesh_closest_points(m2s_mesh* mesh, const float* queries, size_t n_queri
 int m2s_mesh_grid_closest_points(m2s_mesh* mesh, const m2s_grid* grid,
                                  uint32_t* triangle_out, float* point_out, float* distance_out, const m2s_opts* opts);
 
+/* ---- generalized winding numbers: a robust inside / outside for meshes that are not watertight -------------------------------
+ * Raycast needs a watertight mesh and Normal leaks; on scans and game assets with holes, open borders, doubled sheets or
+ * self-intersections the remedy of libigl (SIGNED_DISTANCE_TYPE_WINDING_NUMBER), Houdini and Open3D is
+ *   w(p) = (1 / 4 pi) sum_t Omega_t(p),   Omega_t = the signed solid angle of triangle t seen from p
+ * (Jacobson et al. 2013).  Orientation: the right-hand normal (b - a) x (c - a) points outward, as for the isosurface below; then w is 1
+ * inside and 0 outside a closed mesh, degrades smoothly across holes, and w >= 1/2 is the inside test (threshold; callers default to 0.5).
+ *   winding_out[i]  w(p_i), f32.
+ *   sdf_out[i]      w >= threshold ? -d : d, with d the unsigned distance of the closest-point calls: |sdf_out[i]| is bit-equal to their
+ *                   distance_out[i].  A NaN w gives +d.
+ * Either output may be NULL, not both (M2S_ERR_BAD_ARG).
+ * Arithmetic.  Exact term (Van Oosterom-Strackee), f32, a, b, c relative to p and n = the raw normal of the triangle:
+ *   Omega = 2 atan2(a . n, |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|)          (a . n = a . (b x c), formed from the edge vectors);
+ * a triangle whose raw normal is zero, or whose numerator is exactly 0 (p in its plane), contributes 0; a NaN point gives NaN.
+ * Every point must account for every triangle, so the walk is a Barnes-Hut one (Barill et al. 2018, order 1): every node of the tree
+ * has a centre c~ (area-weighted mean of its triangles' centroids), a radius r (>= the distance from c~ to any of its vertices), and the
+ * moments S = sum a_t and M = sum a_t (x) (c_t - c~) of its area vectors a_t = (b - a) x (c - a) / 2.  A point with |c~ - p| > beta r
+ * takes S . K(x) + <M, grad K(x)>, x = c~ - p, K(x) = x / (4 pi |x|^3), grad K = (I / |x|^3 - 3 x x^T / |x|^5) / 4 pi, instead of the
+ * node's triangles; subtrees of at most 8 triangles are summed exactly.  beta is finite and >= 1, or +inf (no node is ever accepted:
+ * the exact sum through the tree); NaN or < 1: M2S_ERR_BAD_ARG.  M2S_WINDING_BETA_DEFAULT = 3: tests/winding_model.py measures a largest
+ * error of 4.1e-2 / 1.7e-2 / 8.4e-3 at beta = 2 / 3 / 4 (tests/golden/winding_model_error.json); 1.7e-2 is well inside the band
+ * |w - 1/2| < 0.1 in which a hole, not the expansion, decides the sign (4.1e-2 is nearly half of it), and the walk's cost grows with beta.
+ * algorithm = 1: every triangle for every point, exactly, in the tree's triangle order (validation).
+ * Reproducibility.  A point's value depends only on (tree, point, beta): on one m2s_mesh the grid forms, their x-slabs and the point
+ * forms agree bit for bit at the same f32 point, whatever other calls re-marked the tree in between.  One-shot calls may build
+ * different trees from call to call (M2S_TREELETS) and agree only within the accuracy above.
+ * A mesh without triangles: w = 0 everywhere, M2S_ERR_EMPTY_MESH only if sdf_out is asked for.
+ * m2s_opts as for the closest-point calls — device, stream / stream_mode, mem_kind, synchronous, lane, x_begin / x_end for the grid forms
+ * (only the slab is written); x_period or peer_out: M2S_ERR_BAD_ARG.  timings: accel_build_ms = the build, seed_ms = the moments (a
+ * persistent mesh makes them in its first winding call and keeps them until m2s_mesh_destroy), distance_ms = the distance pass (only
+ * with sdf_out) + the winding walk, total_ms = the whole device time.  Host-memory arguments are checked before any device work.
+ * Asynchronous calls on a mesh finish, and add their spans up, in m2s_mesh_drain_timings. */
+#define M2S_WINDING_BETA_DEFAULT 3.0f
+int m2s_winding_numbers(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes,
+                        int topology, const float* queries, size_t n_queries, float beta, float threshold,
+                        float* winding_out, float* sdf_out, const m2s_opts* opts);
+/* The grid's cell centres in its output layout z + y*nz + x*ny*nz, as m2s_grid_closest_points addresses them. */
+int m2s_grid_winding_numbers(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes,
+                             int topology, const m2s_grid* grid, float beta, float threshold,
+                             float* winding_out, float* sdf_out, const m2s_opts* opts);
+int m2s_mesh_winding_numbers(m2s_mesh* mesh, const float* queries, size_t n_queries, float beta, float threshold,
+                             float* winding_out, float* sdf_out, const m2s_opts* opts);
+int m2s_mesh_grid_winding_numbers(m2s_mesh* mesh, const m2s_grid* grid, float beta, float threshold,
+                                  float* winding_out, float* sdf_out, const m2s_opts* opts);
+
 /* Grid helpers with the reference's exact f32 arithmetic (so callers need not re-derive it).
  * m2s_grid_from_bounding_box — Grid::from_bounding_box, grid.rs:59-74.
  * m2s_grid_cell_center      — Grid::get_cell_center,   grid.rs:135-141.

@@ -11,6 +11,7 @@
 //   Grid<V>                grid.rs:30-170                      new_ / from_bounding_box / getters / snap_point_to_grid
 //   generate_grid_sdf      generate/grid.rs:265-378
 //   closest_points / grid_closest_points                       nearest triangle + closest point (no reference counterpart; m2s.h)
+//   winding_numbers / grid_winding_numbers / generate_grid_sdf_winding   generalized winding numbers and their sign (m2s.h)
 //   sample_grid / raymarch_grid  client draw_raymarching.wgsl  sdf_grid / estimate_normal / sdf_3d on a finished grid (m2s.h)
 //   grid_isosurface                                            marching-cubes mesh of a level set of a finished grid (no reference counterpart; m2s.h)
 //   serde::*               serde.rs:75-221                     SerializeSdf / DeserializeSdf / save_to_file / read_from_file
@@ -289,6 +290,51 @@ ClosestPoints grid_closest_points(const V* vertices, size_t n_vertices, const To
 template <class V, class I = uint32_t>
 ClosestPoints grid_closest_points(const std::vector<V>& vertices, const Topology<I>& indices, const Grid<V>& grid) {
   return grid_closest_points(vertices.data(), vertices.size(), indices, grid);
+}
+
+// ---- generalized winding numbers (m2s_winding_numbers, m2s_grid_winding_numbers) ------------------------------------------
+// w per query point or per grid cell (grid order): 1 inside, 0 outside a closed mesh whose right-hand normals point outward, smooth
+// across holes; w >= 0.5 is the robust inside test.  beta: the Barnes-Hut opening parameter (>= 1, +inf = exact).
+template <class V, class I = uint32_t>
+std::vector<float> winding_numbers(const V* vertices, size_t n_vertices, const Topology<I>& indices, const V* query_points, size_t n_queries,
+                                   float beta = M2S_WINDING_BETA_DEFAULT) {
+  detail::Packed<V> v(vertices, n_vertices), q(query_points, n_queries);
+  detail::IndexArg<I> ia(indices);
+  std::vector<float> w(n_queries);
+  detail::check(m2s_winding_numbers(v.ptr, n_vertices, ia.ptr, indices.count, ia.bytes, indices.kind, q.ptr, n_queries, beta, 0.5f, w.data(),
+                                    nullptr, nullptr));
+  return w;
+}
+template <class V, class I = uint32_t>
+std::vector<float> winding_numbers(const std::vector<V>& vertices, const Topology<I>& indices, const std::vector<V>& query_points,
+                                   float beta = M2S_WINDING_BETA_DEFAULT) {
+  return winding_numbers(vertices.data(), vertices.size(), indices, query_points.data(), query_points.size(), beta);
+}
+template <class V, class I = uint32_t>
+std::vector<float> grid_winding_numbers(const V* vertices, size_t n_vertices, const Topology<I>& indices, const Grid<V>& grid,
+                                        float beta = M2S_WINDING_BETA_DEFAULT) {
+  detail::Packed<V> v(vertices, n_vertices);
+  detail::IndexArg<I> ia(indices);
+  std::vector<float> w(grid.get_total_cell_count());
+  detail::check(m2s_grid_winding_numbers(v.ptr, n_vertices, ia.ptr, indices.count, ia.bytes, indices.kind, &grid.raw(), beta, 0.5f, w.data(),
+                                         nullptr, nullptr));
+  return w;
+}
+template <class V, class I = uint32_t>
+std::vector<float> grid_winding_numbers(const std::vector<V>& vertices, const Topology<I>& indices, const Grid<V>& grid,
+                                        float beta = M2S_WINDING_BETA_DEFAULT) {
+  return grid_winding_numbers(vertices.data(), vertices.size(), indices, grid, beta);
+}
+// Signed distances with the winding number's sign: -d where w >= threshold, else d.
+template <class V, class I = uint32_t>
+std::vector<float> generate_grid_sdf_winding(const std::vector<V>& vertices, const Topology<I>& indices, const Grid<V>& grid,
+                                             float beta = M2S_WINDING_BETA_DEFAULT, float threshold = 0.5f) {
+  detail::Packed<V> v(vertices.data(), vertices.size());
+  detail::IndexArg<I> ia(indices);
+  std::vector<float> d(grid.get_total_cell_count());
+  detail::check(m2s_grid_winding_numbers(v.ptr, vertices.size(), ia.ptr, indices.count, ia.bytes, indices.kind, &grid.raw(), beta, threshold,
+                                         nullptr, d.data(), nullptr));
+  return d;
 }
 
 // ---- queries on a finished grid (m2s_sample_grid, m2s_raymarch_grid) ------------------------------------------------------

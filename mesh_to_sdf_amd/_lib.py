@@ -62,6 +62,7 @@ MAX_PEERS = 15
 PEER_PUSH, PEER_STORE, PEER_TRAIL = 0, 1, 2
 XCHG_AUTO, XCHG_PEER, XCHG_RCCL, XCHG_NONE = 0, 1, 2, 3
 IPC_HANDLE_BYTES = 64
+WINDING_BETA_DEFAULT = 3.0   # M2S_WINDING_BETA_DEFAULT
 
 
 class M2SMultiOpts(C.Structure):
@@ -143,6 +144,10 @@ EXPORTS = [
     "m2s_grid_closest_points",
     "m2s_mesh_closest_points",
     "m2s_mesh_grid_closest_points",
+    "m2s_winding_numbers",
+    "m2s_grid_winding_numbers",
+    "m2s_mesh_winding_numbers",
+    "m2s_mesh_grid_winding_numbers",
     "m2s_sdf_grid_encoded_size",
     "m2s_sdf_generic_encoded_size",
     "m2s_sdf_encode_grid",
@@ -210,6 +215,10 @@ def _prototypes():
         "m2s_grid_closest_points": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(M2SGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
         "m2s_mesh_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
         "m2s_mesh_grid_closest_points": (C.c_int, [C.c_void_p, C.POINTER(M2SGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
+        "m2s_winding_numbers": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
+        "m2s_grid_winding_numbers": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(M2SGrid), C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
+        "m2s_mesh_winding_numbers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
+        "m2s_mesh_grid_winding_numbers": (C.c_int, [C.c_void_p, C.POINTER(M2SGrid), C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
         "m2s_sdf_grid_encoded_size": (C.c_size_t, [C.POINTER(M2SGrid), C.c_size_t]),
         "m2s_sdf_generic_encoded_size": (C.c_size_t, [C.c_size_t, C.c_size_t]),
         "m2s_sdf_encode_grid": (C.c_int, [C.POINTER(M2SGrid), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(M2SOpts)]),

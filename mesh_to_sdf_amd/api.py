@@ -335,6 +335,90 @@ def grid_closest_points(vertices, indices: Topology, grid: "Grid", *, timings: M
     return _closest_result(a, bufs)
 
 
+WINDING_BETA_DEFAULT = _lib.WINDING_BETA_DEFAULT
+
+
+def _queries_of(a, query_points):
+    """(array kept alive, count, raw pointer) of a query set on the side of `a` (device tensor or numpy)."""
+    if a.device:
+        q = query_points if _is_torch(query_points) else a.torch.as_tensor(np.asarray(query_points, np.float32), device=a.dev)
+        q = q.detach().to(device=a.dev, dtype=a.torch.float32).contiguous().reshape(-1, 3)
+        return q, q.shape[0], (q.data_ptr() if q.numel() else None)
+    q = np.ascontiguousarray(np.asarray(query_points, np.float32)).reshape(-1, 3)
+    return q, q.shape[0], (q.ctypes.data if q.size else None)
+
+
+def _f32_buffer(a, n, out=None):
+    """f32[n] on the call's side (or `out`), and its raw pointer."""
+    if out is None:
+        out = a.torch.empty(n, dtype=a.torch.float32, device=a.dev) if a.device else np.empty(n, np.float32)
+    return out, ((out.data_ptr() if a.device else out.ctypes.data) if n else None)
+
+
+def _winding_queries(call, a, n_q, p_q, beta, threshold, signed, timings, algorithm, synchronous=True):
+    """One point-form winding call: `call(p_q, n_q, beta, threshold, p_w, p_sdf, opts)`; returns w, or signed distances."""
+    out, p_out = _f32_buffer(a, n_q)
+    o = a.opts(timings, algorithm, synchronous=synchronous or not a.device)
+    rc = call(p_q, n_q, float(beta), float(threshold), None if signed else p_out, p_out if signed else None, C.byref(o))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    return out
+
+
+def _winding_grid(call, a, grid, beta, threshold, signed, timings, algorithm, x_slab, out, synchronous=True):
+    """One grid-form winding call: `call(grid, beta, threshold, p_w, p_sdf, opts)`."""
+    out, p_out = _f32_buffer(a, grid.get_total_cell_count(), out)
+    xb, xe = (0, 0) if x_slab is None else (int(x_slab[0]), int(x_slab[1]))
+    if x_slab is not None and xb == xe:
+        return out
+    o = a.opts(timings, algorithm, xb, xe, synchronous or not a.device)
+    rc = call(C.byref(grid._g), float(beta), float(threshold), None if signed else p_out, p_out if signed else None, C.byref(o))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    return out
+
+
+def _one_shot_winding_queries(vertices, indices, query_points, beta, threshold, signed, timings, algorithm):
+    a = _Args(vertices, indices, query_points)
+    L = _lib.lib()
+    return _winding_queries(lambda *r: L.m2s_winding_numbers(a.p_verts, a.n_verts, a.p_idx, a.n_idx, a.index_bytes, a.topology, *r),
+                            a, a.n_q, a.p_q, beta, threshold, signed, timings, algorithm)
+
+
+def _one_shot_winding_grid(vertices, indices, grid, beta, threshold, signed, timings, algorithm, x_slab, out):
+    a = _Args(vertices, indices)
+    L = _lib.lib()
+    return _winding_grid(lambda *r: L.m2s_grid_winding_numbers(a.p_verts, a.n_verts, a.p_idx, a.n_idx, a.index_bytes, a.topology, *r),
+                         a, grid, beta, threshold, signed, timings, algorithm, x_slab, out)
+
+
+def winding_numbers(vertices, indices: Topology, query_points, *, beta: float = WINDING_BETA_DEFAULT, algorithm: int = 0,
+                    timings: M2STimings = None):
+    """Generalized winding number of every query (include/m2s.h m2s_winding_numbers): f32[n], 1 inside and 0 outside a closed mesh whose
+    right-hand normals point outward, smooth across holes; `w >= 0.5` is the robust inside test.  `beta` is the Barnes-Hut opening
+    parameter (>= 1; `float('inf')`: the exact sum through the tree); `algorithm=1`: all pairs, no tree."""
+    return _one_shot_winding_queries(vertices, indices, query_points, beta, 0.5, False, timings, algorithm)
+
+
+def grid_winding_numbers(vertices, indices: Topology, grid: "Grid", *, beta: float = WINDING_BETA_DEFAULT, algorithm: int = 0,
+                         timings: M2STimings = None, x_slab: Sequence[int] = None, out=None):
+    """winding_numbers for the cell centres of `grid`, flattened in grid order; `x_slab` / `out` as for grid_closest_points."""
+    return _one_shot_winding_grid(vertices, indices, grid, beta, 0.5, False, timings, algorithm, x_slab, out)
+
+
+def generate_sdf_winding(vertices, indices: Topology, query_points, *, beta: float = WINDING_BETA_DEFAULT, threshold: float = 0.5,
+                         algorithm: int = 0, timings: M2STimings = None):
+    """Signed distances whose sign is the winding number's: -d where w >= threshold, else +d; |result| is bit-equal to the distance of
+    closest_points.  For meshes with holes, open borders or self-intersections, where neither SignMethod gives a usable sign."""
+    return _one_shot_winding_queries(vertices, indices, query_points, beta, threshold, True, timings, algorithm)
+
+
+def generate_grid_sdf_winding(vertices, indices: Topology, grid: "Grid", *, beta: float = WINDING_BETA_DEFAULT, threshold: float = 0.5,
+                              algorithm: int = 0, timings: M2STimings = None, x_slab: Sequence[int] = None, out=None):
+    """generate_sdf_winding for the cell centres of `grid`."""
+    return _one_shot_winding_grid(vertices, indices, grid, beta, threshold, True, timings, algorithm, x_slab, out)
+
+
 class SampleMode(enum.IntEnum):
     """How a grid is read between cell centres (include/m2s.h m2s_sample_mode = the client shader's MODE_*)."""
     Snap = 0
@@ -866,6 +950,35 @@ class Mesh:
         if rc != _lib.M2S_OK:
             _raise(rc)
         return _closest_result(a, bufs)
+
+    def _mesh_winding_queries(self, query_points, beta, threshold, signed, timings, algorithm, synchronous):
+        q, n_q, p_q = _queries_of(self._a, query_points)   # q stays alive through the call
+        L = _lib.lib()
+        return _winding_queries(lambda *r: L.m2s_mesh_winding_numbers(self._h, *r), self._a, n_q, p_q, beta, threshold, signed, timings,
+                                algorithm, synchronous)
+
+    def _mesh_winding_grid(self, grid, beta, threshold, signed, timings, algorithm, x_slab, out, synchronous):
+        L = _lib.lib()
+        return _winding_grid(lambda *r: L.m2s_mesh_grid_winding_numbers(self._h, *r), self._a, grid, beta, threshold, signed, timings,
+                             algorithm, x_slab, out, synchronous)
+
+    def winding_numbers(self, query_points, *, beta: float = WINDING_BETA_DEFAULT, algorithm: int = 0, timings: M2STimings = None,
+                        synchronous: bool = True):
+        """winding_numbers on the resident tree; its moments are made by the first winding call and kept.  On one Mesh a point's value
+        depends only on the point and beta: the grid forms, their x-slabs and the point forms agree bit for bit."""
+        return self._mesh_winding_queries(query_points, beta, 0.5, False, timings, algorithm, synchronous)
+
+    def grid_winding_numbers(self, grid: Grid, *, beta: float = WINDING_BETA_DEFAULT, algorithm: int = 0, timings: M2STimings = None,
+                             x_slab: Sequence[int] = None, out=None, synchronous: bool = True):
+        return self._mesh_winding_grid(grid, beta, 0.5, False, timings, algorithm, x_slab, out, synchronous)
+
+    def generate_sdf_winding(self, query_points, *, beta: float = WINDING_BETA_DEFAULT, threshold: float = 0.5, algorithm: int = 0,
+                             timings: M2STimings = None, synchronous: bool = True):
+        return self._mesh_winding_queries(query_points, beta, threshold, True, timings, algorithm, synchronous)
+
+    def generate_grid_sdf_winding(self, grid: Grid, *, beta: float = WINDING_BETA_DEFAULT, threshold: float = 0.5, algorithm: int = 0,
+                                  timings: M2STimings = None, x_slab: Sequence[int] = None, out=None, synchronous: bool = True):
+        return self._mesh_winding_grid(grid, beta, threshold, True, timings, algorithm, x_slab, out, synchronous)
 
     def debug_digest(self):
         """FNV-1a digests of the resident arrays (test hook `m2s_debug_mesh_digest`): triangle records, pre-test planes, box nodes,

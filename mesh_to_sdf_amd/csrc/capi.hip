@@ -838,6 +838,10 @@ struct m2s_mesh {
   bool tree_last_async = false, tree_async_other = false;
   hipStream_t tree_stream = nullptr;
   bool tree_used = false;
+  // winding numbers: the nodes' moments (winding.hip NodeMom), made by the first winding call in a block of their own
+  char* mom_mem = nullptr;
+  hipEvent_t mom_ready = nullptr;     // recorded after the moments were made, on mom_stream
+  hipStream_t mom_stream = nullptr;
 };
 
 // The leaf size a call wants its tree to have (grid_leaf_max / query_leaf_max): the resident tree is re-marked when it differs — one
@@ -1014,6 +1018,151 @@ int mesh_call_opts(const m2s_mesh* m, const m2s_opts* opts, m2s_opts* o) {
   if (o->device < 0) o->device = m->device;
   if (o->device != m->device) return fail(M2S_ERR_BAD_ARG, "mesh lives on device %d, call asked for %d", m->device, o->device);
   if (!opts) o->synchronous = 1;
+  return 0;
+}
+
+// ---- winding numbers (m2s_winding_numbers and its three siblings) --------------------------------------------------------------
+// The moments of the tree's nodes (winding.hip k_moments; ev[2] .. ev[4] = seed_ms), then — only where signed distances are asked
+// for — the unsigned distance walk of the closest-point calls, unchanged, into a workspace buffer, then the Barnes-Hut walk, which
+// writes w and / or (w >= threshold ? -d : d).  ev[4] .. ev[3] = distance_ms.
+struct WindingArgs {
+  float* w;
+  float* sdf;
+  float beta, threshold;
+};
+
+int check_winding_args(const WindingArgs& o) {
+  if (!o.w && !o.sdf) return fail(M2S_ERR_BAD_ARG, "winding_out and sdf_out are both NULL");
+  if (!(o.beta >= 1.0f)) return fail(M2S_ERR_BAD_ARG, "beta must be >= 1 (or +inf: no expansion is ever used), got %g", (double)o.beta);
+  return 0;
+}
+
+int winding_outputs(Arena& ws, const CallCtx& c, const WindingArgs& o, size_t n, uint64_t first, WindingOut* d) {
+  *d = WindingOut{o.w, o.sdf, 0};
+  if (c.mem_kind == M2S_MEM_DEVICE) return 0;
+  d->w = o.w ? ws.take<float>(n) : nullptr;
+  d->sdf = o.sdf ? ws.take<float>(n) : nullptr;
+  d->off = first;
+  if ((o.w && !d->w) || (o.sdf && !d->sdf)) return fail(M2S_ERR_HIP, "internal: workspace");
+  return 0;
+}
+int winding_copy_out(DeviceState& st, const CallCtx& c, const WindingArgs& o, const WindingOut& d, size_t n, uint64_t first) {
+  if (c.mem_kind == M2S_MEM_DEVICE) return 0;
+  int rc = 0;
+  if (o.w && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.w + first), reinterpret_cast<const char*>(d.w), n * 4))) return rc;
+  if (o.sdf && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.sdf + first), reinterpret_cast<const char*>(d.sdf), n * 4))) return rc;
+  return 0;
+}
+size_t winding_workspace_bytes(const CallCtx& c, size_t n) {
+  return align_up(n * 4) + (c.mem_kind == M2S_MEM_HOST ? 2 * align_up(n * 4) : 0) + 1024;
+}
+
+// A mesh without triangles: w = 0 everywhere (entries [first, first + n) of winding_out); no distance exists.
+int winding_of_nothing(const m2s_opts* opts, const WindingArgs& o, size_t first, size_t n) {
+  if (o.sdf) return fail(M2S_ERR_EMPTY_MESH, "signed distances on a mesh without triangles");
+  if (n == 0) return M2S_OK;
+  if (!opts || opts->mem_kind == M2S_MEM_HOST) { memset(o.w + first, 0, n * 4); return M2S_OK; }
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if (const int rc = resolve_ctx(opts, &c, &st)) return rc;
+  M2S_HIP_CHECK(hipMemsetAsync(o.w + first, 0, n * 4, c.stream));
+  if (c.sync) M2S_HIP_CHECK(hipStreamSynchronize(c.stream));
+  return M2S_OK;
+}
+
+// The moments of a one-shot call's tree, in its workspace; ev[4] closes the span.
+int winding_moments(Arena& ws, const CallCtx& c, DeviceState& st, const DeviceMesh& mesh, const NodeMom** moms) {
+  *moms = nullptr;
+  if (c.algorithm != 1) {
+    NodeMom* m = ws.take<NodeMom>(mesh.n_nodes);
+    if (!m) return fail(M2S_ERR_HIP, "internal: workspace");
+    if (const int rc = launch_winding_moments(c.stream, mesh, m)) return rc;
+    *moms = m;
+  }
+  M2S_HIP_CHECK(hipEventRecord(st.ev[4], c.stream));
+  return 0;
+}
+
+// The moments of a persistent mesh: made by its first winding call, kept in a block of their own until m2s_mesh_destroy.
+int mesh_winding_moments(m2s_mesh* m, const CallCtx& c, DeviceState& st, const NodeMom** moms) {
+  *moms = nullptr;
+  if (c.algorithm != 1) {
+    if (!m->mom_mem) {
+      M2S_HIP_CHECK(hipMalloc((void**)&m->mom_mem, (size_t)m->dm.n_nodes * sizeof(NodeMom)));
+      if (const int rc = launch_winding_moments(c.stream, m->dm, reinterpret_cast<NodeMom*>(m->mom_mem))) return rc;
+      if (!m->mom_ready) M2S_HIP_CHECK(hipEventCreateWithFlags(&m->mom_ready, hipEventDisableTiming));
+      M2S_HIP_CHECK(hipEventRecord(m->mom_ready, c.stream));
+      m->mom_stream = c.stream;
+    } else if (c.stream != m->mom_stream) {   // made (perhaps still being made) on another stream
+      M2S_HIP_CHECK(hipStreamWaitEvent(c.stream, m->mom_ready, 0));
+    }
+    *moms = reinterpret_cast<const NodeMom*>(m->mom_mem);
+  }
+  M2S_HIP_CHECK(hipEventRecord(st.ev[4], c.stream));
+  return 0;
+}
+
+int run_grid_winding(Arena& ws, const CallCtx& c, DeviceState& st, const DeviceMesh& mesh, const NodeMom* moms, const GridParams& g,
+                     size_t slab_cells, const WindingArgs& o, int* d_err) {
+  const uint64_t first = (uint64_t)g.xb * g.n[1] * g.n[2];
+  float* d_dist = o.sdf ? ws.take<float>(slab_cells) : nullptr;
+  WindingOut d;
+  if (o.sdf && !d_dist) return fail(M2S_ERR_HIP, "internal: workspace");
+  int rc = winding_outputs(ws, c, o, slab_cells, first, &d);
+  if (rc) return rc;
+  if (o.sdf) {
+    GridParams gd = g;
+    gd.out_off = first;                                  // the distance pass writes the slab into d_dist
+    rc = launch_grid_distance(ws, c.stream, mesh, gd, MODE_UNSIGNED, nullptr, c.algorithm, d_dist, d_err, nullptr, nullptr, !c.sync);
+    if (rc) return rc;
+  }
+  rc = launch_winding_grid(c.stream, mesh, moms, g, o.beta, o.threshold, d_dist, first, c.algorithm, d);
+  if (rc) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st.ev[3], c.stream));
+  return winding_copy_out(st, c, o, d, slab_cells, first);
+}
+
+int run_query_winding(Arena& ws, const CallCtx& c, DeviceState& st, const DeviceMesh& mesh, const NodeMom* moms, const float* d_q, size_t n_q,
+                      const WindingArgs& o, int* d_err) {
+  float* d_dist = o.sdf ? ws.take<float>(n_q) : nullptr;
+  WindingOut d;
+  if (o.sdf && !d_dist) return fail(M2S_ERR_HIP, "internal: workspace");
+  int rc = winding_outputs(ws, c, o, n_q, 0, &d);
+  if (rc) return rc;
+  QueryPlan plan;   // the Morton order (perm) makes the packets coherent; algorithm 1 has none (input order)
+  rc = prepare_query_walk(ws, c.stream, d_q, n_q, mesh.n_tris, SIGN_NONE, c.algorithm, &plan);
+  if (rc) return rc;
+  if (o.sdf) {
+    if (query_is_tiny(n_q, mesh.n_tris, c.algorithm, SIGN_NONE))
+      rc = launch_query_brute_split(ws, c.stream, mesh, d_q, n_q, MODE_UNSIGNED, SIGN_NONE, d_dist, d_err);
+    else
+      rc = launch_query_walk(ws, c.stream, mesh, d_q, plan, MODE_UNSIGNED, SIGN_NONE, c.algorithm, d_dist, d_err);
+    if (rc) return rc;
+  }
+  rc = launch_winding_queries(c.stream, mesh, moms, d_q, plan.perm, n_q, o.beta, o.threshold, d_dist, c.algorithm, d);
+  if (rc) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st.ev[3], c.stream));
+  return winding_copy_out(st, c, o, d, n_q, 0);
+}
+
+int finish_winding(const CallCtx& c, DeviceState& st, int* d_err, size_t n_tris, size_t n_units, const WindingArgs& o) {
+  const int rc = finish_call(c, st, d_err, c.timings, n_tris, n_units, false, true);
+  if (rc == M2S_OK && c.sync && c.timings) c.timings->distance_launches = o.sdf ? 2 : 1;
+  return rc;
+}
+
+// An asynchronous call on a mesh: its event pair ev[4] .. ev[3] moves into the mesh's pending list (m2s_mesh_drain_timings waits for it
+// and adds the span up), and the context gets fresh events for the next call.
+int park_async_events(m2s_mesh* m, DeviceState& st, uint64_t units, uint32_t launches) {
+  hipEvent_t fresh[2];
+  for (hipEvent_t& e : fresh) {
+    if (!m->free_events.empty()) { e = m->free_events.back(); m->free_events.pop_back(); }
+    else if (!st.timing_events.empty()) { e = st.timing_events.back(); st.timing_events.pop_back(); }
+    else M2S_HIP_CHECK(hipEventCreate(&e));
+  }
+  m->pending.push_back({st.ev[4], st.ev[3], units, launches});
+  st.ev[4] = fresh[0];
+  st.ev[3] = fresh[1];
   return 0;
 }
 
@@ -1513,6 +1662,8 @@ void m2s_mesh_destroy(m2s_mesh* m) {
       ds.spare_plane_bytes = m->plane_bytes;
     } else if (m->plane_mem) (void)hipFree(m->plane_mem);
     if (m->plane_ready) (void)hipEventDestroy(m->plane_ready);
+    if (m->mom_mem) (void)hipFree(m->mom_mem);
+    if (m->mom_ready) (void)hipEventDestroy(m->mom_ready);
     for (auto& p : m->pending) { m->free_events.push_back(p.a); m->free_events.push_back(p.b); }
     for (auto e : m->free_events) {
       if (ds.timing_events.size() < 64) ds.timing_events.push_back(e);
@@ -1900,6 +2051,181 @@ int m2s_mesh_grid_closest_points(m2s_mesh* m, const m2s_grid* grid, uint32_t* tr
   if ((rc = remark_leaves(m, c, m->dm.leaf_max))) return rc;
   if ((rc = run_grid_closest(ws, c, *st, m->dm, g, slab_cells, o, d_err))) return rc;
   return finish_closest(c, *st, d_err, m->n_tris, slab_cells);
+}
+
+int m2s_winding_numbers(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology,
+                        const float* queries, size_t n_queries, float beta, float threshold, float* winding_out, float* sdf_out,
+                        const m2s_opts* opts) {
+  g_err[0] = 0;
+  const WindingArgs o{winding_out, sdf_out, beta, threshold};
+  int rc = check_mesh_args(vertices, n_vertices, indices, n_indices, index_bytes, topology);
+  if (rc) return rc;
+  if ((rc = check_winding_args(o))) return rc;
+  if (n_queries && !queries) return fail(M2S_ERR_BAD_ARG, "queries is NULL");
+  if (n_queries >= 0xffffffc0ull) return fail(M2S_ERR_BAD_ARG, "too many queries for one call");
+  const size_t n_tris = m2s_triangle_count(n_vertices, n_indices, indices != nullptr, topology);
+  if (n_tris == 0) return winding_of_nothing(opts, o, 0, n_queries);
+  if (!opts || opts->mem_kind == M2S_MEM_HOST) {
+    if ((rc = check_host_indices(indices, n_indices, index_bytes, topology, n_vertices, n_tris))) return rc;
+  }
+  if (n_queries == 0) return M2S_OK;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(opts, &c, &st))) return rc;
+  size_t need = bvh_workspace_bytes(n_tris) + align_up(2 * n_tris * sizeof(NodeMom)) + query_workspace_bytes(n_queries) + align_up(n_queries * 16) +
+                winding_workspace_bytes(c, n_queries) + 4096;
+  if (c.mem_kind == M2S_MEM_HOST)
+    need += align_up(n_vertices * 12) + align_up(n_indices * (size_t)(indices ? index_bytes : 0)) + align_up(n_queries * 12) + 1024;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  StagedMesh sm;
+  if ((rc = stage_mesh(ws, c, vertices, n_vertices, indices, n_indices, index_bytes, &sm))) return rc;
+  const float* d_q = queries;
+  if (c.mem_kind == M2S_MEM_HOST) {
+    float* dq = ws.take<float>(n_queries * 3);
+    if (!dq) return fail(M2S_ERR_HIP, "internal: workspace");
+    if ((rc = staged_h2d(*st, c.stream, reinterpret_cast<char*>(dq), reinterpret_cast<const char*>(queries), n_queries * 12))) return rc;
+    d_q = dq;
+  }
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  DeviceMesh mesh;
+  rc = build_device_mesh(ws, c.stream, sm.d_verts, n_vertices, sm.d_indices, n_indices, index_bytes, topology, n_tris, d_err, &mesh,
+                         nullptr, false, query_leaf_max(n_queries, n_tris, SIGN_NONE));
+  if (rc) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  st->planes_done = nullptr;
+  const NodeMom* moms = nullptr;
+  if ((rc = winding_moments(ws, c, *st, mesh, &moms))) return rc;
+  if ((rc = run_query_winding(ws, c, *st, mesh, moms, d_q, n_queries, o, d_err))) return rc;
+  return finish_winding(c, *st, d_err, n_tris, n_queries, o);
+}
+
+int m2s_grid_winding_numbers(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology,
+                             const m2s_grid* grid, float beta, float threshold, float* winding_out, float* sdf_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  const WindingArgs o{winding_out, sdf_out, beta, threshold};
+  int rc = check_mesh_args(vertices, n_vertices, indices, n_indices, index_bytes, topology);
+  if (rc) return rc;
+  if ((rc = check_winding_args(o))) return rc;
+  GridParams g;
+  size_t slab_cells = 0;
+  if ((rc = closest_grid_params(grid, opts, &g, &slab_cells))) return rc;
+  const size_t n_tris = m2s_triangle_count(n_vertices, n_indices, indices != nullptr, topology);
+  if (n_tris == 0) return winding_of_nothing(opts, o, (size_t)g.xb * g.n[1] * g.n[2], slab_cells);
+  if (!opts || opts->mem_kind == M2S_MEM_HOST) {
+    if ((rc = check_host_indices(indices, n_indices, index_bytes, topology, n_vertices, n_tris))) return rc;
+  }
+  if (slab_cells == 0) return M2S_OK;   // an empty slab [x, x)
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(opts, &c, &st))) return rc;
+  size_t need = bvh_workspace_bytes(n_tris) + align_up(2 * n_tris * sizeof(NodeMom)) + grid_distance_workspace_bytes(g, n_tris) +
+                winding_workspace_bytes(c, slab_cells) + 4096;
+  if (c.mem_kind == M2S_MEM_HOST) need += align_up(n_vertices * 12) + align_up(n_indices * (size_t)(indices ? index_bytes : 0)) + 1024;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  StagedMesh sm;
+  if ((rc = stage_mesh(ws, c, vertices, n_vertices, indices, n_indices, index_bytes, &sm))) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  DeviceMesh mesh;
+  rc = build_device_mesh(ws, c.stream, sm.d_verts, n_vertices, sm.d_indices, n_indices, index_bytes, topology, n_tris, d_err, &mesh,
+                         nullptr, false, grid_leaf_max(g, n_tris), (uint64_t)slab_cells);
+  if (rc) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  st->planes_done = nullptr;
+  st->have_raw_seeds = false;
+  const NodeMom* moms = nullptr;
+  if ((rc = winding_moments(ws, c, *st, mesh, &moms))) return rc;
+  if ((rc = run_grid_winding(ws, c, *st, mesh, moms, g, slab_cells, o, d_err))) return rc;
+  return finish_winding(c, *st, d_err, n_tris, slab_cells, o);
+}
+
+int m2s_mesh_winding_numbers(m2s_mesh* m, const float* queries, size_t n_queries, float beta, float threshold, float* winding_out,
+                             float* sdf_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  if (!m) return fail(M2S_ERR_BAD_ARG, "mesh is NULL");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  const WindingArgs o{winding_out, sdf_out, beta, threshold};
+  int rc = check_winding_args(o);
+  if (rc) return rc;
+  if (n_queries && !queries) return fail(M2S_ERR_BAD_ARG, "queries is NULL");
+  if (n_queries >= 0xffffffc0ull) return fail(M2S_ERR_BAD_ARG, "too many queries for one call");
+  m2s_opts mo;
+  if ((rc = mesh_call_opts(m, opts, &mo))) return rc;
+  if (m->n_tris == 0) return winding_of_nothing(&mo, o, 0, n_queries);
+  if (n_queries == 0) return M2S_OK;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(&mo, &c, &st))) return rc;
+  size_t need = query_workspace_bytes(n_queries) + align_up(n_queries * 16) + winding_workspace_bytes(c, n_queries) + 8192;
+  if (c.mem_kind == M2S_MEM_HOST) need += align_up(n_queries * 12) + 1024;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  if (c.sync) M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  else d_err = m->d_err_async;   // asynchronous calls report through the mesh (m2s_mesh_drain_timings)
+  const float* d_q = queries;
+  if (c.mem_kind == M2S_MEM_HOST) {
+    float* dq = ws.take<float>(n_queries * 3);
+    if (!dq) return fail(M2S_ERR_HIP, "internal: workspace");
+    if ((rc = staged_h2d(*st, c.stream, reinterpret_cast<char*>(dq), reinterpret_cast<const char*>(queries), n_queries * 12))) return rc;
+    d_q = dq;
+  }
+  if (!c.sync) reap_pending(m, false);
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  st->planes_done = nullptr;
+  if ((rc = remark_leaves(m, c, m->dm.leaf_max))) return rc;   // the tree as it is: the walk reads no leaf marks; keeps the mesh's stream bookkeeping
+  const NodeMom* moms = nullptr;
+  if ((rc = mesh_winding_moments(m, c, *st, &moms))) return rc;
+  if ((rc = run_query_winding(ws, c, *st, m->dm, moms, d_q, n_queries, o, d_err))) return rc;
+  if (!c.sync) return park_async_events(m, *st, n_queries, o.sdf ? 2 : 1);
+  return finish_winding(c, *st, d_err, m->n_tris, n_queries, o);
+}
+
+int m2s_mesh_grid_winding_numbers(m2s_mesh* m, const m2s_grid* grid, float beta, float threshold, float* winding_out, float* sdf_out,
+                                  const m2s_opts* opts) {
+  g_err[0] = 0;
+  if (!m) return fail(M2S_ERR_BAD_ARG, "mesh is NULL");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  const WindingArgs o{winding_out, sdf_out, beta, threshold};
+  int rc = check_winding_args(o);
+  if (rc) return rc;
+  GridParams g;
+  size_t slab_cells = 0;
+  if ((rc = closest_grid_params(grid, opts, &g, &slab_cells))) return rc;
+  m2s_opts mo;
+  if ((rc = mesh_call_opts(m, opts, &mo))) return rc;
+  if (m->n_tris == 0) return winding_of_nothing(&mo, o, (size_t)g.xb * g.n[1] * g.n[2], slab_cells);
+  if (slab_cells == 0) return M2S_OK;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(&mo, &c, &st))) return rc;
+  size_t need = grid_distance_workspace_bytes(g, m->n_tris) + winding_workspace_bytes(c, slab_cells) + 8192;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  if (c.sync) M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  else d_err = m->d_err_async;
+  if (!c.sync) reap_pending(m, false);
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  st->planes_done = nullptr;
+  st->have_raw_seeds = false;
+  if ((rc = remark_leaves(m, c, m->dm.leaf_max))) return rc;
+  const NodeMom* moms = nullptr;
+  if ((rc = mesh_winding_moments(m, c, *st, &moms))) return rc;
+  if ((rc = run_grid_winding(ws, c, *st, m->dm, moms, g, slab_cells, o, d_err))) return rc;
+  if (!c.sync) return park_async_events(m, *st, slab_cells, o.sdf ? 2 : 1);
+  return finish_winding(c, *st, d_err, m->n_tris, slab_cells, o);
 }
 
 // Peer-write bandwidth probe (include/m2s.h): the copy kernel of M2S_PEER_PUSH, timed with HIP events on a stream of its own.

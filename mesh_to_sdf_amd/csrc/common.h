@@ -372,6 +372,28 @@ int launch_closest_grid(hipStream_t st, const DeviceMesh& mesh, const GridParams
 int launch_closest_queries(hipStream_t st, const DeviceMesh& mesh, const float* d_queries, const uint32_t* perm, size_t n_q, const float* d_dist,
                            int algorithm, const ClosestOut& out);
 
+// winding.hip: generalized winding numbers.  Multipole record of a tree node, 64 B, same slot as NodeRec: the area
+// vectors a_t = (b - a) x (c - a) / 2 of the subtree's triangles expanded to first order about their area-weighted centroid.
+struct alignas(64) NodeMom {
+  float cx, cy, cz;   // expansion centre: sum |a_t| c_t / sum |a_t| (c_t = triangle centroid; the plain mean when all areas vanish)
+  float r;            // >= distance from the centre to any vertex of the subtree, rounded up
+  float ax, ay, az;   // sum a_t
+  float m[9];         // sum a_t (x) (c_t - centre), row-major
+};
+static_assert(sizeof(NodeMom) == 64, "NodeMom must be 64 bytes");
+struct WindingOut {
+  float* w;           // winding number per point, or nullptr
+  float* sdf;         // w >= threshold ? -d : d with d of the first pass, or nullptr
+  uint64_t off;       // a point's entry is its output index - off
+};
+int launch_winding_moments(hipStream_t st, const DeviceMesh& mesh, NodeMom* moms);   // n_nodes records
+// Grid / queries addressed exactly as launch_closest_grid / launch_closest_queries address them; d_dist is read only when out.sdf is set.
+// beta = +inf: no node is ever accepted (exact sum through the tree); algorithm 1: every triangle in sorted order, no tree.
+int launch_winding_grid(hipStream_t st, const DeviceMesh& mesh, const NodeMom* moms, const GridParams& g, float beta, float threshold,
+                        const float* d_dist, uint64_t dist_off, int algorithm, const WindingOut& out);
+int launch_winding_queries(hipStream_t st, const DeviceMesh& mesh, const NodeMom* moms, const float* d_queries, const uint32_t* perm, size_t n_q,
+                           float beta, float threshold, const float* d_dist, int algorithm, const WindingOut& out);
+
 
 // grid_query.hip: sampling and ray-marching a finished grid SDF (the client's draw_raymarching.wgsl).  The grid's scalars travel as a
 // kernel argument; start / end are the shader's uniforms (first_cell, Grid::get_last_cell), n[] >= 1, cs[] > 0 and finite.

@@ -72,6 +72,14 @@ def sheet(nx=251, ny=201, rotate=True):
     return verts.astype(np.float32), idx
 
 
+def cube(half=1.0):
+    """Closed axis-aligned cube [-half, half]^3, 12 triangles, outward CCW."""
+    v = np.array([[x, y, z] for x in (-half, half) for y in (-half, half) for z in (-half, half)], np.float32)   # index = 4x + 2y + z
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]   # -x +x -y +y -z +z, seen from outside
+    idx = np.array([t for a, b, c, d in quads for t in (a, b, c, a, c, d)], np.uint32)
+    return v, idx
+
+
 def named(name):
     if name == "blob-100k":
         return blob(250, 201)
