@@ -370,6 +370,61 @@ int m2s_mesh_winding_numbers(m2s_mesh* mesh, const float* queries, size_t n_quer
 int m2s_mesh_grid_winding_numbers(m2s_mesh* mesh, const m2s_grid* grid, float beta, float threshold,
                                   float* winding_out, float* sdf_out, const m2s_opts* opts);
 
+/* ---- ray casting against the mesh: first hit, hit count, occlusion -----------------------------------------------------------------
+ * What Open3D RaycastingScene cast_rays / count_intersections / test_occlusions, trimesh ray.intersects_* and libigl ray_mesh_intersect
+ * answer, with the watertight test of Woop, Benthin and Wald (2013) instead of Moeller-Trumbore, which leaks through the shared edges
+ * and vertices of a closed mesh in f32.  Per ray (o, d) and the call's range [t_min, t_max]:
+ *   t_out[i]             the smallest t over all triangles the ray hits in range; +inf when none.
+ *   triangle_out[i]      the triangle attaining it, in the caller's triangle order (Topology::get_triangles); the lowest index on exact
+ *                        ties of t; UINT32_MAX when none.
+ *   uv_out[2i], [2i+1]   barycentric weights of b and c at that hit: hit = a + u (b - a) + v (c - a); NaN x 2 when none.
+ *   count_out[i]         the number of triangles hit in range.  A ray through a shared edge or vertex counts EVERY triangle that includes
+ *                        it (zeros of the edge functions are inside), so on a closed mesh the count's parity is an inside test only for
+ *                        rays that avoid edges and vertices.
+ *   occluded_out[i]      uint8, 1 iff at least one hit in range.  When this is the only output asked for the walk stops at a ray's first hit.
+ * Any output may be NULL, not all of them (M2S_ERR_BAD_ARG; with n_rays == 0 nothing is written and none is needed).  d is used as given, not normalised: t is in units of |d|.
+ * Arithmetic: IEEE binary32, no FMA, sums left to right, correctly rounded divisions (mesh_to_sdf_amd/csrc/ray.hip.h; tests/ray_model.py
+ * restates it in numpy).
+ *   Ray:       kz = the index of the largest |d_k| (the lowest index on ties), kx = (kz + 1) % 3, ky = (kx + 1) % 3, kx and ky swapped if
+ *              d[kz] < 0;  Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz].
+ *   Triangle:  (a, b, c) the caller's vertices.  A = a - o;  Ax = A[kx] - Sx * A[kz], Ay = A[ky] - Sy * A[kz], Az = Sz * A[kz]; the same for
+ *              B and C.  U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax.
+ *              Miss if (U < 0 || V < 0 || W < 0) && (U > 0 || V > 0 || W > 0): zeros are inside, nothing is culled, there is no f64 fallback.
+ *              det = U + V + W; miss if det == 0 or NaN.
+ *              Miss unless the ray's axis (0, 0) lies in the rectangle of (Ax, Ay), (Bx, By), (Cx, Cy) widened by mxy: miss if
+ *              min(Ax, Bx, Cx) > mxy, max(Ax, Bx, Cx) < -mxy, or the same in y;  mxy = 2^-20 * the largest of |Ax| ... |Cy|.
+ *              t = (U * Az + V * Bz + W * Cz) / det.  Miss if t < min(Az, Bz, Cz) - mz or t > max(Az, Bz, Cz) + mz;
+ *              mz = 2^-21 * the largest of |Az|, |Bz|, |Cz|.  Hit iff t_min <= t <= t_max.
+ *              u = V / det, v = W / det.  Swapping b and c keeps the hit; u and v change places and, like t, agree only up to
+ *              rounding (det and the numerator are summed in another order).
+ *   A ray with a non-finite component in o or d, or d = (0, 0, 0): no hit, count 0.  A mesh without triangles: no hit anywhere, M2S_OK.
+ * The two "miss unless" clauses are this library's addition to the paper's test.  They change no bit for a triangle whose image in
+ * the ray's frame is not degenerate.  For one seen EDGE-ON — the ray lies in its plane, or it is a sliver below the
+ * resolution of its coordinates — U, V and W are rounding noise, and with zeros inside and no f64 fallback the bare test reports hits
+ * although the axis passes far outside the three points; the clauses make those misses, by a rule a tree can prune for exactly.  They do
+ * not open a closed mesh: a ray through a shared edge or vertex has its axis on the rectangle of every triangle that includes it.
+ * algorithm = 1 (every triangle for every ray, no tree) is the definition.  The default walks the tree and skips a node only when the
+ * same clauses, applied to the node's box with the triangle test's own operations, exclude every triangle below it: it returns the same
+ * bits for every output on every ray, however the tree's leaves are marked.
+ * The range: m2s_ray_opts, NULL = [0, +inf]; t_min <= t_max with neither NaN, otherwise M2S_ERR_BAD_ARG.
+ * m2s_opts as for the closest-point calls: device, stream / stream_mode, mem_kind (EVERY data pointer on one side), synchronous, lane,
+ * algorithm.  M2S_ERR_BAD_ARG before any device work: x_begin, x_end, x_period or peer_out not zero; NULL inputs with n > 0; every output
+ * NULL; bad enums; host-memory indices out of range.  n_rays == 0: M2S_OK.  timings: accel_build_ms = the build, distance_ms = the ray
+ * kernel, n_units = rays. */
+typedef struct m2s_ray_opts {
+  uint32_t struct_size;  /* sizeof(m2s_ray_opts) */
+  float t_min;           /* NULL opts: 0 */
+  float t_max;           /* NULL opts: +inf */
+} m2s_ray_opts;
+/* origins, directions: n_rays packed xyz. */
+int m2s_cast_rays(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology,
+                  const float* origins, const float* directions, size_t n_rays, const m2s_ray_opts* ropts,
+                  float* t_out, uint32_t* triangle_out, float* uv_out, uint32_t* count_out, uint8_t* occluded_out, const m2s_opts* opts);
+/* The same on a persistent mesh: its resident tree as it is — no build, no re-marking of its leaves — and the same bits as the one-shot
+ * call.  Asynchronous calls finish, and add their spans up, in m2s_mesh_drain_timings. */
+int m2s_mesh_cast_rays(m2s_mesh* mesh, const float* origins, const float* directions, size_t n_rays, const m2s_ray_opts* ropts,
+                       float* t_out, uint32_t* triangle_out, float* uv_out, uint32_t* count_out, uint8_t* occluded_out, const m2s_opts* opts);
+
 /* Grid helpers with the reference's exact f32 arithmetic (so callers need not re-derive it).
  * m2s_grid_from_bounding_box — Grid::from_bounding_box, grid.rs:59-74.
  * m2s_grid_cell_center      — Grid::get_cell_center,   grid.rs:135-141.

@@ -12,6 +12,7 @@
 //   generate_grid_sdf      generate/grid.rs:265-378
 //   closest_points / grid_closest_points                       nearest triangle + closest point (no reference counterpart; m2s.h)
 //   winding_numbers / grid_winding_numbers / generate_grid_sdf_winding   generalized winding numbers and their sign (m2s.h)
+//   cast_rays / count_intersections / test_occlusions   watertight ray casting against the mesh (m2s.h)
 //   sample_grid / raymarch_grid  client draw_raymarching.wgsl  sdf_grid / estimate_normal / sdf_3d on a finished grid (m2s.h)
 //   grid_isosurface                                            marching-cubes mesh of a level set of a finished grid (no reference counterpart; m2s.h)
 //   serde::*               serde.rs:75-221                     SerializeSdf / DeserializeSdf / save_to_file / read_from_file
@@ -23,6 +24,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -335,6 +337,56 @@ std::vector<float> generate_grid_sdf_winding(const std::vector<V>& vertices, con
   detail::check(m2s_grid_winding_numbers(v.ptr, vertices.size(), ia.ptr, indices.count, ia.bytes, indices.kind, &grid.raw(), beta, threshold,
                                          nullptr, d.data(), nullptr));
   return d;
+}
+
+// ---- ray casting against the mesh (m2s_cast_rays) -------------------------------------------------------------------------------
+// The watertight test of Woop, Benthin and Wald, defined to the bit (m2s.h): per ray o + t d, t_min <= t <= t_max, the first hit (t = +inf,
+// triangle = UINT32_MAX, uv = NaN when none), the number of triangles hit, or whether anything is in the way.  Directions are used as
+// given, so t is in units of |d|.
+struct RayHits {
+  std::vector<float> t;
+  std::vector<uint32_t> triangle;
+  std::vector<std::array<float, 2>> uv;   // hit = a + u (b - a) + v (c - a)
+};
+namespace detail {
+template <class V, class I>
+void cast_rays_call(const std::vector<V>& vertices, const Topology<I>& indices, const std::vector<V>& origins, const std::vector<V>& directions,
+                    float t_min, float t_max, float* t, uint32_t* triangle, float* uv, uint32_t* count, uint8_t* occluded) {
+  if (origins.size() != directions.size()) throw Panic(M2S_ERR_BAD_ARG, "origins and directions differ in length");
+  Packed<V> v(vertices.data(), vertices.size()), o(origins.data(), origins.size()), d(directions.data(), directions.size());
+  IndexArg<I> ia(indices);
+  const m2s_ray_opts ro = {sizeof(m2s_ray_opts), t_min, t_max};
+  check(m2s_cast_rays(v.ptr, vertices.size(), ia.ptr, indices.count, ia.bytes, indices.kind, o.ptr, d.ptr, origins.size(), &ro, t, triangle, uv,
+                      count, occluded, nullptr));
+}
+}  // namespace detail
+template <class V, class I = uint32_t>
+RayHits cast_rays(const std::vector<V>& vertices, const Topology<I>& indices, const std::vector<V>& origins, const std::vector<V>& directions,
+                  float t_min = 0.0f, float t_max = std::numeric_limits<float>::infinity()) {
+  RayHits r;
+  r.t.resize(origins.size());
+  r.triangle.resize(origins.size());
+  r.uv.resize(origins.size());
+  detail::cast_rays_call(vertices, indices, origins, directions, t_min, t_max, r.t.data(), r.triangle.data(),
+                         r.uv.empty() ? nullptr : r.uv.data()->data(), nullptr, nullptr);
+  return r;
+}
+// A ray through a shared edge or vertex counts every triangle that includes it.
+template <class V, class I = uint32_t>
+std::vector<uint32_t> count_intersections(const std::vector<V>& vertices, const Topology<I>& indices, const std::vector<V>& origins,
+                                          const std::vector<V>& directions, float t_min = 0.0f,
+                                          float t_max = std::numeric_limits<float>::infinity()) {
+  std::vector<uint32_t> n(origins.size());
+  detail::cast_rays_call(vertices, indices, origins, directions, t_min, t_max, nullptr, nullptr, nullptr, n.data(), nullptr);
+  return n;
+}
+template <class V, class I = uint32_t>
+std::vector<uint8_t> test_occlusions(const std::vector<V>& vertices, const Topology<I>& indices, const std::vector<V>& origins,
+                                     const std::vector<V>& directions, float t_min = 0.0f,
+                                     float t_max = std::numeric_limits<float>::infinity()) {
+  std::vector<uint8_t> occ(origins.size());
+  detail::cast_rays_call(vertices, indices, origins, directions, t_min, t_max, nullptr, nullptr, nullptr, nullptr, occ.data());
+  return occ;
 }
 
 // ---- queries on a finished grid (m2s_sample_grid, m2s_raymarch_grid) ------------------------------------------------------

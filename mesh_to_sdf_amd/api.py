@@ -15,7 +15,7 @@ stream, nothing crosses PCIe).  Where the reference panics this raises M2SPanic.
 import ctypes as C
 import enum
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -417,6 +417,76 @@ def generate_grid_sdf_winding(vertices, indices: Topology, grid: "Grid", *, beta
                               algorithm: int = 0, timings: M2STimings = None, x_slab: Sequence[int] = None, out=None):
     """generate_sdf_winding for the cell centres of `grid`."""
     return _one_shot_winding_grid(vertices, indices, grid, beta, threshold, True, timings, algorithm, x_slab, out)
+
+
+class RayHits(NamedTuple):
+    """First hit of every ray: t f32[n] (+inf: none), triangle uint32[n] (0xFFFFFFFF: none), uv f32[n, 2] (NaN: none)."""
+    t: object
+    triangle: object
+    uv: object
+
+
+def _ray_call(call, a, origins, directions, t_min, t_max, want, timings, algorithm, synchronous=True):
+    """One ray call, `call(p_org, p_dir, n, ropts, p_t, p_tri, p_uv, p_count, p_occ, opts)`; `want` names the outputs: "hits" (t, triangle,
+    uv), "count" or "occluded".  Returns the arrays asked for, on the side of `a`."""
+    org, n, p_org = _queries_of(a, origins)
+    dirs, n_d, p_dir = _queries_of(a, directions)
+    if n != n_d:
+        raise M2SPanic(_lib.ERR_BAD_ARG, "origins and directions differ in length (%d, %d)" % (n, n_d))
+    ro = _lib.M2SRayOpts(C.sizeof(_lib.M2SRayOpts), float(t_min), float(t_max))
+
+    def buf(shape, np_dtype, torch_dtype):
+        x = a.torch.empty(shape, dtype=getattr(a.torch, torch_dtype), device=a.dev) if a.device else np.empty(shape, np_dtype)
+        return x, ((x.data_ptr() if a.device else x.ctypes.data) if n else None)
+
+    ptrs = [None] * 5
+    if want == "hits":
+        (t, ptrs[0]), (tri, ptrs[1]), (uv, ptrs[2]) = buf(n, np.float32, "float32"), buf(n, np.uint32, "int32"), buf((n, 2), np.float32, "float32")
+        if a.device and hasattr(a.torch, "uint32"):
+            tri = tri.view(a.torch.uint32)
+        res = RayHits(t, tri, uv)
+    elif want == "count":
+        res, ptrs[3] = buf(n, np.uint32, "int32")
+    else:
+        res, ptrs[4] = buf(n, np.uint8, "uint8")
+    o = a.opts(timings, algorithm, synchronous=synchronous or not a.device)
+    rc = call(p_org, p_dir, n, C.byref(ro), *ptrs, C.byref(o))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    if want == "occluded":
+        return res.bool() if a.device else res.astype(bool)
+    return res
+
+
+def _one_shot_rays(vertices, indices, origins, directions, t_min, t_max, want, timings, algorithm):
+    a = _Args(vertices, indices)
+    L = _lib.lib()
+    return _ray_call(lambda *r: L.m2s_cast_rays(a.p_verts, a.n_verts, a.p_idx, a.n_idx, a.index_bytes, a.topology, *r), a, origins, directions,
+                     t_min, t_max, want, timings, algorithm)
+
+
+def cast_rays(vertices, indices: Topology, origins, directions, t_min: float = 0.0, t_max: float = float("inf"), algorithm: int = 0, *,
+              timings: M2STimings = None) -> RayHits:
+    """First hit of every ray o + t d, t_min <= t <= t_max, on the mesh (include/m2s.h m2s_cast_rays): RayHits(t, triangle, uv) with the
+    watertight test of Woop, Benthin and Wald, defined to the bit.  `directions` are used as given, so t is in units of |d|; the triangle
+    index is in Topology order (the lowest index on exact ties of t); hit = a + u (b - a) + v (c - a).  `algorithm=1`: every triangle for
+    every ray, no tree.  Host arrays or device tensors, as the other calls take them."""
+    return _one_shot_rays(vertices, indices, origins, directions, t_min, t_max, "hits", timings, algorithm)
+
+
+def count_intersections(vertices, indices: Topology, origins, directions, t_min: float = 0.0, t_max: float = float("inf"), algorithm: int = 0,
+                        *, timings: M2STimings = None):
+    """Number of triangles every ray hits in range, uint32[n].  A ray through a shared edge or vertex counts every triangle that includes it."""
+    return _one_shot_rays(vertices, indices, origins, directions, t_min, t_max, "count", timings, algorithm)
+
+
+def test_occlusions(vertices, indices: Topology, origins, directions, t_min: float = 0.0, t_max: float = float("inf"), algorithm: int = 0, *,
+                    timings: M2STimings = None):
+    """bool[n]: is anything in the way of the ray within [t_min, t_max].  The walk stops at a ray's first hit."""
+    return _one_shot_rays(vertices, indices, origins, directions, t_min, t_max, "occluded", timings, algorithm)
+
+
+test_occlusions.__test__ = False   # (a public name that starts with "test": not a test for pytest to collect)
 
 
 class SampleMode(enum.IntEnum):
@@ -979,6 +1049,24 @@ class Mesh:
     def generate_grid_sdf_winding(self, grid: Grid, *, beta: float = WINDING_BETA_DEFAULT, threshold: float = 0.5, algorithm: int = 0,
                                   timings: M2STimings = None, x_slab: Sequence[int] = None, out=None, synchronous: bool = True):
         return self._mesh_winding_grid(grid, beta, threshold, True, timings, algorithm, x_slab, out, synchronous)
+
+    def _mesh_rays(self, origins, directions, t_min, t_max, want, timings, algorithm, synchronous):
+        L = _lib.lib()
+        return _ray_call(lambda *r: L.m2s_mesh_cast_rays(self._h, *r), self._a, origins, directions, t_min, t_max, want, timings, algorithm,
+                         synchronous)
+
+    def cast_rays(self, origins, directions, t_min: float = 0.0, t_max: float = float("inf"), algorithm: int = 0, *,
+                  timings: M2STimings = None, synchronous: bool = True) -> RayHits:
+        """cast_rays on the resident tree as it is (no build, no re-marking of its leaves): the same bits as the one-shot function."""
+        return self._mesh_rays(origins, directions, t_min, t_max, "hits", timings, algorithm, synchronous)
+
+    def count_intersections(self, origins, directions, t_min: float = 0.0, t_max: float = float("inf"), algorithm: int = 0, *,
+                            timings: M2STimings = None, synchronous: bool = True):
+        return self._mesh_rays(origins, directions, t_min, t_max, "count", timings, algorithm, synchronous)
+
+    def test_occlusions(self, origins, directions, t_min: float = 0.0, t_max: float = float("inf"), algorithm: int = 0, *,
+                        timings: M2STimings = None, synchronous: bool = True):
+        return self._mesh_rays(origins, directions, t_min, t_max, "occluded", timings, algorithm, synchronous)
 
     def debug_digest(self):
         """FNV-1a digests of the resident arrays (test hook `m2s_debug_mesh_digest`): triangle records, pre-test planes, box nodes,

@@ -1151,6 +1151,73 @@ int finish_winding(const CallCtx& c, DeviceState& st, int* d_err, size_t n_tris,
   return rc;
 }
 
+// ---- ray casting (m2s_cast_rays, m2s_mesh_cast_rays) ---------------------------------------------------------------------------------
+// One kernel on the call's stream (rays.hip), ev[4] .. ev[3] = distance_ms.
+struct RayArgs {
+  float* t;
+  uint32_t* tri;
+  float* uv;
+  uint32_t* count;
+  uint8_t* occluded;
+  float t_min, t_max;
+};
+
+int check_ray_args(const m2s_ray_opts* ropts, const float* origins, const float* directions, size_t n_rays, const m2s_opts* opts, RayArgs* o) {
+  if (ropts) {
+    if (ropts->struct_size < sizeof(m2s_ray_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_ray_opts.struct_size too small");
+    o->t_min = ropts->t_min;
+    o->t_max = ropts->t_max;
+  }
+  if (!(o->t_min <= o->t_max)) return fail(M2S_ERR_BAD_ARG, "ray range needs t_min <= t_max, neither NaN (got %g, %g)", (double)o->t_min, (double)o->t_max);
+  // (without rays nothing is written, so callers whose empty arrays have no address pass)
+  if (n_rays && !o->t && !o->tri && !o->uv && !o->count && !o->occluded) return fail(M2S_ERR_BAD_ARG, "every ray output is NULL");
+  if (n_rays && (!origins || !directions)) return fail(M2S_ERR_BAD_ARG, "origins / directions is NULL");
+  if (n_rays >= 0xffffffc0ull) return fail(M2S_ERR_BAD_ARG, "too many rays for one call");
+  if (opts && (opts->x_begin != 0 || opts->x_end != 0)) return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_begin / x_end do not apply to ray calls");
+  if (opts && opts->struct_size >= sizeof(m2s_opts) && (opts->x_period != 0 || opts->n_peer_out != 0 || opts->peer_out != nullptr))
+    return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_period / peer_out do not apply to ray calls");
+  if (opts && opts->mem_kind != M2S_MEM_HOST && opts->mem_kind != M2S_MEM_DEVICE) return fail(M2S_ERR_BAD_ARG, "bad mem_kind");
+  if (opts && opts->algorithm != 0 && opts->algorithm != 1) return fail(M2S_ERR_BAD_ARG, "bad algorithm");
+  return 0;
+}
+
+size_t ray_workspace_bytes(const CallCtx& c, size_t n) {
+  return (c.mem_kind == M2S_MEM_HOST ? 2 * align_up(n * 12) + 3 * align_up(n * 4) + align_up(n * 8) + align_up(n) : 0) + 2048;
+}
+
+// Rays to the device (host memory), the kernel, results back.  `mesh` may be empty (n_tris == 0): every ray then reports no hit.
+int run_cast_rays(Arena& ws, const CallCtx& c, DeviceState& st, const DeviceMesh& mesh, const float* origins, const float* directions, size_t n,
+                  const RayArgs& o) {
+  const float *d_org = origins, *d_dir = directions;
+  RayOut d{o.t, o.tri, o.uv, o.count, o.occluded};
+  int rc = 0;
+  if (c.mem_kind == M2S_MEM_HOST) {
+    float* org = ws.take<float>(3 * n);
+    float* dir = ws.take<float>(3 * n);
+    d.t = o.t ? ws.take<float>(n) : nullptr;
+    d.tri = o.tri ? ws.take<uint32_t>(n) : nullptr;
+    d.uv = o.uv ? ws.take<float>(2 * n) : nullptr;
+    d.count = o.count ? ws.take<uint32_t>(n) : nullptr;
+    d.occluded = o.occluded ? ws.take<uint8_t>(n) : nullptr;
+    if (!org || !dir || (o.t && !d.t) || (o.tri && !d.tri) || (o.uv && !d.uv) || (o.count && !d.count) || (o.occluded && !d.occluded))
+      return fail(M2S_ERR_HIP, "internal: workspace");
+    if ((rc = staged_h2d(st, c.stream, reinterpret_cast<char*>(org), reinterpret_cast<const char*>(origins), n * 12))) return rc;
+    if ((rc = staged_h2d(st, c.stream, reinterpret_cast<char*>(dir), reinterpret_cast<const char*>(directions), n * 12))) return rc;
+    d_org = org;
+    d_dir = dir;
+  }
+  M2S_HIP_CHECK(hipEventRecord(st.ev[4], c.stream));
+  if ((rc = launch_cast_rays(c.stream, mesh, d_org, d_dir, n, o.t_min, o.t_max, c.algorithm, d))) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st.ev[3], c.stream));
+  if (c.mem_kind == M2S_MEM_DEVICE) return 0;
+  if (o.t && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.t), reinterpret_cast<const char*>(d.t), n * 4))) return rc;
+  if (o.tri && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.tri), reinterpret_cast<const char*>(d.tri), n * 4))) return rc;
+  if (o.uv && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.uv), reinterpret_cast<const char*>(d.uv), n * 8))) return rc;
+  if (o.count && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.count), reinterpret_cast<const char*>(d.count), n * 4))) return rc;
+  if (o.occluded && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.occluded), reinterpret_cast<const char*>(d.occluded), n))) return rc;
+  return 0;
+}
+
 // An asynchronous call on a mesh: its event pair ev[4] .. ev[3] moves into the mesh's pending list (m2s_mesh_drain_timings waits for it
 // and adds the span up), and the context gets fresh events for the next call.
 int park_async_events(m2s_mesh* m, DeviceState& st, uint64_t units, uint32_t launches) {
@@ -1589,6 +1656,7 @@ int m2s_warmup(int device, size_t workspace_bytes, size_t host_ring_bytes) {
   warm_serde(c.stream);
   warm_client(c.stream);
   warm_grid_query(c.stream);
+  warm_rays(c.stream);
   warm_sortlib(c.stream);                                        // (the rocPRIM sorts of large meshes and of the query path: units of their own,
   warm_sortlib_query(c.stream);                                  // which a grid call over a mesh of <= 229 376 triangles never loads)
   M2S_HIP_CHECK(hipGetLastError());
@@ -2226,6 +2294,77 @@ int m2s_mesh_grid_winding_numbers(m2s_mesh* m, const m2s_grid* grid, float beta,
   if ((rc = run_grid_winding(ws, c, *st, m->dm, moms, g, slab_cells, o, d_err))) return rc;
   if (!c.sync) return park_async_events(m, *st, slab_cells, o.sdf ? 2 : 1);
   return finish_winding(c, *st, d_err, m->n_tris, slab_cells, o);
+}
+
+// Ray casting (include/m2s.h): the one-shot call builds the tree, the mesh call walks the resident one as it is marked.
+int m2s_cast_rays(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology,
+                  const float* origins, const float* directions, size_t n_rays, const m2s_ray_opts* ropts, float* t_out, uint32_t* triangle_out,
+                  float* uv_out, uint32_t* count_out, uint8_t* occluded_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  RayArgs o{t_out, triangle_out, uv_out, count_out, occluded_out, 0.0f, __builtin_inff()};
+  int rc = check_mesh_args(vertices, n_vertices, indices, n_indices, index_bytes, topology);
+  if (rc) return rc;
+  if ((rc = check_ray_args(ropts, origins, directions, n_rays, opts, &o))) return rc;
+  const size_t n_tris = m2s_triangle_count(n_vertices, n_indices, indices != nullptr, topology);
+  if (!opts || opts->mem_kind == M2S_MEM_HOST) {
+    if ((rc = check_host_indices(indices, n_indices, index_bytes, topology, n_vertices, n_tris))) return rc;
+  }
+  if (n_rays == 0) return M2S_OK;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(opts, &c, &st))) return rc;
+  size_t need = (n_tris ? bvh_workspace_bytes(n_tris) : 0) + ray_workspace_bytes(c, n_rays) + 4096;
+  if (c.mem_kind == M2S_MEM_HOST) need += align_up(n_vertices * 12) + align_up(n_indices * (size_t)(indices ? index_bytes : 0)) + 1024;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  DeviceMesh mesh{};   // without triangles: no tree, and every ray reports no hit
+  if (n_tris) {
+    StagedMesh sm;
+    if ((rc = stage_mesh(ws, c, vertices, n_vertices, indices, n_indices, index_bytes, &sm))) return rc;
+    M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+    rc = build_device_mesh(ws, c.stream, sm.d_verts, n_vertices, sm.d_indices, n_indices, index_bytes, topology, n_tris, d_err, &mesh,
+                           nullptr, false, query_leaf_max(n_rays, n_tris, SIGN_NONE));
+    if (rc) return rc;
+  }
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  st->planes_done = nullptr;
+  if ((rc = run_cast_rays(ws, c, *st, mesh, origins, directions, n_rays, o))) return rc;
+  return finish_call(c, *st, d_err, c.timings, n_tris, n_rays, false, true);
+}
+
+int m2s_mesh_cast_rays(m2s_mesh* m, const float* origins, const float* directions, size_t n_rays, const m2s_ray_opts* ropts, float* t_out,
+                       uint32_t* triangle_out, float* uv_out, uint32_t* count_out, uint8_t* occluded_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  if (!m) return fail(M2S_ERR_BAD_ARG, "mesh is NULL");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  RayArgs o{t_out, triangle_out, uv_out, count_out, occluded_out, 0.0f, __builtin_inff()};
+  int rc = check_ray_args(ropts, origins, directions, n_rays, opts, &o);
+  if (rc) return rc;
+  m2s_opts mo;
+  if ((rc = mesh_call_opts(m, opts, &mo))) return rc;
+  if (n_rays == 0) return M2S_OK;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(&mo, &c, &st))) return rc;
+  if ((rc = ensure_capacity(*st, ray_workspace_bytes(c, n_rays) + 8192))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  if (c.sync) M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  else d_err = m->d_err_async;   // asynchronous calls report through the mesh (m2s_mesh_drain_timings)
+  if (!c.sync) reap_pending(m, false);
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  st->planes_done = nullptr;
+  DeviceMesh none{};
+  if (m->n_tris && (rc = remark_leaves(m, c, m->dm.leaf_max))) return rc;   // the tree as it is marked; keeps the mesh's stream bookkeeping
+  if ((rc = run_cast_rays(ws, c, *st, m->n_tris ? m->dm : none, origins, directions, n_rays, o))) return rc;
+  if (!c.sync) return park_async_events(m, *st, n_rays, 1);
+  return finish_call(c, *st, d_err, c.timings, m->n_tris, n_rays, false, true);
 }
 
 // Peer-write bandwidth probe (include/m2s.h): the copy kernel of M2S_PEER_PUSH, timed with HIP events on a stream of its own.

@@ -230,6 +230,7 @@ void warm_client(hipStream_t st);
 void warm_sortlib(hipStream_t st);
 void warm_sortlib_query(hipStream_t st);
 void warm_grid_query(hipStream_t st);
+void warm_rays(hipStream_t st);
 // bvh.hip: flatten topology, build triangle records + LBVH in pre-order layout.
 size_t bvh_workspace_bytes(size_t n_tris);
 // `after_setup` (optional) is called twice with the input-order centroid array and triangle records: with phase 0 once the kernels that fill
@@ -394,6 +395,18 @@ int launch_winding_grid(hipStream_t st, const DeviceMesh& mesh, const NodeMom* m
 int launch_winding_queries(hipStream_t st, const DeviceMesh& mesh, const NodeMom* moms, const float* d_queries, const uint32_t* perm, size_t n_q,
                            float beta, float threshold, const float* d_dist, int algorithm, const WindingOut& out);
 
+
+// rays.hip: watertight ray casting against the mesh.  Each output may be nullptr; entries are per ray, in input order.
+struct RayOut {
+  float* t;            // smallest t in range, +inf when none
+  uint32_t* tri;       // the triangle attaining it (input order), 0xffffffff when none
+  float* uv;           // 2 per ray: barycentric weights of b and c, NaN when none
+  uint32_t* count;     // hits in range
+  uint8_t* occluded;   // 1 iff count > 0
+};
+// One ray per lane over the tree as it is marked; algorithm 1: every triangle for every ray.  A mesh with n_tris == 0 gives "no hit".
+int launch_cast_rays(hipStream_t st, const DeviceMesh& mesh, const float* d_org, const float* d_dir, size_t n_rays, float t_min, float t_max,
+                     int algorithm, const RayOut& out);
 
 // grid_query.hip: sampling and ray-marching a finished grid SDF (the client's draw_raymarching.wgsl).  The grid's scalars travel as a
 // kernel argument; start / end are the shader's uniforms (first_cell, Grid::get_last_cell), n[] >= 1, cs[] > 0 and finite.

@@ -1,6 +1,7 @@
-// geo_probe.hip — HOST build of the device math in geo.hip.h, for CPU unit tests only
-// (tests/test_device_math_host.py).  Not linked into libm2s_hip.so.
+// geo_probe.hip — HOST build of the device math in geo.hip.h and ray.hip.h, for CPU unit tests only
+// (tests/test_device_math_host.py, tests/test_rays_cpu.py).  Not linked into libm2s_hip.so.
 #include "geo.hip.h"
+#include "ray.hip.h"
 
 using namespace m2s;
 
@@ -31,5 +32,20 @@ void probe_tri_box(const float* a, const float* b, const float* c, float* mn, fl
   f3 lo, hi;
   triangle_bounding_box(mk3(a[0], a[1], a[2]), mk3(b[0], b[1], b[2]), mk3(c[0], c[1], c[2]), &lo, &hi);
   mn[0] = lo.x; mn[1] = lo.y; mn[2] = lo.z; mx[0] = hi.x; mx[1] = hi.y; mx[2] = hi.z;
+}
+// ray.hip.h: k = (kx, ky, kz), s = (Sx, Sy, Sz); returns RaySetup::valid
+int probe_ray_setup(const float* o, const float* d, int* k, float* s) {
+  const RaySetup r = ray_setup(mk3(o[0], o[1], o[2]), mk3(d[0], d[1], d[2]));
+  k[0] = r.kx; k[1] = r.ky; k[2] = r.kz;
+  s[0] = r.Sx; s[1] = r.Sy; s[2] = r.Sz;
+  return r.valid ? 1 : 0;
+}
+// tuv = (t, u, v) where the ray's line meets the triangle (det != 0, signs agree), else untouched; returns 1 iff the ray is valid and
+// hits within [t_min, t_max]
+int probe_ray_triangle(const float* o, const float* d, const float* a, const float* b, const float* c, float t_min, float t_max, float* tuv) {
+  const f3 O = mk3(o[0], o[1], o[2]);
+  const RaySetup r = ray_setup(O, mk3(d[0], d[1], d[2]));
+  const bool hit = ray_triangle_in_range(r, O, mk3(a[0], a[1], a[2]), mk3(b[0], b[1], b[2]), mk3(c[0], c[1], c[2]), t_min, t_max, &tuv[0], &tuv[1], &tuv[2]);
+  return (r.valid && hit) ? 1 : 0;
 }
 }
