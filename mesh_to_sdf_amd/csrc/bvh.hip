@@ -3,7 +3,7 @@
 // Replaces, as behaviour, Topology::get_triangles (lib.rs:175-193) and the acceleration
 // structures the reference builds inside every call (bvh 0.10 Bvh::build_par at
 // generate/grid.rs:95-111, generic/bvh.rs:74; rstar bulk_load at generic/rtree.rs:111): they
-// only select candidates, the kernels in distance.hip take the exact minimum.
+// only select candidates, the kernels in distance.hip and brute.hip take the exact minimum.
 //
 // Pipeline (all on the call's stream, no host round trip):
 //   k_tri_setup     : indices -> (a,b,c), degeneracy class, padded box (geo.rs:4-22), scene bounds

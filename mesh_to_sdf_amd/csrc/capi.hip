@@ -1379,7 +1379,7 @@ int m2s_generate_grid_sdf(const float* vertices, size_t n_vertices, const void* 
   st->have_raw_seeds = false;
   const uint32_t* plane = nullptr;
   st->early_planes = false;
-  // tiny problems (cells x triangles small): all voxels against all triangles, no tree (distance.hip k_brute_split)
+  // tiny problems (cells x triangles small): all voxels against all triangles, no tree (brute.hip k_brute_split)
   const bool stats = tuning().stats != 0;
   const bool tiny = grid_is_tiny(g, n_tris, c.algorithm, sign_method == M2S_SIGN_RAYCAST) && !stats;
   const bool beside = !tiny && c.algorithm == 0 && !stats && grid_walk_wants_seeds(g, n_tris, c.algorithm);
@@ -1546,7 +1546,7 @@ int m2s_generate_sdf(const float* vertices, size_t n_vertices, const void* indic
     hc.done("m2s_generate_sdf (small query set)");
     return rc;
   }
-  // What the queries need before the walk — bounding box, Morton keys, sort, packet table, gather (distance.hip prepare_query_walk) — does
+  // What the queries need before the walk — bounding box, Morton keys, sort, packet table, gather (query_order.hip prepare_query_walk) — does
   // not need the tree: a synchronous call runs it on the side stream beside the build
   QueryPlan qplan;
   const bool beside = algorithm == 0 && n_tris != 0 && n_queries >= 32768 && side_stream_wanted(c.sync) && !tuning().stats;
@@ -1653,6 +1653,11 @@ int m2s_warmup(int device, size_t workspace_bytes, size_t host_ring_bytes) {
   warm_bvh(c.stream);                                            // one empty kernel per translation unit: the runtime loads a code object
   warm_sign(c.stream);                                           // (all the unit's kernels) at the first launch out of it
   warm_distance(c.stream);
+  warm_seeds(c.stream);                                          // (the stages of a distance call: units of their own)
+  warm_cut(c.stream);
+  warm_brute(c.stream);
+  warm_query_order(c.stream);
+  warm_peer_push(c.stream);
   warm_serde(c.stream);
   warm_client(c.stream);
   warm_grid_query(c.stream);
@@ -2464,7 +2469,7 @@ int m2s_debug_mesh_digest(m2s_mesh* m, uint64_t out[8]) {
   return M2S_OK;
 }
 
-// Test hook (not part of include/m2s.h): the cut-list word of one range and what the walk decodes from it (distance.hip CutList) —
+// Test hook (not part of include/m2s.h): the cut-list word of one range and what the walk decodes from it (dist.hip.h CutList) —
 // host arithmetic only, no device needed.  tests/test_capi_cpu.py checks the superset property for every tree size.
 int m2s_debug_cut_code(uint32_t n_nodes, uint32_t start, uint32_t len, uint32_t out[3]) {
   g_err[0] = 0;

@@ -109,11 +109,11 @@ struct GridParams {
   // brick is as close to a cube in WORLD space as powers of two allow (anisotropic cell sizes): the walk's cost
   // grows with the brick's diameter, not its voxel count.
   uint32_t bl[3];
-  // ceil(2^32 / d) for d = super-bricks along z and along y (distance.hip brick_coords divides a packet's super-brick
+  // ceil(2^32 / d) for d = super-bricks along z and along y (walk.hip.h brick_coords divides a packet's super-brick
   // index by them: one multiply-high instead of a 30-instruction u32 division per wave); 0 = divide (d == 1, or a grid so
   // large that the product could be off by one)
   uint32_t sz_magic, sy_magic;
-  uint32_t xl_cap;   // 0: super-bricks up to 8 bricks wide in x (distance.hip super_brick_xlog); k: at most 2^(k-1) bricks wide, so
+  uint32_t xl_cap;   // 0: super-bricks up to 8 bricks wide in x (walk.hip.h super_brick_xlog); k: at most 2^(k-1) bricks wide, so
                      // that the x-layers of a slab are finished in order at that granularity (M2S_PEER_TRAIL)
   // Interleaved slab (m2s_opts.x_period): the call owns the chunks [xb + j * period, xb + j * period + 2^chunk_log), j = 0, 1, ...
   // [xb, xe) then is the VIRTUAL slab — the chunks laid end to end — which is what bricks, seeds and cut lists are numbered
@@ -225,6 +225,11 @@ hipError_t select_flagged_indices(void* tmp, size_t& bytes, const uint8_t* flags
 void warm_bvh(hipStream_t st);
 void warm_sign(hipStream_t st);
 void warm_distance(hipStream_t st);
+void warm_seeds(hipStream_t st);
+void warm_cut(hipStream_t st);
+void warm_brute(hipStream_t st);
+void warm_query_order(hipStream_t st);
+void warm_peer_push(hipStream_t st);
 void warm_serde(hipStream_t st);
 void warm_client(hipStream_t st);
 void warm_sortlib(hipStream_t st);
@@ -253,7 +258,8 @@ size_t sign_workspace_bytes(const GridParams& g, size_t n_tris);
 int build_grid_sign_plane(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const GridParams& g,
                           const uint32_t** d_inside_plane, bool slab_only);
 
-// distance.hip
+// distance.hip: the walks and their policy — which path a call takes, what it needs prepared, the launches.  The stages it strings together
+// are units of their own: seeds.hip, cut.hip, brute.hip, query_order.hip, peer_push.hip (marked below).
 size_t grid_distance_workspace_bytes(const GridParams& g, size_t n_tris);
 // Split walk (distance.hip): a packet still walking when the launch runs dry hands the rest of its pre-order ranges to other waves.
 // `cnt`: [0] suspended packets (= accumulator slots taken), [1 + r] items in the list of follow-up round r (r = 1 ..),
@@ -297,7 +303,9 @@ struct GridWalkPlan {
   const uint2* group_top = nullptr;   // GROUP: the tree's top subtrees (k_tree_top)
   uint32_t* brute_acc = nullptr;      // ALL_PAIRS_SPLIT: per-voxel minima of k_brute_split; no seeds, no lists, no tree
 };
+// brute.hip: tiny problems take all voxels x all triangles, no tree
 bool grid_is_tiny(const GridParams& g, size_t n_tris, int algorithm, bool raycast);   // raycast: the call's sign rule (the limits differ)
+bool grid_is_tiny(const GridParams& g, size_t n_tris, int algorithm, bool raycast, const Tuning& tn);   // ... under the knobs `tn` (choose_grid_walk)
 // Seed lattice of a slab: one triangle id per packet brick (ids index the centroid array it was computed from).
 struct SeedLattice {
   uint32_t* ids = nullptr;
@@ -307,14 +315,30 @@ struct SeedLattice {
 };
 bool grid_walk_wants_seeds(const GridParams& g, size_t n_tris, int algorithm);
 uint32_t host_packet_bricks(const GridParams& g);   // packet bricks of the slab (= points of its seed lattice), padded to super-bricks
+// seeds.hip
 int launch_grid_seeds(Arena& ws, hipStream_t st, const float4* cen, uint32_t n_tris, const GridParams& g, SeedLattice* out);
+void launch_seed_remap(hipStream_t st, uint32_t* ids, size_t n, const uint32_t* slot_of, uint32_t n_tris);   // ids of input triangles -> sorted slots
+// cut.hip: the cut lists of a slab from its seed lattice (`lists`: CUT_WORDS words per packet brick; `coarse` set: in two levels) and of a
+// query set's packets (dist.hip.h has the format and the sizes)
+void launch_grid_cut(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, const uint32_t* seeds, uint32_t seed_shift, uint32_t seed_ny,
+                     uint32_t seed_nz, uint32_t* lists, uint32_t* coarse);
+void launch_query_cut(hipStream_t st, const DeviceMesh& mesh, const uint32_t* seeds, uint32_t launched, uint32_t* lists, const float4* centres,
+                      const uint32_t* table, const GridParams* d_lat);
+// brute.hip: what launch_grid_walk does on the paths ALL_PAIRS_SPLIT (`acc`: GridWalkPlan::brute_acc, preset to +inf; `real`: the slab's bricks
+// without padding) and ALL_PAIRS, and launch_query_walk for algorithm 1.  `plane`: the sign planes or nullptr.
+int launch_grid_brute_split(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, int mode, const uint32_t* plane, uint32_t* acc, uint32_t real,
+                            float* d_out, int* d_err, const PeerOut& peers);
+int launch_grid_brute(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, int mode, const uint32_t* plane, float* d_out, int* d_err,
+                      uint32_t packets, const PeerOut& peers);
+int launch_query_brute(hipStream_t st, const DeviceMesh& mesh, const float* d_queries, uint32_t n_q, int mode, int sign_src, float* d_out, int* d_err);
+// distance.hip
 int prepare_grid_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const GridParams& g, int algorithm, bool pipelined,
                       GridWalkPlan* plan, const SeedLattice* raw_seeds = nullptr);
 // `g` may be an x-piece of the slab the plan was prepared for, starting bx_off bricks into it (a multiple of 2 bricks).
 // `peers` (optional): buffers that receive the same values in the walk's epilogue (M2S_PEER_STORE).
 int launch_grid_walk(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, int mode, const uint32_t* d_inside_plane,
                      const GridWalkPlan& plan, uint32_t bx_off, float* d_out, int* d_err, const PeerOut* peers = nullptr);
-// M2S_PEER_PUSH: copies the cells [first, first + count) of the whole-grid buffer `src` to the same range of every peer
+// peer_push.hip.  M2S_PEER_PUSH: copies the cells [first, first + count) of the whole-grid buffer `src` to the same range of every peer
 // (16 B per lane where the range allows).
 int launch_push_cells(hipStream_t st, const float* src, const PeerOut& peers, uint64_t first, uint64_t count);
 // M2S_PEER_TRAIL: bricks per progress unit (log2), number of units of the slab, and the copy kernel that trails the walk.
@@ -322,18 +346,19 @@ uint32_t trail_unit_log(const GridParams& g);
 uint32_t trail_units(const GridParams& g);
 uint32_t trail_rows(const GridParams& g);
 int launch_push_trailing(hipStream_t st, const float* src, const PeerOut& peers, const GridParams& g, int* d_err);
-// Records `ev_before_final` (if non-null) between the seed passes and the final k_packet launch.
+// distance.hip.  Records `ev_before_final` (if non-null) between the seed passes and the final k_packet launch.
 int launch_grid_distance(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const GridParams& g, int mode,
                          const uint32_t* d_inside_plane, int algorithm, float* d_out, int* d_err,
                          hipEvent_t ev_before_final, hipEvent_t wait_before_final = nullptr, bool pipelined = false,
                          const SeedLattice* raw_seeds = nullptr, hipEvent_t wait_raw_seeds = nullptr,
                          const PeerOut* peers = nullptr);
-void cut_word_roundtrip(uint32_t n_nodes, uint32_t start, uint32_t len, uint32_t* word, uint32_t* first, uint32_t* end);   // test hook
-size_t query_workspace_bytes(size_t n_q);
+void cut_word_roundtrip(uint32_t n_nodes, uint32_t start, uint32_t len, uint32_t* word, uint32_t* first, uint32_t* end);   // cut.hip: test hook
+size_t query_workspace_bytes(size_t n_q);   // query_order.hip
+// brute.hip
 bool query_is_tiny(size_t n_q, size_t n_tris, int algorithm, int sign_src);   // small query sets: all queries x all triangles, no tree
 int launch_query_brute_split(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const float* d_queries, size_t n_q, int mode, int sign_src,
                              float* d_out, int* d_err);
-// What the walk of a generic query set needs besides the mesh (prepare_query_walk; device pointers into the call's arena).
+// What the walk of a generic query set needs besides the mesh (query_order.hip prepare_query_walk; device pointers into the call's arena).
 struct QueryPlan {
   size_t n_q = 0;
   const int* qb = nullptr;          // ordered-int bounding box of the queries
@@ -352,7 +377,8 @@ struct QuerySeeds {
 // `after_lattice` (optional): recorded on `st` once the bounding box and the lattice description are enqueued (what launch_query_seeds needs)
 int prepare_query_walk(Arena& ws, hipStream_t st, const float* d_queries, size_t n_q, size_t n_tris, int sign_src, int algorithm, QueryPlan* plan,
                        hipEvent_t after_lattice = nullptr);
-int launch_query_seeds(Arena& ws, hipStream_t st, const float4* cen, uint32_t n_tris, const QueryPlan& plan, bool raw, QuerySeeds* out);
+int launch_query_seeds(Arena& ws, hipStream_t st, const float4* cen, uint32_t n_tris, const QueryPlan& plan, bool raw, QuerySeeds* out);   // seeds.hip
+// distance.hip
 int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const float* d_queries, const QueryPlan& plan,
                       int mode, int sign_src, int algorithm, float* d_out, int* d_err, const QuerySeeds* pre = nullptr);
 int launch_query_distance(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const float* d_queries, size_t n_q,

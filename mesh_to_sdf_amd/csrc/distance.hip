@@ -1,20 +1,23 @@
-// distance.hip — nearest-triangle distance + sign resolve, the dominant kernels (gfx950).
+// distance.hip — nearest-triangle distance + sign resolve: the walks, the dominant kernels (gfx950), and their policy.
 //
 // Semantics: D(p) = min over ALL triangles of geo.rs:26-30 in the reference's
 // f32 operation order; sign by the rule the caller's SignMethod / AccelerationMethod selects.
 //
-// Two kernel families, same arithmetic (geo.hip.h):
-//   k_brute  : every point against every triangle, triangle records staged through LDS in tiles
-//              (AccelerationMethod::None, and the on-device cross-check of the BVH path).
 //   k_packet : one wave = 64 spatially adjacent points (a 4x4x4 brick of voxels, or 64 Morton-
 //              sorted queries).  The wave walks the stackless pre-order BVH TOGETHER: the node
 //              index is wave-uniform (SGPR), node and triangle records arrive through scalar
 //              loads, each lane tests its own point, and a subtree is skipped when the ballot of
 //              "my bound reaches this box" is empty.  No per-lane stack, no divergence, no gather.
+//   k_lane   : one point per lane, every lane on its own through the tree (k_lane_q: sorted queries).
 //
 // Pruning is conservative: a subtree is dropped only if its box is farther than the lane's
 // current best by a margin that covers f32 rounding of both the box test and the reference
 // arithmetic (see prune_bound), so the minimum is the brute-force minimum bit for bit.
+//
+// This unit also decides which path a call takes (choose_grid_walk) and strings the stages together (prepare_grid_walk,
+// launch_grid_walk, launch_query_walk).  The other stages are units of their own: seeds.hip (seed lattices), cut.hip (k_cut),
+// brute.hip (all pairs, same arithmetic: k_brute and the tiny paths), query_order.hip (Morton order and packets of generic
+// queries), peer_push.hip (copies to peer devices); dist.hip.h holds what they share.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -26,12 +29,11 @@
 #include "geo.hip.h"
 #include "tuning.h"
 #include "walk.hip.h"
+#include "dist.hip.h"
 
 namespace m2s {
 
 namespace {
-
-constexpr int TILE = 128;  // triangles per LDS tile in k_brute (12 KiB)
 
 template <int AXIS>
 __device__ __forceinline__ uint32_t stab_count(const DeviceMesh& mesh, f3 p) {
@@ -117,83 +119,6 @@ __device__ __forceinline__ uint32_t stab_count_dense(const DeviceMesh& mesh, f3 
   while (n != 0u) flush();
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   return hits[lane];
-}
-
-// ---- cut lists ------------------------------------------------------------------------------
-// A third of a packet's node tests fall on nodes much larger than the packet (512^3 x blob-100k: 46 of 158 on nodes
-// wider than 28 voxels, 69 on nodes wider than 14), and neighbouring packets repeat them with the same outcome.
-// k_cut walks that top part of the tree ONCE per block of 2^log bricks per axis, against a bound that holds for every
-// voxel of the block, and leaves at most CUT_MAX pre-order ranges [start, end) of NodeExt byte offsets per block: the
-// subtrees that can still matter there.  k_packet then walks those ranges instead of starting at the root.
-// A subtree is dropped only if   bound(block centre, subtree) - r_block  >  D + margins,   where D bounds the
-// distance of every voxel of the block to the seed triangle of its own packet (which k_packet evaluates first):
-// such a subtree cannot hold a triangle nearer than, or tied with, any voxel's final minimum.
-#ifndef M2S_CUT_MAX
-#define M2S_CUT_MAX 15   // 7: 12.0 ms, 15: 11.7 ms (512^3 x blob-100k)
-#endif
-// A list is ONE 64-byte record (round 2: 128 B of (start, end) byte offsets — 268 MB of lists for a 537 MB output):
-//   word 0        number of ranges
-//   word 1 + k    low S bits: start of range k (node record index), S = bits needed for the tree's node count; the other 32 - S bits:
-//                 its length as a small float — 5 bits of exponent e, M = 27 - S bits of mantissa m: m << e records, the smallest
-//                 such value that is >= the true length
-// Lengths below 2^M records are exact and longer ones exceed the truth by less than 2^-(M-1) (100 k triangles: M = 9, 0.4 %; 1 M: M = 6,
-// 3 %; the 2^25-triangle limit: M = 1): a superset of the subtrees, which a walk may always take, and one that hardly costs — a first
-// form with 6-bit power-of-two lengths walked up to twice a long range: 14 % more node tests and 4.8 % more time on 512^3 x blob-1M
-// (same box: 26.60 against 25.37 ms; the headline 8.40 against 8.43 ms).  A range that
-// reaches into the next one is walked there twice (harmless: a minimum).  k_cut writes a word when its range closes, as before (ranges
-// kept in LDS or scratch until the end and written as one record cost k_cut 20-35 %: five waves per SIMD, or scratch traffic).
-__host__ __device__ __forceinline__ uint32_t cut_start_bits(uint32_t n_nodes) {
-  uint32_t b = 1;
-  while (b < 27u && (1u << b) < n_nodes) ++b;
-  return b;
-}
-// length code: 5 bits of exponent e above M bits of mantissa, len = mantissa << e (explicit leading bit: no special case in the walk's
-// decode, which runs once per range of every packet on the scalar unit)
-__host__ __device__ __forceinline__ uint32_t cut_decode_len(uint32_t code, uint32_t M) { return (code & ((1u << M) - 1u)) << (code >> M); }
-__host__ __device__ __forceinline__ uint32_t cut_encode_len(uint32_t len, uint32_t M) { // smallest representable value >= len (len >= 1)
-  if (len < (1u << M)) return len;                                                      // exact, e = 0
-  uint32_t e = (32u - (uint32_t)__builtin_clz(len)) - M;                                // len >> e lies in [2^(M-1), 2^M)
-  uint32_t mant = (len + (1u << e) - 1u) >> e;
-  if (mant == (1u << M)) { mant >>= 1; ++e; }
-  return (e << M) | mant;
-}
-constexpr uint32_t CUT_MAX = M2S_CUT_MAX, CUT_WORDS = M2S_CUT_MAX + 1;
-static_assert(M2S_CUT_MAX <= 15, "the range count has four bits");
-struct CutList {
-  const uint32_t* lists;   // CUT_WORDS words per block, nullptr: walk the whole tree
-  uint32_t log, ny, nz;    // bricks per block per axis = 2^log; blocks along y and z
-  uint32_t bx_off;         // grid: this launch covers a piece of the slab the seed lattice and the lists were built for,
-                           // starting bx_off bricks into it along x (a multiple of 2^log)
-  const float4* centres;   // generic queries: (centre, radius) of every packet's bounding box (k_qpacket_bounds); one list per packet
-};
-
-// Generic queries: the sorted queries [first, first + cnt) of packet k (table of launch_query_distance / k_qcells).
-__device__ __forceinline__ bool query_packet_range(const uint32_t* __restrict__ table, uint32_t packet, uint32_t n_q,
-                                                   uint32_t* first, uint32_t* cnt) {
-  uint32_t f = packet * 64u, c = 64u;
-  if (table != nullptr) {
-    const uint32_t count = table[0];
-    if (packet >= count) return false;
-    if (table[1] == 0u) {
-      f = table[2u + packet];
-      c = (packet + 1u < count ? table[3u + packet] : n_q) - f;
-    }
-  }
-  if (f >= n_q) return false;
-  *first = f;
-  *cnt = min(c, n_q - f);
-  return true;
-}
-// Cell of the generic path's seed lattice that holds x (k_qlattice).
-__device__ __forceinline__ uint32_t query_lattice_cell(const GridParams& L, float x, float y, float z) {
-  const float q0[3] = {x, y, z};
-  uint32_t cell[3];
-  for (int k = 0; k < 3; ++k) {
-    float f = (q0[k] - L.first[k]) / L.size[k] + 0.5f;
-    f = (f == f) ? fminf(fmaxf(f, 0.0f), (float)(L.n[k] - 1)) : 0.0f;
-    cell[k] = min((uint32_t)f, L.n[k] - 1);
-  }
-  return (cell[0] * L.n[1] + cell[1]) * L.n[2] + cell[2];
 }
 
 // ---- the packet walk ------------------------------------------------------------------------
@@ -613,7 +538,7 @@ __device__ __forceinline__ void store_grid_result(float* __restrict__ out, size_
 
 // ---- k_packet -------------------------------------------------------------------------------
 // `seed_in` (one TriRec slot per 2^seed_shift bricks per axis, may be null) replaces the greedy descent:
-// the packet starts from a triangle near its own centre (jump-flooding seed pass below).
+// the packet starts from a triangle near its own centre (jump-flooding seed pass, seeds.hip).
 // (eight waves per SIMD: the split variant's bookkeeping would otherwise take the kernel to 106 SGPRs — seven waves, - 12 %; the
 // compiler parks what does not fit in spare VGPR lanes)
 template <bool GRID, int MODE, int SIGN, bool STATS, bool SPLIT, int DEFER = 0>
@@ -1009,75 +934,6 @@ __global__ void k_split_init(uint32_t* __restrict__ cnt, uint32_t forced) {
   for (uint32_t i = threadIdx.x; i < SPLIT_CNT_WORDS; i += blockDim.x) cnt[i] = i >= 16u ? forced : 0u;   // forced: every flag starts raised
 }
 
-// M2S_PEER_TRAIL: pushes the slab to the peers unit by unit while the walk is still running.  Unit u = the x-layers of
-// 2^unit_log bricks; it is complete when progress[u] has reached the number of packets that lie in it.  Every workgroup waits
-// for the unit (one lane polls, s_sleep between polls), then copies its share of it with 16 B per lane to every peer.
-// A walk that never finishes (a fault on its stream) would leave this kernel spinning: after ~2 s without progress it
-// raises ERRF_TRAIL_TIMEOUT and leaves.
-__global__ __launch_bounds__(256) void k_push_trailing(const float* __restrict__ src, PeerOut peers, uint64_t slab_first, uint64_t row_cells,
-                                                       uint32_t layers, uint32_t layers_per_unit, uint32_t n_units, int* __restrict__ err) {
-  __shared__ int ok;
-  for (uint32_t u = 0; u < n_units; ++u) {
-    if (threadIdx.x == 0) {
-      int good = 1;
-      uint32_t spins = 0;
-      while (__hip_atomic_load(&peers.progress[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < peers.rows) {   // all brick rows of the unit
-        __builtin_amdgcn_s_sleep(127);
-        if (++spins > 10000000u) { good = 0; atomicOr(err, ERRF_TRAIL_TIMEOUT); break; }
-      }
-      ok = good;
-    }
-    __syncthreads();
-    if (!ok) return;
-    const uint32_t x0 = u * layers_per_unit, x1 = min(layers, x0 + layers_per_unit);
-    const uint64_t first = slab_first + (uint64_t)x0 * row_cells, count = (uint64_t)(x1 - x0) * row_cells;
-    // row_cells * 4 B and the slab start need not be 16-byte multiples: head / body / tail as in k_push_cells
-    const uint64_t head = min(count, (uint64_t)((4u - (uint32_t)(first & 3u)) & 3u));
-    const uint64_t n4 = (count - head) >> 2, tail0 = head + (n4 << 2);
-    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (uint64_t)gridDim.x * blockDim.x;
-    // the values were written by waves on other XCDs: read them past this XCD's L2 (device-scope loads; they only exist in 32 bits)
-    const float* s1 = src + first + head;
-    for (uint64_t i = tid; i < n4; i += stride) {
-      float4 v;
-      v.x = __hip_atomic_load(s1 + 4 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      v.y = __hip_atomic_load(s1 + 4 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      v.z = __hip_atomic_load(s1 + 4 * i + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      v.w = __hip_atomic_load(s1 + 4 * i + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (uint32_t k = 0; k < peers.n; ++k) reinterpret_cast<float4*>(peers.p[k] + first + head)[i] = v;
-    }
-    if (tid < head) {
-      const float v = __hip_atomic_load(src + first + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (uint32_t k = 0; k < peers.n; ++k) peers.p[k][first + tid] = v;
-    }
-    if (tid < count - tail0) {
-      const float v = __hip_atomic_load(src + first + tail0 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (uint32_t k = 0; k < peers.n; ++k) peers.p[k][first + tail0 + tid] = v;
-    }
-    __syncthreads();                                         // `ok` is rewritten for the next unit
-  }
-}
-
-// M2S_PEER_PUSH: one slab piece of the finished whole-grid buffer to every peer, 16 B per lane.
-__global__ __launch_bounds__(256) void k_push_cells(const float* __restrict__ src, PeerOut peers, uint64_t first, uint64_t count) {
-  // head: up to the next 16-byte boundary; body: float4; tail: the rest
-  const uint64_t head = min(count, (uint64_t)((4u - (uint32_t)(first & 3u)) & 3u));
-  const uint64_t n4 = (count - head) >> 2, tail0 = head + (n4 << 2);
-  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (uint64_t)gridDim.x * blockDim.x;
-  const float4* s4 = reinterpret_cast<const float4*>(src + first + head);
-  for (uint64_t i = tid; i < n4; i += stride) {
-    const float4 v = s4[i];
-    for (uint32_t k = 0; k < peers.n; ++k) reinterpret_cast<float4*>(peers.p[k] + first + head)[i] = v;
-  }
-  if (tid < head) {
-    const float v = src[first + tid];
-    for (uint32_t k = 0; k < peers.n; ++k) peers.p[k][first + tid] = v;
-  }
-  if (tid < count - tail0) {
-    const float v = src[first + tail0 + tid];
-    for (uint32_t k = 0; k < peers.n; ++k) peers.p[k][first + tail0 + tid] = v;
-  }
-}
-
 // The lane walks gather per-lane records; the compiler's own choice (104 VGPRs, 4 waves per SIMD) hides less of that latency than six
 // waves with 96 bytes of scratch do: 128^3 x blob-1M 8.9 -> 7.7 ms, 1 M queries 2.75 -> 2.63 ms, the small cases unchanged.
 #ifndef M2S_LANE_WAVES
@@ -1278,248 +1134,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M2S_LANE_WA
   }
 }
 
-// ---- jump-flooding seed pass ------------------------------------------------------------------
-// Seeds only have to be GOOD, never exact (they bound the first prune, nothing else), so the seed
-// lattice (one point per 4^3 brick) is filled by jump flooding (Rong & Tan 2006) over triangle
-// CENTROIDS instead of a second exact tree walk: fully data parallel, cost proportional to the
-// lattice (no long-running waves), ~10 ops per candidate.  k_jfa_splat drops every triangle into
-// the lattice cell of its centroid (clamped, so triangles outside an x-slab still enter at the
-// border); each k_jfa_pass lets a cell adopt the best candidate of its 26 neighbours at +-step.
-__device__ __forceinline__ f3 lattice_point(const GridParams& g, uint32_t x, uint32_t y, uint32_t z) {
-  // x is numbered along the virtual slab (interleaved chunks laid end to end); g.xb of a lattice is 0
-  return {cell_center(g.first[0], g.size[0], slab_x(g, x)), cell_center(g.first[1], g.size[1], y), cell_center(g.first[2], g.size[2], z)};
-}
-// Lattice index along x (virtual numbering) of the point nearest to real position index `ir` (lattice units from the
-// slab's first point): inside another rank's chunks it is the nearer end of the neighbouring own chunk.
-__device__ __forceinline__ uint32_t lattice_x_from_real(const GridParams& g, float fr) {
-  if (g.chunk_log >= 31u) return min((uint32_t)fminf(fmaxf(fr, 0.0f), (float)(g.n[0] - 1u)), g.n[0] - 1u);
-  const float C = (float)(1u << g.chunk_log), P = (float)g.period;
-  fr = fmaxf(fr, 0.0f);
-  float j = floorf(fr / P), o = fr - j * P;                         // period, offset inside it
-  if (o >= C) {                                                      // between two own chunks
-    if (o - C < P - o) o = C - 1.0f;                                 // nearer to the end of chunk j
-    else { j += 1.0f; o = 0.0f; }                                    // nearer to the start of chunk j + 1
-  }
-  const float v = j * C + o;
-  return min((uint32_t)fminf(v, (float)(g.n[0] - 1u)), g.n[0] - 1u);
-}
-
-// `gp` (device pointer) overrides `g0` when the lattice is only known on the device (generic queries).
-__global__ __launch_bounds__(256) void k_jfa_splat(DeviceMesh mesh, GridParams g0, const GridParams* __restrict__ gp,
-                                                   unsigned long long* __restrict__ keys) {
-  const GridParams g = gp ? *gp : g0;
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= mesh.n_tris) return;
-  const float4 c = mesh.cen[t];
-  const float cc[3] = {c.x, c.y, c.z};
-  uint32_t cell[3];
-  for (int k = 0; k < 3; ++k) {
-    float f = (cc[k] - g.first[k]) / g.size[k] + 0.5f;
-    if (!(f == f)) return;                                   // NaN centroid: not a useful seed
-    if (k == 0) { cell[0] = lattice_x_from_real(g, f); continue; }
-    f = fminf(fmaxf(f, 0.0f), (float)(g.n[k] - 1));
-    cell[k] = min((uint32_t)f, g.n[k] - 1);
-  }
-  // several triangles land in one cell (all those clamped onto a border cell in particular): keep the one
-  // whose centroid is nearest to the cell centre — 64-bit min over (distance bits, slot)
-  const f3 p = lattice_point(g, cell[0], cell[1], cell[2]);
-  const float ex = p.x - c.x, ey = p.y - c.y, ez = p.z - c.z;
-  const float d2 = __builtin_fmaf(ex, ex, __builtin_fmaf(ey, ey, ez * ez));
-  if (!(d2 == d2)) return;
-  const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | t;
-  atomicMin(&keys[((size_t)cell[0] * g.n[1] + cell[1]) * g.n[2] + cell[2]], key);
-}
-
-// The lattice carries the candidate's centroid beside its id (xyz, id bits in w): a pass then reads 27 neighbouring 16-byte
-// records — structured, cache-friendly reads — instead of 27 ids plus a dependent random gather of each candidate's centroid.
-__global__ __launch_bounds__(256) void k_jfa_load(DeviceMesh mesh, const unsigned long long* __restrict__ keys, size_t n,
-                                                  float4* __restrict__ lat) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t id = (uint32_t)(keys[i] & 0xffffffffull);    // untouched cells hold ~0: id 0xffffffff = none
-  float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (id != 0xffffffffu) c = mesh.cen[id];
-  c.w = __uint_as_float(id);
-  lat[i] = c;
-}
-
-__global__ __launch_bounds__(256) void k_jfa_pass(GridParams g0, const GridParams* __restrict__ gp, const float4* __restrict__ in,
-                                                  float4* __restrict__ out, int step, uint32_t* __restrict__ ids_out) {
-  const GridParams g = gp ? *gp : g0;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t total = (size_t)g.n[0] * g.n[1] * g.n[2];
-  if (i >= total) return;
-  const int z = (int)(i % g.n[2]), y = (int)((i / g.n[2]) % g.n[1]), x = (int)(i / ((size_t)g.n[2] * g.n[1]));
-  const f3 p = lattice_point(g, (uint32_t)x, (uint32_t)y, (uint32_t)z);
-  uint32_t best = 0xffffffffu;
-  float4 bc = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xffffffffu));
-  float bd = __builtin_inff();
-  // Nine records per x-plane are requested TOGETHER (clamped addresses, validity as a flag) and only then compared.  Written with a
-  // `continue` per out-of-range or empty neighbour the loop was a chain of 27 dependent memory round trips per point — 56 us per pass of
-  // the 512^3 call's lattice, 400 us for 1024^3, whatever the cache hit rate (an LDS-tiled form was no faster for the same reason).
-  const int n0 = (int)g.n[0], n1 = (int)g.n[1], n2 = (int)g.n[2];
-#pragma unroll
-  for (int dx = -1; dx <= 1; ++dx) {
-    const int xx = x + dx * step;
-    const bool okx = xx >= 0 && xx < n0;
-    const size_t xbase = (size_t)min(max(xx, 0), n0 - 1) * (size_t)n1;
-    float4 c[9];
-    bool ok[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int yy = y + (k / 3 - 1) * step, zz = z + (k % 3 - 1) * step;
-      ok[k] = okx && yy >= 0 && yy < n1 && zz >= 0 && zz < n2;
-      c[k] = in[(xbase + (size_t)min(max(yy, 0), n1 - 1)) * (size_t)n2 + (size_t)min(max(zz, 0), n2 - 1)];
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const uint32_t cand = __float_as_uint(c[k].w);
-      const float ex = p.x - c[k].x, ey = p.y - c[k].y, ez = p.z - c[k].z;
-      const float d = __builtin_fmaf(ex, ex, __builtin_fmaf(ey, ey, ez * ez));
-      const bool take = ok[k] && cand != 0xffffffffu && (d < bd || (d == bd && cand < best));
-      bd = take ? d : bd;
-      best = take ? cand : best;
-      bc.x = take ? c[k].x : bc.x;
-      bc.y = take ? c[k].y : bc.y;
-      bc.z = take ? c[k].z : bc.z;
-      bc.w = take ? c[k].w : bc.w;
-    }
-  }
-  out[i] = bc;
-  if (ids_out) ids_out[i] = best;
-}
-
-// The pass for lattices of fewer than 2^31 points, written for the VALU: the kernel above spends ~900 vector instructions per point —
-// 64-bit index arithmetic per neighbour, three compares and six selects per candidate — and is bound by exactly that (an LDS-tiled form
-// and one with all 27 loads in flight took the same 56 us per pass of the 512^3 call's lattice, 390 us for 1024^3).  Here a neighbour's
-// index is the point's own 32-bit index plus a wave-uniform offset, (distance bits, id) is one 64-bit key so that "nearer, or as near
-// with the smaller id" is one unsigned compare, only the key and the neighbour's number are carried (the winner's record is fetched
-// again at the end), and out-of-range neighbours are bits of a precomputed mask.  Same candidates, same tie rule: the same seeds.
-__global__ __launch_bounds__(256) void k_jfa_pass32(GridParams g, const float4* __restrict__ in, float4* __restrict__ out, int step,
-                                                    uint32_t* __restrict__ ids_out) {
-  const uint32_t n0 = g.n[0], n1 = g.n[1], n2 = g.n[2];
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n0 * n1 * n2) return;
-  const uint32_t z = i % n2, xy = i / n2, y = xy % n1, x = xy / n1;
-  const f3 p = lattice_point(g, x, y, z);
-  const uint32_t s = (uint32_t)step;
-  // bit (3 a + b) of m[axis]... one flag per axis and direction: is the neighbour at -step / 0 / +step inside the lattice?
-  const bool okx[3] = {x >= s, true, x + s < n0}, oky[3] = {y >= s, true, y + s < n1}, okz[3] = {z >= s, true, z + s < n2};
-  const int sx = (int)(s * n1 * n2), sy = (int)(s * n2), sz = (int)s;
-  unsigned long long key = 0x7f800000ffffffffull;             // (+inf, no triangle)
-  uint32_t kbest = 13u;                                      // the point itself
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    float4 c[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const bool ok = okx[a] && oky[k / 3] && okz[k % 3];
-      const int off = (a - 1) * sx + (k / 3 - 1) * sy + (k % 3 - 1) * sz;
-      c[k] = in[ok ? (uint32_t)((int)i + off) : i];            // an out-of-range neighbour reads the point's own record and is masked below
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const bool ok = okx[a] && oky[k / 3] && okz[k % 3];
-      const uint32_t cand = __float_as_uint(c[k].w);
-      const float ex = p.x - c[k].x, ey = p.y - c[k].y, ez = p.z - c[k].z;
-      const float d = __builtin_fmaf(ex, ex, __builtin_fmaf(ey, ey, ez * ez));
-      // d >= +0 orders like its bit pattern; NaN (bits above +inf's) never wins, as `d < bd || d == bd` never held for it
-      const unsigned long long kk = ((unsigned long long)__float_as_uint(d) << 32) | cand;
-      const bool take = ok && cand != 0xffffffffu && kk < key;
-      key = take ? kk : key;
-      kbest = take ? (uint32_t)(9 * a + k) : kbest;
-    }
-  }
-  const uint32_t best = (uint32_t)key;
-  float4 bc = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xffffffffu));
-  if (best != 0xffffffffu) {
-    const int a = (int)(kbest / 9u), k = (int)(kbest % 9u);
-    bc = in[(uint32_t)((int)i + (a - 1) * sx + (k / 3 - 1) * sy + (k % 3 - 1) * sz)];
-  }
-  out[i] = bc;
-  if (ids_out) ids_out[i] = best;
-}
-// Lattices of at most JFA_SMALL_MAX points (a 64^3 grid: 16^3 brick centres): the whole flood — clear, splat, load, every pass — in ONE
-// workgroup with the lattice in LDS.  Seven to nine launches of 2 - 4 us kernels cost the host ~45 us to enqueue, during which the caller's
-// stream sat idle behind the build's sort (suzanne, 968 triangles, 64^3: hierarchy started 55 us after the sort had ended; timeline in
-// profiles/r06_small_calls.txt).  Same candidates, same tie rule as k_jfa_splat / k_jfa_pass32: the same seeds.
-constexpr uint32_t JFA_SMALL_MAX = 4096, JFA_SMALL_THREADS = 1024;
-__global__ __launch_bounds__(JFA_SMALL_THREADS) void k_jfa_small(DeviceMesh mesh, GridParams g, uint32_t* __restrict__ ids_out) {
-  __shared__ float4 lat_a[JFA_SMALL_MAX], lat_b[JFA_SMALL_MAX];
-  unsigned long long* const keys = reinterpret_cast<unsigned long long*>(lat_b);   // the splat's keys live in the second buffer until the load
-  const uint32_t n0 = g.n[0], n1 = g.n[1], n2 = g.n[2], n = n0 * n1 * n2, tid = threadIdx.x;
-  for (uint32_t i = tid; i < n; i += JFA_SMALL_THREADS) keys[i] = ~0ull;
-  __syncthreads();
-  for (uint32_t t = tid; t < mesh.n_tris; t += JFA_SMALL_THREADS) {          // k_jfa_splat
-    const float4 c = mesh.cen[t];
-    const float cc[3] = {c.x, c.y, c.z};
-    uint32_t cell[3];
-    bool ok = true;
-    for (int k = 0; k < 3; ++k) {
-      float f = (cc[k] - g.first[k]) / g.size[k] + 0.5f;
-      if (!(f == f)) { ok = false; break; }                                  // NaN centroid: not a useful seed
-      if (k == 0) { cell[0] = lattice_x_from_real(g, f); continue; }
-      f = fminf(fmaxf(f, 0.0f), (float)(g.n[k] - 1));
-      cell[k] = min((uint32_t)f, g.n[k] - 1);
-    }
-    if (!ok) continue;
-    const f3 p = lattice_point(g, cell[0], cell[1], cell[2]);
-    const float ex = p.x - c.x, ey = p.y - c.y, ez = p.z - c.z;
-    const float d2 = __builtin_fmaf(ex, ex, __builtin_fmaf(ey, ey, ez * ez));
-    if (!(d2 == d2)) continue;
-    atomicMin(&keys[(cell[0] * n1 + cell[1]) * n2 + cell[2]], ((unsigned long long)__float_as_uint(d2) << 32) | t);
-  }
-  __syncthreads();
-  for (uint32_t i = tid; i < n; i += JFA_SMALL_THREADS) {                    // k_jfa_load
-    const uint32_t id = (uint32_t)(keys[i] & 0xffffffffull);
-    float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (id != 0xffffffffu) c = mesh.cen[id];
-    c.w = __uint_as_float(id);
-    lat_a[i] = c;
-  }
-  __syncthreads();
-  const uint32_t maxdim = max(n0, max(n1, n2));
-  uint32_t step = 1;
-  while (step * 2u < maxdim) step *= 2u;
-  float4* in = lat_a;
-  float4* out = lat_b;
-  for (bool last = false;; ) {                                                // steps ... 2, 1, then one more unit pass (launch_grid_seeds)
-    for (uint32_t i = tid; i < n; i += JFA_SMALL_THREADS) {                  // k_jfa_pass32
-      const uint32_t z = i % n2, xy = i / n2, y = xy % n1, x = xy / n1;
-      const f3 p = lattice_point(g, x, y, z);
-      const bool okx[3] = {x >= step, true, x + step < n0}, oky[3] = {y >= step, true, y + step < n1}, okz[3] = {z >= step, true, z + step < n2};
-      const int sx = (int)(step * n1 * n2), sy = (int)(step * n2), sz = (int)step;
-      unsigned long long key = 0x7f800000ffffffffull;
-      float4 bc = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xffffffffu));
-      for (int a = 0; a < 3; ++a)
-        for (int k = 0; k < 9; ++k) {
-          if (!(okx[a] && oky[k / 3] && okz[k % 3])) continue;
-          const float4 c = in[(uint32_t)((int)i + (a - 1) * sx + (k / 3 - 1) * sy + (k % 3 - 1) * sz)];
-          const uint32_t cand = __float_as_uint(c.w);
-          const float ex = p.x - c.x, ey = p.y - c.y, ez = p.z - c.z;
-          const float d = __builtin_fmaf(ex, ex, __builtin_fmaf(ey, ey, ez * ez));
-          const unsigned long long kk = ((unsigned long long)__float_as_uint(d) << 32) | cand;
-          if (cand != 0xffffffffu && kk < key) { key = kk; bc = c; }
-        }
-      out[i] = bc;
-      if (last) ids_out[i] = (uint32_t)key;
-    }
-    __syncthreads();
-    float4* t = in; in = out; out = t;
-    if (last) break;
-    if (step == 1u) last = true; else step >>= 1;
-  }
-}
-// One flooding pass over the lattice g.
-static void launch_jfa_pass(hipStream_t st, const GridParams& g, const float4* in, float4* out, int step, uint32_t* ids) {
-  const size_t total = (size_t)g.n[0] * g.n[1] * g.n[2];
-  const unsigned nb = (unsigned)((total + 255) / 256);
-  if (total < (1ull << 30) && (unsigned long long)step * g.n[1] * g.n[2] < (1ull << 30))
-    hipLaunchKernelGGL(k_jfa_pass32, dim3(nb), dim3(256), 0, st, g, in, out, step, ids);
-  else
-    hipLaunchKernelGGL(k_jfa_pass, dim3(nb), dim3(256), 0, st, g, (const GridParams*)nullptr, in, out, step, ids);
-}
-
 // ---- k_lane_q: the lane walk for generic queries ---------------------------------------------
 // One sorted query per lane, every lane on its own through the tree (as k_lane) and, for the best-of-three-rays sign, through the
 // box tree along each axis.  For SPARSE query sets: a packet of 64 of 100 000 queries in the benchmark box is 44 cells of the 512^3
@@ -1591,647 +1205,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(M2S_LANE_WA
   out[perm[i]] = finish<MODE>(best, negate);
 }
 
-// ---- k_cut: one wave per 4 x 4 x 4 bricks, lane = brick, one cut list per brick (see CutList) ---------------
-// The 64 bricks of a wave are neighbours, so they visit nearly the same top of the tree: the wave walks it ONCE, like
-// k_packet does (wave-uniform position, node records through scalar loads, a subtree left when no lane keeps it), one
-// test per lane per node; a lane that has dropped or emitted a subtree sits out until the walk has left it (`resume`).
-//
-// What a brick may drop.  Brick: centre q, every voxel centre v = q + w with |w| <= r.  k_packet evaluates the brick's seed
-// triangle T first, so voxel v ends with a minimum <= dist(v, T) <= |v - s|, s = the point of T closest to q, a = q - s,
-// D = |a|, e = a / D.  Subtree X lies inside its convex disc-slab C_X; c = the point of C_X closest to q, L = |q - c|,
-// n = (q - c) / L, and convexity gives dist(v, C_X) >= n . (v - c) = L + n . w.  X holds nothing within (or tied with) any
-// voxel's minimum if   L + n . w > |a + w|   for all |w| <= r.  Two sufficient conditions, either drops X:
-//   sphere     L - r > D + r                                                       (1-Lipschitz; the only test so far)
-//   gradient   L - D > |n - e| r + r^2 / (2 D)          from |a + w| <= D + e . w + |w|^2 / (2 D)
-// The sphere test wastes 2 r = 5 cells: far from the surface (D = 64 cells) it keeps every triangle of a cap of ~25
-// cells radius, so the lists had to stay coarse and the packets walked the rest voxel by voxel — 64 lanes repeating
-// nearly the same decision (84 % of the packets of 512^3 x blob-100k are farther than 16 cells from the surface and
-// they are the expensive ones: 129 node tests at D >= 64 cells against 45 next to the surface).  The gradient test sees
-// that all voxels of the brick look at X from (almost) the same direction as at their seed: its slack is
-// |n - e| r ~ (lateral offset / D) r, a few tenths of a cell, so the lists can go down to subtrees of a few triangles.
-// All margins are far above f32 rounding (relative 1e-4 on lengths, sqrt(2e-5) on |n - e|), always towards keeping.
-//
-// Earlier versions (512^3 x blob-100k / the 64-layer slab of an 8-GPU rank; lists per block of 2 x 2 x 2 bricks, sphere
-// test): one lane per block, per-lane record fetches: 0.27 / 0.24 ms; eight lanes per block: 0.40 / 0.15 ms; one wave per
-// eight blocks with scalar record loads: 0.22 / 0.07 ms.
-// GRID = false (generic queries): "brick" = packet of sorted queries, lane = packet, 64 consecutive packets (neighbours in
-// the Morton order) per wave; centre and radius from `centres` (k_qpacket_bounds), the seed from the lattice cell of the
-// centre (as k_packet<false> does), `nbx` = the number of wave slots the packet walk was launched with.
-constexpr uint32_t NB_CUT = (uint32_t)sizeof(NodeExt);
-// Two levels (round 6; grids only).  Of a fine wave's node visits on 512^3 x blob-100k 44 % fall on nodes larger than the wave's own block
-// of 4 x 4 x 4 bricks (16 % on nodes larger than four blocks; 1024^3 x sheet-100k: 61 % / 29 %; counted, profiles/r06_kcut_visits.txt),
-// and its 63 neighbours inside a 64^3-voxel region repeat them with the same outcome.  LEVEL 1 walks that top ONCE per region: lane =
-// a block of 4 x 4 x 4 bricks (the same tests with the block's radius; witness triangle = the seed of the brick at the block's centre —
-// any triangle bounds the final minimum from above), one wave per 4 x 4 x 4 blocks AND per one of CUTC_S subtrees of the tree's top
-// (a single wave per region would be a chain of ~300 dependent visits on a launch of a few hundred waves: as long as what it saves),
-// and leaves CUTC_S sub-lists of <= CUTC_MAX ranges per block.  LEVEL 2 is the fine walk started from its block's ranges instead of
-// the root.  A subtree the coarse level drops holds nothing a voxel of the block can need, whatever the fine level's own seeds say,
-// so the fine lists can only get shorter; the packets' results cannot change (parity suite, soaks).
-constexpr uint32_t CUTC_S_LOG = 3, CUTC_S = 1u << CUTC_S_LOG, CUTC_WORDS = 8, CUTC_MAX = CUTC_WORDS - 1;   // 64 words = 256 B per block
-static_assert(CUTC_S * CUTC_WORDS == 64, "a fine wave fetches its block's coarse record with one load, lane = word");
-template <bool GRID, int LEVEL = 0>
-__global__ __launch_bounds__(64) void k_cut(DeviceMesh mesh, GridParams g, const uint32_t* __restrict__ seeds, uint32_t seed_shift,
-                                            uint32_t seed_ny, uint32_t seed_nz, uint32_t nbx, uint32_t nby, uint32_t nbz,
-                                            uint32_t* __restrict__ lists, float emit_near, float emit_far, uint32_t budget, uint32_t wave_cap,
-                                            const float4* __restrict__ centres, const uint32_t* __restrict__ table,
-                                            const GridParams* __restrict__ seed_lattice, const uint32_t* __restrict__ coarse = nullptr) {
-  static_assert(GRID || LEVEL == 0, "the two-level form is the grid's");
-  // LEVEL 1: the "bricks" of this launch are blocks of 4 x 4 x 4 packet bricks (nbx, nby, nbz count blocks), eight waves per 4 x 4 x 4 of them
-  constexpr uint32_t UL = LEVEL == 1 ? 2u : 0u;               // log2 packet bricks per lane unit and axis
-  constexpr uint32_t NMAX = LEVEL == 1 ? CUTC_MAX : CUT_MAX;  // ranges per list
-  constexpr uint32_t OUT_WORDS = LEVEL == 1 ? CUTC_WORDS : CUT_WORDS;
-  const uint32_t nsy = (nby + 3u) >> 2, nsz = (nbz + 3u) >> 2;
-  const uint32_t sb = LEVEL == 1 ? blockIdx.x >> CUTC_S_LOG : blockIdx.x;   // 4 x 4 x 4 units
-  const uint32_t sub = LEVEL == 1 ? blockIdx.x & (CUTC_S - 1u) : 0u;        // LEVEL 1: which subtree of the top
-  const uint32_t sz = sb % nsz, sy = (sb / nsz) % nsy, sx = sb / (nsz * nsy);
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t bk[3] = {4u * sx + (lane >> 4), 4u * sy + ((lane >> 2) & 3u), 4u * sz + (lane & 3u)};
-  const uint32_t pk = blockIdx.x * 64u + lane;               // !GRID: this lane's packet
-  bool in_grid = bk[0] < nbx && bk[1] < nby && bk[2] < nbz;
-  float r = 0.0f, qq[3];
-  if (GRID) {
-    // first cell of the unit in the grid (a brick never straddles two chunks of an interleaved slab: capi.hip checks; a block
-    // does not either where the coarse level is used: prepare_grid_walk)
-    const uint32_t cell0[3] = {slab_x(g, bk[0] << (g.bl[0] + UL)), bk[1] << (g.bl[1] + UL), bk[2] << (g.bl[2] + UL)};
-    for (int k = 0; k < 3; ++k) {
-      const float hb = 0.5f * (float)((1u << (g.bl[k] + UL)) - 1u) * fabsf(g.size[k]);   // half extent between voxel centres
-      r = __builtin_fmaf(hb, hb, r);
-      qq[k] = g.first[k] + ((float)cell0[k] + 0.5f * (float)((1u << (g.bl[k] + UL)) - 1u)) * g.size[k];
-    }
-    r = sqrtf(r) * 1.0001f;
-  } else {
-    in_grid = pk < nbx && pk < table[0];
-    const float4 c = centres[in_grid ? pk : 0u];
-    qq[0] = c.x; qq[1] = c.y; qq[2] = c.z;
-    r = c.w;                                                 // already rounded up; NaN / inf (non-finite queries): nothing is dropped
-    if (!(r < 3.0e37f)) r = __builtin_inff();
-  }
-  const f3 q = mk3(qq[0], qq[1], qq[2]);
-  const float scale = fmaxf(mesh_scale(mesh), fmaxf(fabsf(q.x), fmaxf(fabsf(q.y), fabsf(q.z))) + r);
-  const float abs_margin = 6.4e-5f * scale + 4.0e-5f;        // the packet walk's own slack is <= 4e-6 * scale + 2.5e-6
-  float R2 = -1.0f, R = 0.0f, D = 0.0f;                      // unit outside the grid: never keeps anything
-  f3 e = mk3(0.0f, 0.0f, 0.0f);
-  float grad_c0 = __builtin_inff(), grad_c1 = 0.0f;          // gradient test: drop if L * (1 - 1e-4) - grad_c0 > grad_c1 * |n - e|
-  if (in_grid) {
-    uint32_t sidx;
-    if (!GRID) sidx = query_lattice_cell(*seed_lattice, q.x, q.y, q.z);
-    else if (LEVEL == 1) {                                    // the brick at the block's centre (seed lattice: one point per brick)
-      const uint32_t lx = bricks_along(g.xe - g.xb, g.bl[0]);
-      const uint32_t b0 = min((bk[0] << 2) + 2u, lx - 1u), b1 = min((bk[1] << 2) + 2u, seed_ny - 1u), b2 = min((bk[2] << 2) + 2u, seed_nz - 1u);
-      sidx = (b0 * seed_ny + b1) * seed_nz + b2;
-    } else sidx = ((bk[0] >> seed_shift) * seed_ny + (bk[1] >> seed_shift)) * seed_nz + (bk[2] >> seed_shift);
-    const uint32_t slot = min(seeds[sidx], mesh.n_tris - 1);
-    const TriRec& t = mesh.tris[slot];
-    const f3 a = mk3(t.ax, t.ay, t.az), bq = mk3(t.bx, t.by, t.bz), c = mk3(t.cx, t.cy, t.cz);
-    const TriEdges ed = {mk3(t.abx, t.aby, t.abz), mk3(t.acx, t.acy, t.acz), mk3(t.bcx, t.bcy, t.bcz)};
-    const f3 s = closest_point_triangle(q, a, bq, c, ed, t.cls);
-    const f3 av = sub3(q, s);
-    const float d2 = dot3(av, av);
-    D = (d2 == d2) ? sqrtf(d2) : __builtin_inff();
-    // sphere: the packet walk keeps a node while bound <= d * (1 + PRUNE_REL) + slack: stay well above that
-    R = (D * 1.0001f + 2.0f * r) * 1.0003f + abs_margin;
-    R2 = R * R;                                              // inf: nothing is dropped
-    if (D > r && D < 3.0e37f) {                              // (valid for any D > 0; useless when r^2 / 2D is large)
-      const float inv = 1.0f / D;
-      e = mk3(av.x * inv, av.y * inv, av.z * inv);
-      grad_c0 = D * 1.0003f + (r * r * 0.5f * inv) * 1.01f + abs_margin;
-      grad_c1 = r * 1.001f;
-    }
-  }
-  const float grad_c1sq = grad_c1 * grad_c1 * 1.000001f;     // the test compares squares (no root per node): rounded up
-  const float emit_radius = fmaxf(emit_near * r, R * emit_far);
-
-  constexpr uint32_t NB = (uint32_t)sizeof(NodeExt);
-  const uint32_t tree_end = mesh.n_nodes * NB;
-  uint32_t* out = lists + ((size_t)(in_grid ? (GRID ? (bk[0] * nby + bk[1]) * nbz + bk[2] : pk) : 0u)) * (LEVEL == 1 ? CUTC_S * CUTC_WORDS : OUT_WORDS)
-                  + sub * CUTC_WORDS;
-  const uint32_t cut_S = cut_start_bits(mesh.n_nodes);
-  auto cut_word = [cut_S](uint32_t start, uint32_t stop) {   // byte offsets -> list word (see CUT_WORDS)
-    return (start / NB_CUT) | (cut_encode_len((stop - start) / NB_CUT, 27u - cut_S) << cut_S);
-  };
-  uint32_t n = 0, last_start = 0, last_end = 0, resume = 0, opened = 0;   // per lane
-  uint32_t off = 0, end = tree_end, steps = 0;                // wave-uniform
-  if (LEVEL == 1) {
-    // this wave's subtree: CUTC_S_LOG levels down from the root, left or right by the bits of `sub`.  A leaf met on the way belongs to
-    // the wave whose remaining bits are zero; the others have nothing to walk.
-    for (uint32_t lv = 0; lv < CUTC_S_LOG && off < end; ++lv) {
-      const NodeExt* nr = reinterpret_cast<const NodeExt*>(reinterpret_cast<const char*>(mesh.ext) + off);
-      const uint32_t rest = sub & ((1u << (CUTC_S_LOG - lv)) - 1u);
-      if (__builtin_amdgcn_readfirstlane(nr->tri) >= 0) { if (rest != 0u) end = off; break; }
-      const uint32_t left = off + NB;
-      const uint32_t right = __builtin_amdgcn_readfirstlane(reinterpret_cast<const NodeExt*>(reinterpret_cast<const char*>(mesh.ext) + left)->skip);
-      const uint32_t skip = __builtin_amdgcn_readfirstlane(nr->skip);
-      if ((sub >> (CUTC_S_LOG - 1u - lv)) & 1u) { off = right; end = skip; } else { off = left; end = right; }
-    }
-  }
-  // LEVEL 2: the block's coarse record, lane = word; ranges are taken from it one by one
-  uint32_t cw = 0, c_sub = 0, c_k = 0, c_cnt = 0;
-  if (LEVEL == 2) {
-    cw = coarse[(size_t)sb * (CUTC_S * CUTC_WORDS) + lane];
-    off = end = 0;
-    c_cnt = (uint32_t)__builtin_amdgcn_readlane((int)cw, 0);
-  }
-#ifdef M2S_STATS_BUILD
-  // M2S_STATS: where a wave's node visits go — on nodes larger than the wave's own block of 4 x 4 x 4 bricks (what a coarser level
-  // of lists could decide once for several waves) or below
-  uint32_t st_visits = 0, st_above1 = 0, st_above4 = 0;
-  const float st_block = (LEVEL == 1 ? 1.0f : 4.0f) * __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, r)));
-#endif
-  for (;;) {
-    if (LEVEL == 2) {
-      while (c_k >= c_cnt) {                                  // next non-empty sub-list
-        if (++c_sub >= CUTC_S) break;
-        c_k = 0;
-        c_cnt = (uint32_t)__builtin_amdgcn_readlane((int)cw, (int)(c_sub * CUTC_WORDS));
-      }
-      if (c_sub >= CUTC_S) break;
-      const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)cw, (int)(c_sub * CUTC_WORDS + 1u + c_k));
-      ++c_k;
-      const uint32_t first = w & ((1u << cut_S) - 1u);
-      const uint32_t len = ((w >> cut_S) & ((1u << (27u - cut_S)) - 1u)) << (w >> 27);
-      off = max(first * NB, off);                             // (a rounded-up range may reach into the next one: never walk back)
-      end = min(first + len, mesh.n_nodes) * NB;
-    }
-  while (off < end) {
-    off = __builtin_amdgcn_readfirstlane(off);
-    ++steps;
-    const NodeExt nr = *reinterpret_cast<const NodeExt*>(reinterpret_cast<const char*>(mesh.ext) + off);
-#ifdef M2S_STATS_BUILD
-    {
-      const float ext = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, fmaxf(nr.R, nr.half))));
-      ++st_visits;
-      st_above1 += ext > st_block ? 1u : 0u;
-      st_above4 += ext > 4.0f * st_block ? 1u : 0u;
-    }
-#endif
-    const bool active = off >= resume;                        // this brick has not dropped / emitted an ancestor
-    // closest point of the disc-slab to q:  q - c = ax * n_s + lat * l / |l|   (common.h NodeExt, ext_dist2)
-    const float vx = q.x - nr.cx, vy = q.y - nr.cy, vz = q.z - nr.cz;
-    const float t = __builtin_fmaf(nr.nz, vz, __builtin_fmaf(nr.ny, vy, nr.nx * vx));
-    const float v2 = __builtin_fmaf(vz, vz, __builtin_fmaf(vy, vy, vx * vx));
-    const float l2 = fmaxf(__builtin_fmaf(-1.0e-6f, v2, __builtin_fmaf(-t, t, v2)), 0.0f);
-    const float inv_ell = __builtin_amdgcn_rsqf(l2);                  // one transcendental for ell and 1 / ell (inf at l2 = 0: guarded below)
-    const float ell = l2 > 0.0f ? l2 * inv_ell : 0.0f;
-    const float lat = fmaxf(ell - nr.R, 0.0f);
-    const float dt = t - nr.mid;
-    const float ax = copysignf(fmaxf(fabsf(dt) - nr.half, 0.0f), dt);
-    const float L2 = __builtin_fmaf(ax, ax, lat * lat);
-    bool keep = active & !(L2 > R2);                          // sphere test; NaN keeps the node
-    if (__ballot(keep) == 0ull) { off = nr.skip; continue; }
-    {
-      // gradient test (lanes without it carry grad_c0 = inf: never dropped).  rcp / rsq instead of IEEE divisions: their
-      // 1-ulp error is nothing beside the 2e-5 added under the root
-      const float ne_s = __builtin_fmaf(nr.nz, e.z, __builtin_fmaf(nr.ny, e.y, nr.nx * e.x));            // n_s . e
-      const float ve = __builtin_fmaf(vz, e.z, __builtin_fmaf(vy, e.y, vx * e.x));                       // (q - c0) . e
-      const float le = ve - t * ne_s;                                                                    // l . e
-      const float lat_dir = lat > 0.0f ? lat * inv_ell : 0.0f;       // lat > 0 means ell > R >= 0
-      const float num = __builtin_fmaf(ax, ne_s, lat_dir * le);                                          // (q - c) . e
-      const float inv_L = __builtin_amdgcn_rsqf(L2);
-      const float cosne = fminf(num * inv_L, 1.0f);                                                      // n . e (NaN / inf if L == 0: kept)
-      const float nme2 = fmaxf(2.0f - 2.0f * cosne, 0.0f) + 2.0e-5f;                                     // >= |n - e|^2
-      const float A = __builtin_fmaf(L2 * inv_L, 0.9999f, -grad_c0);                                     // L (1 - 1e-4) - c0
-      const bool drop = (A > 0.0f) & (A * A > grad_c1sq * nme2);                                         // A > c1 |n - e| without the root; false on NaN
-      keep = keep & !drop;
-    }
-    const unsigned long long bal = __ballot(keep);
-    if (bal == 0ull) { off = nr.skip; continue; }
-    // Where many triangles are (nearly) equidistant — towards the medial axis, e.g. deep inside a round body — the brick-level
-    // test keeps a large part of the tree however far it descends: a brick that has already opened `budget` nodes emits what
-    // it meets next as it is and leaves the rest to the packet's per-voxel tests (which are 200 times sharper there).
-    // (a saturated list — NMAX ranges — only grows its last range over every gap from here on: nothing finer can be said)
-    const bool emit = keep & (nr.tri >= 0 || fmaxf(nr.R, nr.half) <= emit_radius || opened >= budget || n == NMAX || steps >= wave_cap);
-    if (emit) {
-      // keep this subtree: [off, skip).  Adjacent subtrees merge; past NMAX ranges the last one grows over the gap
-      if (n > 0 && (last_end == off || n == NMAX)) last_end = nr.skip;
-      else {
-        if (n > 0) out[n] = cut_word(last_start, last_end);
-        ++n; last_start = off; last_end = nr.skip;
-      }
-    }
-    opened += (keep & !emit) ? 1u : 0u;
-    if (active & (emit | !keep)) resume = nr.skip;            // done with this subtree either way
-    off = (__ballot(keep & !emit) != 0ull) ? off + NB : nr.skip;   // some brick still has to look inside
-  }
-    if (LEVEL != 2) break;
-  }
-#ifdef M2S_STATS_BUILD
-  if (mesh.stats != nullptr && lane == 0u) {
-    unsigned long long* sc = mesh.stats + (LEVEL == 1 ? 112 : 104);
-    atomicAdd(&sc[0], 1ull);
-    atomicAdd(&sc[1], (unsigned long long)st_visits);
-    atomicAdd(&sc[2], (unsigned long long)st_above1);
-    atomicAdd(&sc[3], (unsigned long long)st_above4);
-    atomicMax(&sc[4], (unsigned long long)st_visits);
-  }
-#endif
-  if (!in_grid) return;
-  if (LEVEL == 1) {                                           // an empty sub-list is fine: the other subtrees hold what the block needs
-    if (n > 0) out[n] = cut_word(last_start, last_end);
-    out[0] = n;
-    return;
-  }
-  if (n == 0) { n = 1; last_start = 0; last_end = tree_end; }    // cannot happen with finite input; never walk nothing
-  out[n] = cut_word(last_start, last_end);
-  out[0] = n;
-}
-
-// ---- k_brute --------------------------------------------------------------------------------
-template <bool GRID, int MODE, int SIGN>
-__global__ __launch_bounds__(256) void k_brute(DeviceMesh mesh, GridParams g, const float* __restrict__ queries,
-                                               uint32_t n_q, const uint32_t* __restrict__ plane,
-                                               float* __restrict__ out, int* __restrict__ err, uint32_t n_packets, PeerOut peers) {
-  __shared__ TriRec tile[TILE];
-  const int lane = threadIdx.x & 63;
-  const uint32_t packet = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const bool active = packet < n_packets;
-
-  f3 p = {0, 0, 0};
-  size_t out_index = 0;
-  bool store = false;
-  GridBrick vox{};
-  if (active) {
-    if (GRID) {
-      vox = grid_lane_voxel(g, packet, lane);
-      p = grid_point(g, vox);
-      out_index = ((size_t)vox.x * g.n[1] + vox.y) * g.n[2] + vox.z - (size_t)g.out_off;
-      store = vox.in_range;
-    } else {
-      const uint32_t i = min(packet * 64u + lane, n_q - 1);
-      p = mk3(queries[3 * (size_t)i], queries[3 * (size_t)i + 1], queries[3 * (size_t)i + 2]);
-      out_index = i;
-      store = packet * 64u + lane < n_q;
-    }
-  }
-
-  Best<MODE> best;
-  uint32_t hits[3] = {0, 0, 0};
-  for (uint32_t t0 = 0; t0 < mesh.n_tris; t0 += TILE) {
-    const uint32_t nt = min((uint32_t)TILE, mesh.n_tris - t0);
-    __syncthreads();
-    {  // 128 records x 96 B = 768 float4; 256 threads x 3
-      const float4* src = reinterpret_cast<const float4*>(mesh.tris + t0);
-      float4* dst = reinterpret_cast<float4*>(tile);
-      for (uint32_t i = threadIdx.x; i < nt * 6; i += 256) dst[i] = src[i];
-    }
-    __syncthreads();
-    for (uint32_t k = 0; k < nt; ++k) {
-      const TriRec& tr = tile[k];
-      const f3 a = mk3(tr.ax, tr.ay, tr.az), b = mk3(tr.bx, tr.by, tr.bz), c = mk3(tr.cx, tr.cy, tr.cz);
-      eval_triangle<MODE>(best, p, tr);
-      if (MODE == MODE_UNSIGNED && SIGN == SIGN_XRAY_ALL) {
-        float t;
-        hits[0] += ray_triangle_aligned<0>(p, a, b, c, &t) ? 1u : 0u;   // default.rs:35-37: every triangle
-      }
-      if (MODE == MODE_UNSIGNED && SIGN == SIGN_RAYS3) {
-        f3 mn, mx;
-        triangle_bounding_box(a, b, c, &mn, &mx);
-        float t;
-        hits[0] += (ray_meets_box<0>(p, mn, mx) & ray_triangle_aligned<0>(p, a, b, c, &t)) ? 1u : 0u;
-        hits[1] += (ray_meets_box<1>(p, mn, mx) & ray_triangle_aligned<1>(p, a, b, c, &t)) ? 1u : 0u;
-        hits[2] += (ray_meets_box<2>(p, mn, mx) & ray_triangle_aligned<2>(p, a, b, c, &t)) ? 1u : 0u;
-      }
-    }
-  }
-
-  bool negate = false;
-  if (MODE == MODE_UNSIGNED) {
-    if (SIGN == SIGN_GRID_PLANE && active) {
-      const size_t w = ((size_t)vox.x * g.n[1] + vox.y) * g.nzw + (vox.z >> 5);
-      negate = (plane[w] >> (vox.z & 31u)) & 1u;
-    } else if (SIGN == SIGN_XRAY_ALL) {
-      negate = hits[0] & 1u;                                            // default.rs:65-72
-    } else if (SIGN == SIGN_RAYS3) {
-      negate = ((hits[0] & 1u) + (hits[1] & 1u) + (hits[2] & 1u)) > 1u;
-    }
-  }
-  if (MODE == MODE_NORMAL_FOLD && best.nan && store) atomicOr(err, ERRF_NAN);
-  const float result = finish<MODE>(best, negate);
-  if (store) out[out_index] = result;
-  if (GRID && store)
-    for (uint32_t i = 0; i < peers.n; ++i) peers.p[i][out_index + (size_t)g.out_off] = result;
-}
-
-// ---- k_brute_split: tiny problems without a tree -------------------------------------------------------------------
-// The reference's own criterion shapes include a 16^3 grid over an 11 k-triangle mesh (benches/generate_grid_sdf.rs:8-34): 4 096
-// voxels are 64 waves, each lane walks the tree alone, and the call lasts as long as its slowest lane's chain of dependent loads
-// (0.7 ms) on top of a 0.17 ms build.  All voxels x all triangles is only 46 M evaluations there — 0.1 ms if the whole chip takes
-// part, and no tree is needed at all.  k_brute gives a block ALL triangles (16 blocks for 16^3); here the triangles are cut into
-// chunks as well: block (x, y) evaluates voxel block x against triangle chunk y and folds its minima into per-voxel words with
-// atomic minima (non-negative floats order like their bit patterns; min is associative and commutative: bit-identical to k_brute
-// and to every walk), k_brute_finish turns them into signed distances.  Chosen for cells x triangles <= M2S_BRUTE_MAX.
-template <int MODE>
-__global__ __launch_bounds__(256) void k_brute_split(DeviceMesh mesh, GridParams g, uint32_t* __restrict__ acc, int* __restrict__ err,
-                                                     uint32_t n_packets, uint32_t tiles_per_chunk) {
-  __shared__ TriRec tile[TILE];
-  const int lane = threadIdx.x & 63;
-  const uint32_t packet = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const bool active = packet < n_packets;
-  f3 p = {0, 0, 0};
-  bool store = false;
-  if (active) {
-    const GridBrick vox = grid_lane_voxel_plain(g, packet, lane);
-    p = grid_point(g, vox);
-    store = vox.in_range;
-  }
-  Best<MODE> best;
-  const uint32_t t_begin = blockIdx.y * tiles_per_chunk * TILE, t_end = min(mesh.n_tris, t_begin + tiles_per_chunk * TILE);
-  for (uint32_t t0 = t_begin; t0 < t_end; t0 += TILE) {
-    const uint32_t nt = min((uint32_t)TILE, t_end - t0);
-    __syncthreads();
-    {
-      const float4* src = reinterpret_cast<const float4*>(mesh.tris + t0);
-      float4* dst = reinterpret_cast<float4*>(tile);
-      for (uint32_t i = threadIdx.x; i < nt * 6; i += 256) dst[i] = src[i];
-    }
-    __syncthreads();
-    for (uint32_t k = 0; k < nt; ++k) eval_triangle<MODE>(best, p, tile[k]);
-  }
-  if (!active || !store) return;
-  const size_t slot = ((size_t)packet * 64u + lane) * 2u;
-  atomicMin(&acc[slot], __float_as_uint(best.d2));
-  if (MODE == MODE_NORMAL_FOLD) {
-    atomicMin(&acc[slot + 1], __float_as_uint(best.d2pos));
-    if (best.nan) atomicOr(err, ERRF_NAN);
-  }
-}
-template <int MODE, int SIGN>
-__global__ __launch_bounds__(256) void k_brute_finish(GridParams g, const uint32_t* __restrict__ plane, const uint32_t* __restrict__ acc,
-                                                      float* __restrict__ out, uint32_t n_packets, PeerOut peers) {
-  const int lane = threadIdx.x & 63;
-  const uint32_t packet = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (packet >= n_packets) return;
-  const GridBrick vox = grid_lane_voxel_plain(g, packet, lane);
-  if (!vox.in_range) return;
-  const size_t slot = ((size_t)packet * 64u + lane) * 2u;
-  Best<MODE> best;
-  best.d2 = __uint_as_float(acc[slot]);
-  best.d2pos = __uint_as_float(acc[slot + 1]);
-  bool negate = false;
-  if (MODE == MODE_UNSIGNED && SIGN == SIGN_GRID_PLANE) {
-    const size_t w = ((size_t)vox.x * g.n[1] + vox.y) * g.nzw + (vox.z >> 5);
-    negate = (plane[w] >> (vox.z & 31u)) & 1u;
-  }
-  const float result = finish<MODE>(best, negate);
-  const size_t out_index = ((size_t)vox.x * g.n[1] + vox.y) * g.n[2] + vox.z - (size_t)g.out_off;
-  out[out_index] = result;
-  for (uint32_t i = 0; i < peers.n; ++i) peers.p[i][out_index + (size_t)g.out_off] = result;
-}
-
-// ---- k_brute_split_q: small query sets without a tree ---------------------------------------------------------------
-// The crate's documented use is a handful of query points (lib.rs:13-31, examples/demo.rs:29-54): for those the LBVH build (0.16 -
-// 0.24 ms), the query sort and a lane walk that lasts as long as its slowest lane's chain of dependent loads (~1 ms) are all
-// overhead — queries x triangles is a few 10^7 evaluations, 0.1 - 0.3 ms if the whole chip takes part.  As k_brute_split: block
-// (x, y) evaluates query block x against triangle chunk y and folds into per-query words with atomics — minima for the distances
-// (non-negative floats order like their bits), a 64-bit (d2, index, !positive) key for the Rtree rule (lowest index on ties, as
-// the walks and k_brute take it), XOR for the three ray parities (the parity of a sum is the XOR of the parities) — and
-// k_brute_finish_q turns the words into signed distances.  Per query: [0] d2, [1] d2 of the positive side (Normal fold) or the
-// hit parities (bits 0..2: +X, +Y, +Z), [2..3] the key.  Same arithmetic per pair as everywhere else: bit-identical.
-__global__ __launch_bounds__(256) void k_brute_q_init(uint32_t* __restrict__ acc, uint32_t n_q, uint32_t second) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_q) return;
-  reinterpret_cast<uint4*>(acc)[i] = make_uint4(0x7f800000u, second, 0xffffffffu, 0xffffffffu);   // +inf, +inf or no hits, "no triangle"
-}
-template <int MODE, int SIGN>
-__global__ __launch_bounds__(256) void k_brute_split_q(DeviceMesh mesh, const float* __restrict__ queries, uint32_t n_q, uint32_t* __restrict__ acc,
-                                                       int* __restrict__ err, uint32_t tiles_per_chunk) {
-  __shared__ TriRec tile[TILE];
-  const uint32_t i_raw = blockIdx.x * 256u + threadIdx.x, i = min(i_raw, n_q - 1u);
-  const f3 p = mk3(queries[3 * (size_t)i], queries[3 * (size_t)i + 1], queries[3 * (size_t)i + 2]);
-  Best<MODE> best;
-  uint32_t hits[3] = {0, 0, 0};
-  const uint32_t t_begin = blockIdx.y * tiles_per_chunk * TILE, t_end = min(mesh.n_tris, t_begin + tiles_per_chunk * TILE);
-  for (uint32_t t0 = t_begin; t0 < t_end; t0 += TILE) {
-    const uint32_t nt = min((uint32_t)TILE, t_end - t0);
-    __syncthreads();
-    {
-      const float4* src = reinterpret_cast<const float4*>(mesh.tris + t0);
-      float4* dst = reinterpret_cast<float4*>(tile);
-      for (uint32_t k = threadIdx.x; k < nt * 6; k += 256) dst[k] = src[k];
-    }
-    __syncthreads();
-    for (uint32_t k = 0; k < nt; ++k) {
-      const TriRec& tr = tile[k];
-      eval_triangle<MODE>(best, p, tr);
-      if (MODE == MODE_UNSIGNED && SIGN == SIGN_RAYS3) {               // the candidate rule of bvh.rs:119 / rtree_bvh.rs:149: the triangle's own padded box
-        const f3 a = mk3(tr.ax, tr.ay, tr.az), b = mk3(tr.bx, tr.by, tr.bz), c = mk3(tr.cx, tr.cy, tr.cz);
-        f3 mn, mx;
-        triangle_bounding_box(a, b, c, &mn, &mx);
-        float t;
-        hits[0] += (ray_meets_box<0>(p, mn, mx) & ray_triangle_aligned<0>(p, a, b, c, &t)) ? 1u : 0u;
-        hits[1] += (ray_meets_box<1>(p, mn, mx) & ray_triangle_aligned<1>(p, a, b, c, &t)) ? 1u : 0u;
-        hits[2] += (ray_meets_box<2>(p, mn, mx) & ray_triangle_aligned<2>(p, a, b, c, &t)) ? 1u : 0u;
-      }
-    }
-  }
-  if (i_raw >= n_q) return;
-  uint32_t* w = acc + 4 * (size_t)i;
-  if (MODE == MODE_NEAREST_NORMAL) {
-    if (best.idx != 0xffffffffu)
-      atomicMin(reinterpret_cast<unsigned long long*>(w + 2), ((unsigned long long)__float_as_uint(best.d2) << 32) | ((unsigned long long)best.idx << 1) | (best.pos ? 0ull : 1ull));
-    return;
-  }
-  atomicMin(&w[0], __float_as_uint(best.d2));
-  if (MODE == MODE_NORMAL_FOLD) {
-    atomicMin(&w[1], __float_as_uint(best.d2pos));
-    if (best.nan) atomicOr(err, ERRF_NAN);
-  } else if (SIGN == SIGN_RAYS3) {
-    const uint32_t par = (hits[0] & 1u) | ((hits[1] & 1u) << 1) | ((hits[2] & 1u) << 2);
-    if (par) atomicXor(&w[1], par);
-  }
-}
-template <int MODE, int SIGN>
-__global__ __launch_bounds__(256) void k_brute_finish_q(const uint32_t* __restrict__ acc, uint32_t n_q, float* __restrict__ out) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n_q) return;
-  const uint4 w = reinterpret_cast<const uint4*>(acc)[i];
-  Best<MODE> best;
-  bool negate = false;
-  if (MODE == MODE_NEAREST_NORMAL) {
-    best.d2 = __uint_as_float(w.w);                                    // high word of the key; "no triangle" reads as NaN, as a walk over nothing would not
-    best.pos = (w.z & 1u) == 0u;
-    if (w.w == 0xffffffffu && w.z == 0xffffffffu) { best.d2 = __builtin_inff(); best.pos = false; }
-  } else {
-    best.d2 = __uint_as_float(w.x);
-    if (MODE == MODE_NORMAL_FOLD) best.d2pos = __uint_as_float(w.y);
-    else if (SIGN == SIGN_RAYS3) negate = ((w.y & 1u) + ((w.y >> 1) & 1u) + ((w.y >> 2) & 1u)) > 1u;   // bvh.rs:131-141, rtree_bvh.rs:161-171
-  }
-  out[i] = finish<MODE>(best, negate);
-}
-
-// ---- query ordering (generic path): Morton sort so that a packet is spatially compact ---------
-__device__ __forceinline__ int ordf(float f) {
-  int i = __float_as_int(f);
-  return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ __forceinline__ float unordf(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-
-// Bounding box of the queries (order-encoded ints): grid-stride partials per block, folded by a second
-// one-block launch — no atomics on six hot addresses.
-constexpr unsigned QB_BLOCKS = 1024;
-__device__ __forceinline__ void qb_block_reduce(int lo[3], int hi[3], int* __restrict__ dst) {
-  __shared__ int part[6][4];
-  const int wv = threadIdx.x >> 6;
-  for (int k = 0; k < 3; ++k) {
-    int l = lo[k], h = hi[k];
-    for (int off = 32; off > 0; off >>= 1) { l = min(l, __shfl_xor(l, off)); h = max(h, __shfl_xor(h, off)); }
-    if ((threadIdx.x & 63) == 0) { part[k][wv] = l; part[3 + k][wv] = h; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int k = threadIdx.x;
-    int v = part[k][0];
-    for (int w = 1; w < 4; ++w) v = k < 3 ? min(v, part[k][w]) : max(v, part[k][w]);
-    dst[k] = v;
-  }
-}
-__global__ __launch_bounds__(256) void k_qbounds(const float* __restrict__ q, uint32_t n_q, int* __restrict__ partial) {
-  int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_q; i += (size_t)gridDim.x * blockDim.x)
-    for (int k = 0; k < 3; ++k) {
-      const float v = q[3 * i + k];
-      if (v == v && fabsf(v) < 3.0e38f) { const int o = ordf(v); lo[k] = min(lo[k], o); hi[k] = max(hi[k], o); }
-    }
-  qb_block_reduce(lo, hi, partial + 6 * blockIdx.x);
-}
-__global__ __launch_bounds__(256) void k_qbounds_final(const int* __restrict__ partial, uint32_t n_blocks, int* __restrict__ b) {
-  int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
-  for (uint32_t j = threadIdx.x; j < n_blocks; j += 256)
-    for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], partial[6 * j + k]); hi[k] = max(hi[k], partial[6 * j + 3 + k]); }
-  qb_block_reduce(lo, hi, b);
-}
-// 30-bit Morton key of a query in the query bounding box (10 bits per axis: 1024^3 cells — far finer than a packet of 64 of
-// any realistic query count, and a 32-bit key sorts in four radix passes instead of the eight of the 63-bit key used before:
-// 0.83 -> 0.45 ms for 10 M queries).  Queries of one cell keep their input order among themselves.
-constexpr int QKEY_BITS = 30;
-__device__ __forceinline__ uint32_t expand10q(uint32_t v) {
-  uint32_t x = v & 0x3ffu;
-  x = (x | x << 16) & 0x030000ffu;
-  x = (x | x << 8) & 0x0300f00fu;
-  x = (x | x << 4) & 0x030c30c3u;
-  x = (x | x << 2) & 0x09249249u;
-  return x;
-}
-// `drop`: low key bits cleared.  The sort then runs over the bits [drop, 30) only — 10 M queries need 21 bits (2 M cells) to form their
-// packets, three radix passes instead of four; queries of one finest cell stay in input order, which k_qcells treats like identical keys.
-__global__ __launch_bounds__(256) void k_qkeys(const float* __restrict__ q, uint32_t n_q, const int* __restrict__ b,
-                                               uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t drop) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_q) return;
-  uint32_t c[3];
-  for (int k = 0; k < 3; ++k) {
-    const float lo = unordf(b[k]), hi = unordf(b[3 + k]);
-    float u = (q[3 * (size_t)i + k] - lo) / (hi - lo);
-    u = (u == u) ? fminf(fmaxf(u, 0.0f), 1.0f) : 0.0f;
-    c[k] = min((uint32_t)(u * 1024.0f), 1023u);
-  }
-  keys[i] = (((expand10q(c[0]) << 2) | (expand10q(c[1]) << 1) | expand10q(c[2])) >> drop) << drop;
-  vals[i] = i;
-}
-// Seed lattice for generic queries: QL^3 cells over the query bounding box (description kept on the device).
-constexpr uint32_t QL = 64;
-__global__ void k_qlattice(const int* __restrict__ b, GridParams* __restrict__ L) {
-  if (threadIdx.x != 0) return;
-  GridParams g{};
-  for (int k = 0; k < 3; ++k) {
-    const float lo = unordf(b[k]), hi = unordf(b[3 + k]);
-    float cs = (hi - lo) / (float)QL;
-    if (!(cs > 0.0f) || !(cs < 3.0e38f)) cs = 1.0f;
-    g.n[k] = QL;
-    g.size[k] = cs;
-    g.first[k] = ((lo == lo && fabsf(lo) < 3.0e38f) ? lo : 0.0f) + 0.5f * cs;
-  }
-  g.xb = 0; g.xe = QL; g.nzw = 0; g.out_off = 0; g.chunk_log = 31; g.period = 0;
-  *L = g;
-}
-
-__global__ __launch_bounds__(256) void k_qgather(const float* __restrict__ q, const uint32_t* __restrict__ perm,
-                                                 uint32_t n_q, float4* __restrict__ sorted) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_q) return;
-  const size_t s = perm[i];
-  sorted[i] = make_float4(q[3 * s], q[3 * s + 1], q[3 * s + 2], 0.0f);
-}
-
-// Packets of the generic path.  64 CONSECUTIVE queries of the Morton order are a loose group (the run straddles cell
-// boundaries of every level: bounding radius 1.6 x that of a cube holding 64 uniform points, r^2 2.9 x) and the wave-uniform
-// walk pays for the union of what its 64 lanes need.  The packets are therefore the LEAVES OF THE BUCKET K-D TREE over the
-// keys, capacity 64: the largest key-prefix cells holding at most 64 queries — aligned boxes of aspect <= 2, 46 queries on
-// average for uniform points (1.38 x the packets, radius 0.88, r^2 0.78 of that cube's).  No tree is built: with
-// w[j] = common prefix length of keys j and j + 64, query i sits in an over-full cell of prefix length b iff some window
-// j in [i - 64, i] has w[j] >= b, so its leaf has prefix length m(i) + 1, m(i) = max of w over those windows, the same for
-// every query of the leaf; i starts a packet iff it differs from i - 1 within that prefix.  More than 64 queries with
-// identical keys (m = QKEY_BITS) are cut at multiples of 64.
-__global__ __launch_bounds__(256) void k_qcells(const uint32_t* __restrict__ keys, uint32_t n, uint8_t* __restrict__ head) {
-  __shared__ uint32_t sk[256 + 128];   // keys[base - 64, base + 320)
-  __shared__ int sw[256 + 64];         // w[j], j in [base - 64, base + 256)
-  const long long base = (long long)blockIdx.x * 256;
-  for (uint32_t t = threadIdx.x; t < 384u; t += 256u) {
-    const long long idx = base - 64 + t;
-    sk[t] = (idx >= 0 && idx < (long long)n) ? keys[idx] : 0u;
-  }
-  __syncthreads();
-  for (uint32_t t = threadIdx.x; t < 320u; t += 256u) {
-    const long long j = base - 64 + t;
-    const uint32_t x = sk[t] ^ sk[t + 64];
-    sw[t] = (j >= 0 && j + 64 < (long long)n) ? (x == 0u ? QKEY_BITS : __clz((int)x) - (32 - QKEY_BITS)) : -1;
-  }
-  __syncthreads();
-  const long long i = base + threadIdx.x;
-  if (i >= (long long)n) return;
-  int m = -1;
-  for (uint32_t t = 0; t <= 64u; ++t) m = max(m, sw[threadIdx.x + t]);
-  const uint32_t plen = (uint32_t)min(m + 1, QKEY_BITS);
-  const uint32_t key = sk[threadIdx.x + 64], prev = sk[threadIdx.x + 63];
-  bool h = i == 0 || (plen != 0u && ((key ^ prev) >> ((uint32_t)QKEY_BITS - plen)) != 0u);
-  if (m >= QKEY_BITS) h |= (i & 63) == 0;                   // more than 64 queries in one cell of the finest level
-  head[i] = h ? 1 : 0;
-}
-__global__ void k_qtable_mode(uint32_t* __restrict__ table, uint32_t n, uint32_t launched) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const bool over = table[0] > launched;                    // cannot be ruled out (63 levels of 1 + 64 splits): consecutive packets then
-  table[1] = over ? 1u : 0u;
-  if (over) table[0] = (n + 63u) / 64u;
-}
-
-// (centre, radius) of the bounding box of every packet's queries: one wave per packet.  The radius is rounded up; a packet
-// with a non-finite coordinate gets radius inf (its cut list then keeps the whole tree).
-// `raw` != nullptr: the kernel also brings the packet's queries into sorted order (sorted[i] = raw[perm[i]]; the packets partition the
-// sorted range, so every query is written once) — the gather that k_qgather does in a pass of its own otherwise.
-__global__ __launch_bounds__(256) void k_qpacket_bounds(float4* __restrict__ sorted, const uint32_t* __restrict__ table,
-                                                        uint32_t n_q, uint32_t launched, float4* __restrict__ centres,
-                                                        const float* __restrict__ raw, const uint32_t* __restrict__ perm) {
-  const uint32_t packet = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  if (packet >= launched) return;
-  uint32_t first, cnt;
-  if (!query_packet_range(table, packet, n_q, &first, &cnt)) return;
-  float4 v;
-  if (raw != nullptr) {
-    const size_t s = perm[first + min(lane, cnt - 1u)];
-    v = make_float4(raw[3 * s], raw[3 * s + 1], raw[3 * s + 2], 0.0f);
-    if (lane < cnt) sorted[first + lane] = v;
-  } else {
-    v = sorted[first + min(lane, cnt - 1u)];
-  }
-  float lo[3] = {v.x, v.y, v.z}, hi[3] = {v.x, v.y, v.z};
-  bool bad = !(fabsf(v.x) < 3.0e37f) | !(fabsf(v.y) < 3.0e37f) | !(fabsf(v.z) < 3.0e37f);
-  for (int o = 32; o >= 1; o >>= 1)
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = fminf(lo[k], __shfl_xor(lo[k], o));
-      hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], o));
-    }
-  bad = __ballot(bad) != 0ull;
-  if (lane != 0u) return;
-  float c[3], r2 = 0.0f;
-  for (int k = 0; k < 3; ++k) {
-    c[k] = 0.5f * lo[k] + 0.5f * hi[k];
-    const float h = fmaxf(hi[k] - c[k], c[k] - lo[k]);
-    r2 = __builtin_fmaf(h, h, r2);
-  }
-  float r = sqrtf(r2) * 1.0001f + 1.0e-30f;
-  if (bad) { c[0] = c[1] = c[2] = 0.0f; r = __builtin_inff(); }
-  centres[packet] = make_float4(c[0], c[1], c[2], r);
-}
-
 // ---- host part: which path a call takes (choose_grid_walk), then the launches -------------------------------------------------
 
 // k_packet's parameter list by name.  A call site assigns what it has: the grid path the planes, the seed lattice's shape, the peers and the
@@ -2296,73 +1269,10 @@ void launch_split_rounds(hipStream_t st, const DeviceMesh& mesh, const GridParam
   hipLaunchKernelGGL((k_split_finish<MODE, SIGN>), dim3(2048), dim3(256), 0, st, g, plane, out, split, peers);
   if (trace) { const hipError_t e = hipStreamSynchronize(st); fprintf(stderr, "[m2s split] finish: %s\n", hipGetErrorString(e)); }
 }
-template <bool GRID, int MODE, int SIGN>
-void launch_brute(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, const float* q, uint32_t n_q,
-                  const uint32_t* plane, float* out, int* err, uint32_t n_packets, const PeerOut& peers = PeerOut{}) {
-  hipLaunchKernelGGL((k_brute<GRID, MODE, SIGN>), dim3((n_packets + 3) / 4), dim3(256), 0, st, mesh, g, q, n_q, plane,
-                     out, err, n_packets, peers);
-}
 
-// The (mode, sign) of a call as compile-time constants for a generic lambda: f(WalkForm<MODE, SIGN>{}).  The grid walks exist in three forms,
-// the query walks in four — every kernel of this file that takes <MODE, SIGN> is instantiated for these and no others (launch_brute<false>
-// alone has a fifth, SIGN_XRAY_ALL: launch_query_walk).  The Normal fold and the nearest normal carry their own sign: no planes, no rays.
-template <int M, int S>
-struct WalkForm { static constexpr int MODE = M, SIGN = S; };
-template <class F>
-void for_grid_form(int mode, bool planes, F&& f) {
-  if (mode == MODE_UNSIGNED && planes) f(WalkForm<MODE_UNSIGNED, SIGN_GRID_PLANE>{});
-  else if (mode == MODE_UNSIGNED) f(WalkForm<MODE_UNSIGNED, SIGN_NONE>{});
-  else f(WalkForm<MODE_NORMAL_FOLD, SIGN_NONE>{});
-}
-template <class F>
-void for_query_form(int mode, int sign_src, F&& f) {
-  if (mode == MODE_UNSIGNED && sign_src == SIGN_RAYS3) f(WalkForm<MODE_UNSIGNED, SIGN_RAYS3>{});
-  else if (mode == MODE_UNSIGNED) f(WalkForm<MODE_UNSIGNED, SIGN_NONE>{});
-  else if (mode == MODE_NORMAL_FOLD) f(WalkForm<MODE_NORMAL_FOLD, SIGN_NONE>{});
-  else f(WalkForm<MODE_NEAREST_NORMAL, SIGN_NONE>{});
-}
-
-// Packet bricks of the slab [g.xb, g.xe) per axis and in all: the real ones, those of the whole grid (all g.n[0] layers; the crossovers
-// that must not depend on how a caller cuts the grid into slabs count these) and the launch's — padded to whole super-bricks.
-struct BrickCounts { uint32_t nb[3]; uint64_t real, grid; uint32_t padded; };
-static bool slab_is_empty(const GridParams& g) { return g.xe <= g.xb || g.n[1] == 0 || g.n[2] == 0; }
-BrickCounts brick_counts(const GridParams& g) {
-  BrickCounts c;
-  c.nb[0] = bricks_along(g.xe - g.xb, g.bl[0]), c.nb[1] = bricks_along(g.n[1], g.bl[1]), c.nb[2] = bricks_along(g.n[2], g.bl[2]);
-  c.real = (uint64_t)c.nb[0] * c.nb[1] * c.nb[2];
-  c.grid = (uint64_t)bricks_along(g.n[0], g.bl[0]) * c.nb[1] * c.nb[2];
-  const uint32_t xl = super_brick_xlog(c.nb[0], g.xl_cap);
-  c.padded = ((c.nb[0] + (1u << xl) - 1u) >> xl) * ((c.nb[1] + 7) >> 3) * ((c.nb[2] + 7) >> 3) * (64u << xl);
-  return c;
-}
 uint32_t host_brick_count(const GridParams& g) { return brick_counts(g).padded; }
 
 }  // namespace
-
-// Coarse lattice whose points sit at the centres of the `stride`-sized blocks of `fine`.
-static GridParams coarse_level(const GridParams& fine, const uint32_t log2_stride[3], uint32_t x_origin) {
-  GridParams c = fine;
-  for (int k = 0; k < 3; ++k) {
-    const uint32_t span = k == 0 ? fine.xe - fine.xb : fine.n[k];
-    const uint32_t stride = 1u << log2_stride[k];
-    c.n[k] = (span + stride - 1) / stride;
-    c.first[k] = fine.first[k] + ((float)(k == 0 ? x_origin : 0u) + 0.5f * (float)(stride - 1u)) * fine.size[k];   // brick centre
-    c.size[k] = (float)stride * fine.size[k];
-  }
-  c.xb = 0;
-  c.xe = c.n[0];
-  c.out_off = 0;
-  if (fine.chunk_log < 31u) {           // interleaved slab: chunk and period in lattice points (whole numbers: capi.hip checks)
-    c.chunk_log = fine.chunk_log - log2_stride[0];
-    c.period = fine.period >> log2_stride[0];
-  }
-  return c;
-}
-
-static size_t cut_blocks(const GridParams& g, uint32_t log) {
-  const BrickCounts bc = brick_counts(g);
-  return (size_t)bricks_along(bc.nb[0], log) * bricks_along(bc.nb[1], log) * bricks_along(bc.nb[2], log);
-}
 
 // Split walk: accumulator slots for up to SPLIT_CAP_SLOTS suspended packets, lists of SPLIT_ITEMS_PER_SLOT items per slot and round.
 // A launch of more packets than SPLIT_MAX_PACKETS is not split at all: it is hundreds of rounds of the chip's wave slots deep, its tail a
@@ -2375,25 +1285,6 @@ static uint32_t split_patience_q8(uint32_t packets, const Tuning& tn) {
   const double rounds_before = std::max(1.0, (double)packets / 8192.0 - 1.0);
   return (uint32_t)std::min(65535.0 * 256.0, 256.0 * tn.split_patience / rounds_before);
 }
-
-// Tiny problems take k_brute_split: at most 2^22 cells and cells x triangles <= 1e8 + 3000 x triangles (M2S_BRUTE_MAX overrides the
-// product's limit).  Measured (tools/exp_tiny.py, whole calls, brute / build + walk): blob-11k 16^3
-// 0.34 / 0.92 ms, 20^3 0.58 / 0.96, 24^3 0.92 / 0.83; blob-100k 8^3 0.41 / 2.21, 12^3 1.08 / 2.55, 16^3 2.21 / 2.22; blob-6k 16^3 0.20 / 0.74,
-// 32^3 1.10 / 0.61 — brute force runs at 178 G point-triangle pairs per second (half the chip's fp32 issue rate), the walks of such
-// grids as long as their slowest lane's chain of dependent loads, which grows with the mesh.
-// Round 6 (packet groups, one-workgroup seed flood: the walks of small problems got faster), whole one-shot calls, brute / build + walk
-// (tools/exp_tiny.py, profiles/r06_tiny.txt): suzanne (968 triangles) 16^3 Raycast 0.120 / 0.125 ms, 24^3 0.151 / 0.127, Normal 24^3 0.097 / 0.132, 32^3
-// 0.136 / 0.128; blob-11k 12^3 Raycast 0.190 / 0.276, 16^3 0.323 / 0.232, Normal 16^3 0.204 / 0.231, 20^3 0.347 / 0.252; blob-100k 8^3 0.40 / 1.17,
-// 12^3 Raycast 1.05 / 0.94, Normal 0.66 / 0.93.  Brute force costs 0.08 ms + pairs / 1.9e11 per s with the Raycast planes (0.06 + pairs / 3e11 for
-// Normal), the walk 0.12 ms + 1e-5 ms per triangle: the limits below are where they cross (rounds 2 - 5: 1e8 + 3 000 per triangle for both).
-static bool grid_is_tiny(const GridParams& g, size_t n_tris, int algorithm, bool raycast, const Tuning& tn) {
-  if (algorithm != 0 || n_tris == 0 || slab_is_empty(g) || g.chunk_log < 31u) return false;
-  const double automatic = raycast ? 7.6e6 + 1.9e3 * (double)n_tris : 1.8e7 + 3.0e3 * (double)n_tris;
-  const double limit = tn.brute_max >= 0.0 ? tn.brute_max : automatic;
-  const double cells = (double)(g.xe - g.xb) * g.n[1] * g.n[2];
-  return cells <= 4194304.0 && cells * (double)n_tris <= limit;
-}
-bool grid_is_tiny(const GridParams& g, size_t n_tris, int algorithm, bool raycast) { return grid_is_tiny(g, n_tris, algorithm, raycast, tuning()); }
 
 // Which path the walk of the slab [g.xb, g.xe) takes, with every crossover of DESIGN.md §9 — the ONE place where they live.  Pure: no HIP call,
 // no arena memory, nothing read but the arguments (tests/test_capi_cpu.py pins the defaults through m2s_debug_grid_walk_choice).  `n_nodes`,
@@ -2513,75 +1404,8 @@ size_t grid_distance_workspace_bytes(const GridParams& g, size_t n_tris) {
   return bricks * 44 + bricks + 16384 + cut_blocks(g, 0) * CUT_WORDS * 4 + cut_blocks(g, 2) * CUTC_S * CUTC_WORDS * 4 + 512 + TOP_SUBTREES * 8 + 256 + trail_counters + 1024 + split_workspace_bytes(g, n_tris, bricks);   // seeds + cut lists (one per brick) + split walk
 }
 
-__global__ __launch_bounds__(256) void k_seed_remap(uint32_t* __restrict__ ids, size_t n, const uint32_t* __restrict__ slot_of, uint32_t n_tris) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t t = ids[i];
-  ids[i] = t < n_tris ? slot_of[t] : 0xffffffffu;
-}
-
 uint32_t host_packet_bricks(const GridParams& g) { return slab_is_empty(g) ? 0u : host_brick_count(g); }
 bool grid_walk_wants_seeds(const GridParams& g, size_t n_tris, int algorithm) { return algorithm != 1 && n_tris && host_packet_bricks(g) >= 8; }
-
-// Seeding: every 4^3 brick starts its walk from a triangle near its own centre (jump flooding over the lattice of brick
-// centres); that halves the nodes visited compared with a greedy descent.  `cen` are the triangle centroids the ids of
-// the result refer to: the sorted array of the finished mesh, or the input-order array while the mesh is still being built.
-int launch_grid_seeds(Arena& ws, hipStream_t st, const float4* cen, uint32_t n_tris, const GridParams& g, SeedLattice* out) {
-  DeviceMesh mesh{};
-  mesh.cen = cen;
-  mesh.n_tris = n_tris;
-  // one lattice point per packet brick, at its centre (one per 2 x 2 x 2 bricks — shift 1 — costs the headline walk 8.11 -> 9.23 ms)
-  constexpr uint32_t seed_shift = 0u;
-  const uint32_t stride_log[3] = {g.bl[0] + seed_shift, g.bl[1] + seed_shift, g.bl[2] + seed_shift};
-  const GridParams g1 = coarse_level(g, stride_log, g.xb);
-  const size_t points1 = (size_t)g1.n[0] * g1.n[1] * g1.n[2];
-  uint32_t* ids = ws.take<uint32_t>(points1);
-  float4* la = ws.take<float4>(points1);
-  float4* lb = ws.take<float4>(points1);
-  unsigned long long* keys = ws.take<unsigned long long>(points1);
-  if (!ids || !la || !lb || !keys) { set_error("internal: seed workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-  const unsigned nb1 = (unsigned)((points1 + 255) / 256);
-  if (points1 <= JFA_SMALL_MAX) {                               // the whole flood in one workgroup
-    hipLaunchKernelGGL(k_jfa_small, dim3(1), dim3(JFA_SMALL_THREADS), 0, st, mesh, g1, ids);
-  } else {
-    M2S_HIP_CHECK(hipMemsetAsync(keys, 0xff, points1 * 8, st));
-    hipLaunchKernelGGL(k_jfa_splat, dim3((mesh.n_tris + 255) / 256), dim3(256), 0, st, mesh, g1, nullptr, keys);
-    // (Round 6, measured and not kept: the flood's long steps on a lattice of half the resolution + a refinement pass — the seeds get worse by
-    // a few hundredths of a cell far from the surface, where a packet's candidate set grows with the square root of exactly that: the
-    // headline walk 6.44 -> 7.00 ms with every step but the last two at half resolution, 6.76 -> 7.16 with only the steps >= 16 there;
-    // profiles/r06_seed_coarse_*.txt.  A bound from the lanes' FINAL minima would take 1.5 % of the node tests, 12 % of the pre-tests and
-    // 18 % of the exact evaluations: profiles/r06_stats2_headline.txt.)
-    const uint32_t maxdim = max(g1.n[0], max(g1.n[1], g1.n[2]));
-    hipLaunchKernelGGL(k_jfa_load, dim3(nb1), dim3(256), 0, st, mesh, keys, points1, la);
-    int step = 1;
-    while ((uint32_t)step * 2 < maxdim) step *= 2;
-    float4 *src = la, *dst = lb;
-    for (; step >= 1; step /= 2) {
-      launch_jfa_pass(st, g1, src, dst, step, nullptr);
-      float4* t = src; src = dst; dst = t;
-    }
-    launch_jfa_pass(st, g1, src, dst, 1, ids);   // "JFA+1": one more unit pass; leaves the ids
-  }
-  out->ids = ids;
-  out->ny = g1.n[1];
-  out->nz = g1.n[2];
-  out->points = points1;
-  out->shift = seed_shift;
-  return 0;
-}
-
-// What k_cut is launched with, for grids and for queries.
-struct CutParams { float emit_near, emit_far; uint32_t budget, wave_cap; };   // emission radius of a list entry: emit_near brick radii next to the surface, emit_far of the distance far from it
-static CutParams cut_params(uint32_t n_tris, const Tuning& tn) {
-  // A wave that has visited wave_cap nodes lets its bricks emit whatever they meet next: the long union walks of the
-  // regions with many near-ties (deep inside a round body) are the tail of the launch — on the 64-layer slab of an 8-GPU
-  // rank, 4 waves per SIMD, they WERE its duration (0.39 -> 0.19 ms; 512^3: flat between 300 and 450, 200 costs the
-  // packets 0.5 ms) — and what they still decide so deep in the tree the packets decide almost as cheaply.
-  uint32_t depth = 1;
-  while ((1ull << depth) < (unsigned long long)n_tris + 1ull) ++depth;
-  // (emit_far 1/32: re-tuned at the end of round 3 (1/16 before): headline 9.19 -> 9.11 ms, 1024^3 x sheet-100k 92.95 -> 89.33 ms)
-  return {tn.cut_near, tn.cut_far, 100000u, tn.cut_wave_cap ? tn.cut_wave_cap : std::max(120u, 20u * depth)};
-}
 
 // Seeds and cut lists for the slab [g.xb, g.xe) (everything a walk needs besides the mesh) — what choose_grid_walk says the walk takes;
 // `launch_grid_walk` then walks the slab, or any x-piece of it that starts on a block boundary.  `raw_seeds` (optional): a seed lattice
@@ -2604,7 +1428,7 @@ int prepare_grid_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const G
     SeedLattice lat;
     if (raw_seeds && raw_seeds->ids) {
       lat = *raw_seeds;
-      hipLaunchKernelGGL(k_seed_remap, dim3((unsigned)((lat.points + 255) / 256)), dim3(256), 0, st, lat.ids, lat.points, mesh.slot_of, mesh.n_tris);
+      launch_seed_remap(st, lat.ids, lat.points, mesh.slot_of, mesh.n_tris);
     } else {
       const int rc = launch_grid_seeds(ws, st, mesh.cen, mesh.n_tris, g, &lat);
       if (rc) return rc;
@@ -2612,26 +1436,15 @@ int prepare_grid_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const G
     plan->seeds = lat.ids; plan->seed_shift = lat.shift; plan->seed_ny = lat.ny; plan->seed_nz = lat.nz;
   }
   if (ch.cut_levels) {   // the top of the tree is walked once per block of 4 x 4 x 4 bricks (k_cut), in one level or two
-    const CutParams cp = cut_params(mesh.n_tris, tn);
-    const uint32_t nbx = bc.nb[0], nby = bc.nb[1], nbz = bc.nb[2], sh1 = plan->seed_shift, s1ny = plan->seed_ny, s1nz = plan->seed_nz;
-    const uint32_t* seed1 = plan->seeds;
     uint32_t* lists = ws.take<uint32_t>((size_t)bc.real * CUT_WORDS);
     if (!lists) { set_error("internal: cut-list workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-    const uint32_t cbx = bricks_along(nbx, 2), cby = bricks_along(nby, 2), cbz = bricks_along(nbz, 2);   // blocks of 4 x 4 x 4 bricks = fine waves
-    const size_t waves = cut_blocks(g, 2);
+    uint32_t* coarse = nullptr;
     if (ch.cut_levels == 2) {
-      uint32_t* coarse = ws.take<uint32_t>(waves * CUTC_S * CUTC_WORDS);
+      coarse = ws.take<uint32_t>(cut_blocks(g, 2) * CUTC_S * CUTC_WORDS);   // blocks of 4 x 4 x 4 bricks = fine waves
       if (!coarse) { set_error("internal: cut-list workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-      const size_t groups = cut_blocks(g, 4);   // 4 x 4 x 4 blocks
-      const uint32_t coarse_cap = tn.cut_coarse_cap ? tn.cut_coarse_cap : cp.wave_cap;
-      hipLaunchKernelGGL((k_cut<true, 1>), dim3((unsigned)(groups * CUTC_S)), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, cbx, cby, cbz, coarse, 1.0f, cp.emit_far, cp.budget,
-                         coarse_cap, (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, (const uint32_t*)nullptr);
-      hipLaunchKernelGGL((k_cut<true, 2>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap,
-                         (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, (const uint32_t*)coarse);
-    } else
-    hipLaunchKernelGGL((k_cut<true, 0>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap,
-                       (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, (const uint32_t*)nullptr);
-    plan->cut_lists = lists; plan->cut_log = 0; plan->cut_ny = nby; plan->cut_nz = nbz;
+    }
+    launch_grid_cut(st, mesh, g, plan->seeds, plan->seed_shift, plan->seed_ny, plan->seed_nz, lists, coarse);
+    plan->cut_lists = lists; plan->cut_log = 0; plan->cut_ny = bc.nb[1]; plan->cut_nz = bc.nb[2];
   }
   if (ch.path == GridWalkChoice::GROUP) {
     uint2* top = ws.take<uint2>(TOP_SUBTREES);
@@ -2659,38 +1472,6 @@ int prepare_grid_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const G
   return 0;
 }
 
-int launch_push_cells(hipStream_t st, const float* src, const PeerOut& peers, uint64_t first, uint64_t count) {
-  if (peers.n == 0 || count == 0) return 0;
-  // a bandwidth-bound copy next to the walk of the following piece: enough workgroups to keep every xGMI link busy,
-  // few enough to leave the CUs to the walk (M2S_PUSH_BLOCKS)
-  const unsigned max_blocks = tuning().push_blocks ? tuning().push_blocks : 256u;
-  const uint64_t want = (count / 4 + 255) / 256 + 1;
-  const unsigned blocks = (unsigned)std::min<uint64_t>(max_blocks, want);
-  hipLaunchKernelGGL(k_push_cells, dim3(blocks), dim3(256), 0, st, src, peers, first, count);
-  M2S_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-uint32_t trail_unit_log(const GridParams& g) {
-  (void)g;
-  return 2u;   // 4 bricks = 16 layers of a 4^3-brick grid (16 MB per peer and unit at 512^2 rows): 2-brick units stream finer but
-               // their packet order (super-bricks 2 bricks wide) costs the walk 20 % of its locality
-}
-uint32_t trail_units(const GridParams& g) {
-  const uint32_t nbx = bricks_along(g.xe - g.xb, g.bl[0]), ul = trail_unit_log(g);
-  return (nbx + (1u << ul) - 1u) >> ul;
-}
-uint32_t trail_rows(const GridParams& g) { return bricks_along(g.n[1], g.bl[1]); }
-int launch_push_trailing(hipStream_t st, const float* src, const PeerOut& peers, const GridParams& g, int* d_err) {
-  if (peers.n == 0 || g.xe <= g.xb) return 0;
-  const unsigned blocks = tuning().push_blocks ? tuning().push_blocks : 64u;
-  const uint64_t row = (uint64_t)g.n[1] * g.n[2];
-  hipLaunchKernelGGL(k_push_trailing, dim3(blocks), dim3(256), 0, st, src, peers, (uint64_t)g.xb * row - g.out_off, row, g.xe - g.xb,
-                     (1u << g.bl[0]) << peers.unit_log, trail_units(g), d_err);
-  M2S_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
 int launch_grid_walk(hipStream_t st, const DeviceMesh& mesh, const GridParams& g, int mode, const uint32_t* d_inside_plane,
                      const GridWalkPlan& plan, uint32_t bx_off, float* d_out, int* d_err, const PeerOut* peers) {
   const GridWalkChoice& ch = plan.choice;
@@ -2701,8 +1482,11 @@ int launch_grid_walk(hipStream_t st, const DeviceMesh& mesh, const GridParams& g
   const uint32_t packets = bc.padded, real = (uint32_t)bc.real;   // (no super-brick padding for k_brute_split)
   const uint32_t* plane = mode == MODE_UNSIGNED ? d_inside_plane : nullptr;   // the Normal fold carries its own sign
   const CutList cut = {plan.cut_lists, plan.cut_log, plan.cut_ny, plan.cut_nz, bx_off, nullptr};
-  if (ch.path == GridWalkChoice::ALL_PAIRS_SPLIT)
+  if (ch.path == GridWalkChoice::ALL_PAIRS_SPLIT) {
     M2S_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)plan.brute_acc, 0x7f800000, (size_t)packets * 64 * 2, st));   // +inf: where every search starts (Best<>)
+    return launch_grid_brute_split(st, mesh, g, mode, plane, plan.brute_acc, real, d_out, d_err, pz);
+  }
+  if (ch.path == GridWalkChoice::ALL_PAIRS) return launch_grid_brute(st, mesh, g, mode, plane, d_out, d_err, packets, pz);
   // (the Normal fold's split variants — k_packet<GRID, NORMAL_FOLD, ..., SPLIT, {1, 3}>, k_split_round<NORMAL_FOLD> — need 9 - 11 registers
   // more than eight waves per SIMD leave and spill them to scratch, the very thing that costs this kernel 10 - 40 %: the automatic choice
   // leaves the Normal sign to the plain walk; M2S_SPLIT=1 / 2 still runs them — the tests do)
@@ -2719,17 +1503,7 @@ int launch_grid_walk(hipStream_t st, const DeviceMesh& mesh, const GridParams& g
   for_grid_form(mode, plane != nullptr, [&](auto form) {
     constexpr int MODE = decltype(form)::MODE, SIGN = decltype(form)::SIGN;
     switch (ch.path) {
-      case GridWalkChoice::NOTHING: break;
-      case GridWalkChoice::ALL_PAIRS_SPLIT: {
-        // ~4 blocks per CU over (voxel blocks x triangle chunks); a chunk is a whole number of 128-triangle tiles
-        const uint32_t vblocks = (real + 3) / 4, tiles = (mesh.n_tris + TILE - 1) / TILE;
-        const uint32_t chunks = std::max(1u, std::min(tiles, (1024u + vblocks - 1) / vblocks));
-        const uint32_t tiles_per_chunk = (tiles + chunks - 1) / chunks, ychunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
-        hipLaunchKernelGGL((k_brute_split<MODE>), dim3(vblocks, ychunks), dim3(256), 0, st, mesh, g, plan.brute_acc, d_err, real, tiles_per_chunk);
-        hipLaunchKernelGGL((k_brute_finish<MODE, SIGN>), dim3(vblocks), dim3(256), 0, st, g, plane, (const uint32_t*)plan.brute_acc, d_out, real, pz);
-        break;
-      }
-      case GridWalkChoice::ALL_PAIRS: launch_brute<true, MODE, SIGN>(st, mesh, g, nullptr, 0, plane, d_out, d_err, packets, pz); break;
+      case GridWalkChoice::NOTHING: case GridWalkChoice::ALL_PAIRS_SPLIT: case GridWalkChoice::ALL_PAIRS: break;   // (brute.hip: launched above)
       case GridWalkChoice::LANE:
         hipLaunchKernelGGL((k_lane<MODE, SIGN>), dim3((packets + 3) / 4), dim3(256), 0, st, mesh, g, plane, d_out, d_err, packets, a.seed_in, a.seed_shift, a.seed_ny, a.seed_nz, bx_off, pz);
         break;
@@ -2775,22 +1549,6 @@ int launch_grid_distance(Arena& ws, hipStream_t st, const DeviceMesh& mesh, cons
   return launch_grid_walk(st, mesh, g, mode, d_inside_plane, plan, 0, d_out, d_err, peers);
 }
 
-// Test hook (capi.hip m2s_debug_cut_code): the list word k_cut writes for the range [start, start + len) of a tree of n_nodes records,
-// and the (first, end) records k_packet reads back from it.
-void cut_word_roundtrip(uint32_t n_nodes, uint32_t start, uint32_t len, uint32_t* word, uint32_t* first, uint32_t* end) {
-  const uint32_t S = cut_start_bits(n_nodes);
-  const uint32_t w = start | (cut_encode_len(len, 27u - S) << S);
-  *word = w;
-  const uint32_t f = w & ((1u << S) - 1u);
-  const uint32_t l = ((w >> S) & ((1u << (27u - S)) - 1u)) << (w >> 27);                // as k_packet decodes it
-  *first = f;
-  *end = std::min(f + l, n_nodes);
-}
-
-// Small query sets take k_brute_split_q: queries x triangles <= 1.2e8, 6e7 with the three ray tests per pair (M2S_BRUTE_MAX overrides; 0:
-// never).  Measured (tools/exp_small_queries.py, whole one-shot calls, all pairs / build + walk): 11 k triangles x 1 ... 1 000 queries
-// 0.085 - 0.15 / 0.25 - 0.70 ms, x 10 000 0.47 (0.83 with rays) / 0.55 (0.66); 100 k triangles x 64 0.13 - 0.22 / 1.0 - 1.3 ms, x 1 000
-// 0.46 (0.81) / 0.74 (0.94), x 10 000 3.2 (5.8) / 0.9 (1.0): 240 G pairs/s for the distance alone, 135 G with the rays.
 // Sparse query sets take the lane walk (k_lane_q): fewer than M2S_QUERY_LANE_COEFF (2.5) queries per triangle.
 bool query_walk_is_lane(size_t n_q, size_t n_tris, int sign_src) {
   const int lane_env = tuning().lane_walk;   // -1 auto, 0 never, 1 always
@@ -2821,172 +1579,13 @@ uint32_t grid_leaf_max(const GridParams& g, size_t n_tris) {
   return per_brick >= 40.0 ? 16u : per_brick >= 3.0 ? 8u : per_brick >= 0.6 ? 4u : 2u;   // (16: blob-100k 32^3, 195 per brick, 1.31 -> 1.11 ms; blob-1M 80^3 3.14 -> 2.53)
 }
 
-bool query_is_tiny(size_t n_q, size_t n_tris, int algorithm, int sign_src) {
-  if (algorithm != 0 || n_tris == 0 || n_q == 0 || sign_src == SIGN_XRAY_ALL) return false;
-  const double limit = tuning().brute_max >= 0.0 ? tuning().brute_max : (sign_src == SIGN_RAYS3 ? 6.0e7 : 1.2e8);
-  return (double)n_q * (double)n_tris <= limit;
-}
-int launch_query_brute_split(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const float* d_queries, size_t n_q, int mode, int sign_src,
-                             float* d_out, int* d_err) {
-  const uint32_t nq = (uint32_t)n_q;
-  uint32_t* acc = ws.take<uint32_t>(4 * n_q);
-  if (!acc) { set_error("internal: query workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-  const uint32_t qblocks = (nq + 255u) / 256u, tiles = (mesh.n_tris + TILE - 1) / TILE;
-  // ~4 blocks per CU over (query blocks x triangle chunks); a chunk is a whole number of 128-triangle tiles
-  const uint32_t chunks = std::max(1u, std::min(tiles, (1024u + qblocks - 1) / qblocks));
-  const uint32_t tiles_per_chunk = (tiles + chunks - 1) / chunks, ychunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
-  const dim3 grid(qblocks, ychunks);
-  hipLaunchKernelGGL(k_brute_q_init, dim3(qblocks), dim3(256), 0, st, acc, nq, mode == MODE_NORMAL_FOLD ? 0x7f800000u : 0u);
-  for_query_form(mode, sign_src, [&](auto form) {
-    constexpr int MODE = decltype(form)::MODE, SIGN = decltype(form)::SIGN;
-    hipLaunchKernelGGL((k_brute_split_q<MODE, SIGN>), grid, dim3(256), 0, st, mesh, d_queries, nq, acc, d_err, tiles_per_chunk);
-    hipLaunchKernelGGL((k_brute_finish_q<MODE, SIGN>), dim3(qblocks), dim3(256), 0, st, (const uint32_t*)acc, nq, d_out);
-  });
-  M2S_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-size_t query_workspace_bytes(size_t n_q) {
-  size_t n = n_q ? n_q : 1, tmp = 0;
-  (void)sort_pairs_u32(nullptr, tmp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                            n, 0, 30, (hipStream_t)0);
-  size_t sel = 0;
-  (void)select_flagged_indices(nullptr, sel, (const uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, (hipStream_t)0);
-  return n * (8 + 8 + 4 + 4 + 16 + 1 + 4) + n * 16 + 256 + (n / 32 + 64) * (16 + 4 * CUT_WORDS) + tmp + sel + 21 * 256 + (size_t)64 * 64 * 64 * 44 + 8192 + 24 * 1024 + 256;
-}
-
-// Generic queries in two parts.  prepare_query_walk needs the queries only — bounding box, Morton keys, sort, packet table, the
-// packets' centres and the gather into sorted order — so a one-shot call runs it on a side stream BESIDE the LBVH build (capi.hip:
-// 0.8 ms of bandwidth-bound passes next to 0.24 ms of latency-bound launches for 10 M queries x 100 k triangles); launch_query_walk
-// needs the tree: seed lattice, cut lists, walk.  launch_query_distance is both on one stream (persistent meshes, asynchronous calls).
-int prepare_query_walk(Arena& ws, hipStream_t st, const float* d_queries, size_t n_q, size_t n_tris, int sign_src, int algorithm, QueryPlan* plan,
-                       hipEvent_t after_lattice) {
-  *plan = QueryPlan{};
-  plan->n_q = n_q;
-  if (n_q == 0 || algorithm == 1) return 0;
-  const uint32_t nq = (uint32_t)n_q;
-  const uint32_t packets = (nq + 63) / 64;
-  // Morton order
-  int* qb = ws.take<int>(8 + 6 * QB_BLOCKS);
-  uint32_t* keys = ws.take<uint32_t>(n_q);
-  uint32_t* keys2 = ws.take<uint32_t>(n_q);
-  uint32_t* vals = ws.take<uint32_t>(n_q);
-  uint32_t* perm = ws.take<uint32_t>(n_q);
-  float4* sorted = ws.take<float4>(n_q);
-  size_t tmp_bytes = 0;
-  (void)sort_pairs_u32(nullptr, tmp_bytes, keys, keys2, vals, perm, n_q, 0, QKEY_BITS, st);
-  void* tmp = ws.take<char>(tmp_bytes ? tmp_bytes : 1);
-  if (!qb || !keys || !keys2 || !vals || !perm || !sorted || !tmp) {
-    set_error("internal: query workspace too small");
-    return M2S_ERR_HIP_INTERNAL;
-  }
-  // key bits that matter: cells of ~8 queries at the finest level, whole Morton triples, 12 ... 30
-  uint32_t bits = 12;
-  while (bits < (uint32_t)QKEY_BITS && (1ull << bits) * 8ull < (unsigned long long)n_q) bits += 3;
-  const uint32_t drop = (uint32_t)QKEY_BITS - bits;
-  const unsigned B = 256, nb = (nq + B - 1) / B;
-  const unsigned qblocks = nb < QB_BLOCKS ? nb : QB_BLOCKS;
-  hipLaunchKernelGGL(k_qbounds, dim3(qblocks), dim3(B), 0, st, d_queries, nq, qb + 8);
-  hipLaunchKernelGGL(k_qbounds_final, dim3(1), dim3(B), 0, st, qb + 8, qblocks, qb);
-  const bool seeds = n_tris && packets >= 8;
-  if (seeds) {                                   // the seed lattice's description: QL^3 cells over the queries' bounding box
-    GridParams* lat = ws.take<GridParams>(1);
-    if (!lat) { set_error("internal: query workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-    hipLaunchKernelGGL(k_qlattice, dim3(1), dim3(64), 0, st, qb, lat);
-    plan->lat = lat;
-  }
-  if (after_lattice) M2S_HIP_CHECK(hipEventRecord(after_lattice, st));
-  hipLaunchKernelGGL(k_qkeys, dim3(nb), dim3(B), 0, st, d_queries, nq, qb, keys, vals, drop);
-  M2S_HIP_CHECK(sort_pairs_u32(tmp, tmp_bytes, keys, keys2, vals, perm, n_q, drop, QKEY_BITS, st));
-  // Sparse query sets take the lane walk (k_lane_q).  Measured crossover, uniform queries in the extended box (lane / packet walk,
-  // RtreeBvh): blob-100k 100 k queries 1.36 / 3.65 ms, 1 M 2.70 / 3.45, 3 M 5.00 / 4.38, 10 M 12.3 / 6.7 (crossover ~2 M);
-  // blob-1M 1 M 6.3 / 12.8 ms, 10 M 26.4 / 22.4 (~7 M).  Below it the packet walk lasts as long as its worst packet's chain of
-  // dependent loads (2.7 ms), above it the lane walk's divergence costs more than the packets' union.  n* ~ 3500 T^0.55 fits both.
-  // (End of round 4, leaf work queued and leaves of 4 - 8 for the packets — query_leaf_max: lane / packets, whole call: blob-100k 100 k queries 1.12 /
-  // 1.53 ms, 300 k 1.47 / 1.46, 1 M 2.13 / 1.39, 10 M 10.9 / 3.60; blob-11k 30 k 0.72 / 0.66, 300 k 0.80 / 0.63: the crossover is at ~2.5 queries
-  // per triangle now.)
-  const bool lane_walk = query_walk_is_lane(n_q, n_tris, sign_src);
-  // packets = leaves of the bucket k-d tree over the sorted keys (k_qcells); the launch has room for twice the consecutive
-  // count, and k_qtable_mode falls back to consecutive packets should there be more
-  const uint32_t* table = nullptr;
-  uint32_t launched = packets;
-  if (!lane_walk) {
-    launched = nq / 32u + 64u;
-    if (tuning().query_launch_tight != 0) launched = packets + 1u;   // test hook: forces the consecutive-packet fallback
-    uint8_t* head = ws.take<uint8_t>(n_q);
-    uint32_t* tb = ws.take<uint32_t>(n_q + 2);               // [0] count, [1] mode, then one start per head (at most n_q)
-    size_t sel_bytes = 0;
-    (void)select_flagged_indices(nullptr, sel_bytes, head, tb + 2, tb, n_q, st);
-    void* sel_tmp = ws.take<char>(sel_bytes ? sel_bytes : 1);
-    if (!head || !tb || !sel_tmp) { set_error("internal: query workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-    hipLaunchKernelGGL(k_qcells, dim3(nb), dim3(B), 0, st, keys2, nq, head);
-    M2S_HIP_CHECK(select_flagged_indices(sel_tmp, sel_bytes, head, tb + 2, tb, n_q, st));
-    hipLaunchKernelGGL(k_qtable_mode, dim3(1), dim3(1), 0, st, tb, nq, launched);
-    table = tb;
-  }
-  // cut lists, one per packet (k_cut<false>): they need the packets' centres, and the kernel that finds those gathers the queries too
-  const uint32_t qcut_min = tuning().query_cut_min;
-  float4* centres = nullptr;
-  if (table != nullptr && seeds && packets >= qcut_min) {
-    centres = ws.take<float4>(launched);
-    if (!centres) { set_error("internal: query workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-    hipLaunchKernelGGL(k_qpacket_bounds, dim3((launched + 3) / 4), dim3(256), 0, st, sorted, table, nq, launched, centres, d_queries, (const uint32_t*)perm);
-  } else {
-    hipLaunchKernelGGL(k_qgather, dim3(nb), dim3(B), 0, st, d_queries, perm, nq, sorted);
-  }
-  M2S_HIP_CHECK(hipGetLastError());
-  plan->qb = qb; plan->perm = perm; plan->sorted = sorted; plan->table = table; plan->centres = centres;
-  plan->launched = launched; plan->lane_walk = lane_walk; plan->seeds = seeds;
-  return 0;
-}
-
-// Seed lattice of a query set: jump flooding over the QL^3 cells of plan.lat from the centroids `cen` (the sorted array of the finished
-// mesh, or the input-order array while the mesh is being built: `ids` then name input triangles and launch_query_walk translates them).
-int launch_query_seeds(Arena& ws, hipStream_t st, const float4* cen, uint32_t n_tris, const QueryPlan& plan, bool raw, QuerySeeds* out) {
-  *out = QuerySeeds{};
-  if (!plan.seeds || plan.lat == nullptr || n_tris == 0) return 0;
-  DeviceMesh mesh{};
-  mesh.cen = cen;
-  mesh.n_tris = n_tris;
-  GridParams g{};
-  const size_t cells = (size_t)QL * QL * QL;
-  unsigned long long* k64 = ws.take<unsigned long long>(cells);
-  uint32_t* ids = ws.take<uint32_t>(cells);
-  float4* la = ws.take<float4>(cells);
-  float4* lb = ws.take<float4>(cells);
-  if (!k64 || !ids || !la || !lb) { set_error("internal: query workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-  const GridParams* lat = plan.lat;
-  M2S_HIP_CHECK(hipMemsetAsync(k64, 0xff, cells * 8, st));
-  hipLaunchKernelGGL(k_jfa_splat, dim3((n_tris + 255) / 256), dim3(256), 0, st, mesh, g, lat, k64);
-  const unsigned nbl = (unsigned)((cells + 255) / 256);
-  hipLaunchKernelGGL(k_jfa_load, dim3(nbl), dim3(256), 0, st, mesh, k64, cells, la);
-  float4 *src = la, *dst = lb;
-  for (int step = QL / 2; step >= 1; step /= 2) {
-    hipLaunchKernelGGL(k_jfa_pass, dim3(nbl), dim3(256), 0, st, g, lat, src, dst, step, nullptr);
-    float4* t = src; src = dst; dst = t;
-  }
-  hipLaunchKernelGGL(k_jfa_pass, dim3(nbl), dim3(256), 0, st, g, lat, src, dst, 1, ids);
-  M2S_HIP_CHECK(hipGetLastError());
-  out->ids = ids;
-  out->raw = raw;
-  return 0;
-}
-
 int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const float* d_queries, const QueryPlan& plan,
                       int mode, int sign_src, int algorithm, float* d_out, int* d_err, const QuerySeeds* pre) {
   const size_t n_q = plan.n_q;
   if (n_q == 0) return 0;
   GridParams g{};
   const uint32_t nq = (uint32_t)n_q;
-  const uint32_t packets = (nq + 63) / 64;
-  if (algorithm == 1) {
-    if (mode == MODE_UNSIGNED && sign_src == SIGN_XRAY_ALL) launch_brute<false, MODE_UNSIGNED, SIGN_XRAY_ALL>(st, mesh, g, d_queries, nq, nullptr, d_out, d_err, packets);
-    else for_query_form(mode, sign_src, [&](auto form) {
-      launch_brute<false, decltype(form)::MODE, decltype(form)::SIGN>(st, mesh, g, d_queries, nq, nullptr, d_out, d_err, packets);
-    });
-    M2S_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
+  if (algorithm == 1) return launch_query_brute(st, mesh, d_queries, nq, mode, sign_src, d_out, d_err);
   const uint32_t launched = plan.launched;
   // seeds: jump flooding over a QL^3 lattice on the query bounding box (as for the grid path) — here, or beside the build (`pre`)
   const uint32_t* seeds = nullptr;
@@ -2998,8 +1597,7 @@ int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const f
       if (rc) return rc;
       pre = &own;
     } else if (pre->raw) {
-      const size_t cells = (size_t)QL * QL * QL;
-      hipLaunchKernelGGL(k_seed_remap, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, pre->ids, cells, mesh.slot_of, mesh.n_tris);
+      launch_seed_remap(st, pre->ids, (size_t)QL * QL * QL, mesh.slot_of, mesh.n_tris);
     }
     seeds = pre->ids;
     d_lat = plan.lat;
@@ -3008,9 +1606,7 @@ int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const f
   if (plan.centres != nullptr && seeds != nullptr) {
     uint32_t* lists = ws.take<uint32_t>((size_t)launched * CUT_WORDS);
     if (!lists) { set_error("internal: query workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-    const CutParams cp = cut_params(mesh.n_tris, tuning());
-    hipLaunchKernelGGL((k_cut<false, 0>), dim3((launched + 63) / 64), dim3(64), 0, st, mesh, g, seeds, 0u, 0u, 0u, launched, 1u, 1u, lists,
-                       cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap, (const float4*)plan.centres, plan.table, d_lat);
+    launch_query_cut(st, mesh, seeds, launched, lists, plan.centres, plan.table, d_lat);
     cut = {lists, 0, 0, 0, 0, plan.centres};
   }
   PacketArgs a;
@@ -3053,25 +1649,8 @@ void warm_distance(hipStream_t st) {
       (const void*)k_split_round<MODE_NORMAL_FOLD>,
       (const void*)k_split_finish<MODE_UNSIGNED, SIGN_GRID_PLANE>,
       (const void*)k_split_finish<MODE_NORMAL_FOLD, SIGN_NONE>,
-      (const void*)k_cut<true, 0>,
-      (const void*)k_cut<true, 1>,
-      (const void*)k_cut<true, 2>,
-      (const void*)k_cut<false, 0>,
       (const void*)k_lane<MODE_UNSIGNED, SIGN_GRID_PLANE>,
-      (const void*)k_lane_q<MODE_UNSIGNED, SIGN_RAYS3>,
-      (const void*)k_jfa_splat,
-      (const void*)k_jfa_load,
-      (const void*)k_jfa_pass32,
-      (const void*)k_seed_remap,
-      (const void*)k_qbounds,
-      (const void*)k_qbounds_final,
-      (const void*)k_qkeys,
-      (const void*)k_qgather,
-      (const void*)k_qcells,
-      (const void*)k_qtable_mode,
-      (const void*)k_qpacket_bounds,
-      (const void*)k_qlattice,
-      (const void*)k_push_cells};
+      (const void*)k_lane_q<MODE_UNSIGNED, SIGN_RAYS3>};
   hipFuncAttributes attr;
   for (const void* f : fns) (void)hipFuncGetAttributes(&attr, f);
   (void)hipGetLastError();

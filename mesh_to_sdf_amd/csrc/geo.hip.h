@@ -63,7 +63,7 @@ M2S_HD f3 closest_point_segment(f3 p, f3 a, f3 ab /* = b.sub(a) */) {
 // geo.rs:90-137 for a non-degenerate-class triangle.  One IEEE division per call, as in the
 // reference (each region divides once; the numerator / denominator pair is selected first).
 // In two halves, so that the packet walk can stop after the first one when every lane that still matters lies in a
-// vertex region (distance.hip eval_triangle_leaf): the head is the six dot products and the three vertex-region tests
+// vertex region (walk.hip.h eval_triangle_leaf): the head is the six dot products and the three vertex-region tests
 // the reference makes first (geo.rs:97, 104, 111), the tail the edge / interior regions.
 struct RegularHead {
   float d1, d2, d3, d4, d5, d6;

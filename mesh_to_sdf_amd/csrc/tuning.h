@@ -14,7 +14,7 @@ struct Tuning {
   // ---- diagnostics
   int stats = 0;                    // M2S_STATS        1: traversal counters of the packet walk on stderr, 2: + a counting pass from the final bound
   int host_times = 0;               // M2S_HOST_TIMES   1: where the host time of a call goes, on stderr
-  // ---- which walk (tests force each flavour; the defaults are measured crossovers, distance.hip)
+  // ---- which walk (tests force each flavour; the defaults are measured crossovers: distance.hip choose_grid_walk, brute.hip for M2S_BRUTE_MAX, query_order.hip for the query packets)
   int lane_walk = -1;               // M2S_LANE_WALK    -1 automatic, 0 never, 1 always: one voxel / query per lane instead of one packet per wave
   double lane_ratio = 60.0;         // M2S_LANE_RATIO   grid: lane walk above this many triangles per packet brick
   double lane_ratio_split = 100.0;  // M2S_LANE_RATIO_SPLIT   ... and above this many where the packet walk's stragglers can be split (below)
@@ -29,7 +29,7 @@ struct Tuning {
   int group = -1;                   // M2S_GROUP        packets as workgroups of 2 or 4 waves (launches shallower than the chip): -1 automatic, 0 never, 1 always (where the walk form allows it; four waves)
   uint32_t group_target_waves = 32768; // M2S_GROUP_TARGET_WAVES  ... as many waves per packet (2 or 4) as keep the launch within this many waves
   double group_min_ratio = 1.0;     // M2S_GROUP_MIN_RATIO     ... and from this many triangles per packet brick on
-  // ---- cut lists
+  // ---- cut lists (cut.hip)
   float cut_near = 2.0f;            // M2S_CUT_NEAR     emission radius of a list entry, in brick radii (next to the surface)
   float cut_far = 1.0f / 32.0f;     // M2S_CUT_FAR      ... and as a fraction of the distance (far from it)
   int cut_coarse = -1;              // M2S_CUT_COARSE   grid cut lists in two levels (a coarse pass per 4 x 4 x 4 bricks first): -1 automatic (from M2S_CUT_COARSE_MIN_WAVES fine waves on), 0 never, 1 always
@@ -45,7 +45,7 @@ struct Tuning {
   uint32_t split_rounds = 2;        // M2S_SPLIT_ROUNDS follow-up launches: the continuations of the suspended packets, then their subtrees (with more rounds, subtrees may be suspended in their turn; the last round walks to the end)
   int split_report = 0;             // M2S_SPLIT_REPORT 1: suspended packets and items per round of every grid walk, on stderr (synchronises)
   int defer = -1;                   // M2S_DEFER        the packet walk's leaf work: -1 automatic (by triangles per brick: 2 / 1 / 3), 0 wave-wide at once, 1 exact evaluations queued as (voxel, triangle) pairs and run 64 at a time, 2 + wave-wide where >= 48 lanes are reached, 3 the pre-tests queued too
-  // ---- host-pointer calls and peer delivery
+  // ---- host-pointer calls and peer delivery (capi.hip, multi.hip, peer_push.hip)
   uint32_t host_piece_mb = 32;      // M2S_HOST_PIECE_MB   x-pieces of the result streamed to the host while the next is walked
   uint32_t push_pieces = 4;         // M2S_PUSH_PIECES     x-pieces of a slab pushed to the peers while the next is walked
   uint32_t push_blocks = 0;         // M2S_PUSH_BLOCKS     workgroups of a push kernel; 0: 256 (pieces) / 64 (trailing)

@@ -1,7 +1,7 @@
 // walk.hip.h — the pieces of the nearest-triangle walks that more than one translation unit needs:
 // record loads, the grid's point source, the per-lane search state with its tie rule, the pruning
 // threshold and the lower bounds of a node and of a leaf triangle.  Included by distance.hip (the
-// distance walks) and closest.hip (the closest-point pass); every definition is inline and lives in
+// distance walks), its sibling units (dist.hip.h) and closest.hip (the closest-point pass); every definition is inline and lives in
 // an anonymous namespace, so each translation unit keeps its own copy and inlines it as before.
 #pragma once
 #include "common.h"

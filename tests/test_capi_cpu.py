@@ -286,7 +286,7 @@ def test_grid_walk_choice_rules(lib):
 
 
 def test_cut_list_words_are_supersets_for_every_tree_size(lib):
-    """distance.hip CutList: a list word carries a range's start exactly and its length as a small float rounded UP — the walk may take a
+    """dist.hip.h CutList: a list word carries a range's start exactly and its length as a small float rounded UP — the walk may take a
     superset of a subtree range, never less.  Host arithmetic of the library itself (test hook m2s_debug_cut_code), every width of the
     start field from 1 to 26 bits (1 … 2^25 triangles), lengths around every power of two and random ones."""
     fn = lib.m2s_debug_cut_code

@@ -994,7 +994,7 @@ def _box_surface(n):
 @pytest.mark.parametrize("shape", ["sphere from inside", "sphere from outside", "box", "two sheets", "shell far from the origin"])
 @pytest.mark.parametrize("sign", [SignMethod.Raycast, SignMethod.Normal])
 def test_cut_lists_where_many_triangles_are_equidistant(shape, sign):
-    """The brick-level tests of k_cut (sphere and gradient test, distance.hip) on inputs built to hurt them: voxels for which
+    """The brick-level tests of k_cut (sphere and gradient test, cut.hip) on inputs built to hurt them: voxels for which
     hundreds of triangles are (nearly) equidistant — the centre of a sphere, the medial planes of a box, the mid-plane between
     two sheets — and far-field bricks at many cells from the surface, where the gradient test does the pruning.  The lists are
     forced onto these small grids (fixture) and the result must equal the on-device brute force bit for bit."""

@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
-"""Compares the per-kernel gfx950 instruction streams of two hipcc -S listings of one translation unit.
+"""Compares the per-kernel gfx950 instruction streams of hipcc -S listings, kernel by kernel, by symbol name.
 
 usage: tools/isa_kernel_diff.py <before.s> <after.s>
+       tools/isa_kernel_diff.py <before.s> ... -- <after.s> ...
+
+Each side is one listing or several (code that moved between translation units: a kernel's symbol does not depend on the
+file that defines it); the kernels of a side's listings are taken together.
 
 A kernel's body is every instruction from its symbol to its .Lfunc_end label, with comments removed and
 local labels (.LBB*, .Ltmp*) renamed by order of appearance, so that code that only moved inside the file
@@ -41,8 +45,23 @@ def kernels(path):
     return out
 
 
+def side(paths):
+    out = {}
+    for path in paths:
+        for name, k in kernels(path).items():
+            if name in out:
+                sys.exit("%s: %s is defined by another listing of the same side too" % (path, name))
+            out[name] = k
+    return out
+
+
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    args = sys.argv[1:]
+    cut = args.index("--") if "--" in args else 1
+    before, after = args[:cut], [p for p in args[cut:] if p != "--"]
+    if not before or not after:
+        sys.exit(__doc__)
+    a, b = side(before), side(after)
     differ = 0
     for name in sorted(set(a) | set(b)):
         if name not in a or name not in b:
