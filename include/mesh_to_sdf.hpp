@@ -13,6 +13,7 @@
 //   closest_points / grid_closest_points                       nearest triangle + closest point (no reference counterpart; m2s.h)
 //   winding_numbers / grid_winding_numbers / generate_grid_sdf_winding   generalized winding numbers and their sign (m2s.h)
 //   cast_rays / count_intersections / test_occlusions   watertight ray casting against the mesh (m2s.h)
+//   sample_surface / surface_area   area-weighted surface samples, defined to the bit (m2s.h)
 //   sample_grid / raymarch_grid  client draw_raymarching.wgsl  sdf_grid / estimate_normal / sdf_3d on a finished grid (m2s.h)
 //   grid_isosurface                                            marching-cubes mesh of a level set of a finished grid (no reference counterpart; m2s.h)
 //   serde::*               serde.rs:75-221                     SerializeSdf / DeserializeSdf / save_to_file / read_from_file
@@ -387,6 +388,37 @@ std::vector<uint8_t> test_occlusions(const std::vector<V>& vertices, const Topol
   std::vector<uint8_t> occ(origins.size());
   detail::cast_rays_call(vertices, indices, origins, directions, t_min, t_max, nullptr, nullptr, nullptr, nullptr, occ.data());
   return occ;
+}
+
+// ---- area-weighted surface sampling (m2s_sample_surface) ---------------------------------------------------------------------------
+// Points distributed uniformly over the surface, defined to the bit (m2s.h): sample i is global sample first_sample + i and depends only
+// on the triangles in Topology order, the seed and that number.  A mesh without area throws (M2S_ERR_EMPTY_MESH) when n > 0.
+struct SurfaceSamples {
+  std::vector<std::array<float, 3>> points;
+  std::vector<uint32_t> triangle;            // Topology order
+  std::vector<std::array<float, 2>> uv;      // point = a + u (b - a) + v (c - a)
+  std::vector<std::array<float, 3>> normal;  // unit right-hand normal of the triangle; empty unless asked for
+  double area = 0.0;                         // total area of the triangles the sampler can reach
+};
+template <class V, class I = uint32_t>
+SurfaceSamples sample_surface(const std::vector<V>& vertices, const Topology<I>& indices, size_t n, uint64_t seed = 0, uint64_t first_sample = 0,
+                              bool normals = false) {
+  detail::Packed<V> v(vertices.data(), vertices.size());
+  detail::IndexArg<I> ia(indices);
+  SurfaceSamples r;
+  r.points.resize(n);
+  r.triangle.resize(n);
+  r.uv.resize(n);
+  if (normals) r.normal.resize(n);
+  const m2s_surface_sample_opts so = {sizeof(m2s_surface_sample_opts), 0, seed, first_sample};
+  detail::check(m2s_sample_surface(v.ptr, vertices.size(), ia.ptr, indices.count, ia.bytes, indices.kind, n, &so,
+                                   n ? r.points.data()->data() : nullptr, n ? r.triangle.data() : nullptr, n ? r.uv.data()->data() : nullptr,
+                                   (n && normals) ? r.normal.data()->data() : nullptr, &r.area, nullptr));
+  return r;
+}
+template <class V, class I = uint32_t>
+double surface_area(const std::vector<V>& vertices, const Topology<I>& indices) {
+  return sample_surface(vertices, indices, 0).area;
 }
 
 // ---- queries on a finished grid (m2s_sample_grid, m2s_raymarch_grid) ------------------------------------------------------

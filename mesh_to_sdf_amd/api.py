@@ -489,6 +489,137 @@ def test_occlusions(vertices, indices: Topology, origins, directions, t_min: flo
 test_occlusions.__test__ = False   # (a public name that starts with "test": not a test for pytest to collect)
 
 
+class SurfaceSamples(NamedTuple):
+    """Area-weighted surface samples: points f32[n, 3], triangle uint32[n] (Topology order), uv f32[n, 2] (weights of b and c),
+    normal f32[n, 3] (unit right-hand normal; None unless asked for), area (float: the total area of the triangles with area)."""
+    points: object
+    triangle: object
+    uv: object
+    normal: object
+    area: float
+
+
+def _sample_call(call, a, n, seed, first_sample, normals, timings, algorithm, synchronous=True, points_only=False):
+    """One sampling call, `call(n, sopts, p_point, p_tri, p_uv, p_normal, p_area, opts)`; the arrays are made on the side of `a`."""
+    n = int(n)
+    if n < 0:
+        raise M2SPanic(_lib.ERR_BAD_ARG, "negative sample count")
+    so = _lib.M2SSurfaceSampleOpts(C.sizeof(_lib.M2SSurfaceSampleOpts), 0, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_sample))
+
+    def buf(shape, np_dtype, torch_dtype):
+        x = a.torch.empty(shape, dtype=getattr(a.torch, torch_dtype), device=a.dev) if a.device else np.empty(shape, np_dtype)
+        return x, ((x.data_ptr() if a.device else x.ctypes.data) if n else None)
+
+    pts, p_pts = buf((n, 3), np.float32, "float32")
+    tri = uv = nrm = None
+    p_tri = p_uv = p_nrm = None
+    if not points_only:
+        (tri, p_tri), (uv, p_uv) = buf(n, np.uint32, "int32"), buf((n, 2), np.float32, "float32")
+        if a.device and hasattr(a.torch, "uint32"):
+            tri = tri.view(a.torch.uint32)
+    if normals:
+        nrm, p_nrm = buf((n, 3), np.float32, "float32")
+    area = C.c_double(0.0)
+    o = a.opts(timings, algorithm, synchronous=synchronous or not a.device)
+    rc = call(n, C.byref(so), p_pts, p_tri, p_uv, p_nrm, C.byref(area), C.byref(o))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    return SurfaceSamples(pts, tri, uv, nrm, float(area.value))
+
+
+def sample_surface(vertices, indices: Topology, n: int, seed: int = 0, first_sample: int = 0, normals: bool = False, *, algorithm: int = 0,
+                   timings: M2STimings = None) -> SurfaceSamples:
+    """`n` points distributed uniformly over the surface (include/m2s.h m2s_sample_surface), defined to the bit: sample i is global sample
+    first_sample + i, and its value depends only on the triangles in Topology order, `seed` and that number — so ranks of a job take
+    disjoint ranges of one seed, and two half calls equal one whole call.  Triangles without area are never chosen; a mesh with none
+    raises.  Host arrays or device tensors, as the other calls take them; tests/sample_model.py is the definition in numpy."""
+    a = _Args(vertices, indices)
+    L = _lib.lib()
+    return _sample_call(lambda *r: L.m2s_sample_surface(a.p_verts, a.n_verts, a.p_idx, a.n_idx, a.index_bytes, a.topology, *r), a, n, seed,
+                        first_sample, normals, timings, algorithm)
+
+
+def surface_area(vertices, indices: Topology) -> float:
+    """Total area of the mesh's triangles as the sampler weighs them (non-finite areas count as 0); 0.0 for a mesh without area."""
+    a = _Args(vertices, indices)
+    area = C.c_double(0.0)
+    o = a.opts()
+    rc = _lib.lib().m2s_sample_surface(a.p_verts, a.n_verts, a.p_idx, a.n_idx, a.index_bytes, a.topology, 0, None, None, None, None, None,
+                                       C.byref(area), C.byref(o))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    return float(area.value)
+
+
+# DeepSDF's near-surface noise (Park et al. 2019: variances 0.0025 and 0.00025 in a unit sphere), as fractions of half the bounding-box diagonal
+NEAR_SURFACE_SIGMAS = (0.05, 0.0158)
+
+
+def _near_surface_points(a, surf, lo, hi, n, sigmas, uniform_fraction, seed):
+    """The query points of sample_sdf_near_surface on the side of `a`: `surf` displaced by equal shares of Gaussian noise of every sigma,
+    then uniform points in the 1.1x bounding box [lo, hi]."""
+    n_uniform = n - surf.shape[0]
+    if a.device:
+        t = a.torch
+        gen = t.Generator(device=a.dev)
+        gen.manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        noise = t.randn(surf.shape, generator=gen, device=a.dev, dtype=t.float32)
+        share = t.as_tensor(np.asarray(sigmas, np.float32), device=a.dev)[t.arange(surf.shape[0], device=a.dev) % len(sigmas)]
+        near = surf + noise * share[:, None]
+        box_lo, box_hi = t.as_tensor(lo, device=a.dev), t.as_tensor(hi, device=a.dev)
+        uni = box_lo + t.rand((n_uniform, 3), generator=gen, device=a.dev, dtype=t.float32) * (box_hi - box_lo)
+        return t.cat([near, uni]).contiguous()
+    rng = np.random.default_rng(int(seed) & 0xFFFFFFFFFFFFFFFF)
+    noise = rng.standard_normal(surf.shape, dtype=np.float32)
+    share = np.asarray(sigmas, np.float32)[np.arange(surf.shape[0]) % len(sigmas)]
+    near = (surf + noise * share[:, None]).astype(np.float32)
+    uni = (lo + rng.random((n_uniform, 3), dtype=np.float32) * (hi - lo)).astype(np.float32)
+    return np.ascontiguousarray(np.concatenate([near, uni]))
+
+
+def _sample_sdf_near_surface(mesh, n, sigmas, uniform_fraction, sign, seed):
+    a = mesh._a
+    n = int(n)
+    if not 0.0 <= uniform_fraction <= 1.0:
+        raise M2SPanic(_lib.ERR_BAD_ARG, "uniform_fraction must lie in [0, 1]")
+    if sign not in ("winding", "raycast", "normal"):
+        raise M2SPanic(_lib.ERR_BAD_ARG, "sign must be 'winding', 'raycast' or 'normal'")
+    v = a.keep[0]
+    if a.device:
+        lo, hi = v.min(0).values.cpu().numpy(), v.max(0).values.cpu().numpy()
+    else:
+        lo, hi = v.min(0), v.max(0)
+    lo, hi = lo.astype(np.float64), hi.astype(np.float64)
+    half_diagonal = 0.5 * float(np.linalg.norm(hi - lo))
+    if sigmas is None:
+        sigmas = [s * half_diagonal for s in NEAR_SURFACE_SIGMAS]
+    sigmas = [float(s) for s in sigmas]
+    n_uniform = int(round(n * uniform_fraction)) if sigmas else n
+    centre, half = 0.5 * (lo + hi), 0.55 * (hi - lo)
+    surf = mesh.sample_surface(n - n_uniform, seed=seed).points
+    pts = _near_surface_points(a, surf, (centre - half).astype(np.float32), (centre + half).astype(np.float32), n, sigmas, uniform_fraction, seed)
+    if sign == "winding":
+        sdf = mesh.generate_sdf_winding(pts)
+    elif sign == "raycast":
+        sdf = mesh.generate_sdf(pts, AccelerationMethod.RtreeBvh)
+    else:
+        sdf = mesh.generate_sdf(pts, AccelerationMethod.Bvh(SignMethod.Normal))
+    return pts, sdf
+
+
+def sample_sdf_near_surface(vertices, indices: Topology, n: int, sigmas=None, uniform_fraction: float = 0.05, sign: str = "winding",
+                            seed: int = 0):
+    """Training samples for a neural SDF, as DeepSDF and the `mesh_to_sdf` package draw them: (points f32[n, 3], sdf f32[n]).  All but
+    `uniform_fraction` of the points are surface samples (sample_surface under `seed`) displaced by isotropic Gaussian noise — equal shares
+    for every entry of `sigmas`, row i taking sigmas[i % len(sigmas)]; default: 0.05 and 0.0158 of half the bounding-box diagonal — and the
+    rest, the last rows, lie uniformly in the bounding box scaled by 1.1.  The noise comes from torch.randn under a seeded generator on the
+    data's device (numpy for host arrays) and is not part of any bit contract; `sdf` is: it is bit-equal to the named distance call on the
+    returned points — "winding": Mesh.generate_sdf_winding, "raycast": Mesh.generate_sdf with RtreeBvh, "normal": Mesh.generate_sdf with
+    Bvh(Normal).  One persistent mesh serves the whole call."""
+    with Mesh(vertices, indices) as mesh:
+        return _sample_sdf_near_surface(mesh, n, sigmas, uniform_fraction, sign, seed)
+
+
 class SampleMode(enum.IntEnum):
     """How a grid is read between cell centres (include/m2s.h m2s_sample_mode = the client shader's MODE_*)."""
     Snap = 0
@@ -1067,6 +1198,26 @@ class Mesh:
     def test_occlusions(self, origins, directions, t_min: float = 0.0, t_max: float = float("inf"), algorithm: int = 0, *,
                         timings: M2STimings = None, synchronous: bool = True):
         return self._mesh_rays(origins, directions, t_min, t_max, "occluded", timings, algorithm, synchronous)
+
+    def sample_surface(self, n: int, seed: int = 0, first_sample: int = 0, normals: bool = False, *, algorithm: int = 0,
+                       timings: M2STimings = None, synchronous: bool = True, points_only: bool = False) -> SurfaceSamples:
+        """sample_surface on the resident triangles: the same bits as the one-shot function.  The weight table is made by the first
+        sampling call and kept.  `points_only`: triangle and uv are not written (None)."""
+        L = _lib.lib()
+        return _sample_call(lambda *r: L.m2s_mesh_sample_surface(self._h, *r), self._a, n, seed, first_sample, normals, timings, algorithm,
+                            synchronous, points_only)
+
+    def surface_area(self) -> float:
+        area = C.c_double(0.0)
+        o = self._a.opts()
+        rc = _lib.lib().m2s_mesh_sample_surface(self._h, 0, None, None, None, None, None, C.byref(area), C.byref(o))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        return float(area.value)
+
+    def sample_sdf_near_surface(self, n: int, sigmas=None, uniform_fraction: float = 0.05, sign: str = "winding", seed: int = 0):
+        """sample_sdf_near_surface on this mesh."""
+        return _sample_sdf_near_surface(self, n, sigmas, uniform_fraction, sign, seed)
 
     def debug_digest(self):
         """FNV-1a digests of the resident arrays (test hook `m2s_debug_mesh_digest`): triangle records, pre-test planes, box nodes,

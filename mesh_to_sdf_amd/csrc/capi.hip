@@ -1,6 +1,7 @@
 // capi.hip — the C ABI of include/m2s.h: argument checks that mirror the reference's panics,
 // per-device workspace, host<->device staging for the drop-in (host pointer) case, phase timing.
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +16,7 @@
 #include "../../include/m2s.h"
 #include "capi_internal.h"
 #include "common.h"
+#include "sample.hip.h"
 #include "tuning.h"
 
 namespace m2s {
@@ -842,6 +844,13 @@ struct m2s_mesh {
   char* mom_mem = nullptr;
   hipEvent_t mom_ready = nullptr;     // recorded after the moments were made, on mom_stream
   hipStream_t mom_stream = nullptr;
+  // surface sampling: the running sums C of the triangle weights and their strided top (sample.hip SampleTable), made by the first sampling
+  // call in a block of their own.  That call synchronises its stream to bring Amax and W to the host, so the block is complete before any
+  // later call, on whatever stream, can see it: no ready event is needed.
+  char* samp_mem = nullptr;
+  m2s::SampleTable samp{};
+  uint32_t samp_amax_bits = 0;
+  uint64_t samp_W = 0;
 };
 
 // The leaf size a call wants its tree to have (grid_leaf_max / query_leaf_max): the resident tree is re-marked when it differs — one
@@ -1215,6 +1224,91 @@ int run_cast_rays(Arena& ws, const CallCtx& c, DeviceState& st, const DeviceMesh
   if (o.uv && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.uv), reinterpret_cast<const char*>(d.uv), n * 8))) return rc;
   if (o.count && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.count), reinterpret_cast<const char*>(d.count), n * 4))) return rc;
   if (o.occluded && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.occluded), reinterpret_cast<const char*>(d.occluded), n))) return rc;
+  return 0;
+}
+
+// ---- surface sampling (m2s_sample_surface, m2s_mesh_sample_surface) -------------------------------------------------------------------
+// The weight table (sample.hip; ev[2] .. ev[4] = seed_ms, its header's trip to the host included), then one kernel (ev[4] .. ev[3] =
+// distance_ms).
+struct SampleArgs {
+  float* point;
+  uint32_t* tri;
+  float* uv;
+  float* normal;
+  double* area;
+  uint64_t seed, first;
+};
+
+int check_sample_args(const m2s_surface_sample_opts* sopts, size_t n_samples, const m2s_opts* opts, SampleArgs* o) {
+  if (!o->point && !o->tri && !o->uv && !o->normal && !o->area) return fail(M2S_ERR_BAD_ARG, "every sampling output is NULL, area_out included");
+  if (sopts) {
+    if (sopts->struct_size != sizeof(m2s_surface_sample_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_surface_sample_opts.struct_size is not sizeof(m2s_surface_sample_opts)");
+    if (sopts->reserved != 0) return fail(M2S_ERR_BAD_ARG, "m2s_surface_sample_opts.reserved must be 0");
+    o->seed = sopts->seed;
+    o->first = sopts->first_sample;
+  }
+  if (o->first > UINT64_MAX - (uint64_t)n_samples) return fail(M2S_ERR_BAD_ARG, "first_sample + n_samples overflows 64 bits");
+  if (n_samples >= 0xffffffc0ull) return fail(M2S_ERR_BAD_ARG, "too many samples for one call");
+  if (opts && (opts->x_begin != 0 || opts->x_end != 0)) return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_begin / x_end do not apply to sampling calls");
+  if (opts && opts->struct_size >= sizeof(m2s_opts) && (opts->x_period != 0 || opts->n_peer_out != 0 || opts->peer_out != nullptr))
+    return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_period / peer_out do not apply to sampling calls");
+  if (opts && opts->mem_kind != M2S_MEM_HOST && opts->mem_kind != M2S_MEM_DEVICE) return fail(M2S_ERR_BAD_ARG, "bad mem_kind");
+  if (opts && opts->algorithm != 0 && opts->algorithm != 1) return fail(M2S_ERR_BAD_ARG, "bad algorithm");
+  return 0;
+}
+
+// No triangle the sampler can reach: the area is 0 and there is nothing to draw from.
+int sample_of_nothing(const SampleArgs& o, size_t n_samples) {
+  if (o.area) *o.area = 0.0;
+  return n_samples ? fail(M2S_ERR_EMPTY_MESH, "surface samples of a mesh without area") : M2S_OK;
+}
+
+size_t sample_workspace_bytes(const CallCtx& c, size_t n) {
+  return (c.mem_kind == M2S_MEM_HOST ? 2 * align_up(n * 12) + align_up(n * 4) + align_up(n * 8) : 0) + 2048;
+}
+
+// Makes the table of `src` and brings its header to the host (the stream is synchronised): Amax decides whether there is anything to
+// sample, W feeds the pick and *area_out.  d_err (optional): the call's device error word, for a one-shot call's vertex indices.
+int make_sample_table(const CallCtx& c, DeviceState& st, const SampleSrc& src, const SampleTable& tb, int* d_err, uint32_t* amax_bits, uint64_t* W) {
+  int rc = launch_sample_table(c.stream, src, tb, d_err);
+  if (rc) return rc;
+  uint32_t* h = reinterpret_cast<uint32_t*>(st.h_err);   // 64 pinned bytes
+  h[4] = 0;
+  M2S_HIP_CHECK(hipMemcpyAsync(h, tb.hdr, 16, hipMemcpyDeviceToHost, c.stream));
+  if (d_err) M2S_HIP_CHECK(hipMemcpyAsync(h + 4, d_err, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+  M2S_HIP_CHECK(hipStreamSynchronize(c.stream));
+  if (h[4] & ERRF_INDEX_OOB) return fail(M2S_ERR_BAD_ARG, "vertex index out of range (the reference panics indexing `vertices`)");
+  *amax_bits = h[0];
+  memcpy(W, h + 2, 8);
+  return 0;
+}
+
+double sample_total_area(uint32_t amax_bits, uint64_t W) {
+  float amax;
+  memcpy(&amax, &amax_bits, 4);
+  return ldexp((double)W, sample_exponent(amax) - 38);
+}
+
+// The sampling kernel over a finished table, results back (host memory).  Records ev[4] and ev[3] also when there is nothing to launch.
+int run_sample_surface(Arena& ws, const CallCtx& c, DeviceState& st, const SampleSrc& src, const SampleTable& tb, uint64_t W, size_t n,
+                       const SampleArgs& o) {
+  SampleOut d{o.point, o.tri, o.uv, o.normal};
+  int rc = 0;
+  if (c.mem_kind == M2S_MEM_HOST && n) {
+    d.point = o.point ? ws.take<float>(3 * n) : nullptr;
+    d.tri = o.tri ? ws.take<uint32_t>(n) : nullptr;
+    d.uv = o.uv ? ws.take<float>(2 * n) : nullptr;
+    d.normal = o.normal ? ws.take<float>(3 * n) : nullptr;
+    if ((o.point && !d.point) || (o.tri && !d.tri) || (o.uv && !d.uv) || (o.normal && !d.normal)) return fail(M2S_ERR_HIP, "internal: workspace");
+  }
+  M2S_HIP_CHECK(hipEventRecord(st.ev[4], c.stream));
+  if ((rc = launch_sample_surface(c.stream, src, tb, W, o.seed, o.first, n, c.algorithm, d))) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st.ev[3], c.stream));
+  if (c.mem_kind == M2S_MEM_DEVICE || n == 0) return 0;
+  if (o.point && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.point), reinterpret_cast<const char*>(d.point), n * 12))) return rc;
+  if (o.tri && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.tri), reinterpret_cast<const char*>(d.tri), n * 4))) return rc;
+  if (o.uv && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.uv), reinterpret_cast<const char*>(d.uv), n * 8))) return rc;
+  if (o.normal && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.normal), reinterpret_cast<const char*>(d.normal), n * 12))) return rc;
   return 0;
 }
 
@@ -1662,6 +1756,7 @@ int m2s_warmup(int device, size_t workspace_bytes, size_t host_ring_bytes) {
   warm_client(c.stream);
   warm_grid_query(c.stream);
   warm_rays(c.stream);
+  warm_sample(c.stream);
   warm_sortlib(c.stream);                                        // (the rocPRIM sorts of large meshes and of the query path: units of their own,
   warm_sortlib_query(c.stream);                                  // which a grid call over a mesh of <= 229 376 triangles never loads)
   M2S_HIP_CHECK(hipGetLastError());
@@ -1737,6 +1832,7 @@ void m2s_mesh_destroy(m2s_mesh* m) {
     if (m->plane_ready) (void)hipEventDestroy(m->plane_ready);
     if (m->mom_mem) (void)hipFree(m->mom_mem);
     if (m->mom_ready) (void)hipEventDestroy(m->mom_ready);
+    if (m->samp_mem) (void)hipFree(m->samp_mem);
     for (auto& p : m->pending) { m->free_events.push_back(p.a); m->free_events.push_back(p.b); }
     for (auto e : m->free_events) {
       if (ds.timing_events.size() < 64) ds.timing_events.push_back(e);
@@ -2370,6 +2466,95 @@ int m2s_mesh_cast_rays(m2s_mesh* m, const float* origins, const float* direction
   if ((rc = run_cast_rays(ws, c, *st, m->n_tris ? m->dm : none, origins, directions, n_rays, o))) return rc;
   if (!c.sync) return park_async_events(m, *st, n_rays, 1);
   return finish_call(c, *st, d_err, c.timings, m->n_tris, n_rays, false, true);
+}
+
+// Surface sampling (include/m2s.h): the one-shot call reads the caller's triangles and builds no tree; the mesh call keeps the table.
+int m2s_sample_surface(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology,
+                       size_t n_samples, const m2s_surface_sample_opts* sopts, float* point_out, uint32_t* triangle_out, float* uv_out,
+                       float* normal_out, double* area_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  SampleArgs o{point_out, triangle_out, uv_out, normal_out, area_out, 0, 0};
+  int rc = check_mesh_args(vertices, n_vertices, indices, n_indices, index_bytes, topology);
+  if (rc) return rc;
+  if ((rc = check_sample_args(sopts, n_samples, opts, &o))) return rc;
+  const size_t n_tris = m2s_triangle_count(n_vertices, n_indices, indices != nullptr, topology);
+  if (n_tris > ((size_t)1 << 25)) return fail(M2S_ERR_BAD_ARG, "more than 2^25 triangles");
+  if (!opts || opts->mem_kind == M2S_MEM_HOST) {
+    if ((rc = check_host_indices(indices, n_indices, index_bytes, topology, n_vertices, n_tris))) return rc;
+  }
+  if (n_tris == 0) return sample_of_nothing(o, n_samples);
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(opts, &c, &st))) return rc;
+  size_t need = sample_table_bytes(n_tris) + sample_scratch_bytes(n_tris) + sample_workspace_bytes(c, n_samples) + 4096;
+  if (c.mem_kind == M2S_MEM_HOST) need += align_up(n_vertices * 12) + align_up(n_indices * (size_t)(indices ? index_bytes : 0)) + 1024;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  StagedMesh sm;
+  if ((rc = stage_mesh(ws, c, vertices, n_vertices, indices, n_indices, index_bytes, &sm))) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));   // no tree: the build's span is empty
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  st->planes_done = nullptr;
+  SampleTable tb;
+  if (sample_table_carve(ws, ws, n_tris, &tb)) return fail(M2S_ERR_HIP, "internal: workspace");
+  const SampleSrc src{sm.d_verts, sm.d_indices, (uint32_t)n_vertices, index_bytes, topology, nullptr, nullptr, (uint32_t)n_tris};
+  uint32_t amax_bits = 0;
+  uint64_t W = 0;
+  if ((rc = make_sample_table(c, *st, src, tb, d_err, &amax_bits, &W))) return rc;
+  if (amax_bits == 0 || W == 0) return sample_of_nothing(o, n_samples);
+  if (o.area) *o.area = sample_total_area(amax_bits, W);
+  if ((rc = run_sample_surface(ws, c, *st, src, tb, W, n_samples, o))) return rc;
+  return finish_call(c, *st, d_err, c.timings, n_tris, n_samples, false, true);
+}
+
+int m2s_mesh_sample_surface(m2s_mesh* m, size_t n_samples, const m2s_surface_sample_opts* sopts, float* point_out, uint32_t* triangle_out,
+                            float* uv_out, float* normal_out, double* area_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  if (!m) return fail(M2S_ERR_BAD_ARG, "mesh is NULL");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  SampleArgs o{point_out, triangle_out, uv_out, normal_out, area_out, 0, 0};
+  int rc = check_sample_args(sopts, n_samples, opts, &o);
+  if (rc) return rc;
+  m2s_opts mo;
+  if ((rc = mesh_call_opts(m, opts, &mo))) return rc;
+  if (m->n_tris == 0) return sample_of_nothing(o, n_samples);
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(&mo, &c, &st))) return rc;
+  if ((rc = ensure_capacity(*st, (m->samp_mem ? 0 : sample_scratch_bytes(m->n_tris)) + sample_workspace_bytes(c, n_samples) + 8192))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  if (c.sync) M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  else d_err = m->d_err_async;   // asynchronous calls report through the mesh (m2s_mesh_drain_timings)
+  if (!c.sync) reap_pending(m, false);
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[2], c.stream));
+  st->planes_done = nullptr;
+  if ((rc = remark_leaves(m, c, m->dm.leaf_max))) return rc;   // no mark is read or moved; keeps the mesh's stream bookkeeping (`corners` is read)
+  const SampleSrc src{nullptr, nullptr, 0, 4, M2S_TRIANGLE_LIST, m->dm.corners, m->dm.slot_of, (uint32_t)m->n_tris};
+  if (!m->samp_mem) {
+    char* block = nullptr;
+    const size_t bytes = sample_table_bytes(m->n_tris);
+    M2S_HIP_CHECK(hipMalloc((void**)&block, bytes));
+    Arena table{block, bytes, 0};
+    SampleTable tb;
+    rc = sample_table_carve(table, ws, m->n_tris, &tb) ? fail(M2S_ERR_HIP, "internal: workspace") : 0;
+    if (!rc) rc = make_sample_table(c, *st, src, tb, nullptr, &m->samp_amax_bits, &m->samp_W);
+    if (rc) { (void)hipFree(block); return rc; }
+    m->samp_mem = block;
+    m->samp = tb;
+    m->samp.A = nullptr;          // scratch of the build: gone with this call's workspace
+    m->samp.tile_sum = nullptr;
+  }
+  if (m->samp_amax_bits == 0 || m->samp_W == 0) return sample_of_nothing(o, n_samples);
+  if (o.area) *o.area = sample_total_area(m->samp_amax_bits, m->samp_W);
+  if ((rc = run_sample_surface(ws, c, *st, src, m->samp, m->samp_W, n_samples, o))) return rc;
+  if (!c.sync) return park_async_events(m, *st, n_samples, 1);
+  return finish_call(c, *st, d_err, c.timings, m->n_tris, n_samples, false, true);
 }
 
 // Peer-write bandwidth probe (include/m2s.h): the copy kernel of M2S_PEER_PUSH, timed with HIP events on a stream of its own.

@@ -236,6 +236,7 @@ void warm_sortlib(hipStream_t st);
 void warm_sortlib_query(hipStream_t st);
 void warm_grid_query(hipStream_t st);
 void warm_rays(hipStream_t st);
+void warm_sample(hipStream_t st);
 // bvh.hip: flatten topology, build triangle records + LBVH in pre-order layout.
 size_t bvh_workspace_bytes(size_t n_tris);
 // `after_setup` (optional) is called twice with the input-order centroid array and triangle records: with phase 0 once the kernels that fill
@@ -433,6 +434,42 @@ struct RayOut {
 // One ray per lane over the tree as it is marked; algorithm 1: every triangle for every ray.  A mesh with n_tris == 0 gives "no hit".
 int launch_cast_rays(hipStream_t st, const DeviceMesh& mesh, const float* d_org, const float* d_dir, size_t n_rays, float t_min, float t_max,
                      int algorithm, const RayOut& out);
+
+// sample.hip: area-weighted surface sampling.  Where a triangle's vertices come from: a persistent mesh's resident
+// arrays (corners != nullptr: `corners` through `slot_of`), or the caller's vertices and indices as a one-shot call received them.
+struct SampleSrc {
+  const float* verts;
+  const void* indices;      // nullptr: 0 .. n_verts-1
+  uint32_t n_verts;
+  int index_bytes, topology;
+  const float4* corners;
+  const uint32_t* slot_of;
+  uint32_t n_tris;
+};
+constexpr uint32_t SAMPLE_TOP = 2048;   // entries of the table's strided top that k_sample keeps in LDS
+// The table: C[t] = w_0 + ... + w_t and its top (these two are what a persistent mesh keeps); hdr[0] = the bits of Amax, hdr[2..3] = W;
+// A (twice the areas) and tile_sum are scratch of the build.
+struct SampleTable {
+  uint64_t* C;
+  uint64_t* top;
+  uint32_t* hdr;
+  float* A;
+  uint64_t* tile_sum;
+};
+struct SampleOut {      // each may be nullptr; entries are per sample of the call
+  float* point;         // 3 per sample
+  uint32_t* tri;
+  float* uv;            // 2 per sample
+  float* normal;        // 3 per sample
+};
+size_t sample_table_bytes(size_t n_tris);     // C, top and hdr
+size_t sample_scratch_bytes(size_t n_tris);   // A and tile_sum
+int sample_table_carve(Arena& table, Arena& scratch, size_t n_tris, SampleTable* tb);   // -1: out of space
+// A_t, Amax, the weights and their running sums, all on `st`; a vertex index out of range raises ERRF_INDEX_OOB in *d_err.
+int launch_sample_table(hipStream_t st, const SampleSrc& src, const SampleTable& tb, int* d_err);
+// Samples first .. first + n_samples - 1 under `seed`; W = the table's total (> 0).  algorithm 1: the pick scans C linearly.
+int launch_sample_surface(hipStream_t st, const SampleSrc& src, const SampleTable& tb, uint64_t W, uint64_t seed, uint64_t first, size_t n_samples,
+                          int algorithm, const SampleOut& out);
 
 // grid_query.hip: sampling and ray-marching a finished grid SDF (the client's draw_raymarching.wgsl).  The grid's scalars travel as a
 // kernel argument; start / end are the shader's uniforms (first_cell, Grid::get_last_cell), n[] >= 1, cs[] > 0 and finite.

@@ -1,7 +1,8 @@
-// geo_probe.hip — HOST build of the device math in geo.hip.h and ray.hip.h, for CPU unit tests only
-// (tests/test_device_math_host.py, tests/test_rays_cpu.py).  Not linked into libm2s_hip.so.
+// geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h and sample.hip.h, for CPU unit tests only
+// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py).  Not linked into libm2s_hip.so.
 #include "geo.hip.h"
 #include "ray.hip.h"
+#include "sample.hip.h"
 
 using namespace m2s;
 
@@ -47,5 +48,34 @@ int probe_ray_triangle(const float* o, const float* d, const float* a, const flo
   const RaySetup r = ray_setup(O, mk3(d[0], d[1], d[2]));
   const bool hit = ray_triangle_in_range(r, O, mk3(a[0], a[1], a[2]), mk3(b[0], b[1], b[2]), mk3(c[0], c[1], c[2]), t_min, t_max, &tuv[0], &tuv[1], &tuv[2]);
   return (r.valid && hit) ? 1 : 0;
+}
+// sample.hip.h
+void probe_philox(const uint32_t* counter, const uint32_t* key, uint32_t* out) {
+  const Philox4 r = philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1]);
+  for (int k = 0; k < 4; ++k) out[k] = r.r[k];
+}
+void probe_sample_random(uint64_t seed, uint64_t g, uint32_t* out) {
+  const Philox4 r = sample_random(seed, g);
+  for (int k = 0; k < 4; ++k) out[k] = r.r[k];
+}
+// n = the raw normal; returns A_t (0 when it is not finite)
+float probe_tri_weight_area(const float* a, const float* b, const float* c, float* n) {
+  f3 nn;
+  const float A = tri_weight_area(mk3(a[0], a[1], a[2]), mk3(b[0], b[1], b[2]), mk3(c[0], c[1], c[2]), &nn);
+  n[0] = nn.x; n[1] = nn.y; n[2] = nn.z;
+  return A;
+}
+int probe_sample_exponent(float amax) { return sample_exponent(amax); }
+uint64_t probe_sample_weight(float A, int e) { return sample_weight(A, e); }
+uint64_t probe_sample_target(uint32_t r0, uint32_t r1, uint64_t W) { return sample_target(r0, r1, W); }
+uint64_t probe_sample_pick(const uint64_t* C, uint64_t n, uint64_t T) { return sample_upper_bound(C, 0, n, T); }
+void probe_sample_fold(uint32_t r2, uint32_t r3, float* uv) { sample_fold(r2, r3, &uv[0], &uv[1]); }
+void probe_sample_point(const float* a, const float* b, const float* c, float u, float v, float* out) {
+  const f3 p = sample_point(mk3(a[0], a[1], a[2]), mk3(b[0], b[1], b[2]), mk3(c[0], c[1], c[2]), u, v);
+  out[0] = p.x; out[1] = p.y; out[2] = p.z;
+}
+void probe_sample_normal(const float* n, float A, float* out) {
+  const f3 q = sample_normal(mk3(n[0], n[1], n[2]), A);
+  out[0] = q.x; out[1] = q.y; out[2] = q.z;
 }
 }
