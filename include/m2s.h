@@ -49,7 +49,7 @@ extern "C" {
 #endif
 
 #define M2S_VERSION_MAJOR 0
-#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
+#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
 
 /* Return codes.  The reference panics where this ABI returns a negative code; the Rust shim
  * turns a negative code back into panic!(m2s_last_error()). */
@@ -473,6 +473,59 @@ int m2s_sample_surface(const float* vertices, size_t n_vertices, const void* ind
                        float* point_out, uint32_t* triangle_out, float* uv_out, float* normal_out, double* area_out, const m2s_opts* opts);
 int m2s_mesh_sample_surface(m2s_mesh* mesh, size_t n_samples, const m2s_surface_sample_opts* sopts,
                             float* point_out, uint32_t* triangle_out, float* uv_out, float* normal_out, double* area_out, const m2s_opts* opts);
+
+/* ---- voxelization: which cells the mesh occupies -----------------------------------------------------------------------------------------
+ * What trimesh voxelized, Open3D VoxelGrid.create_from_triangle_mesh, kaolin trianglemeshes_to_voxelgrids and binvox compute: one bit per
+ * cell of the grid, set where a triangle touches the cell's box (SURFACE) or, in addition, where the cell's centre is inside (SOLID).  The
+ * result is defined to the bit (mesh_to_sdf_amd/csrc/voxel.hip.h; tests/voxel_model.py restates it in numpy).  IEEE binary32, no FMA, sums
+ * left to right.
+ *   Cell (i, j, k).  Centre q_m = first_cell_m + (float)idx_m * cell_size_m (m2s_grid_cell_center); half extent h_m = cell_size_m * 0.5f.  The
+ *               box is closed: touching counts.
+ *   Triangle t = (a, b, c) in the caller's order (Topology::get_triangles).  A triangle with any non-finite coordinate overlaps nothing.
+ *               e0 = b - a, e1 = c - b, e2 = a - c;  n = e0 x e1 (n.x = e0.y*e1.z - e0.z*e1.y, ...).  Per cell: v0 = a - q, v1 = b - q, v2 = c - q.
+ *   overlap(t, cell) holds iff none of 13 clauses misses.  `min(x, y, z) > r` below means "x > r and y > r and z > r" and `max(x, y, z) < -r`
+ *               means "x < -r and y < -r and z < -r": a NaN in any term never misses.
+ *     box axes,   m = x, y, z:  miss if min(v0_m, v1_m, v2_m) > h_m or max(v0_m, v1_m, v2_m) < -h_m.
+ *     plane:      d = (n.x*v0.x + n.y*v0.y) + n.z*v0.z;  r = (h.x*|n.x| + h.y*|n.y|) + h.z*|n.z|;  miss if d > r or d < -r.
+ *     cross axes, each edge e = e_j (j = 0, 1, 2) and each m with (m1, m2) = ((m+1)%3, (m+2)%3):  p_i = e_m1 * vi_m2 - e_m2 * vi_m1 for i = 0, 1,
+ *                 2 (all three computed, none reused);  r = h_m1*|e_m2| + h_m2*|e_m1|;  miss if min(p_0, p_1, p_2) > r or max(p_0, p_1, p_2) < -r.
+ *               This is the separating-axis test of Akenine-Moller (2001) with its operations fixed.  A zero-area triangle (a segment, a
+ *               point) takes the same clauses with n = 0; there is no special case.
+ *   M2S_VOXELIZE_SURFACE  the cell is set iff overlap(t, cell) holds for some t.
+ *   M2S_VOXELIZE_SOLID    the surface set, OR the inside bit that m2s_generate_grid_sdf(..., M2S_SIGN_RAYCAST) applies to that cell (the
+ *               majority plane of sign.hip): on any mesh, solid == surface | signbit(generate_grid_sdf(Raycast)), cell for cell.  A cell
+ *               whose centre lies on a triangle is a surface cell, so the sign of a zero distance never matters.
+ * m2s_opts.algorithm = 1 evaluates every triangle against every cell and is the definition; the default path returns the same bits in every
+ * output on every input, one-shot or m2s_mesh, host or device memory.  The result is an OR: it does not depend on the order of evaluation.
+ *   bits_out       uint32[nx*ny*nzw], nzw = ceil(nz/32): cell (i, j, k) is bit k & 31 of word (i*ny + j)*nzw + (k >> 5) (the layout of the sign
+ *                  planes); bits at k >= nz are 0.
+ *   occupancy_out  uint8[nx*ny*nz], 0 or 1, at L = k + j*nz + i*ny*nz (Grid::get_cell_idx).
+ *   cells_out      the L of every set cell as uint64, ascending; cell_capacity = the entries it can hold.
+ *   n_set_out      the number of set cells: one uint64 on the HOST, whatever mem_kind says (like area_out); written by every call that passes
+ *                  the argument checks.
+ * Each may be NULL; all four NULL is M2S_ERR_BAD_ARG.  A cell_capacity below the count is M2S_ERR_BAD_ARG with *n_set_out written, bits_out
+ * and occupancy_out complete and cells_out untouched.  A call that asks for cells_out or n_set_out synchronises its stream once for the
+ * count; one that asks only for bits_out / occupancy_out honours synchronous = 0.
+ * m2s_voxelize_opts: NULL = SURFACE.  M2S_ERR_BAD_ARG before any device work: NULL grid; a zero cell count, a face of 2^32 or more lines or
+ * 2^36 or more cells; a cell size <= 0 or not finite; a non-finite first_cell; a bad mode or a struct_size other than
+ * sizeof(m2s_voxelize_opts); x_begin, x_end, x_period or peer_out not zero (slabs are out of scope here: the whole grid is voxelized); bad
+ * enums; host-memory indices out of range.  A mesh without triangles sets nothing and returns M2S_OK, in both modes.
+ * m2s_opts otherwise as for the ray calls: device, stream / stream_mode, mem_kind (EVERY data pointer on one side, n_set_out excepted),
+ * synchronous, lane, algorithm.  timings: accel_build_ms = the triangle records (the one-shot form builds no tree), seed_ms = the sign
+ * planes (0 for SURFACE), distance_ms = the voxelization kernels, n_units = the grid's cells.  The tree of an m2s_mesh is not consulted, so
+ * re-marking its leaves changes nothing; asynchronous calls on a mesh add their spans up in m2s_mesh_drain_timings.
+ * Cost: proportional to the sum over triangles of (candidate columns x z extent) of their boxes — a mesh of many grid-spanning skewed
+ * triangles in a 1024^3 grid is legal and slow. */
+enum { M2S_VOXELIZE_SURFACE = 0, M2S_VOXELIZE_SOLID = 1 };
+typedef struct m2s_voxelize_opts {
+  uint32_t struct_size;   /* sizeof(m2s_voxelize_opts) */
+  uint32_t mode;          /* M2S_VOXELIZE_SURFACE / M2S_VOXELIZE_SOLID */
+} m2s_voxelize_opts;
+int m2s_voxelize(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology,
+                 const m2s_grid* grid, const m2s_voxelize_opts* vopts, uint32_t* bits_out, uint8_t* occupancy_out,
+                 uint64_t* cells_out, uint64_t cell_capacity, uint64_t* n_set_out, const m2s_opts* opts);
+int m2s_mesh_voxelize(m2s_mesh* mesh, const m2s_grid* grid, const m2s_voxelize_opts* vopts, uint32_t* bits_out, uint8_t* occupancy_out,
+                      uint64_t* cells_out, uint64_t cell_capacity, uint64_t* n_set_out, const m2s_opts* opts);
 
 /* Grid helpers with the reference's exact f32 arithmetic (so callers need not re-derive it).
  * m2s_grid_from_bounding_box — Grid::from_bounding_box, grid.rs:59-74.

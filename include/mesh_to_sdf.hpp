@@ -14,6 +14,7 @@
 //   winding_numbers / grid_winding_numbers / generate_grid_sdf_winding   generalized winding numbers and their sign (m2s.h)
 //   cast_rays / count_intersections / test_occlusions   watertight ray casting against the mesh (m2s.h)
 //   sample_surface / surface_area   area-weighted surface samples, defined to the bit (m2s.h)
+//   voxelize                        surface / solid occupancy of a grid, defined to the bit (m2s.h)
 //   sample_grid / raymarch_grid  client draw_raymarching.wgsl  sdf_grid / estimate_normal / sdf_3d on a finished grid (m2s.h)
 //   grid_isosurface                                            marching-cubes mesh of a level set of a finished grid (no reference counterpart; m2s.h)
 //   serde::*               serde.rs:75-221                     SerializeSdf / DeserializeSdf / save_to_file / read_from_file
@@ -419,6 +420,29 @@ SurfaceSamples sample_surface(const std::vector<V>& vertices, const Topology<I>&
 template <class V, class I = uint32_t>
 double surface_area(const std::vector<V>& vertices, const Topology<I>& indices) {
   return sample_surface(vertices, indices, 0).area;
+}
+
+// ---- voxelization (m2s_voxelize) -----------------------------------------------------------------------------------------------------
+// Which cells of the grid the mesh occupies, defined to the bit (m2s.h): a cell is set when its closed box touches a triangle, and with
+// `solid` also when its centre is inside by the Raycast sign of generate_grid_sdf.
+struct Voxels {
+  std::vector<uint8_t> occupancy;   // 0 / 1 per cell, grid order (Grid::get_cell_idx)
+  std::vector<uint32_t> bits;       // cell (i, j, k) is bit k & 31 of word (i * ny + j) * ceil(nz / 32) + (k >> 5); empty unless asked for
+  uint64_t count = 0;               // set cells
+};
+template <class V, class I = uint32_t>
+Voxels voxelize(const std::vector<V>& vertices, const Topology<I>& indices, const Grid<V>& grid, bool solid = false, bool bits = false) {
+  detail::Packed<V> v(vertices.data(), vertices.size());
+  detail::IndexArg<I> ia(indices);
+  Voxels r;
+  const auto n = grid.get_cell_count();
+  r.occupancy.resize(grid.get_total_cell_count());
+  if (bits) r.bits.resize(n[0] * n[1] * ((n[2] + 31) / 32));
+  const m2s_voxelize_opts vo = {sizeof(m2s_voxelize_opts), (uint32_t)(solid ? M2S_VOXELIZE_SOLID : M2S_VOXELIZE_SURFACE)};
+  detail::check(m2s_voxelize(v.ptr, vertices.size(), ia.ptr, indices.count, ia.bytes, indices.kind, &grid.raw(), &vo,
+                             r.bits.empty() ? nullptr : r.bits.data(), r.occupancy.empty() ? nullptr : r.occupancy.data(), nullptr, 0, &r.count,
+                             nullptr));
+  return r;
 }
 
 // ---- queries on a finished grid (m2s_sample_grid, m2s_raymarch_grid) ------------------------------------------------------

@@ -551,6 +551,65 @@ def surface_area(vertices, indices: Topology) -> float:
     return float(area.value)
 
 
+class Voxels(NamedTuple):
+    """Occupancy of a grid: occupancy uint8[nx, ny, nz] (0 / 1), bits uint32[nx, ny, ceil(nz / 32)] (cell k of a row is bit k & 31 of
+    word k >> 5; None unless asked for), cells (grid-order indices of the set cells, ascending; uint64 on the host, int64 on the device;
+    None unless asked for), count (set cells; None for an asynchronous call)."""
+    occupancy: object
+    bits: object
+    cells: object
+    count: Optional[int]
+
+
+def _voxel_call(call, a, grid, solid, bits, cells, timings, algorithm, synchronous=True, occupancy=True, count=True):
+    """One voxelization, `call(grid, vopts, p_bits, p_occ, p_cells, capacity, p_count, opts)`; the arrays are made on the side of `a`.
+    `cells` takes a counting call first: its capacity is the count."""
+    nx, ny, nz = (int(v) for v in grid.get_cell_count())
+    nzw = (nz + 31) // 32
+    vo = _lib.M2SVoxelizeOpts(C.sizeof(_lib.M2SVoxelizeOpts), 1 if solid else 0)
+    synchronous = synchronous or not a.device
+    if cells and not synchronous:
+        raise M2SPanic(_lib.ERR_BAD_ARG, "cells needs a synchronous call")
+
+    def buf(shape, np_dtype, torch_dtype):
+        x = a.torch.empty(shape, dtype=getattr(a.torch, torch_dtype), device=a.dev) if a.device else np.empty(shape, np_dtype)
+        filled = x.numel() if a.device else x.size
+        return x, ((x.data_ptr() if a.device else x.ctypes.data) if filled else None)
+
+    want_count = synchronous and (count or cells)
+    count = C.c_uint64(0)
+    cell_arr, p_cells, capacity = None, None, 0
+    if cells:
+        o = a.opts(None, algorithm)
+        rc = call(C.byref(grid._g), C.byref(vo), None, None, None, 0, C.byref(count), C.byref(o))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        capacity = int(count.value)
+        cell_arr, p_cells = buf(capacity, np.uint64, "int64")
+    occ, p_occ = buf((nx, ny, nz), np.uint8, "uint8") if occupancy else (None, None)
+    bit_arr, p_bits = buf((nx, ny, nzw), np.uint32, "int32") if bits else (None, None)
+    if bits and a.device and hasattr(a.torch, "uint32"):
+        bit_arr = bit_arr.view(a.torch.uint32)
+    o = a.opts(timings, algorithm, synchronous=synchronous)
+    rc = call(C.byref(grid._g), C.byref(vo), p_bits, p_occ, p_cells, capacity, C.byref(count) if want_count else None, C.byref(o))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    return Voxels(occ, bit_arr, cell_arr, int(count.value) if want_count else None)
+
+
+def voxelize(vertices, indices: Topology, grid: "Grid", solid: bool = False, *, bits: bool = False, cells: bool = False, algorithm: int = 0,
+             timings: M2STimings = None, occupancy: bool = True, count: bool = True) -> Voxels:
+    """Which cells of `grid` the mesh occupies (include/m2s.h m2s_voxelize), defined to the bit: a cell is set when its closed box touches
+    a triangle (the separating-axis test of Akenine-Moller with its operations fixed), and with `solid` also when its centre is inside by
+    the Raycast sign of generate_grid_sdf.  `algorithm=1` tests every cell against every triangle (the definition; the same bits).  Host
+    arrays or device tensors, as the other calls take them; tests/voxel_model.py is the definition in numpy.  `occupancy=False` /
+    `count=False` leave those outputs out (None): the count costs one synchronisation of the stream."""
+    a = _Args(vertices, indices)
+    L = _lib.lib()
+    return _voxel_call(lambda *r: L.m2s_voxelize(a.p_verts, a.n_verts, a.p_idx, a.n_idx, a.index_bytes, a.topology, *r), a, grid, solid, bits,
+                       cells, timings, algorithm, True, occupancy, count)
+
+
 # DeepSDF's near-surface noise (Park et al. 2019: variances 0.0025 and 0.00025 in a unit sphere), as fractions of half the bounding-box diagonal
 NEAR_SURFACE_SIGMAS = (0.05, 0.0158)
 
@@ -1214,6 +1273,13 @@ class Mesh:
         if rc != _lib.M2S_OK:
             _raise(rc)
         return float(area.value)
+
+    def voxelize(self, grid: Grid, solid: bool = False, *, bits: bool = False, cells: bool = False, algorithm: int = 0,
+                 timings: M2STimings = None, synchronous: bool = True, occupancy: bool = True, count: bool = True) -> Voxels:
+        """voxelize on the resident triangles: the same bits as the one-shot function.  The tree is not consulted."""
+        L = _lib.lib()
+        return _voxel_call(lambda *r: L.m2s_mesh_voxelize(self._h, *r), self._a, grid, solid, bits, cells, timings, algorithm, synchronous,
+                           occupancy, count)
 
     def sample_sdf_near_surface(self, n: int, sigmas=None, uniform_fraction: float = 0.05, sign: str = "winding", seed: int = 0):
         """sample_sdf_near_surface on this mesh."""

@@ -1312,6 +1312,104 @@ int run_sample_surface(Arena& ws, const CallCtx& c, DeviceState& st, const Sampl
   return 0;
 }
 
+// ---- voxelization (m2s_voxelize, m2s_mesh_voxelize) ------------------------------------------------------------------------------------
+// ev[0] .. ev[1] the triangle records (one-shot), ev[2] .. ev[4] the sign planes (SOLID; seed_ms), ev[4] .. ev[3] the voxelization
+// kernels (distance_ms).  The mask is made in the caller's bits_out (device memory) or in the workspace; everything else derives from it.
+struct VoxelArgs {
+  uint32_t* bits;
+  uint8_t* occ;
+  uint64_t* cells;
+  uint64_t capacity;
+  uint64_t* n_set;
+  uint32_t mode;
+};
+
+int check_voxel_args(const m2s_grid* grid, const m2s_voxelize_opts* vopts, const m2s_opts* opts, VoxelArgs* o, GridParams* g, size_t* cells) {
+  if (!grid) return fail(M2S_ERR_BAD_ARG, "grid is NULL");
+  if (!o->bits && !o->occ && !o->cells && !o->n_set) return fail(M2S_ERR_BAD_ARG, "bits_out, occupancy_out, cells_out and n_set_out are all NULL");
+  if (vopts) {
+    if (vopts->struct_size != sizeof(m2s_voxelize_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_voxelize_opts.struct_size is not sizeof(m2s_voxelize_opts)");
+    if (vopts->mode != M2S_VOXELIZE_SURFACE && vopts->mode != M2S_VOXELIZE_SOLID) return fail(M2S_ERR_BAD_ARG, "bad m2s_voxelize_opts.mode %u", vopts->mode);
+    o->mode = vopts->mode;
+  }
+  if (opts && (opts->x_begin != 0 || opts->x_end != 0)) return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_begin / x_end do not apply to voxelization calls");
+  if (opts && opts->struct_size >= sizeof(m2s_opts) && (opts->x_period != 0 || opts->n_peer_out != 0 || opts->peer_out != nullptr))
+    return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_period / peer_out do not apply to voxelization calls");
+  if (opts && opts->mem_kind != M2S_MEM_HOST && opts->mem_kind != M2S_MEM_DEVICE) return fail(M2S_ERR_BAD_ARG, "bad mem_kind");
+  if (opts && opts->algorithm != 0 && opts->algorithm != 1) return fail(M2S_ERR_BAD_ARG, "bad algorithm");
+  for (int k = 0; k < 3; ++k) {
+    if (grid->cell_count[k] == 0) return fail(M2S_ERR_BAD_ARG, "cell_count[%d] is 0", k);
+    if (!(grid->cell_size[k] > 0.0f) || !std::isfinite(grid->cell_size[k])) return fail(M2S_ERR_BAD_ARG, "cell_size[%d] must be positive and finite", k);
+    if (!std::isfinite(grid->first_cell[k])) return fail(M2S_ERR_BAD_ARG, "first_cell[%d] is not finite", k);
+  }
+  const int rc = fill_grid_params(grid, nullptr, g, cells);
+  if (rc) return rc;
+  if ((uint64_t)grid->cell_count[0] * grid->cell_count[1] * grid->cell_count[2] >= (1ull << 36)) return fail(M2S_ERR_BAD_ARG, "2^36 or more cells");
+  return 0;
+}
+
+size_t voxel_workspace_bytes(const CallCtx& c, const GridParams& g, size_t n_tris, size_t cells, const VoxelArgs& o) {
+  const size_t words = (size_t)g.n[0] * g.n[1] * g.nzw;
+  size_t b = voxel_scratch_bytes(g, n_tris) + align_up(words * 4) + 4096;
+  if (o.mode == M2S_VOXELIZE_SOLID) b += sign_workspace_bytes(g, n_tris);
+  if (c.mem_kind == M2S_MEM_HOST) b += (o.occ ? align_up(cells) : 0) + (o.cells ? align_up((size_t)std::min<uint64_t>(o.capacity, cells) * 8) : 0);
+  return b;
+}
+
+// Everything after the triangle records exist.  Records ev[2], ev[4], ev[3]; *short_capacity: cell_capacity is below the count
+// (bits_out and occupancy_out are complete, cells_out untouched).
+int run_voxelize(Arena& ws, const CallCtx& c, DeviceState& st, const DeviceMesh& mesh, const GridParams& g, size_t cells, const VoxelArgs& o,
+                 bool* short_capacity) {
+  *short_capacity = false;
+  const size_t words = (size_t)g.n[0] * g.n[1] * g.nzw;
+  const bool host = c.mem_kind == M2S_MEM_HOST;
+  VoxelScratch vs;
+  if (voxel_scratch_carve(ws, g, mesh.n_tris, &vs)) return fail(M2S_ERR_HIP, "internal: workspace");
+  uint32_t* d_bits = (!host && o.bits) ? o.bits : ws.take<uint32_t>(words);
+  uint8_t* d_occ = (!host || !o.occ) ? o.occ : ws.take<uint8_t>(cells);
+  if (!d_bits || (o.occ && !d_occ)) return fail(M2S_ERR_HIP, "internal: workspace");
+  int rc = 0;
+  M2S_HIP_CHECK(hipEventRecord(st.ev[2], c.stream));
+  st.planes_done = nullptr;
+  const uint32_t* plane = nullptr;
+  if (o.mode == M2S_VOXELIZE_SOLID && (rc = build_grid_sign_plane(ws, c.stream, mesh, g, &plane, false))) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st.ev[4], c.stream));
+  if ((rc = launch_voxelize_surface(c.stream, mesh.tris, mesh.n_tris, g, c.algorithm, vs, d_bits))) return rc;
+  if (plane && mesh.n_tris && (rc = launch_voxel_or_plane(c.stream, g, plane, d_bits))) return rc;
+  if (o.occ && (rc = launch_voxel_expand(c.stream, g, d_bits, d_occ))) return rc;
+  uint64_t count = 0;
+  if (o.cells || o.n_set) {
+    if ((rc = launch_voxel_count(c.stream, g, d_bits, vs))) return rc;
+    uint64_t* h = reinterpret_cast<uint64_t*>(st.h_err) + 1;   // 64 pinned bytes; the first word stays the call's error flags
+    M2S_HIP_CHECK(hipMemcpyAsync(h, vs.hdr, 8, hipMemcpyDeviceToHost, c.stream));
+    M2S_HIP_CHECK(hipStreamSynchronize(c.stream));
+    count = *h;
+    if (o.n_set) *o.n_set = count;
+    *short_capacity = o.cells && o.capacity < count;
+  }
+  uint64_t* d_cells = o.cells;
+  if (o.cells && !*short_capacity && count) {
+    if (host && !(d_cells = ws.take<uint64_t>(count))) return fail(M2S_ERR_HIP, "internal: workspace");
+    if ((rc = launch_voxel_cells(c.stream, g, d_bits, vs, count, d_cells))) return rc;
+  }
+  M2S_HIP_CHECK(hipEventRecord(st.ev[3], c.stream));
+  if (!host) return 0;
+  if (o.bits && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.bits), reinterpret_cast<const char*>(d_bits), words * 4))) return rc;
+  if (o.occ && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.occ), reinterpret_cast<const char*>(d_occ), cells))) return rc;
+  if (o.cells && !*short_capacity && count &&
+      (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.cells), reinterpret_cast<const char*>(d_cells), count * 8)))
+    return rc;
+  return 0;
+}
+
+int finish_voxelize(const CallCtx& c, DeviceState& st, int* d_err, size_t n_tris, size_t cells, const VoxelArgs& o, bool short_capacity) {
+  const int rc = finish_call(c, st, d_err, c.timings, n_tris, cells, false, true);
+  if (c.sync && c.timings && o.mode != M2S_VOXELIZE_SOLID) c.timings->seed_ms = 0.0f;
+  if (rc) return rc;
+  if (short_capacity) return fail(M2S_ERR_BAD_ARG, "cell_capacity %llu is below the number of set cells (*n_set_out)", (unsigned long long)o.capacity);
+  return M2S_OK;
+}
+
 // An asynchronous call on a mesh: its event pair ev[4] .. ev[3] moves into the mesh's pending list (m2s_mesh_drain_timings waits for it
 // and adds the span up), and the context gets fresh events for the next call.
 int park_async_events(m2s_mesh* m, DeviceState& st, uint64_t units, uint32_t launches) {
@@ -1757,6 +1855,7 @@ int m2s_warmup(int device, size_t workspace_bytes, size_t host_ring_bytes) {
   warm_grid_query(c.stream);
   warm_rays(c.stream);
   warm_sample(c.stream);
+  warm_voxelize(c.stream);
   warm_sortlib(c.stream);                                        // (the rocPRIM sorts of large meshes and of the query path: units of their own,
   warm_sortlib_query(c.stream);                                  // which a grid call over a mesh of <= 229 376 triangles never loads)
   M2S_HIP_CHECK(hipGetLastError());
@@ -2555,6 +2654,76 @@ int m2s_mesh_sample_surface(m2s_mesh* m, size_t n_samples, const m2s_surface_sam
   if ((rc = run_sample_surface(ws, c, *st, src, m->samp, m->samp_W, n_samples, o))) return rc;
   if (!c.sync) return park_async_events(m, *st, n_samples, 1);
   return finish_call(c, *st, d_err, c.timings, m->n_tris, n_samples, false, true);
+}
+
+// Voxelization (include/m2s.h): the one-shot call builds the triangle records and nothing else; the mesh call reads its resident records.
+int m2s_voxelize(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology,
+                 const m2s_grid* grid, const m2s_voxelize_opts* vopts, uint32_t* bits_out, uint8_t* occupancy_out, uint64_t* cells_out,
+                 uint64_t cell_capacity, uint64_t* n_set_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  VoxelArgs o{bits_out, occupancy_out, cells_out, cell_capacity, n_set_out, M2S_VOXELIZE_SURFACE};
+  GridParams g;
+  size_t cells = 0;
+  int rc = check_voxel_args(grid, vopts, opts, &o, &g, &cells);
+  if (rc) return rc;
+  if ((rc = check_mesh_args(vertices, n_vertices, indices, n_indices, index_bytes, topology))) return rc;
+  const size_t n_tris = m2s_triangle_count(n_vertices, n_indices, indices != nullptr, topology);
+  if (n_tris > ((size_t)1 << 25)) return fail(M2S_ERR_BAD_ARG, "more than 2^25 triangles");
+  if (!opts || opts->mem_kind == M2S_MEM_HOST) {
+    if ((rc = check_host_indices(indices, n_indices, index_bytes, topology, n_vertices, n_tris))) return rc;
+  }
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(opts, &c, &st))) return rc;
+  size_t need = bvh_workspace_bytes(n_tris) + voxel_workspace_bytes(c, g, n_tris, cells, o) + 4096;
+  if (c.mem_kind == M2S_MEM_HOST) need += align_up(n_vertices * 12) + align_up(n_indices * (size_t)(indices ? index_bytes : 0)) + 1024;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  StagedMesh sm;
+  if ((rc = stage_mesh(ws, c, vertices, n_vertices, indices, n_indices, index_bytes, &sm))) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  DeviceMesh mesh;
+  if ((rc = build_device_mesh(ws, c.stream, sm.d_verts, n_vertices, sm.d_indices, n_indices, index_bytes, topology, n_tris, d_err, &mesh, nullptr, true)))
+    return rc;
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  bool short_capacity = false;
+  if ((rc = run_voxelize(ws, c, *st, mesh, g, cells, o, &short_capacity))) return rc;
+  return finish_voxelize(c, *st, d_err, n_tris, cells, o, short_capacity);
+}
+
+int m2s_mesh_voxelize(m2s_mesh* m, const m2s_grid* grid, const m2s_voxelize_opts* vopts, uint32_t* bits_out, uint8_t* occupancy_out,
+                      uint64_t* cells_out, uint64_t cell_capacity, uint64_t* n_set_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  if (!m) return fail(M2S_ERR_BAD_ARG, "mesh is NULL");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  VoxelArgs o{bits_out, occupancy_out, cells_out, cell_capacity, n_set_out, M2S_VOXELIZE_SURFACE};
+  GridParams g;
+  size_t cells = 0;
+  int rc = check_voxel_args(grid, vopts, opts, &o, &g, &cells);
+  if (rc) return rc;
+  m2s_opts mo;
+  if ((rc = mesh_call_opts(m, opts, &mo))) return rc;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(&mo, &c, &st))) return rc;
+  if ((rc = ensure_capacity(*st, voxel_workspace_bytes(c, g, m->n_tris, cells, o) + 8192))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  if (c.sync) M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  else d_err = m->d_err_async;   // asynchronous calls report through the mesh (m2s_mesh_drain_timings)
+  if (!c.sync) reap_pending(m, false);
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  if ((rc = remark_leaves(m, c, m->dm.leaf_max))) return rc;   // no mark is read or moved; keeps the mesh's stream bookkeeping (the records are read)
+  bool short_capacity = false;
+  if ((rc = run_voxelize(ws, c, *st, m->dm, g, cells, o, &short_capacity))) return rc;
+  if (!c.sync) {
+    if ((rc = park_async_events(m, *st, cells, 1))) return rc;
+    return short_capacity ? fail(M2S_ERR_BAD_ARG, "cell_capacity %llu is below the number of set cells (*n_set_out)", (unsigned long long)cell_capacity) : M2S_OK;
+  }
+  return finish_voxelize(c, *st, d_err, m->n_tris, cells, o, short_capacity);
 }
 
 // Peer-write bandwidth probe (include/m2s.h): the copy kernel of M2S_PEER_PUSH, timed with HIP events on a stream of its own.

@@ -237,6 +237,7 @@ void warm_sortlib_query(hipStream_t st);
 void warm_grid_query(hipStream_t st);
 void warm_rays(hipStream_t st);
 void warm_sample(hipStream_t st);
+void warm_voxelize(hipStream_t st);
 // bvh.hip: flatten topology, build triangle records + LBVH in pre-order layout.
 size_t bvh_workspace_bytes(size_t n_tris);
 // `after_setup` (optional) is called twice with the input-order centroid array and triangle records: with phase 0 once the kernels that fill
@@ -470,6 +471,25 @@ int launch_sample_table(hipStream_t st, const SampleSrc& src, const SampleTable&
 // Samples first .. first + n_samples - 1 under `seed`; W = the table's total (> 0).  algorithm 1: the pick scans C linearly.
 int launch_sample_surface(hipStream_t st, const SampleSrc& src, const SampleTable& tb, uint64_t W, uint64_t seed, uint64_t first, size_t n_samples,
                           int algorithm, const SampleOut& out);
+
+// voxelize.hip: surface and solid occupancy of a grid, one bit per cell in the layout of the sign planes.
+struct VoxelScratch {
+  uint32_t* iv;         // per triangle: the x, y and z intervals of cells that pass its box clauses (lo, hi) x 3
+  uint64_t* cols;       // per triangle: candidate columns
+  uint64_t* S;          // n_tris + 1 exclusive running sums of cols
+  uint64_t* tile_sum;   // scratch of both scans
+  uint64_t* hdr;        // [0]: set cells (launch_voxel_count), [1]: candidate columns
+};
+size_t voxel_scratch_bytes(const GridParams& g, size_t n_tris);
+int voxel_scratch_carve(Arena& ws, const GridParams& g, size_t n_tris, VoxelScratch* s);   // -1: out of space
+// bits (n[0] * n[1] * nzw words, cleared here) = the cells some triangle of `tris` overlaps; any record order.  algorithm 1: all pairs.
+int launch_voxelize_surface(hipStream_t st, const TriRec* tris, uint32_t n_tris, const GridParams& g, int algorithm, const VoxelScratch& s,
+                            uint32_t* bits);
+int launch_voxel_or_plane(hipStream_t st, const GridParams& g, const uint32_t* plane, uint32_t* bits);   // SOLID: bits |= the sign plane
+int launch_voxel_count(hipStream_t st, const GridParams& g, const uint32_t* bits, const VoxelScratch& s);   // s.hdr[0] = set cells; s.tile_sum = per-tile offsets
+int launch_voxel_expand(hipStream_t st, const GridParams& g, const uint32_t* bits, uint8_t* occ);          // one byte per cell, grid order
+// after launch_voxel_count: the grid-order index of every set cell, ascending; entries from `capacity` on are dropped
+int launch_voxel_cells(hipStream_t st, const GridParams& g, const uint32_t* bits, const VoxelScratch& s, uint64_t capacity, uint64_t* cells_out);
 
 // grid_query.hip: sampling and ray-marching a finished grid SDF (the client's draw_raymarching.wgsl).  The grid's scalars travel as a
 // kernel argument; start / end are the shader's uniforms (first_cell, Grid::get_last_cell), n[] >= 1, cs[] > 0 and finite.

@@ -1,8 +1,9 @@
-// geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h and sample.hip.h, for CPU unit tests only
-// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py).  Not linked into libm2s_hip.so.
+// geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h, sample.hip.h and voxel.hip.h, for CPU unit tests only
+// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py).  Not linked into libm2s_hip.so.
 #include "geo.hip.h"
 #include "ray.hip.h"
 #include "sample.hip.h"
+#include "voxel.hip.h"
 
 using namespace m2s;
 
@@ -77,5 +78,38 @@ void probe_sample_point(const float* a, const float* b, const float* c, float u,
 void probe_sample_normal(const float* n, float A, float* out) {
   const f3 q = sample_normal(mk3(n[0], n[1], n[2]), A);
   out[0] = q.x; out[1] = q.y; out[2] = q.z;
+}
+// voxel.hip.h
+// n (triangle, cell) pairs: tris 9 floats each (a, b, c), q and h 3 floats each; out[i] = overlap
+void probe_vox_overlap(uint64_t n, const float* tris, const float* q, const float* h, uint8_t* out) {
+  for (uint64_t i = 0; i < n; ++i) {
+    const float* t = tris + 9 * i;
+    const VoxTri tr = vox_tri(mk3(t[0], t[1], t[2]), mk3(t[3], t[4], t[5]), mk3(t[6], t[7], t[8]));
+    const float qq[3] = {q[3 * i], q[3 * i + 1], q[3 * i + 2]}, hh[3] = {h[3 * i], h[3 * i + 1], h[3 * i + 2]};
+    out[i] = vox_overlap(tr, qq, hh) ? 1 : 0;
+  }
+}
+float probe_vox_centre(float first, float size, uint32_t idx) { return vox_centre(first, size, idx); }
+void probe_vox_interval(float pa, float pb, float pc, float first, float size, uint32_t n, uint32_t* lo_hi) {
+  vox_interval(pa, pb, pc, first, size, n, &lo_hi[0], &lo_hi[1]);
+}
+// One triangle over a whole grid the way the raster kernel goes: intervals, column clauses, cell clauses.  occ: n[0] * n[1] * n[2] bytes, OR-ed into.
+void probe_vox_raster(const float* t, const float* first, const float* size, const uint32_t* n, uint8_t* occ) {
+  const VoxTri tr = vox_tri(mk3(t[0], t[1], t[2]), mk3(t[3], t[4], t[5]), mk3(t[6], t[7], t[8]));
+  if (!tr.finite) return;
+  uint32_t lo[3], hi[3];
+  for (int m = 0; m < 3; ++m) vox_interval(tr.a[m], tr.b[m], tr.c[m], first[m], size[m], n[m], &lo[m], &hi[m]);
+  const float h[3] = {size[0] * 0.5f, size[1] * 0.5f, size[2] * 0.5f};
+  for (uint32_t i = lo[0]; i < hi[0]; ++i)
+    for (uint32_t j = lo[1]; j < hi[1]; ++j) {
+      const float qx = vox_centre(first[0], size[0], i), qy = vox_centre(first[1], size[1], j);
+      float v0[3] = {tr.a[0] - qx, tr.a[1] - qy, 0.0f}, v1[3] = {tr.b[0] - qx, tr.b[1] - qy, 0.0f}, v2[3] = {tr.c[0] - qx, tr.c[1] - qy, 0.0f};
+      if (vox_column_miss(tr, v0, v1, v2, h)) continue;
+      for (uint32_t k = lo[2]; k < hi[2]; ++k) {
+        const float qz = vox_centre(first[2], size[2], k);
+        v0[2] = tr.a[2] - qz; v1[2] = tr.b[2] - qz; v2[2] = tr.c[2] - qz;
+        if (!vox_cell_miss(tr, v0, v1, v2, h)) occ[((size_t)i * n[1] + j) * n[2] + k] = 1;
+      }
+    }
 }
 }
