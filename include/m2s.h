@@ -49,7 +49,7 @@ extern "C" {
 #endif
 
 #define M2S_VERSION_MAJOR 0
-#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
+#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
 
 /* Return codes.  The reference panics where this ABI returns a negative code; the Rust shim
  * turns a negative code back into panic!(m2s_last_error()). */
@@ -526,6 +526,52 @@ int m2s_voxelize(const float* vertices, size_t n_vertices, const void* indices, 
                  uint64_t* cells_out, uint64_t cell_capacity, uint64_t* n_set_out, const m2s_opts* opts);
 int m2s_mesh_voxelize(m2s_mesh* mesh, const m2s_grid* grid, const m2s_voxelize_opts* vopts, uint32_t* bits_out, uint8_t* occupancy_out,
                       uint64_t* cells_out, uint64_t cell_capacity, uint64_t* n_set_out, const m2s_opts* opts);
+
+/* ---- narrow-band grid SDFs: the cells near the surface, and their distances --------------------------------------------------------------
+ * What OpenVDB meshToLevelSet(exteriorBand, interiorBand), kaolin's sparse grids and sparse-brick SDF stores ask for: the signed distance
+ * at the cells within a few cell widths of the surface and nothing else — O(n^2) cells of an n^3 grid.  The result is DEFINED as a filter
+ * of the dense call, so it has no floating-point model of its own:
+ *   D = m2s_generate_grid_sdf(mesh, grid, sign_method), negative inside; exterior >= 0 and interior >= 0 in world units;
+ *   the active set is  A = { L : -interior <= D[L] <= exterior },  L = k + j*nz + i*ny*nz.
+ * Both widths may be +inf.  A NaN in D[L] is never active (both comparisons fail); -0 and +0 count as 0.  With exterior = +inf the cells
+ * where the dense call keeps f32::MAX (a mesh without triangles, or without a finite one) are active like any other; with a finite
+ * exterior such a mesh activates nothing.
+ *   cells_out      the L of every active cell as uint64, ascending.
+ *   distances_out  distances_out[n] = D[cells_out[n]], every bit including the sign bit.
+ *   bits_out       the active set as a mask in the layout of m2s_voxelize's bits_out (the sign planes'); bits at k >= nz are 0.
+ *   n_active_out   the number of active cells: one uint64 on the HOST, whatever mem_kind says; written by every call that passes the
+ *                  argument checks.
+ * Each may be NULL; all four NULL is M2S_ERR_BAD_ARG.  `capacity` = the entries cells_out and distances_out can each hold.  A capacity
+ * below the count is M2S_ERR_BAD_ARG with *n_active_out written, bits_out complete and cells_out / distances_out untouched (the call
+ * compacts into its workspace and copies once the count is known to fit: counting first would walk every candidate twice).
+ * sign_method: M2S_SIGN_NORMAL or M2S_SIGN_RAYCAST, the rules of m2s_generate_grid_sdf.  m2s_opts.algorithm = 1 is the definition made
+ * literal — the dense grid call into the workspace, then the filter — and needs room for the dense grid; the default path returns the
+ * same bits in every output on every input, one-shot or m2s_mesh, host or device memory.  It evaluates only candidates: cells whose
+ * centre is within max(exterior, interior), grown by the walks' own pruning margin, of some triangle's axis-aligned box (band.hip.h gives
+ * the predicate and the argument that no active cell is missed), in chunks of M2S_BAND_CHUNK candidates through the query walk.
+ * M2S_ERR_BAD_ARG before any device work: everything m2s_voxelize rejects for a grid (2^36 or more cells, a face of 2^32 or more lines, ...);
+ * x_begin, x_end, x_period or peer_out not zero; NULL bopts, a width that is negative or NaN, a struct_size other than
+ * sizeof(m2s_band_opts); all outputs NULL; a bad sign method; bad enums; host-memory indices out of range.  M2S_ERR_NAN as
+ * m2s_generate_grid_sdf reports it (Normal) when the walk of a candidate meets a NaN distance.
+ * m2s_opts otherwise as for m2s_voxelize.  The call synchronises its stream twice — for the number of candidates, which sizes the chunks,
+ * and for the number of active cells — so synchronous = 0 on an m2s_mesh only moves the timings into m2s_mesh_drain_timings.
+ * timings: accel_build_ms = the build (the one-shot form builds a tree with the leaf size the query walk asks for), seed_ms = the sign
+ * planes plus the candidate pass, distance_ms = the query walks plus filter and compaction, n_units = the candidates evaluated (the
+ * grid's cells under algorithm 1).
+ * Workspace: two masks, the sign planes (Raycast), one chunk's queries and query workspace, and min(capacity, cells) entries of 12 bytes
+ * when cells_out or distances_out is asked for. */
+typedef struct m2s_band_opts {
+  uint32_t struct_size;   /* sizeof(m2s_band_opts) */
+  float exterior;         /* >= 0, +inf allowed: the band's width outside (D > 0), world units */
+  float interior;         /* >= 0, +inf allowed: its width inside (D < 0) */
+} m2s_band_opts;
+int m2s_narrow_band_sdf(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology,
+                        const m2s_grid* grid, int sign_method, const m2s_band_opts* bopts,
+                        uint64_t* cells_out, float* distances_out, uint64_t capacity, uint32_t* bits_out,
+                        uint64_t* n_active_out, const m2s_opts* opts);
+int m2s_mesh_narrow_band_sdf(m2s_mesh* mesh, const m2s_grid* grid, int sign_method, const m2s_band_opts* bopts,
+                             uint64_t* cells_out, float* distances_out, uint64_t capacity, uint32_t* bits_out,
+                             uint64_t* n_active_out, const m2s_opts* opts);
 
 /* Grid helpers with the reference's exact f32 arithmetic (so callers need not re-derive it).
  * m2s_grid_from_bounding_box — Grid::from_bounding_box, grid.rs:59-74.

@@ -15,6 +15,7 @@
 //   cast_rays / count_intersections / test_occlusions   watertight ray casting against the mesh (m2s.h)
 //   sample_surface / surface_area   area-weighted surface samples, defined to the bit (m2s.h)
 //   voxelize                        surface / solid occupancy of a grid, defined to the bit (m2s.h)
+//   narrow_band_sdf                 the cells of a grid within a band of the surface and their distances: the dense result, filtered (m2s.h)
 //   sample_grid / raymarch_grid  client draw_raymarching.wgsl  sdf_grid / estimate_normal / sdf_3d on a finished grid (m2s.h)
 //   grid_isosurface                                            marching-cubes mesh of a level set of a finished grid (no reference counterpart; m2s.h)
 //   serde::*               serde.rs:75-221                     SerializeSdf / DeserializeSdf / save_to_file / read_from_file
@@ -442,6 +443,35 @@ Voxels voxelize(const std::vector<V>& vertices, const Topology<I>& indices, cons
   detail::check(m2s_voxelize(v.ptr, vertices.size(), ia.ptr, indices.count, ia.bytes, indices.kind, &grid.raw(), &vo,
                              r.bits.empty() ? nullptr : r.bits.data(), r.occupancy.empty() ? nullptr : r.occupancy.data(), nullptr, 0, &r.count,
                              nullptr));
+  return r;
+}
+
+// ---- narrow bands (m2s_narrow_band_sdf) ------------------------------------------------------------------------------------------------
+// The cells whose generate_grid_sdf value D lies in -interior <= D <= exterior (world units, +inf allowed), ascending, and those values bit
+// for bit.  Two calls: the count, then the fill.
+struct NarrowBand {
+  std::vector<uint64_t> cells;      // grid order (Grid::get_cell_idx), ascending
+  std::vector<float> distances;     // distances[n] = the dense value at cells[n]
+  std::vector<uint32_t> bits;       // the active set in the layout of Voxels::bits; empty unless asked for
+  uint64_t count = 0;
+};
+template <class V, class I = uint32_t>
+NarrowBand narrow_band_sdf(const std::vector<V>& vertices, const Topology<I>& indices, const Grid<V>& grid, float interior, float exterior,
+                           SignMethod sign_method = SignMethod::Raycast, bool bits = false) {
+  detail::Packed<V> v(vertices.data(), vertices.size());
+  detail::IndexArg<I> ia(indices);
+  NarrowBand r;
+  const m2s_band_opts bo = {sizeof(m2s_band_opts), exterior, interior};
+  detail::check(m2s_narrow_band_sdf(v.ptr, vertices.size(), ia.ptr, indices.count, ia.bytes, indices.kind, &grid.raw(), (int)sign_method, &bo, nullptr,
+                                    nullptr, 0, nullptr, &r.count, nullptr));
+  const auto n = grid.get_cell_count();
+  r.cells.resize(r.count);
+  r.distances.resize(r.count);
+  if (bits) r.bits.resize(n[0] * n[1] * ((n[2] + 31) / 32));
+  if (r.count == 0 && !bits) return r;
+  detail::check(m2s_narrow_band_sdf(v.ptr, vertices.size(), ia.ptr, indices.count, ia.bytes, indices.kind, &grid.raw(), (int)sign_method, &bo,
+                                    r.count ? r.cells.data() : nullptr, r.count ? r.distances.data() : nullptr, r.count,
+                                    r.bits.empty() ? nullptr : r.bits.data(), &r.count, nullptr));
   return r;
 }
 

@@ -129,6 +129,10 @@ class M2SVoxelizeOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_uint32)]
 
 
+class M2SBandOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("exterior", C.c_float), ("interior", C.c_float)]
+
+
 class M2SSampleOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("iso", C.c_float), ("outside", C.c_float), ("max_steps", C.c_uint32)]
 
@@ -166,6 +170,8 @@ EXPORTS = [
     "m2s_mesh_sample_surface",
     "m2s_voxelize",
     "m2s_mesh_voxelize",
+    "m2s_narrow_band_sdf",
+    "m2s_mesh_narrow_band_sdf",
     "m2s_sdf_grid_encoded_size",
     "m2s_sdf_generic_encoded_size",
     "m2s_sdf_encode_grid",
@@ -249,6 +255,10 @@ def _prototypes():
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(M2SOpts)]),
         "m2s_mesh_voxelize": (C.c_int, [C.c_void_p, C.POINTER(M2SGrid), C.POINTER(M2SVoxelizeOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.POINTER(M2SOpts)]),
+        "m2s_narrow_band_sdf": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(M2SGrid), C.c_int, C.POINTER(M2SBandOpts),
+                                          C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(M2SOpts)]),
+        "m2s_mesh_narrow_band_sdf": (C.c_int, [C.c_void_p, C.POINTER(M2SGrid), C.c_int, C.POINTER(M2SBandOpts), C.c_void_p, C.c_void_p, C.c_uint64,
+                                               C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(M2SOpts)]),
         "m2s_sdf_grid_encoded_size": (C.c_size_t, [C.POINTER(M2SGrid), C.c_size_t]),
         "m2s_sdf_generic_encoded_size": (C.c_size_t, [C.c_size_t, C.c_size_t]),
         "m2s_sdf_encode_grid": (C.c_int, [C.POINTER(M2SGrid), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(M2SOpts)]),

@@ -610,6 +610,92 @@ def voxelize(vertices, indices: Topology, grid: "Grid", solid: bool = False, *, 
                        cells, timings, algorithm, True, occupancy, count)
 
 
+class NarrowBand(NamedTuple):
+    """The cells of a grid within a band of the surface (include/m2s.h m2s_narrow_band_sdf): cells (their grid-order indices L, ascending;
+    uint64 on the host, int64 on the device), distances (float32, distances[n] = the dense generate_grid_sdf value at cells[n], bit for bit),
+    bits (uint32[nx, ny, ceil(nz / 32)], the layout of Voxels.bits; None unless asked for), count, grid."""
+    cells: object
+    distances: object
+    bits: object
+    count: int
+    grid: "Grid"
+
+    def ijk(self):
+        """(count, 3) cell coordinates: L = k + j*nz + i*ny*nz undone."""
+        _, ny, nz = (int(v) for v in self.grid.get_cell_count())
+        if _is_torch(self.cells):
+            L = self.cells
+            out = L.new_empty((L.numel(), 3))
+        else:
+            L = np.asarray(self.cells).astype(np.int64)
+            out = np.empty((L.size, 3), np.int64)
+        out[:, 0], out[:, 1], out[:, 2] = L // (ny * nz), (L // nz) % ny, L % nz
+        return out
+
+    def to_dense(self, fill=float("nan")):
+        """float32[nx, ny, nz] with `fill` outside the band: for small grids (it is the array the band exists to avoid)."""
+        shape = tuple(int(v) for v in self.grid.get_cell_count())
+        if _is_torch(self.cells):
+            out = self.distances.new_full((shape[0] * shape[1] * shape[2],), fill)
+            out[self.cells] = self.distances
+        else:
+            out = np.full(shape[0] * shape[1] * shape[2], fill, np.float32)
+            out[np.asarray(self.cells).astype(np.int64)] = self.distances
+        return out.reshape(shape)
+
+
+def _band_widths(band):
+    """band: one width for both sides, or (interior, exterior)."""
+    interior, exterior = (band, band) if np.isscalar(band) else band
+    return float(interior), float(exterior)
+
+
+def _band_call(call, a, grid, band, sign_method, bits, algorithm, timings, capacity, synchronous=True):
+    """One narrow-band call, `call(grid, sign, bopts, p_cells, p_dist, capacity, p_bits, p_count, opts)`; the arrays are made on the side of
+    `a`.  Without `capacity` the call runs twice: a counting call (no cells, no distances), then the fill with the count as capacity."""
+    nx, ny, nz = (int(v) for v in grid.get_cell_count())
+    interior, exterior = _band_widths(band)
+    bo = _lib.M2SBandOpts(C.sizeof(_lib.M2SBandOpts), exterior, interior)
+    synchronous = synchronous or not a.device
+
+    def buf(shape, np_dtype, torch_dtype):
+        x = a.torch.empty(shape, dtype=getattr(a.torch, torch_dtype), device=a.dev) if a.device else np.empty(shape, np_dtype)
+        filled = x.numel() if a.device else x.size
+        return x, ((x.data_ptr() if a.device else x.ctypes.data) if filled else None)
+
+    count = C.c_uint64(0)
+    if capacity is None:
+        o = a.opts(None, algorithm)
+        rc = call(C.byref(grid._g), int(sign_method), C.byref(bo), None, None, 0, None, C.byref(count), C.byref(o))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        capacity = int(count.value)
+    cell_arr, p_cells = buf(int(capacity), np.uint64, "int64")
+    dist_arr, p_dist = buf(int(capacity), np.float32, "float32")
+    bit_arr, p_bits = buf((nx, ny, (nz + 31) // 32), np.uint32, "int32") if bits else (None, None)
+    if bits and a.device and hasattr(a.torch, "uint32"):
+        bit_arr = bit_arr.view(a.torch.uint32)
+    o = a.opts(timings, algorithm, synchronous=synchronous)
+    rc = call(C.byref(grid._g), int(sign_method), C.byref(bo), p_cells, p_dist, int(capacity), p_bits, C.byref(count), C.byref(o))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    n = int(count.value)
+    return NarrowBand(cell_arr[:n], dist_arr[:n], bit_arr, n, grid)
+
+
+def narrow_band_sdf(vertices, indices: Topology, grid: "Grid", band, sign_method: SignMethod = SignMethod.Raycast, *, bits: bool = False,
+                    algorithm: int = 0, timings: M2STimings = None, capacity: Optional[int] = None) -> NarrowBand:
+    """The cells of `grid` whose generate_grid_sdf value D lies in the band -interior <= D <= exterior, and those values bit for bit
+    (include/m2s.h m2s_narrow_band_sdf): what a level-set or sparse-brick pipeline reads of a grid, at the cost of the cells near the surface
+    instead of all of them.  `band` is one width in world units or (interior, exterior); either may be inf.  `algorithm=1` runs the dense
+    call and filters it (the definition; the same bits).  Host arrays or device tensors, as the other calls take them.  Without `capacity`
+    the call runs twice (count, then fill); with one (an upper bound of the active cells) it runs once and raises when it is short."""
+    a = _Args(vertices, indices)
+    L = _lib.lib()
+    return _band_call(lambda *r: L.m2s_narrow_band_sdf(a.p_verts, a.n_verts, a.p_idx, a.n_idx, a.index_bytes, a.topology, *r), a, grid, band,
+                      sign_method, bits, algorithm, timings, capacity)
+
+
 # DeepSDF's near-surface noise (Park et al. 2019: variances 0.0025 and 0.00025 in a unit sphere), as fractions of half the bounding-box diagonal
 NEAR_SURFACE_SIGMAS = (0.05, 0.0158)
 
@@ -1280,6 +1366,13 @@ class Mesh:
         L = _lib.lib()
         return _voxel_call(lambda *r: L.m2s_mesh_voxelize(self._h, *r), self._a, grid, solid, bits, cells, timings, algorithm, synchronous,
                            occupancy, count)
+
+    def narrow_band_sdf(self, grid: Grid, band, sign_method: SignMethod = SignMethod.Raycast, *, bits: bool = False, algorithm: int = 0,
+                        timings: M2STimings = None, capacity: Optional[int] = None, synchronous: bool = True) -> NarrowBand:
+        """narrow_band_sdf on the resident mesh: the same bits as the one-shot function."""
+        L = _lib.lib()
+        return _band_call(lambda *r: L.m2s_mesh_narrow_band_sdf(self._h, *r), self._a, grid, band, sign_method, bits, algorithm, timings,
+                          capacity, synchronous)
 
     def sample_sdf_near_surface(self, n: int, sigmas=None, uniform_fraction: float = 0.05, sign: str = "winding", seed: int = 0):
         """sample_sdf_near_surface on this mesh."""

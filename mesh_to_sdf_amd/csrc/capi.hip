@@ -1324,17 +1324,13 @@ struct VoxelArgs {
   uint32_t mode;
 };
 
-int check_voxel_args(const m2s_grid* grid, const m2s_voxelize_opts* vopts, const m2s_opts* opts, VoxelArgs* o, GridParams* g, size_t* cells) {
+// What every whole-grid mask call (voxelization, narrow bands) asks of its grid and of m2s_opts: no slabs, no peers, a grid the mask layout and
+// the sign planes can address.
+int check_whole_grid_args(const char* what, const m2s_grid* grid, const m2s_opts* opts, GridParams* g, size_t* cells) {
   if (!grid) return fail(M2S_ERR_BAD_ARG, "grid is NULL");
-  if (!o->bits && !o->occ && !o->cells && !o->n_set) return fail(M2S_ERR_BAD_ARG, "bits_out, occupancy_out, cells_out and n_set_out are all NULL");
-  if (vopts) {
-    if (vopts->struct_size != sizeof(m2s_voxelize_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_voxelize_opts.struct_size is not sizeof(m2s_voxelize_opts)");
-    if (vopts->mode != M2S_VOXELIZE_SURFACE && vopts->mode != M2S_VOXELIZE_SOLID) return fail(M2S_ERR_BAD_ARG, "bad m2s_voxelize_opts.mode %u", vopts->mode);
-    o->mode = vopts->mode;
-  }
-  if (opts && (opts->x_begin != 0 || opts->x_end != 0)) return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_begin / x_end do not apply to voxelization calls");
+  if (opts && (opts->x_begin != 0 || opts->x_end != 0)) return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_begin / x_end do not apply to %s calls", what);
   if (opts && opts->struct_size >= sizeof(m2s_opts) && (opts->x_period != 0 || opts->n_peer_out != 0 || opts->peer_out != nullptr))
-    return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_period / peer_out do not apply to voxelization calls");
+    return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_period / peer_out do not apply to %s calls", what);
   if (opts && opts->mem_kind != M2S_MEM_HOST && opts->mem_kind != M2S_MEM_DEVICE) return fail(M2S_ERR_BAD_ARG, "bad mem_kind");
   if (opts && opts->algorithm != 0 && opts->algorithm != 1) return fail(M2S_ERR_BAD_ARG, "bad algorithm");
   for (int k = 0; k < 3; ++k) {
@@ -1346,6 +1342,17 @@ int check_voxel_args(const m2s_grid* grid, const m2s_voxelize_opts* vopts, const
   if (rc) return rc;
   if ((uint64_t)grid->cell_count[0] * grid->cell_count[1] * grid->cell_count[2] >= (1ull << 36)) return fail(M2S_ERR_BAD_ARG, "2^36 or more cells");
   return 0;
+}
+
+int check_voxel_args(const m2s_grid* grid, const m2s_voxelize_opts* vopts, const m2s_opts* opts, VoxelArgs* o, GridParams* g, size_t* cells) {
+  if (!grid) return fail(M2S_ERR_BAD_ARG, "grid is NULL");
+  if (!o->bits && !o->occ && !o->cells && !o->n_set) return fail(M2S_ERR_BAD_ARG, "bits_out, occupancy_out, cells_out and n_set_out are all NULL");
+  if (vopts) {
+    if (vopts->struct_size != sizeof(m2s_voxelize_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_voxelize_opts.struct_size is not sizeof(m2s_voxelize_opts)");
+    if (vopts->mode != M2S_VOXELIZE_SURFACE && vopts->mode != M2S_VOXELIZE_SOLID) return fail(M2S_ERR_BAD_ARG, "bad m2s_voxelize_opts.mode %u", vopts->mode);
+    o->mode = vopts->mode;
+  }
+  return check_whole_grid_args("voxelization", grid, opts, g, cells);
 }
 
 size_t voxel_workspace_bytes(const CallCtx& c, const GridParams& g, size_t n_tris, size_t cells, const VoxelArgs& o) {
@@ -1423,6 +1430,133 @@ int park_async_events(m2s_mesh* m, DeviceState& st, uint64_t units, uint32_t lau
   st.ev[4] = fresh[0];
   st.ev[3] = fresh[1];
   return 0;
+}
+
+
+// ---- narrow bands (m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf) -------------------------------------------------------------------------
+// ev[0] .. ev[1] the build (one-shot), ev[2] .. ev[4] the sign planes and the candidate pass (seed_ms), ev[4] .. ev[3] the query walks, filter
+// and compaction of every chunk (distance_ms).  Active cells and distances are compacted into the workspace and copied out once the count is
+// known to fit: counting first would walk every candidate twice, and writing straight into the caller's arrays would leave them half
+// filled when the capacity turns out short.
+struct BandArgs {
+  uint64_t* cells;
+  float* dist;
+  uint64_t capacity;
+  uint32_t* bits;
+  uint64_t* n_active;
+  float exterior, interior;
+  int sign_method;
+};
+
+int check_band_args(const m2s_grid* grid, const m2s_band_opts* bopts, const m2s_opts* opts, BandArgs* o, GridParams* g, size_t* cells) {
+  if (!grid) return fail(M2S_ERR_BAD_ARG, "grid is NULL");
+  if (o->sign_method != M2S_SIGN_RAYCAST && o->sign_method != M2S_SIGN_NORMAL) return fail(M2S_ERR_BAD_ARG, "bad sign_method %d", o->sign_method);
+  if (!bopts) return fail(M2S_ERR_BAD_ARG, "bopts is NULL");
+  if (bopts->struct_size != sizeof(m2s_band_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_band_opts.struct_size is not sizeof(m2s_band_opts)");
+  if (!(bopts->exterior >= 0.0f) || !(bopts->interior >= 0.0f)) return fail(M2S_ERR_BAD_ARG, "m2s_band_opts.exterior / interior must be >= 0 (+inf allowed)");
+  if (!o->cells && !o->dist && !o->bits && !o->n_active) return fail(M2S_ERR_BAD_ARG, "cells_out, distances_out, bits_out and n_active_out are all NULL");
+  o->exterior = bopts->exterior;
+  o->interior = bopts->interior;
+  return check_whole_grid_args("narrow-band", grid, opts, g, cells);
+}
+
+size_t band_stage_entries(size_t cells, const BandArgs& o) { return (o.cells || o.dist) ? (size_t)std::min<uint64_t>(o.capacity, cells) : 0; }
+size_t band_chunk_of(size_t cells) { return std::min<size_t>(tuning().band_chunk, cells); }
+
+size_t band_workspace_bytes(const CallCtx& c, const GridParams& g, size_t n_tris, size_t cells, const BandArgs& o) {
+  const size_t words = (size_t)g.n[0] * g.n[1] * g.nzw, stage = band_stage_entries(cells, o);
+  size_t b = voxel_scratch_bytes(g, n_tris) + 2 * align_up(words * 4) + align_up(stage * 8) + align_up(stage * 4) + 8192;
+  if (o.sign_method == M2S_SIGN_RAYCAST) b += sign_workspace_bytes(g, n_tris);
+  if (c.algorithm == 1) b += grid_distance_workspace_bytes(g, n_tris) + align_up(cells * 4);
+  else b += band_chunk_bytes(band_chunk_of(cells)) + query_workspace_bytes(band_chunk_of(cells));
+  return b;
+}
+
+// Everything after the tree exists.  Records ev[2], ev[4], ev[3]; *n_cand: the candidates evaluated; *short_capacity: capacity is below the
+// count (bits_out is complete, cells_out and distances_out untouched).
+int run_narrow_band(Arena& ws, const CallCtx& c, DeviceState& st, const DeviceMesh& mesh, const GridParams& g, size_t cells, const BandArgs& o,
+                    int* d_err, uint64_t* n_cand, bool* short_capacity) {
+  *short_capacity = false;
+  *n_cand = 0;
+  const size_t words = (size_t)g.n[0] * g.n[1] * g.nzw, stage = band_stage_entries(cells, o);
+  const bool host = c.mem_kind == M2S_MEM_HOST, raycast = o.sign_method == M2S_SIGN_RAYCAST;
+  VoxelScratch vs;
+  if (voxel_scratch_carve(ws, g, mesh.n_tris, &vs)) return fail(M2S_ERR_HIP, "internal: workspace");
+  uint32_t* d_bits = (!host && o.bits) ? o.bits : ws.take<uint32_t>(words);
+  uint64_t* s_cells = (o.cells && stage) ? ws.take<uint64_t>(stage) : nullptr;
+  float* s_dist = (o.dist && stage) ? ws.take<float>(stage) : nullptr;
+  uint64_t* running = ws.take<uint64_t>(4);
+  if (!d_bits || !running || (o.cells && stage && !s_cells) || (o.dist && stage && !s_dist)) return fail(M2S_ERR_HIP, "internal: workspace");
+  uint64_t* h = reinterpret_cast<uint64_t*>(st.h_err) + 1;   // 64 pinned bytes; the first word stays the call's error flags
+  int rc = 0;
+  M2S_HIP_CHECK(hipEventRecord(st.ev[2], c.stream));
+  st.planes_done = nullptr;
+  const uint32_t* plane = nullptr;
+  if (raycast && mesh.n_tris && (rc = build_grid_sign_plane(ws, c.stream, mesh, g, &plane, false))) return rc;
+  uint64_t count = 0;
+  if (c.algorithm == 1) {
+    // the definition: the dense call's walk (its default path) into the workspace, the filter over every cell, the cells from the mask
+    float* dense = ws.take<float>(cells);
+    if (!dense) return fail(M2S_ERR_HIP, "internal: workspace");
+    M2S_HIP_CHECK(hipEventRecord(st.ev[4], c.stream));
+    if ((rc = launch_grid_distance(ws, c.stream, mesh, g, raycast ? MODE_UNSIGNED : MODE_NORMAL_FOLD, plane, 0, dense, d_err, nullptr))) return rc;
+    if ((rc = launch_band_dense_mask(c.stream, g, dense, o.interior, o.exterior, d_bits))) return rc;
+    if ((rc = launch_voxel_count(c.stream, g, d_bits, vs))) return rc;
+    M2S_HIP_CHECK(hipMemcpyAsync(h, vs.hdr, 8, hipMemcpyDeviceToHost, c.stream));
+    M2S_HIP_CHECK(hipStreamSynchronize(c.stream));
+    count = *h;
+    *n_cand = cells;
+    if (stage && count <= o.capacity && count) {
+      uint64_t* cl = s_cells ? s_cells : ws.take<uint64_t>(count);
+      if (!cl) return fail(M2S_ERR_HIP, "internal: workspace");
+      if ((rc = launch_voxel_cells(c.stream, g, d_bits, vs, count, cl))) return rc;
+      if (s_dist && (rc = launch_band_gather(c.stream, dense, cl, count, s_dist))) return rc;
+    }
+  } else {
+    uint32_t* cand = ws.take<uint32_t>(words);
+    BandChunk ch;
+    const size_t chunk = band_chunk_of(cells);
+    if (!cand || band_chunk_carve(ws, chunk, &ch)) return fail(M2S_ERR_HIP, "internal: workspace");
+    if ((rc = launch_band_candidates(c.stream, mesh.tris, mesh.n_tris, g, std::max(o.exterior, o.interior), vs, cand))) return rc;
+    if ((rc = launch_voxel_count(c.stream, g, cand, vs))) return rc;
+    M2S_HIP_CHECK(hipMemsetAsync(d_bits, 0, words * 4, c.stream));
+    M2S_HIP_CHECK(hipMemsetAsync(running, 0, 32, c.stream));
+    M2S_HIP_CHECK(hipMemcpyAsync(h, vs.hdr, 8, hipMemcpyDeviceToHost, c.stream));
+    M2S_HIP_CHECK(hipEventRecord(st.ev[4], c.stream));
+    M2S_HIP_CHECK(hipStreamSynchronize(c.stream));
+    const uint64_t total = *h;
+    *n_cand = total;
+    for (uint64_t begin = 0; begin < total; begin += chunk) {
+      const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, total - begin);
+      if ((rc = launch_band_emit(c.stream, g, cand, vs, begin, begin + n, ch))) return rc;
+      Arena qw = ws;   // the query walk's scratch: the same bytes for every chunk
+      if ((rc = launch_query_distance(qw, c.stream, mesh, ch.centres, n, raycast ? MODE_UNSIGNED : MODE_NORMAL_FOLD, SIGN_NONE, 0, ch.dist, d_err))) return rc;
+      if ((rc = launch_band_filter(c.stream, g, ch, n, plane, o.interior, o.exterior, d_bits, running, stage, s_cells, s_dist))) return rc;
+    }
+    M2S_HIP_CHECK(hipMemcpyAsync(h, running, 8, hipMemcpyDeviceToHost, c.stream));
+    M2S_HIP_CHECK(hipStreamSynchronize(c.stream));
+    count = *h;
+  }
+  if (o.n_active) *o.n_active = count;
+  *short_capacity = (o.cells || o.dist) && o.capacity < count;
+  const bool copy = (o.cells || o.dist) && !*short_capacity && count;
+  if (copy && !host) {
+    if (o.cells) M2S_HIP_CHECK(hipMemcpyAsync(o.cells, s_cells, count * 8, hipMemcpyDeviceToDevice, c.stream));
+    if (o.dist) M2S_HIP_CHECK(hipMemcpyAsync(o.dist, s_dist, count * 4, hipMemcpyDeviceToDevice, c.stream));
+  }
+  M2S_HIP_CHECK(hipEventRecord(st.ev[3], c.stream));
+  if (!host) return 0;
+  if (o.bits && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.bits), reinterpret_cast<const char*>(d_bits), words * 4))) return rc;
+  if (copy && o.cells && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.cells), reinterpret_cast<const char*>(s_cells), count * 8))) return rc;
+  if (copy && o.dist && (rc = staged_d2h(st, c.stream, reinterpret_cast<char*>(o.dist), reinterpret_cast<const char*>(s_dist), count * 4))) return rc;
+  return 0;
+}
+
+int finish_narrow_band(const CallCtx& c, DeviceState& st, int* d_err, size_t n_tris, uint64_t n_cand, const BandArgs& o, bool short_capacity) {
+  const int rc = finish_call(c, st, d_err, c.timings, n_tris, n_cand, false, true);
+  if (rc) return rc;
+  if (short_capacity) return fail(M2S_ERR_BAD_ARG, "capacity %llu is below the number of active cells (*n_active_out)", (unsigned long long)o.capacity);
+  return M2S_OK;
 }
 
 }  // namespace
@@ -1856,6 +1990,7 @@ int m2s_warmup(int device, size_t workspace_bytes, size_t host_ring_bytes) {
   warm_rays(c.stream);
   warm_sample(c.stream);
   warm_voxelize(c.stream);
+  warm_band(c.stream);
   warm_sortlib(c.stream);                                        // (the rocPRIM sorts of large meshes and of the query path: units of their own,
   warm_sortlib_query(c.stream);                                  // which a grid call over a mesh of <= 229 376 triangles never loads)
   M2S_HIP_CHECK(hipGetLastError());
@@ -2724,6 +2859,83 @@ int m2s_mesh_voxelize(m2s_mesh* m, const m2s_grid* grid, const m2s_voxelize_opts
     return short_capacity ? fail(M2S_ERR_BAD_ARG, "cell_capacity %llu is below the number of set cells (*n_set_out)", (unsigned long long)cell_capacity) : M2S_OK;
   }
   return finish_voxelize(c, *st, d_err, m->n_tris, cells, o, short_capacity);
+}
+
+// Narrow bands (include/m2s.h): the one-shot call builds the whole tree, with the leaf size the query walk of a chunk asks for (algorithm 1:
+// the dense grid call's).
+int m2s_narrow_band_sdf(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology,
+                        const m2s_grid* grid, int sign_method, const m2s_band_opts* bopts, uint64_t* cells_out, float* distances_out,
+                        uint64_t capacity, uint32_t* bits_out, uint64_t* n_active_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  BandArgs o{cells_out, distances_out, capacity, bits_out, n_active_out, 0.0f, 0.0f, sign_method};
+  GridParams g;
+  size_t cells = 0;
+  int rc = check_band_args(grid, bopts, opts, &o, &g, &cells);
+  if (rc) return rc;
+  if ((rc = check_mesh_args(vertices, n_vertices, indices, n_indices, index_bytes, topology))) return rc;
+  const size_t n_tris = m2s_triangle_count(n_vertices, n_indices, indices != nullptr, topology);
+  if (n_tris > ((size_t)1 << 25)) return fail(M2S_ERR_BAD_ARG, "more than 2^25 triangles");
+  if (!opts || opts->mem_kind == M2S_MEM_HOST) {
+    if ((rc = check_host_indices(indices, n_indices, index_bytes, topology, n_vertices, n_tris))) return rc;
+  }
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(opts, &c, &st))) return rc;
+  size_t need = bvh_workspace_bytes(n_tris) + band_workspace_bytes(c, g, n_tris, cells, o) + 4096;
+  if (c.mem_kind == M2S_MEM_HOST) need += align_up(n_vertices * 12) + align_up(n_indices * (size_t)(indices ? index_bytes : 0)) + 1024;
+  if ((rc = ensure_capacity(*st, need))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  StagedMesh sm;
+  if ((rc = stage_mesh(ws, c, vertices, n_vertices, indices, n_indices, index_bytes, &sm))) return rc;
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  DeviceMesh mesh;
+  const uint32_t leaf = c.algorithm == 1 ? grid_leaf_max(g, n_tris) : query_leaf_max(band_chunk_of(cells), n_tris, SIGN_NONE);
+  if ((rc = build_device_mesh(ws, c.stream, sm.d_verts, n_vertices, sm.d_indices, n_indices, index_bytes, topology, n_tris, d_err, &mesh, nullptr, false, leaf)))
+    return rc;
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  uint64_t n_cand = 0;
+  bool short_capacity = false;
+  if ((rc = run_narrow_band(ws, c, *st, mesh, g, cells, o, d_err, &n_cand, &short_capacity))) return rc;
+  return finish_narrow_band(c, *st, d_err, n_tris, n_cand, o, short_capacity);
+}
+
+int m2s_mesh_narrow_band_sdf(m2s_mesh* m, const m2s_grid* grid, int sign_method, const m2s_band_opts* bopts, uint64_t* cells_out,
+                             float* distances_out, uint64_t capacity, uint32_t* bits_out, uint64_t* n_active_out, const m2s_opts* opts) {
+  g_err[0] = 0;
+  if (!m) return fail(M2S_ERR_BAD_ARG, "mesh is NULL");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  BandArgs o{cells_out, distances_out, capacity, bits_out, n_active_out, 0.0f, 0.0f, sign_method};
+  GridParams g;
+  size_t cells = 0;
+  int rc = check_band_args(grid, bopts, opts, &o, &g, &cells);
+  if (rc) return rc;
+  m2s_opts mo;
+  if ((rc = mesh_call_opts(m, opts, &mo))) return rc;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  if ((rc = resolve_ctx(&mo, &c, &st))) return rc;
+  if ((rc = ensure_capacity(*st, band_workspace_bytes(c, g, m->n_tris, cells, o) + 8192))) return rc;
+  Arena ws{st->base, st->cap, 0};
+  int* d_err = ws.take<int>(16);
+  if (c.sync) M2S_HIP_CHECK(hipMemsetAsync(d_err, 0, 64, c.stream));
+  else d_err = m->d_err_async;   // asynchronous calls report through the mesh (m2s_mesh_drain_timings)
+  if (!c.sync) reap_pending(m, false);
+  M2S_HIP_CHECK(hipEventRecord(st->ev[0], c.stream));
+  M2S_HIP_CHECK(hipEventRecord(st->ev[1], c.stream));
+  const size_t chunk = band_chunk_of(cells);
+  const uint32_t leaf = c.algorithm == 1 ? grid_leaf_max(g, m->n_tris)
+                        : query_is_tiny(chunk, m->n_tris, 0, SIGN_NONE) ? m->dm.leaf_max : query_leaf_max(chunk, m->n_tris, SIGN_NONE);
+  if ((rc = remark_leaves(m, c, leaf))) return rc;
+  uint64_t n_cand = 0;
+  bool short_capacity = false;
+  if ((rc = run_narrow_band(ws, c, *st, m->dm, g, cells, o, d_err, &n_cand, &short_capacity))) return rc;
+  if (!c.sync) {
+    if ((rc = park_async_events(m, *st, n_cand, 1))) return rc;
+    return short_capacity ? fail(M2S_ERR_BAD_ARG, "capacity %llu is below the number of active cells (*n_active_out)", (unsigned long long)capacity) : M2S_OK;
+  }
+  return finish_narrow_band(c, *st, d_err, m->n_tris, n_cand, o, short_capacity);
 }
 
 // Peer-write bandwidth probe (include/m2s.h): the copy kernel of M2S_PEER_PUSH, timed with HIP events on a stream of its own.

@@ -238,6 +238,7 @@ void warm_grid_query(hipStream_t st);
 void warm_rays(hipStream_t st);
 void warm_sample(hipStream_t st);
 void warm_voxelize(hipStream_t st);
+void warm_band(hipStream_t st);
 // bvh.hip: flatten topology, build triangle records + LBVH in pre-order layout.
 size_t bvh_workspace_bytes(size_t n_tris);
 // `after_setup` (optional) is called twice with the input-order centroid array and triangle records: with phase 0 once the kernels that fill
@@ -473,6 +474,7 @@ int launch_sample_surface(hipStream_t st, const SampleSrc& src, const SampleTabl
                           int algorithm, const SampleOut& out);
 
 // voxelize.hip: surface and solid occupancy of a grid, one bit per cell in the layout of the sign planes.
+constexpr int MASK_SCAN_TILE = 4096;   // mask words per tile of launch_voxel_count's offsets (voxelize.hip; band.hip reads them by the same tiles)
 struct VoxelScratch {
   uint32_t* iv;         // per triangle: the x, y and z intervals of cells that pass its box clauses (lo, hi) x 3
   uint64_t* cols;       // per triangle: candidate columns
@@ -490,6 +492,29 @@ int launch_voxel_count(hipStream_t st, const GridParams& g, const uint32_t* bits
 int launch_voxel_expand(hipStream_t st, const GridParams& g, const uint32_t* bits, uint8_t* occ);          // one byte per cell, grid order
 // after launch_voxel_count: the grid-order index of every set cell, ascending; entries from `capacity` on are dropped
 int launch_voxel_cells(hipStream_t st, const GridParams& g, const uint32_t* bits, const VoxelScratch& s, uint64_t capacity, uint64_t* cells_out);
+
+// band.hip: narrow-band grid SDFs.  The candidate mask and the active mask have the layout of the sign planes.
+struct BandChunk {      // scratch of one chunk of candidates
+  uint64_t* cells;      // their L, ascending
+  float* centres;       // 3 per candidate: the queries of launch_query_distance
+  float* dist;          // its result; signed by launch_band_filter
+  uint8_t* flags;       // 1: active
+  uint64_t* tile_sum;   // scratch of the compaction scan
+  uint64_t* hdr;        // [0]: active candidates of the chunk
+};
+size_t band_chunk_bytes(size_t chunk);
+int band_chunk_carve(Arena& ws, size_t chunk, BandChunk* c);   // -1: out of space
+// bits (cleared here) = the cells within reach of some triangle's box (band.hip.h); r = +inf: every cell.  `s`: a VoxelScratch of the grid.
+int launch_band_candidates(hipStream_t st, const TriRec* tris, uint32_t n_tris, const GridParams& g, float r, const VoxelScratch& s, uint32_t* bits);
+// after launch_voxel_count(cand): the candidates of rank [begin, end) into c.cells and c.centres
+int launch_band_emit(hipStream_t st, const GridParams& g, const uint32_t* cand, const VoxelScratch& s, uint64_t begin, uint64_t end, const BandChunk& c);
+// c.dist of n candidates signed by `plane` (nullptr: as it is), filtered, the active bits set in `bits`, and the active cells / distances (each
+// may be nullptr) appended at *running (device), which advances by their number; entries from `capacity` on are dropped
+int launch_band_filter(hipStream_t st, const GridParams& g, const BandChunk& c, uint32_t n, const uint32_t* plane, float interior, float exterior,
+                       uint32_t* bits, uint64_t* running, uint64_t capacity, uint64_t* cells_out, float* d_out);
+// algorithm 1: the active mask of a dense grid result (every word written), and d_out[n] = dense[cells[n]]
+int launch_band_dense_mask(hipStream_t st, const GridParams& g, const float* dense, float interior, float exterior, uint32_t* bits);
+int launch_band_gather(hipStream_t st, const float* dense, const uint64_t* cells, uint64_t n, float* d_out);
 
 // grid_query.hip: sampling and ray-marching a finished grid SDF (the client's draw_raymarching.wgsl).  The grid's scalars travel as a
 // kernel argument; start / end are the shader's uniforms (first_cell, Grid::get_last_cell), n[] >= 1, cs[] > 0 and finite.

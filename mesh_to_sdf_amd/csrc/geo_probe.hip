@@ -1,9 +1,10 @@
-// geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h, sample.hip.h and voxel.hip.h, for CPU unit tests only
-// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py).  Not linked into libm2s_hip.so.
+// geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h, sample.hip.h, voxel.hip.h and band.hip.h, for CPU unit tests only
+// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py, tests/test_narrow_band_cpu.py).  Not linked into libm2s_hip.so.
 #include "geo.hip.h"
 #include "ray.hip.h"
 #include "sample.hip.h"
 #include "voxel.hip.h"
+#include "band.hip.h"
 
 using namespace m2s;
 
@@ -111,5 +112,48 @@ void probe_vox_raster(const float* t, const float* first, const float* size, con
         if (!vox_cell_miss(tr, v0, v1, v2, h)) occ[((size_t)i * n[1] + j) * n[2] + k] = 1;
       }
     }
+}
+// band.hip.h
+float probe_band_reach(float r, float scale) { return band_reach(r, scale); }
+// out: lo[3], hi[3], amax; returns any
+int probe_band_box(const float* t, float* out) {
+  const BandBox bx = band_box(mk3(t[0], t[1], t[2]), mk3(t[3], t[4], t[5]), mk3(t[6], t[7], t[8]));
+  for (int m = 0; m < 3; ++m) { out[m] = bx.lo[m]; out[3 + m] = bx.hi[m]; }
+  out[6] = bx.amax;
+  return bx.any ? 1 : 0;
+}
+// out: n[3], rhs; returns use
+int probe_band_plane(const float* t, float reach, const float* first, const float* size, const uint32_t* n, float* out) {
+  const BandPlane pl = band_plane(mk3(t[0], t[1], t[2]), mk3(t[3], t[4], t[5]), mk3(t[6], t[7], t[8]), reach, {first[0], first[1], first[2]},
+                                  {size[0], size[1], size[2]}, {n[0], n[1], n[2]});
+  for (int m = 0; m < 3; ++m) out[m] = pl.n[m];
+  out[3] = pl.rhs;
+  return pl.use ? 1 : 0;
+}
+// n_tris triangles over a whole grid the way the kernels of band.hip go: the three axis intervals, the column test, the z interval tightened
+// by the x and y gaps and by the plane test.  occ: n[0] * n[1] * n[2] bytes, OR-ed into.
+void probe_band_candidates(uint64_t n_tris, const float* tris, const float* first, const float* size, const uint32_t* n, float r, float grid_scale,
+                           uint8_t* occ) {
+  for (uint64_t ti = 0; ti < n_tris; ++ti) {
+    const float* t = tris + 9 * ti;
+    const f3 a = mk3(t[0], t[1], t[2]), b = mk3(t[3], t[4], t[5]), c = mk3(t[6], t[7], t[8]);
+    const BandBox bx = band_box(a, b, c);
+    if (!bx.any) continue;
+    const float reach = band_reach(r, bx.amax > grid_scale ? bx.amax : grid_scale), reach2 = reach * reach;
+    const BandPlane pl = band_plane(a, b, c, reach, {first[0], first[1], first[2]}, {size[0], size[1], size[2]}, {n[0], n[1], n[2]});
+    uint32_t lo[3], hi[3];
+    for (int m = 0; m < 3; ++m) band_interval(bx.lo[m], bx.hi[m], first[m], size[m], 0u, n[m], 0.0f, 0.0f, reach2, &lo[m], &hi[m]);
+    if (lo[2] >= hi[2]) continue;
+    for (uint32_t i = lo[0]; i < hi[0]; ++i)
+      for (uint32_t j = lo[1]; j < hi[1]; ++j) {
+        const float qx = cell_center(first[0], size[0], i), qy = cell_center(first[1], size[1], j);
+        const float gx = band_gap(bx.lo[0], bx.hi[0], qx), gy = band_gap(bx.lo[1], bx.hi[1], qy);
+        if (!band_near(gx, gy, 0.0f, reach2)) continue;
+        uint32_t klo, khi;
+        band_interval(bx.lo[2], bx.hi[2], first[2], size[2], lo[2], hi[2], gx, gy, reach2, &klo, &khi);
+        band_plane_interval(pl, band_plane_xy(pl, qx, qy), first[2], size[2], klo, khi, &klo, &khi);
+        for (uint32_t k = klo; k < khi; ++k) occ[((size_t)i * n[1] + j) * n[2] + k] = 1;
+      }
+  }
 }
 }

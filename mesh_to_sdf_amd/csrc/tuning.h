@@ -45,6 +45,8 @@ struct Tuning {
   uint32_t split_rounds = 2;        // M2S_SPLIT_ROUNDS follow-up launches: the continuations of the suspended packets, then their subtrees (with more rounds, subtrees may be suspended in their turn; the last round walks to the end)
   int split_report = 0;             // M2S_SPLIT_REPORT 1: suspended packets and items per round of every grid walk, on stderr (synchronises)
   int defer = -1;                   // M2S_DEFER        the packet walk's leaf work: -1 automatic (by triangles per brick: 2 / 1 / 3), 0 wave-wide at once, 1 exact evaluations queued as (voxel, triangle) pairs and run 64 at a time, 2 + wave-wide where >= 48 lanes are reached, 3 the pre-tests queued too
+  // ---- narrow bands (band.hip)
+  uint32_t band_chunk = 1u << 24;   // M2S_BAND_CHUNK      candidates per pass of the query walk in a narrow-band call (1 .. 2^30); every chunk pays the query path's sort and seed passes again (DESIGN.md section 4.13 has the sweep), and the workspace grows by about 100 bytes per candidate of a chunk
   // ---- host-pointer calls and peer delivery (capi.hip, multi.hip, peer_push.hip)
   uint32_t host_piece_mb = 32;      // M2S_HOST_PIECE_MB   x-pieces of the result streamed to the host while the next is walked
   uint32_t push_pieces = 4;         // M2S_PUSH_PIECES     x-pieces of a slab pushed to the peers while the next is walked

@@ -33,6 +33,7 @@ __global__ void k_warm_voxelize() {}
 constexpr int kThreads = 256;
 constexpr int kScanItems = 16;
 constexpr int kScanTile = kThreads * kScanItems;
+static_assert(kScanTile == MASK_SCAN_TILE, "common.h names the tile of launch_voxel_count's offsets");
 constexpr unsigned kRasterBlocks = 4096;   // 16 workgroups per CU's worth of grid-stride lanes
 
 // Exclusive scan over a workgroup of NT threads (64-wide waves); *total = the sum of all.  (sample.hip and isosurface.hip have the same.)
