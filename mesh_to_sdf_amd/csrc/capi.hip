@@ -3083,6 +3083,9 @@ int m2s_debug_grid_walk_choice_slab(const m2s_grid* grid, const m2s_opts* opts, 
   out[7] = choose_grid_walk_for_sizing(g, n_tris).split ? 1u : 0u;
   return M2S_OK;
 }
+// Test hook: launches of the packet walk's gather-ahead form (k_packet's GA variants) by this process so far — tests/test_gpu_gather_ahead.py checks
+// that M2S_GATHER_AHEAD really selects the kernel it names.
+uint64_t m2s_debug_gather_ahead_launches(void) { return gather_ahead_launches(); }
 int m2s_debug_grid_walk_choice(const m2s_grid* grid, size_t n_tris, size_t n_nodes, uint32_t leaf_max, int algorithm, uint32_t out[8]) {
   return m2s_debug_grid_walk_choice_slab(grid, nullptr, n_tris, n_nodes, leaf_max, algorithm, out);
 }

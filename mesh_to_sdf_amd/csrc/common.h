@@ -225,6 +225,7 @@ hipError_t select_flagged_indices(void* tmp, size_t& bytes, const uint8_t* flags
 void warm_bvh(hipStream_t st);
 void warm_sign(hipStream_t st);
 void warm_distance(hipStream_t st);
+uint64_t gather_ahead_launches();   // test hook: launches of k_packet's gather-ahead form so far (distance.hip)
 void warm_seeds(hipStream_t st);
 void warm_cut(hipStream_t st);
 void warm_brute(hipStream_t st);
@@ -291,6 +292,7 @@ struct GridWalkChoice {
   uint32_t group_waves = 0;        // GROUP: waves per packet (2 or 4)
   bool split = false;              // PACKET: split walk ...
   bool split_forced = false;       // ... M2S_SPLIT=2: the flags start raised (tests)
+  int gather_ahead = -1;           // PACKET, defer 3, no split: M2S_GATHER_AHEAD as it stands — 1 / 0 the queued pre-tests' gathers issued ahead of their use or not, -1 where that form is measured to win (distance.hip launch_packet)
   int defer = 0;                   // PACKET: 1 exact evaluations queued and run densely, 2 + direct where most lanes are reached, 3 the pre-tests queued too (distance.hip DeferQueue)
 };
 GridWalkChoice choose_grid_walk(const GridParams& g, size_t n_tris, size_t n_nodes, uint32_t leaf_max, bool counting, int algorithm, const Tuning& tn);

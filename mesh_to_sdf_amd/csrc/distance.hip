@@ -18,6 +18,7 @@
 // launch_grid_walk, launch_query_walk).  The other stages are units of their own: seeds.hip (seed lattices), cut.hip (k_cut),
 // brute.hip (all pairs, same arithmetic: k_brute and the tiny paths), query_order.hip (Morton order and packets of generic
 // queries), peer_push.hip (copies to peer devices); dist.hip.h holds what they share.
+#include <atomic>
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -359,6 +360,19 @@ __device__ __forceinline__ void defer_flush(const DeviceMesh& mesh, f3 p, DeferQ
     if (MODE == MODE_NORMAL_FOLD) { best.d2pos = fminf(best.d2pos, __uint_as_float(dq.slot[64u + lane])); best.nan |= dq.slot[128u + lane] != 0u; }
   }
 }
+// The second half of a pre-test batch (defer_pretest, and pretest_consume of the gather-ahead form): the pairs that passed move on to the second
+// ring, the exact evaluations'; a full ring is flushed.  Returns true if it was (the lanes' bounds have moved).
+template <int MODE>
+__device__ __forceinline__ bool pretest_pass_on(const DeviceMesh& mesh, f3 p, DeferQueue& dq, Best<MODE>& best, uint32_t e, bool pass) {
+  const unsigned long long rb = __ballot(pass);
+  if (rb == 0ull) return false;
+  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(rb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rb, 0u));
+  if (pass) dq.q[(dq.head + dq.n + rank) & 127u] = e;
+  dq.n += (uint32_t)__popcll(rb);
+  if (dq.n < 64u) return false;
+  defer_flush<MODE>(mesh, p, dq, best);
+  return true;
+}
 // DEFER = 3: the leaf pre-test run densely too.  It costs the wave its 20 instructions (and a 64-byte scalar load) per leaf triangle
 // for the 11 (128^3 x blob-100k) ... 30 (headline) of 64 lanes whose bound reaches the leaf at all — the node test has just said
 // which.  Those lanes are queued per leaf triangle (first ring), 64 such pairs are pre-tested at a time — the owner's point and bound
@@ -377,19 +391,55 @@ __device__ __forceinline__ bool defer_pretest(const DeviceMesh& mesh, f3 p, floa
   const bool pass = valid & !(planes_dist2(pv, mesh.planes[t]) > tv);
   dq.head1 = (dq.head1 + take) & 127u;
   dq.n1 -= take;
-  const unsigned long long rb = __ballot(pass);
-  if (rb == 0ull) return false;
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(rb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rb, 0u));
-  if (pass) dq.q[(dq.head + dq.n + rank) & 127u] = e;
-  dq.n += (uint32_t)__popcll(rb);
-  if (dq.n < 64u) return false;
-  defer_flush<MODE>(mesh, p, dq, best);
-  return true;
+  return pretest_pass_on<MODE>(mesh, p, dq, best, e, pass);
 }
 template <int MODE>
 __device__ __forceinline__ void defer_drain(const DeviceMesh& mesh, f3 p, float slack, DeferQueue& dq, Best<MODE>& best) {
   while (dq.n1 != 0u) defer_pretest<MODE>(mesh, p, prune_bound(best.d2, slack), dq, best);
   while (dq.n != 0u) defer_flush<MODE>(mesh, p, dq, best);
+}
+
+// GATHER-AHEAD (k_packet's GA form; M2S_GATHER_AHEAD): defer_pretest in two halves, so that the planes' gather — an L2 round trip whose
+// addresses are known as soon as the first ring holds 64 pairs — passes under the node tests that follow instead of in front of the plane test.
+// pretest_issue reads the 64 ring words (the ring's slots are free again from then on: a pending batch cannot be overrun, whatever the rings'
+// size) and requests the four 16-byte pieces of each lane's TriPlanes; pretest_consume, at the next leaf the walk reaches (or when the ring
+// fills again inside a long leaf, at the end of the packet's ranges at the latest), takes the owner's point and its bound AS IT IS THEN by lane
+// permutes and goes on as defer_pretest does.  The bound a pair is tested against is never older than defer_pretest's, and a batch that waits only
+// delays what its evaluations would have told the lanes: pairs, never a result (the argument above DeferLayout).  What is pending lives in 17
+// VGPRs that the node loop has to spare and the evaluation body has not: the batch is consumed — its registers dead — before defer_flush runs.
+struct PretestAhead {
+  TriPlanes tp;      // the lanes' planes, on their way from the issue on
+  uint32_t e;        // the lanes' pair words
+  bool pending;      // wave-uniform
+};
+__device__ __forceinline__ void pretest_issue(const DeviceMesh& mesh, DeferQueue& dq, PretestAhead& ga) {   // dq.n1 >= 64
+  wave_lds_sync();
+  ga.e = dq.q1[(dq.head1 + (threadIdx.x & 63u)) & 127u];
+  ga.tp = mesh.planes[ga.e >> 6];
+  ga.pending = true;
+  dq.head1 = (dq.head1 + 64u) & 127u;
+  dq.n1 -= 64u;
+}
+// After a consume: the 17 registers hold nothing any more, and the compiler is told so (no instruction: an empty definition) — it cannot see that
+// `pending` guards them and would otherwise carry them through the evaluation body to the next iteration, which has no room for them.
+// This steers the register allocator and nothing checks it but the resource table: after a compiler upgrade, or a change to the walk,
+// run tools/kernel_resources.py on this file again — every GA form must show 0 bytes of scratch (without these lines: 52).
+__device__ __forceinline__ void pretest_forget(PretestAhead& ga) {
+  float* f = reinterpret_cast<float*>(&ga.tp);
+  static_assert(sizeof(TriPlanes) == 64, "sixteen words");
+#pragma unroll
+  for (int i = 0; i < 16; ++i) asm volatile("" : "=v"(f[i]));
+  asm volatile("" : "=v"(ga.e));
+}
+// Returns true if the second ring was flushed (the lanes' bounds have moved).
+template <int MODE>
+__device__ __forceinline__ bool pretest_consume(const DeviceMesh& mesh, f3 p, float thr, DeferQueue& dq, Best<MODE>& best, PretestAhead& ga) {
+  const uint32_t e = ga.e, v = e & 63u;
+  const f3 pv = mk3(__shfl(p.x, (int)v), __shfl(p.y, (int)v), __shfl(p.z, (int)v));
+  const float tv = __shfl(thr, (int)v);
+  const bool pass = !(planes_dist2(pv, ga.tp) > tv);
+  ga.pending = false;
+  return pretest_pass_on<MODE>(mesh, p, dq, best, e, pass);
 }
 
 // (Round 6, measured and not kept — two cursors per wave, so that two record loads are in flight and two node tests issue back to back.  First
@@ -401,9 +451,10 @@ __device__ __forceinline__ void defer_drain(const DeviceMesh& mesh, f3 p, float 
 // records and pre-test planes through scalar loads, a subtree left when no lane's bound reaches it.  BUDGET: the walk may stop
 // early (sp.suspended, off = the first record not yet looked at).  EMIT: a suspended walk — surviving subtrees of em.min_bytes ..
 // em.max_bytes are written to the next round's list instead of being entered.
-template <int MODE, bool STATS, bool BUDGET, bool EMIT = false, bool HANDOVER = false, int DEFER = 0>
+template <int MODE, bool STATS, bool BUDGET, bool EMIT = false, bool HANDOVER = false, int DEFER = 0, bool GA = false>
 __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float slack, Best<MODE>& best, float& thr, uint32_t& off,
-                                          uint32_t end, WalkStats& st, SplitState& sp, EmitState* emp = nullptr, DeferQueue* dqp = nullptr) {
+                                          uint32_t end, WalkStats& st, SplitState& sp, EmitState* emp = nullptr, DeferQueue* dqp = nullptr,
+                                          PretestAhead* gap = nullptr) {
   // The walk addresses NodeExt by BYTE offset (its skip links are stored that way): the scalar loads then take
   // the offset operand directly and the loop carries no address arithmetic.
   constexpr uint32_t NB = (uint32_t)sizeof(NodeExt);
@@ -426,7 +477,14 @@ __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float sl
     if (nr.tri >= 0) {
       const uint32_t cnt = (nr.skip - off + NB) / (2u * NB);    // triangles of this (possibly collapsed) leaf
       if (DEFER == 3) {
+        // GA: the batch pending from an earlier leaf is taken first — one scalar branch per leaf is all the node loop pays —, one issued by
+        // this leaf when the ring fills again inside it (long leaves; rare); the ring never holds 128 pairs.
+        static_assert(!(GA && (BUDGET || DEFER != 3)), "the gather-ahead form exists for the plain DEFER 3 walk only");
         DeferQueue& dq = *dqp;
+        if (GA && gap->pending) {
+          if (pretest_consume<MODE>(mesh, p, thr, dq, best, *gap)) thr = prune_bound(best.d2, slack);
+          pretest_forget(*gap);
+        }
         const bool want = !(ed2 > thr);
         const unsigned long long wb = __ballot(want);
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(wb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wb, 0u));
@@ -436,7 +494,13 @@ __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float sl
           dq.n1 += wn;
           if (dq.n1 >= 64u) {
             if (BUDGET) sp.units += 4u;
-            if (defer_pretest<MODE>(mesh, p, thr, dq, best)) thr = prune_bound(best.d2, slack);
+            if (GA) {
+              if (gap->pending) {
+                if (pretest_consume<MODE>(mesh, p, thr, dq, best, *gap)) thr = prune_bound(best.d2, slack);
+                pretest_forget(*gap);
+              }
+              pretest_issue(mesh, dq, *gap);
+            } else if (defer_pretest<MODE>(mesh, p, thr, dq, best)) thr = prune_bound(best.d2, slack);
           }
         }
       } else
@@ -541,7 +605,8 @@ __device__ __forceinline__ void store_grid_result(float* __restrict__ out, size_
 // the packet starts from a triangle near its own centre (jump-flooding seed pass, seeds.hip).
 // (eight waves per SIMD: the split variant's bookkeeping would otherwise take the kernel to 106 SGPRs — seven waves, - 12 %; the
 // compiler parks what does not fit in spare VGPR lanes)
-template <bool GRID, int MODE, int SIGN, bool STATS, bool SPLIT, int DEFER = 0>
+// GA (DEFER 3 only): the queued pre-tests' gathers issued ahead of their use (PretestAhead).
+template <bool GRID, int MODE, int SIGN, bool STATS, bool SPLIT, int DEFER = 0, bool GA = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_packet(DeviceMesh mesh, GridParams g, const float4* __restrict__ qsorted,
                                                const uint32_t* __restrict__ perm, uint32_t n_q,
                                                const uint32_t* __restrict__ plane, float* __restrict__ out,
@@ -594,6 +659,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     __shared__ unsigned long long defer_lds[DEFER ? DeferLayout<MODE>::DWORDS : 1];
     DeferQueue dq = {nullptr, nullptr, 0u, 0u};
     if (DEFER) dq = defer_begin<MODE>(defer_lds);
+    PretestAhead ga;
+    ga.pending = false;
 
     // pre-order ranges to walk: the brick's cut list (grid path), or the whole tree.  The list is 64 bytes that nobody has
     // touched before (written by k_cut, read once): it is requested here, in front of the seed evaluation, so that the ~1 us of
@@ -672,8 +739,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         off = (uint32_t)__builtin_amdgcn_readlane((int)cut_off_v, (int)(1u + range));
         const uint32_t end = (uint32_t)__builtin_amdgcn_readlane((int)cut_end_v, (int)(1u + range));
         if (STATS) st_rbytes += end - off;
-        walk_span<MODE, STATS, SPLIT, false, SPLIT, DEFER>(mesh, p, slack, best, thr, off, end, st, sp, nullptr, &dq);
+        walk_span<MODE, STATS, SPLIT, false, SPLIT, DEFER, GA>(mesh, p, slack, best, thr, off, end, st, sp, nullptr, &dq, &ga);
       }
+      // (a batch still pending: with the bound the walk ended on, as defer_drain's own)
+      if (GA && ga.pending) pretest_consume<MODE>(mesh, p, prune_bound(best.d2, slack), dq, best, ga);
       if (DEFER) defer_drain<MODE>(mesh, p, slack, dq, best);   // what is still queued (a suspended packet hands over complete minima)
       if (SPLIT && sp.suspended) {
         // (range has been stepped once more by the loop's increment)
@@ -1225,13 +1294,20 @@ struct PacketArgs {
   SplitCtl split{};
 };
 // `defer`: the leaf-work form asked for (GridWalkChoice::defer, M2S_DEFER).  Form 2 exists for grids only, and a split walk (grids; a.split.cnt
-// set) always queues its evaluations — the follow-up rounds do —: DEFER 3 if asked for, else 1.
+// set) always queues its evaluations — the follow-up rounds do —: DEFER 3 if asked for, else 1.  `gather_ahead` (M2S_GATHER_AHEAD): the plain
+// DEFER 3 walk with its pre-test gathers issued ahead (k_packet's GA form); the split walk and the other forms have no such variant.
+// It is taken where it is asked for (1) and, left to the automatic setting (-1), by the forms it was measured to win on: the grid walk of the
+// unsigned distance (the headline, configs 2 and 4) and the queries' walk with the three-ray sign (config 3; Bvh(Raycast) and RtreeBvh both run
+// it).  The Normal fold and the nearest-with-normal walk keep the plain form until they are measured (profiles/gather_ahead_ab.txt).
+std::atomic<uint64_t> g_gather_ahead_launches{0};   // test hook (m2s_debug_gather_ahead_launches): launches of a GA form so far
 template <bool GRID, int MODE, int SIGN>
-void launch_packet(hipStream_t st, const PacketArgs& a, int defer) {
+void launch_packet(hipStream_t st, const PacketArgs& a, int defer, int gather_ahead_knob) {
+  constexpr bool measured = MODE == MODE_UNSIGNED && (GRID || SIGN == SIGN_RAYS3);
+  const bool gather_ahead = gather_ahead_knob > 0 || (gather_ahead_knob < 0 && measured);
   const uint32_t per = 8u << XCD_RUN_LOG;                              // one run on each of the eight XCDs
   const uint32_t grid_blocks = ((a.n_packets + per - 1) / per) * per;  // a whole number of runs per XCD (xcd_remap)
-  const auto launch = [&](auto stats, auto split, auto form) {
-    hipLaunchKernelGGL((k_packet<GRID, MODE, SIGN, decltype(stats)::value, decltype(split)::value, decltype(form)::value>), dim3(grid_blocks), dim3(64), 0, st,
+  const auto launch = [&](auto stats, auto split, auto form, auto ahead) {
+    hipLaunchKernelGGL((k_packet<GRID, MODE, SIGN, decltype(stats)::value, decltype(split)::value, decltype(form)::value, decltype(ahead)::value>), dim3(grid_blocks), dim3(64), 0, st,
                        a.mesh, a.g, a.qsorted, a.perm, a.n_q, a.plane, a.out, a.err, a.n_packets, a.seed_in, a.seed_shift, a.seed_ny, a.seed_nz, a.seed_lattice,
                        a.cut, a.peers, a.split);
   };
@@ -1245,13 +1321,17 @@ void launch_packet(hipStream_t st, const PacketArgs& a, int defer) {
   // M2S_STATS: the counting variant (a few SALU ops more per node); never suspended, so that a packet's counters are whole.  Only the
   // side library libm2s_stats.so (make stats; tools/exp_stats.py loads it through M2S_LIB) carries these instantiations: the product
   // library's code object is seven k_packet variants smaller.
-  if (a.mesh.stats != nullptr) return launch(yes, no, f0);
+  if (a.mesh.stats != nullptr) return launch(yes, no, f0, no);
 #endif
   if constexpr (GRID && MODE != MODE_NEAREST_NORMAL)
-    if (a.split.cnt != nullptr) return defer == 3 ? launch(no, yes, f3) : launch(no, yes, f1);
+    if (a.split.cnt != nullptr) return defer == 3 ? launch(no, yes, f3, no) : launch(no, yes, f1, no);
   if constexpr (GRID)
-    if (defer == 2) return launch(no, no, f2);
-  return defer == 3 ? launch(no, no, f3) : defer ? launch(no, no, f1) : launch(no, no, f0);
+    if (defer == 2) return launch(no, no, f2, no);
+  if (defer == 3 && gather_ahead) {
+    g_gather_ahead_launches.fetch_add(1, std::memory_order_relaxed);
+    return launch(no, no, f3, yes);
+  }
+  return defer == 3 ? launch(no, no, f3, no) : defer ? launch(no, no, f1, no) : launch(no, no, f0, no);
 }
 // The follow-up rounds and the finish of a split grid walk (after launch_packet on the same stream).
 template <int MODE, int SIGN>
@@ -1270,6 +1350,9 @@ void launch_split_rounds(hipStream_t st, const DeviceMesh& mesh, const GridParam
   if (trace) { const hipError_t e = hipStreamSynchronize(st); fprintf(stderr, "[m2s split] finish: %s\n", hipGetErrorString(e)); }
 }
 
+}  // namespace
+uint64_t gather_ahead_launches() { return g_gather_ahead_launches.load(std::memory_order_relaxed); }
+namespace {
 uint32_t host_brick_count(const GridParams& g) { return brick_counts(g).padded; }
 
 }  // namespace
@@ -1379,6 +1462,7 @@ GridWalkChoice choose_grid_walk(const GridParams& g, size_t n_tris, size_t n_nod
   // 256^3 (0.04) 0.60 / 0.63; sheet-100k 512^3 (0.05) 13.2 / 12.0.  (Both forms of pre-test in one kernel, chosen per leaf by the number of lanes that
   // want it, cost the dense regime what they gained the sparse one: 128^3 0.83 -> 0.92, 768^3 17.7 -> 16.9.)
   ch.defer = tn.defer == 0 ? 0 : tn.defer > 0 ? tn.defer : ((double)n_tris < 0.02 * grid_bricks ? 2 : (double)n_tris < 0.045 * grid_bricks ? 1 : 3);
+  ch.gather_ahead = tn.gather_ahead;   // (which forms the automatic setting takes: launch_packet)
   ch.path = lane_walk ? GridWalkChoice::LANE : ch.group_waves ? GridWalkChoice::GROUP : brute ? GridWalkChoice::ALL_PAIRS : GridWalkChoice::PACKET;
   return ch;
 }
@@ -1515,7 +1599,7 @@ int launch_grid_walk(hipStream_t st, const DeviceMesh& mesh, const GridParams& g
         break;
       }
       case GridWalkChoice::PACKET:
-        launch_packet<true, MODE, SIGN>(st, a, ch.defer);
+        launch_packet<true, MODE, SIGN>(st, a, ch.defer, ch.gather_ahead);
         if (split) launch_split_rounds<MODE, SIGN>(st, mesh, g, plane, d_out, d_err, a.split, cut, pz);
         break;
     }
@@ -1616,7 +1700,7 @@ int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const f
   for_query_form(mode, sign_src, [&](auto form) {
     constexpr int MODE = decltype(form)::MODE, SIGN = decltype(form)::SIGN;
     if (plan.lane_walk) hipLaunchKernelGGL((k_lane_q<MODE, SIGN>), dim3((nq + 255u) / 256u), dim3(256), 0, st, mesh, a.qsorted, a.perm, nq, d_out, d_err, seeds, d_lat);
-    else launch_packet<false, MODE, SIGN>(st, a, defer);
+    else launch_packet<false, MODE, SIGN>(st, a, defer, tuning().gather_ahead);
   });
   M2S_HIP_CHECK(hipGetLastError());
   return 0;
@@ -1638,11 +1722,11 @@ void warm_distance(hipStream_t st) {
   hipLaunchKernelGGL(k_warm_distance, dim3(1), dim3(64), 0, st);
   // ... and resolves a kernel FUNCTION at its own first launch (~0.3 ms each): ask for the attributes of the ones a first call uses
   const void* fns[] = {
-      (const void*)k_packet<true, MODE_UNSIGNED, SIGN_GRID_PLANE, false, false, 3>,
+      (const void*)k_packet<true, MODE_UNSIGNED, SIGN_GRID_PLANE, false, false, 3, true>,   // (the GA forms: what launch_packet takes automatically)
       (const void*)k_packet<true, MODE_UNSIGNED, SIGN_GRID_PLANE, false, false, 2>,
       (const void*)k_packet<true, MODE_NORMAL_FOLD, SIGN_NONE, false, false, 3>,
       (const void*)k_packet<true, MODE_NORMAL_FOLD, SIGN_NONE, false, false, 2>,
-      (const void*)k_packet<false, MODE_UNSIGNED, SIGN_RAYS3, false, false, 3>,
+      (const void*)k_packet<false, MODE_UNSIGNED, SIGN_RAYS3, false, false, 3, true>,
       (const void*)k_packet<false, MODE_NEAREST_NORMAL, SIGN_NONE, false, false, 3>,
       (const void*)k_split_init,
       (const void*)k_split_round<MODE_UNSIGNED>,

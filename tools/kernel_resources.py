@@ -17,4 +17,4 @@ for line in out.splitlines():
 for name, r in rows.items():
     if flt in name and "m2s" in name:
         short = name.replace("m2s::(anonymous namespace)::", "").split("(")[0]
-        print(f"{short[:70]:70s} VGPR {r.get('VGPRs', -1):3d} AGPR {r.get('AGPRs', 0):3d} SGPR {r.get('SGPRs', -1):3d} scratch {r.get('ScratchSize', 0):4d} occ {r.get('Occupancy', -1)} LDS {r.get('LDS Size', -1)}")
+        print(f"{short[:70]:70s} VGPR {r.get('VGPRs', -1):3d} AGPR {r.get('AGPRs', 0):3d} SGPR {r.get('SGPRs', r.get('TotalSGPRs', -1)):3d} spilled S {r.get('SGPRs Spill', 0)} V {r.get('VGPRs Spill', 0)} scratch {r.get('ScratchSize', 0):4d} occ {r.get('Occupancy', -1)} LDS {r.get('LDS Size', -1)}")
