@@ -371,3 +371,39 @@ def describe_knobs():
 
 def last_error():
     return lib().m2s_last_error().decode("utf-8", "replace")
+
+
+# m2s_debug_eval (test hook, csrc/bounds_probe.hip): what it evaluates per element, and the bytes of the record each kind reads
+EVAL_EXT, EVAL_PLANES, EVAL_DIST2, EVAL_SLACK, EVAL_PRUNE = range(5)
+EVAL_RECORD_BYTES = {EVAL_EXT: 48, EVAL_PLANES: 64, EVAL_DIST2: 96}
+
+
+def debug_eval(kind, points, records, aux=None):
+    """The device's own value of one of the walks' inline functions for every element (test hook `m2s_debug_eval`): EVAL_EXT / EVAL_PLANES /
+    EVAL_DIST2 take n points and n records (any array of n x 48 / 64 / 96 bytes: a numpy structured array as Mesh.debug_arrays returns them,
+    fancy-indexed), EVAL_SLACK n points and aux = n x (mesh scale, 0 or 1), EVAL_PRUNE aux = n x (best d2, slack).  Returns n f32 values."""
+    import numpy as np
+
+    L = lib()
+    L.m2s_debug_eval.restype = C.c_int
+    L.m2s_debug_eval.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    pts = None if points is None else np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    ax = None if aux is None else np.ascontiguousarray(aux, np.float32).reshape(-1, 2)
+    rec = None if records is None else np.ascontiguousarray(records)
+    counts = set()
+    if pts is not None:
+        counts.add(pts.shape[0])
+    if ax is not None:
+        counts.add(ax.shape[0])
+    if rec is not None:
+        if kind not in EVAL_RECORD_BYTES or rec.nbytes % EVAL_RECORD_BYTES[kind]:
+            raise ValueError("debug_eval: records are not whole records of this kind")
+        counts.add(rec.nbytes // EVAL_RECORD_BYTES[kind])
+    if len(counts) != 1:
+        raise ValueError("debug_eval: points, records and aux must have one common length")
+    n = counts.pop()
+    out = np.empty(n, np.float32)
+    rc = L.m2s_debug_eval(int(kind), n, *(None if a is None or a.size == 0 else a.ctypes.data for a in (pts, rec, ax)), out.ctypes.data if n else None)
+    if rc != M2S_OK:
+        raise RuntimeError(f"m2s_debug_eval failed ({rc}): {last_error()}")
+    return out

@@ -1390,6 +1390,35 @@ class Mesh:
             _raise(rc)
         return [int(x) for x in out]
 
+    DEBUG_ARRAYS = ("tris", "planes", "nodes", "ext", "slot_of", "slot_first", "scene")   # `which` of m2s_debug_mesh_arrays, in order
+
+    def debug_arrays(self, dtypes=None):
+        """The resident arrays as they stand on the device (test hook `m2s_debug_mesh_arrays`): a dict with the triangle records, the
+        pre-test planes, the box nodes, the oriented bounds, the slot table, slot_first, the scene words and `leaf_max`, the leaf size the
+        tree is marked with now.  `dtypes` maps a name to the numpy (structured) dtype its array is viewed through; a name it lacks
+        comes back as uint32 words.  The record layouts are csrc/common.h; tests/bounds_model.py keeps the one Python copy of them."""
+        L = _lib.lib()
+        L.m2s_debug_mesh_arrays.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.m2s_debug_mesh_arrays.restype = C.c_int
+
+        def fetch(which):
+            nbytes = C.c_size_t(0)
+            rc = L.m2s_debug_mesh_arrays(self._h, which, None, 0, C.byref(nbytes))
+            if rc != _lib.M2S_OK:
+                _raise(rc)
+            raw = np.zeros(nbytes.value // 4, np.uint32)
+            rc = L.m2s_debug_mesh_arrays(self._h, which, raw.ctypes.data if raw.size else None, raw.nbytes, C.byref(nbytes))
+            if rc != _lib.M2S_OK:
+                _raise(rc)
+            return raw
+
+        out = {}
+        for which, name in enumerate(self.DEBUG_ARRAYS):
+            raw = fetch(which)
+            out[name] = raw.view(np.dtype(dtypes[name])) if dtypes and name in dtypes else raw
+        out["leaf_max"] = int(fetch(len(self.DEBUG_ARRAYS))[0])
+        return out
+
     def drain_timings(self) -> M2STimings:
         t = M2STimings()
         rc = _lib.lib().m2s_mesh_drain_timings(self._h, C.byref(t))

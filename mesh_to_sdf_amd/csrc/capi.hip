@@ -3035,6 +3035,35 @@ int m2s_debug_mesh_digest(m2s_mesh* m, uint64_t out[8]) {
   return M2S_OK;
 }
 
+// Test hook (not part of include/m2s.h): one resident array of a mesh copied to host memory as it stands — `which` 0 triangle records,
+// 1 pre-test planes, 2 box nodes, 3 oriented bounds, 4 slot table (input triangle -> slot), 5 slot_first (pre-order slot -> first
+// triangle), 6 scene words, 7 the tree's current leaf_max (one uint32, host state).  *bytes (optional unless dst is NULL) receives the
+// array's size; dst == NULL asks for the size alone.  tests/test_gpu_bounds.py checks the tree and its bounds against an f64 model with it.
+int m2s_debug_mesh_arrays(m2s_mesh* m, int which, void* dst, size_t capacity, size_t* bytes) {
+  g_err[0] = 0;
+  if (!m) return fail(M2S_ERR_BAD_ARG, "m2s_debug_mesh_arrays: NULL mesh");
+  if (which < 0 || which > 7) return fail(M2S_ERR_BAD_ARG, "m2s_debug_mesh_arrays: which = %d (0 .. 7)", which);
+  if (!dst && !bytes) return fail(M2S_ERR_BAD_ARG, "m2s_debug_mesh_arrays: NULL dst and NULL bytes");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  const size_t n = m->n_tris, nn = n ? 2 * n - 1 : 0;
+  const void* ptr[8] = {m->dm.tris, m->dm.planes, m->dm.nodes, m->dm.ext, m->dm.slot_of, m->dm.slot_first, m->dm.scene, nullptr};
+  const size_t size[8] = {n * sizeof(TriRec), n * sizeof(TriPlanes), nn * sizeof(NodeRec), nn * sizeof(NodeExt), n * 4, nn * 4, n ? 32u : 0u, 4u};
+  const size_t need = (which == 7 || ptr[which]) ? size[which] : 0;   // an array the mesh does not hold is empty
+  if (bytes) *bytes = need;
+  if (!dst) return M2S_OK;
+  if (capacity < need) return fail(M2S_ERR_BAD_ARG, "m2s_debug_mesh_arrays: capacity %zu < %zu bytes", capacity, need);
+  if (which == 7) {
+    const uint32_t leaf_max = m->dm.leaf_max;
+    memcpy(dst, &leaf_max, 4);
+    return M2S_OK;
+  }
+  if (!need) return M2S_OK;
+  M2S_HIP_CHECK(hipSetDevice(m->device));
+  M2S_HIP_CHECK(hipDeviceSynchronize());
+  M2S_HIP_CHECK(hipMemcpy(dst, ptr[which], need, hipMemcpyDeviceToHost));
+  return M2S_OK;
+}
+
 // Test hook (not part of include/m2s.h): the cut-list word of one range and what the walk decodes from it (dist.hip.h CutList) —
 // host arithmetic only, no device needed.  tests/test_capi_cpu.py checks the superset property for every tree size.
 int m2s_debug_cut_code(uint32_t n_nodes, uint32_t start, uint32_t len, uint32_t out[3]) {
