@@ -49,7 +49,7 @@ extern "C" {
 #endif
 
 #define M2S_VERSION_MAJOR 0
-#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
+#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
 
 /* Return codes.  The reference panics where this ABI returns a negative code; the Rust shim
  * turns a negative code back into panic!(m2s_last_error()). */
@@ -750,6 +750,45 @@ int m2s_raymarch_grid(const m2s_grid* grid, const float* distances, const float*
  *   every call).  timings: distance_ms = the call's kernels, n_units = grid points. */
 int m2s_grid_isosurface(const m2s_grid* grid, const float* distances, float iso, float* vertices_out, uint64_t vertex_capacity,
                         uint32_t* indices_out, uint64_t triangle_capacity, uint64_t* counts, const m2s_opts* opts);
+
+/* ---- isosurface of a narrow band: sparse marching cubes ------------------------------------------------------------------------------
+ * m2s_band_isosurface extracts the level set d = iso from the result of m2s_narrow_band_sdf (or any list of grid points and values) with
+ * work proportional to the list; no array of distances sized by the grid is made.  What volumeToMesh is to meshToLevelSet in OpenVDB.
+ * The result is DEFINED as a filter of m2s_grid_isosurface, so it has no floating-point model of its own:
+ *   cells[0 .. n_cells)      strictly ascending L = k + j*nz + i*ny*nz, every L below the cell count; these grid points are ACTIVE.
+ *   distances[0 .. n_cells)  their values.
+ *   D'                       any dense grid that equals `distances` on the active points and is finite elsewhere;
+ *   (V, T) = m2s_grid_isosurface(grid, D', iso), exactly as defined above (inside is d < iso, t = (iso - d0) / (d1 - d0), no FMA,
+ *                            vertices by ascending 3*L + a, triangles by cell L then table order).
+ * Vertices: the vertices of V whose edge has both ends active, in the same order.
+ * Triangles: the triangles of T whose cell has all 8 corners active, in the same order, their indices renumbered to the kept vertices
+ *   (every one is kept: the 12 edges of a complete cell join active points).
+ * Nothing depends on the values of D' at inactive points: a kept vertex reads 2 active values, a kept cell 8.
+ * Corollary: if every cell of a dense grid D whose 8 corners are not all on one side of iso has all 8 corners in the band, the result on
+ *   that band equals m2s_grid_isosurface(grid, D, iso) bit for bit in both arrays (every axis with at least 2 points).  For an exact
+ *   distance field that holds when the band contains [iso - w, iso + w] with w one cell diagonal sqrt(sx^2 + sy^2 + sz^2).
+ * counts (host, 3 x uint64) = { n_vertices, n_triangles, n_open }.  n_open is the number of active points P that own a cell
+ *   (i < nx-1, j < ny-1, k < nz-1) with two properties: the cell's 8 corners are not all active; among its active corners at least one
+ *   is inside and at least one is outside.  A non-zero value proves the band was too narrow for this iso.  Zero does not prove the
+ *   opposite, because cells whose lowest corner is inactive are not visited.
+ * Counting and capacity: vertices_out == indices_out == NULL only counts; exactly one of them NULL is M2S_ERR_BAD_ARG.  counts is always
+ *   written when the arguments are valid ({0, 0, 0} with M2S_ERR_NAN).  A capacity (3 floats per vertex, 3 uint32 per triangle) below its
+ *   count is M2S_ERR_BAD_ARG with counts written, and nothing is written past either capacity; n_vertices >= 2^32 is M2S_ERR_BAD_ARG
+ *   with counts written (the indices are u32).  Always synchronous.  n_cells == 0: M2S_OK with {0, 0, 0}.
+ * Errors before any device work (M2S_ERR_BAD_ARG): everything m2s_grid_isosurface rejects for grid, iso and opts; a grid of 2^36 or more
+ *   cells; NULL counts; NULL cells or distances with n_cells > 0; n_cells above the cell count; a bad mem_kind.
+ * cells not strictly ascending, or an entry at or above the cell count: M2S_ERR_BAD_ARG, no output and no count written.  Host memory:
+ *   decided on the host, before any device work.  Device memory: decided by a flag the first kernel raises and the host reads with the
+ *   counts; no kernel uses an unchecked entry as an index.
+ * A NaN or +-inf in distances: M2S_ERR_NAN, no output written, counts {0, 0, 0}.  f32::MAX is finite and legal (a band with
+ *   exterior = +inf holds it).
+ * m2s_opts: device, stream / stream_mode, lane; mem_kind covers cells, distances and both outputs.  timings: distance_ms = the call's
+ *   kernels, n_units = n_cells.
+ * Workspace: sized by the grid are the mask (1 bit per point) and one 64-bit list offset per 64 points; the rest is 8 bytes per band
+ *   cell (20 with host memory, plus the staged outputs). */
+int m2s_band_isosurface(const m2s_grid* grid, const uint64_t* cells, const float* distances, uint64_t n_cells, float iso,
+                        float* vertices_out, uint64_t vertex_capacity, uint32_t* indices_out, uint64_t triangle_capacity,
+                        uint64_t* counts /* host, 3: n_vertices, n_triangles, n_open */, const m2s_opts* opts);
 
 /* glTF 2.0 / GLB ingestion (host side) — what the reference client extracts from a file before the merge:
  * mesh_to_sdf_client/src/gltf/mod.rs:56-174 (models keyed by mesh index, one primitive per mesh survives;

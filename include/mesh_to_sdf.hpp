@@ -18,6 +18,8 @@
 //   narrow_band_sdf                 the cells of a grid within a band of the surface and their distances: the dense result, filtered (m2s.h)
 //   sample_grid / raymarch_grid  client draw_raymarching.wgsl  sdf_grid / estimate_normal / sdf_3d on a finished grid (m2s.h)
 //   grid_isosurface                                            marching-cubes mesh of a level set of a finished grid (no reference counterpart; m2s.h)
+//   band_isosurface                                            the same from a narrow band: cells and distances in, mesh and n_open out,
+//                                                              work proportional to the band (no reference counterpart; m2s.h)
 //   serde::*               serde.rs:75-221                     SerializeSdf / DeserializeSdf / save_to_file / read_from_file
 //
 // V is any point type with x(), y(), z() | .x .y .z | operator[] (the reference's `Point` trait adapters,
@@ -558,6 +560,31 @@ Isosurface<V> grid_isosurface(const Grid<V>& grid, const std::vector<float>& dis
   r.indices.resize(3 * counts[1]);
   r.vertices.reserve(counts[0]);
   for (uint64_t i = 0; i < counts[0]; ++i) r.vertices.push_back(detail::make_point<V>(v[3 * i], v[3 * i + 1], v[3 * i + 2]));
+  return r;
+}
+
+// ---- isosurface of a narrow band (m2s_band_isosurface) --------------------------------------------------------------------
+// The same level set from the band's own cells (strictly ascending grid-order indices) and distances: grid_isosurface of any dense
+// grid that agrees with the band, kept where the band alone decides it.  n_open != 0 proves the band was too narrow for this iso
+// (m2s.h: n_open); with a band of one cell diagonal either side of iso and an exact distance field the mesh is the dense call's.
+template <class V>
+struct BandIsosurface : Isosurface<V> {
+  uint64_t n_open = 0;
+};
+template <class V>
+BandIsosurface<V> band_isosurface(const Grid<V>& grid, const std::vector<uint64_t>& cells, const std::vector<float>& distances, float iso = 0.0f) {
+  if (cells.size() != distances.size()) throw Panic(M2S_ERR_BAD_ARG, "band_isosurface: cells and distances differ in length");
+  uint64_t counts[3] = {0, 0, 0};
+  detail::check(m2s_band_isosurface(&grid.raw(), cells.data(), distances.data(), cells.size(), iso, nullptr, 0, nullptr, 0, counts, nullptr));
+  std::vector<float> v(3 * counts[0] + 3);   // never empty: two NULL outputs would mean "count only"
+  BandIsosurface<V> r;
+  r.indices.resize(3 * counts[1] + 3);
+  detail::check(m2s_band_isosurface(&grid.raw(), cells.data(), distances.data(), cells.size(), iso, v.data(), counts[0], r.indices.data(), counts[1],
+                                    counts, nullptr));
+  r.indices.resize(3 * counts[1]);
+  r.vertices.reserve(counts[0]);
+  for (uint64_t i = 0; i < counts[0]; ++i) r.vertices.push_back(detail::make_point<V>(v[3 * i], v[3 * i + 1], v[3 * i + 2]));
+  r.n_open = counts[2];
   return r;
 }
 

@@ -9,6 +9,7 @@ from .api import (AccelerationMethod, Exchange, Grid, M2SError, M2SPanic, Mesh, 
                   grid_closest_points, grid_isosurface, interleaved_slab, slab_bounds, balanced_slabs, peer_bandwidth, raymarch_grid,
                   sample_grid, warmup, winding_numbers, grid_winding_numbers, generate_sdf_winding, generate_grid_sdf_winding,
                   RayHits, cast_rays, count_intersections, test_occlusions, SurfaceSamples, sample_surface, surface_area,
-                  sample_sdf_near_surface, Voxels, voxelize, NarrowBand, narrow_band_sdf)
+                  sample_sdf_near_surface, Voxels, voxelize, NarrowBand, narrow_band_sdf,
+                  band_isosurface, isosurface_band, remesh)
 from ._lib import M2STimings  # noqa: F401
 from . import serde  # noqa: F401,E402  (mesh_to_sdf::serde, serde.rs)

@@ -186,6 +186,7 @@ EXPORTS = [
     "m2s_sample_grid",
     "m2s_raymarch_grid",
     "m2s_grid_isosurface",
+    "m2s_band_isosurface",
     "m2s_merge_instances",
     "m2s_gltf_open",
     "m2s_gltf_instances",
@@ -275,6 +276,8 @@ def _prototypes():
         "m2s_raymarch_grid": (C.c_int, [C.POINTER(M2SGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(M2SSampleOpts), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.POINTER(M2SOpts)]),
         "m2s_grid_isosurface": (C.c_int, [C.POINTER(M2SGrid), C.c_void_p, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                          C.POINTER(C.c_uint64), C.POINTER(M2SOpts)]),
+        "m2s_band_isosurface": (C.c_int, [C.POINTER(M2SGrid), C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                           C.POINTER(C.c_uint64), C.POINTER(M2SOpts)]),
         "m2s_merge_instances": (C.c_int, [C.POINTER(M2SInstance), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(M2SOpts)]),
         "m2s_gltf_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(M2SGltfInfo)]),

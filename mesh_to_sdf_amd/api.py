@@ -643,6 +643,10 @@ class NarrowBand(NamedTuple):
             out[np.asarray(self.cells).astype(np.int64)] = self.distances
         return out.reshape(shape)
 
+    def isosurface(self, iso: float = 0.0, *, timings: M2STimings = None):
+        """band_isosurface on this band's own cells, distances and grid: (vertices, indices, n_open), and no dense array on the way."""
+        return band_isosurface(self.grid, self.cells, self.distances, iso=iso, timings=timings)
+
 
 def _band_widths(band):
     """band: one width for both sides, or (interior, exterior)."""
@@ -908,6 +912,88 @@ def grid_isosurface(grid: Grid, distances, *, iso: float = 0.0, timings: M2STimi
     if q.device and hasattr(q.torch, "uint32"):
         idx = idx.view(q.torch.uint32)
     return verts, idx
+
+
+def band_isosurface(grid: Grid, cells, distances, *, iso: float = 0.0, timings: M2STimings = None):
+    """Extracts the level set d = iso from a narrow band (include/m2s.h m2s_band_isosurface): `cells` are strictly ascending grid-order
+    indices L (uint64 or int64), `distances` their values.  The result is grid_isosurface of any dense grid that agrees with the band,
+    kept where the band decides it alone: the vertices whose edge has both ends in the band and the triangles whose cell has all 8 corners
+    in it, bit for bit and in the same order.  The work is proportional to the band; no array of distances sized by the grid exists.
+    Returns (vertices f32[n, 3], indices u32[m, 3], n_open).  n_open is the number of active points P that own a cell
+    (i < nx-1, j < ny-1, k < nz-1) with two properties: the cell's 8 corners are not all active; among its active corners at least one
+    is inside and at least one is outside.  A non-zero value proves the band was too narrow for this iso.  Zero does not prove the
+    opposite, because cells whose lowest corner is inactive are not visited.  CUDA tensors keep the call on their device and return
+    tensors; the call runs twice, count then fill."""
+    q = _GridQuery(distances, timings)
+    if q.device:
+        t = q.torch
+        c = cells
+        if not _is_torch(c):
+            h = np.ascontiguousarray(np.asarray(c).reshape(-1))
+            c = t.as_tensor(h.view(np.int64) if h.dtype == np.uint64 else h.astype(np.int64))
+        c = c.detach().reshape(-1)
+        if c.dtype != t.int64:
+            c = c.view(t.int64) if c.dtype == getattr(t, "uint64", None) else c.to(t.int64)
+        c = c.to(device=q.dev).contiguous()
+        n = c.numel()
+    else:
+        c = cells.detach().cpu().numpy() if _is_torch(cells) else np.asarray(cells)
+        c = np.ascontiguousarray(c.reshape(-1))
+        c = c.view(np.uint64) if c.dtype in (np.uint64, np.int64) else c.astype(np.uint64)   # a negative int64 is out of range either way
+        n = c.size
+    if n != q.n_cells:
+        raise M2SPanic(_lib.ERR_BAD_ARG, f"{n} cells but {q.n_cells} distances")
+    p_c = q.ptr(c)
+    L = _lib.lib()
+    counts = (C.c_uint64 * 3)()
+    it = float(np.float32(iso))
+    rc = L.m2s_band_isosurface(C.byref(grid._g), p_c, q.p_d, n, it, None, 0, None, 0, counts, C.byref(q.opts))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    nv, nt = int(counts[0]), int(counts[1])
+    verts, p_v = q.empty((max(nv, 1), 3))          # never NULL: NULL for both outputs means "count only"
+    idx, p_i = q.empty((max(nt, 1), 3), np.uint32)
+    rc = L.m2s_band_isosurface(C.byref(grid._g), p_c, q.p_d, n, it, p_v, nv, p_i, nt, counts, C.byref(q.opts))
+    if rc != _lib.M2S_OK:
+        _raise(rc)
+    verts, idx = verts[:nv], idx[:nt]
+    if q.device and hasattr(q.torch, "uint32"):
+        idx = idx.view(q.torch.uint32)
+    return verts, idx, int(counts[2])
+
+
+def _f32_up(x: float) -> float:
+    """The smallest float32 that is not below x."""
+    y = np.float32(x)
+    if float(y) < x:
+        y = np.nextafter(y, np.float32(np.inf))
+    return float(y)
+
+
+def isosurface_band(grid: Grid, iso: float = 0.0):
+    """The (interior, exterior) widths narrow_band_sdf needs so that band_isosurface at `iso` equals grid_isosurface of the dense grid:
+    the band contains [iso - w, iso + w] with w = 1.001 x the cell diagonal sqrt(sx^2 + sy^2 + sz^2), computed in float64 and rounded up
+    to float32; interior = max(0, w - iso) and exterior = max(0, iso + w), each rounded up to float32.  For an exact distance field every
+    cell the level set cuts then has all 8 corners in the band."""
+    sx, sy, sz = (float(v) for v in grid.get_cell_size())
+    w = _f32_up(1.001 * float(np.sqrt(sx * sx + sy * sy + sz * sz)))
+    iso = float(np.float32(iso))
+    return _f32_up(max(0.0, w - iso)), _f32_up(max(0.0, iso + w))
+
+
+def _remesh(band: "NarrowBand", iso):
+    verts, idx, n_open = band.isosurface(iso)
+    if n_open != 0:
+        raise M2SError(_lib.ERR_BAD_ARG, f"remesh: the band is too narrow for iso = {iso}: {n_open} cells are cut but incomplete")
+    return verts, idx
+
+
+def remesh(vertices, indices: Topology, grid: Grid, *, iso: float = 0.0, sign_method: SignMethod = SignMethod.Raycast):
+    """Mesh -> level set -> mesh without a dense grid: narrow_band_sdf with the band of isosurface_band(grid, iso), then its isosurface at
+    `iso`.  The sparse voxel remesh (iso = 0) / offset surface (iso != 0) of the mesh on `grid`; where the distance field is exact the
+    result is grid_isosurface(grid, generate_grid_sdf(...), iso) bit for bit.  Returns (vertices, indices); raises M2SError if the band
+    turns out too narrow (n_open != 0)."""
+    return _remesh(narrow_band_sdf(vertices, indices, grid, isosurface_band(grid, iso), sign_method), iso)
 
 
 class PeerMode(enum.IntEnum):
@@ -1373,6 +1459,10 @@ class Mesh:
         L = _lib.lib()
         return _band_call(lambda *r: L.m2s_mesh_narrow_band_sdf(self._h, *r), self._a, grid, band, sign_method, bits, algorithm, timings,
                           capacity, synchronous)
+
+    def remesh(self, grid: Grid, *, iso: float = 0.0, sign_method: SignMethod = SignMethod.Raycast):
+        """remesh on the resident mesh: the same bits as the one-shot function."""
+        return _remesh(self.narrow_band_sdf(grid, isosurface_band(grid, iso), sign_method), iso)
 
     def sample_sdf_near_surface(self, n: int, sigmas=None, uniform_fraction: float = 0.05, sign: str = "winding", seed: int = 0):
         """sample_sdf_near_surface on this mesh."""

@@ -15,15 +15,14 @@
 //   k_iso_triangles  per active cell: its triangles; an edge owned by another point finds that point's index from the mask word
 //                    offsets, and its vertex id is the owner's first id plus the axis's rank among the owner's flags.
 // 64-bit point indices throughout (a 1040 x 1024 x 1024 grid has byte offsets beyond 2^32).
+// The table, IsoGrid, the workgroup scan, decode, k_scan_tiles and active_index live in isosurface.hip.h, which band_isosurface.hip shares.
 #include "../../include/m2s.h"
 #include "capi_internal.h"
 #include "common.h"
+#include "isosurface.hip.h"
 
 #include <cmath>
 #include <cstring>
-
-#define M2S_ISO_TABLE static __constant__ const
-#include "isosurface_table.h"
 
 #pragma clang fp contract(off)
 
@@ -33,56 +32,6 @@ namespace {
 constexpr int kClassifyThreads = 256;
 constexpr int kTile = 8192;                       // points per classify / compact workgroup = 128 mask words
 constexpr int kTileIters = kTile / kClassifyThreads;
-constexpr int kScanThreads = 1024;
-constexpr int kItemThreads = 256;
-constexpr int kItemsPerThread = 16;
-constexpr int kItemBlock = kItemThreads * kItemsPerThread;   // active points per k_iso_info / vertices / triangles workgroup
-
-struct IsoGrid {
-  float first[3], cs[3];
-  uint64_t n[3];
-  uint64_t nyz;     // n[1] * n[2]
-  uint64_t total;   // n[0] * n[1] * n[2]
-  float iso;
-};
-
-// Exclusive scan over a workgroup of NT threads (64-wide waves); *total = the sum of all.
-template <int NT>
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t* total) {
-  __shared__ uint64_t wave_sum[NT / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wave_sum[wave] = x;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < NT / 64; ++w) {
-    const uint64_t s = wave_sum[w];
-    if (w < wave) before += s;
-    all += s;
-  }
-  __syncthreads();   // wave_sum may be reused by the caller's next scan
-  *total = all;
-  return before + x - v;
-}
-
-struct Pt {
-  uint64_t i, j, k;
-};
-
-__device__ __forceinline__ Pt decode(const IsoGrid& g, uint64_t L) {
-  Pt p;
-  p.i = L / g.nyz;
-  const uint64_t r = L - p.i * g.nyz;
-  p.j = r / g.n[2];
-  p.k = r - p.j * g.n[2];
-  return p;
-}
 
 __device__ __forceinline__ void advance(const IsoGrid& g, Pt& p, uint64_t step) {
   // step <= nz wraps a row at most once: no 64-bit division on the common path
@@ -163,22 +112,6 @@ __global__ void __launch_bounds__(kClassifyThreads) k_iso_classify(IsoGrid g, co
     for (int w = 0; w < kClassifyThreads / 64; ++w) s += wave_count[w];
     tile_count[blockIdx.x] = s;
   }
-}
-
-// In-place exclusive scan of n counts in one workgroup; *total = their sum.
-__global__ void __launch_bounds__(kScanThreads) k_scan_tiles(uint64_t* __restrict__ v, uint64_t n, uint64_t* __restrict__ total) {
-  const uint64_t chunk = (n + kScanThreads - 1) / kScanThreads;
-  const uint64_t b = threadIdx.x * chunk, e = b + chunk < n ? b + chunk : n;
-  uint64_t s = 0;
-  for (uint64_t i = b; i < e; ++i) s += v[i];
-  uint64_t all;
-  uint64_t run = block_exclusive_scan<kScanThreads>(s, &all);
-  for (uint64_t i = b; i < e; ++i) {
-    const uint64_t x = v[i];
-    v[i] = run;
-    run += x;
-  }
-  if (threadIdx.x == 0) *total = all;
 }
 
 __global__ void __launch_bounds__(kTile / 64) k_iso_compact(const uint64_t* __restrict__ mask, uint64_t n_words,
@@ -263,13 +196,6 @@ __global__ void __launch_bounds__(kItemThreads) k_iso_vertices(IsoGrid g, const 
   }
 }
 
-// The index of active point L in the active list: its mask word's offset plus the active points before it in that word.
-__device__ __forceinline__ uint64_t active_index(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ word_off, uint64_t L) {
-  const uint64_t w = L >> 6;
-  const uint64_t below = mask[w] & ((1ull << (L & 63)) - 1);
-  return word_off[w] + (uint64_t)__popcll(below);
-}
-
 __global__ void __launch_bounds__(kItemThreads) k_iso_triangles(IsoGrid g, const uint64_t* __restrict__ act, uint64_t n_act,
                                                                 const uint64_t* __restrict__ mask, const uint64_t* __restrict__ word_off,
                                                                 const uint32_t* __restrict__ info, const uint32_t* __restrict__ voff,
@@ -305,8 +231,6 @@ __global__ void __launch_bounds__(kItemThreads) k_iso_triangles(IsoGrid g, const
     }
   }
 }
-
-unsigned item_blocks(uint64_t n_act) { return (unsigned)((n_act + kItemBlock - 1) / kItemBlock); }
 
 // Validation that needs no device (include/m2s.h: errors before any device work).
 int iso_args(const m2s_grid* grid, const float* distances, float iso, float* vertices_out, uint32_t* indices_out, uint64_t* counts,
