@@ -49,7 +49,7 @@ extern "C" {
 #endif
 
 #define M2S_VERSION_MAJOR 0
-#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
+#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface, m2s_band_create / destroy / info / sample / raymarch); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
 
 /* Return codes.  The reference panics where this ABI returns a negative code; the Rust shim
  * turns a negative code back into panic!(m2s_last_error()). */
@@ -789,6 +789,66 @@ int m2s_grid_isosurface(const m2s_grid* grid, const float* distances, float iso,
 int m2s_band_isosurface(const m2s_grid* grid, const uint64_t* cells, const float* distances, uint64_t n_cells, float iso,
                         float* vertices_out, uint64_t vertex_capacity, uint32_t* indices_out, uint64_t triangle_capacity,
                         uint64_t* counts /* host, 3: n_vertices, n_triangles, n_open */, const m2s_opts* opts);
+
+/* ---- queries on a narrow band: sampling and ray marching without a dense grid ------------------------------------------------------
+ * A resident BAND FIELD answers m2s_sample_grid / m2s_raymarch_grid from a narrow band (m2s_narrow_band_sdf's result, or any list of
+ * grid points and values): distance and normal lookups at arbitrary points, sphere tracing, at 2048^3 and beyond, where the dense
+ * float[nx*ny*nz] costs 32 GiB.  What a sparse level set's sampler and ray intersector are in OpenVDB.  Nothing sized 4 * nx*ny*nz
+ * bytes is ever allocated.  The result is DEFINED as the dense call on a grid the band stands for, so it has no model of its own:
+ *   cells[0 .. n_cells)      strictly ascending L = k + j*nz + i*ny*nz, every L below the cell count; these grid points are ACTIVE.
+ *   distances[0 .. n_cells)  their values, finite.
+ *   background_outside, background_inside   both >= 0 and finite.
+ *   inside_bits              optional: uint32[nx][ny][ceil(nz / 32)], cell k of a row is bit k & 31 of word k >> 5 (m2s_voxelize's
+ *                            bits_out, m2s_narrow_band_sdf's bits_out).
+ *   D'[L] = distances[n]           if L == cells[n]                        (every bit, the sign bit included)
+ *         = -background_inside     else if inside_bits and its bit (i, j, k) is set
+ *         = +background_outside    otherwise
+ *   m2s_band_sample(band, points, ...)                 == m2s_sample_grid(grid, D', points, ...)
+ *   m2s_band_raymarch(band, origins, directions, ...)  == m2s_raymarch_grid(grid, D', origins, directions, ...)
+ * bit for bit in every output, in all three modes.  iso, outside, max_steps, the normals (estimate_normal), the clamped reads at the box
+ * faces and the NaN and +-inf rules are those stated above for the dense calls.  IEEE binary32, no FMA.
+ * support_out (uint8 per point or ray, may be NULL) is the one extra output.  Sample: how many of the sample's K cell reads (K = 1 SNAP,
+ *   8 TRILINEAR, 4 TETRAHEDRAL) hit an active cell, counted after clamping (a cell read twice counts twice); 0 for a point off the box or
+ *   with a NaN coordinate.  March: the support of the last sample the march evaluated; 0 for a ray that never marched.  A value of K
+ *   means the result used band values only.  For the normal outputs it describes the centre sample, not the six offset ones.
+ * Why one sign mask is enough: for a 1-Lipschitz field whose band is at least one cell wide on both sides, a sign change along a grid
+ *   line passes through active cells, so the inactive cells fall into regions of one sign each; m2s_voxelize(..., solid = 1) on the same
+ *   grid has bit = "centre inside by the Raycast sign" on every inactive cell as soon as interior >= half a cell diagonal (a cell whose
+ *   box touches the surface is then active).  The bits are nevertheless taken as given: the definition does not depend on their origin.
+ * Why sphere tracing stays safe: with background_outside <= the band's exterior and background_inside <= its interior, |D'| <= |D| on
+ *   the inactive cells, so a step never passes the surface that the dense field would not pass.  A zero background stalls a march
+ *   that enters the region it fills (dist < eps ends it there).
+ * m2s_band_create copies what it needs into device memory the handle owns and keeps no pointer of the caller's: the active mask (1 bit
+ *   per grid point), one 64-bit list offset per 64 points, the distances and, if given, the sign mask (1 bit per point).  `cells` is not
+ *   kept: after the index is built nothing reads it.  m2s_band_info's device_bytes = 16 * ceil(cells / 64) + 4 * n_cells, + 8 *
+ *   ceil(cells / 64) with a sign mask: 2 GiB (3 GiB) + the band at 2048^3, where a dense grid is 32 GiB.  The handle is immutable and bound to the device it was made on.
+ *   Always synchronous.  n_cells == 0 is a valid band (all background).  f32::MAX is a legal distance.
+ *   Errors before any device work (M2S_ERR_BAD_ARG): NULL grid, out or field opts; field opts' struct_size other than sizeof; a
+ *   background that is negative or not finite; what m2s_sample_grid rejects of a grid, or 2^36 or more cells; NULL cells or distances with
+ *   n_cells > 0; n_cells above the cell count; m2s_opts.algorithm, x_begin, x_end, x_period or peer_out not zero; a bad mem_kind.
+ *   cells not strictly ascending, or an entry at or above the cell count: M2S_ERR_BAD_ARG; a NaN or +-inf distance: M2S_ERR_NAN.  Host
+ *   memory: both decided on the host before any device work.  Device memory: decided by the flag the index kernel raises; no later
+ *   kernel ever uses an unchecked entry as an index.  No handle is returned in either case (*out = NULL).
+ *   m2s_opts: device, stream / stream_mode, lane; mem_kind covers cells, distances and inside_bits.  timings: seed_ms = the index build.
+ * The query calls reject what the dense calls reject (a bad mode, max_steps == 0, every output NULL — support_out alone does not count
+ *   as an output —, NULL inputs with n > 0, the m2s_opts fields above), a NULL handle, and an m2s_opts.device that is not the handle's
+ *   (-1 means the handle's).  mem_kind covers points, rays and outputs; synchronous, stream and lane behave as for m2s_sample_grid;
+ *   timings: distance_ms = the kernel, n_units = points or rays.  A handle may serve calls from several threads; destroy it after the
+ *   last asynchronous call on it has finished (m2s_band_destroy waits for the device). */
+typedef struct m2s_band m2s_band;   /* opaque, immutable after create, bound to one device */
+typedef struct m2s_band_field_opts {
+  uint32_t struct_size;      /* sizeof(m2s_band_field_opts) */
+  float background_outside;  /* D' on inactive cells outside: +background_outside */
+  float background_inside;   /* D' on inactive cells whose inside bit is set: -background_inside */
+} m2s_band_field_opts;
+int m2s_band_create(const m2s_grid* grid, const uint64_t* cells, const float* distances, uint64_t n_cells,
+                    const uint32_t* inside_bits /* may be NULL */, const m2s_band_field_opts* fopts, const m2s_opts* opts, m2s_band** out);
+void m2s_band_destroy(m2s_band* band);
+int m2s_band_info(const m2s_band* band, m2s_grid* grid, uint64_t* n_cells, uint64_t* device_bytes);   /* any output may be NULL */
+int m2s_band_sample(const m2s_band* band, const float* points, size_t n_points, const m2s_sample_opts* sopts, float* value_out,
+                    float* normal_out, uint8_t* support_out, const m2s_opts* opts);
+int m2s_band_raymarch(const m2s_band* band, const float* origins, const float* directions, size_t n_rays, const m2s_sample_opts* sopts,
+                      float* hit_out, uint32_t* steps_out, float* normal_out, uint8_t* support_out, const m2s_opts* opts);
 
 /* glTF 2.0 / GLB ingestion (host side) — what the reference client extracts from a file before the merge:
  * mesh_to_sdf_client/src/gltf/mod.rs:56-174 (models keyed by mesh index, one primitive per mesh survives;

@@ -17,6 +17,7 @@
 //   voxelize                        surface / solid occupancy of a grid, defined to the bit (m2s.h)
 //   narrow_band_sdf                 the cells of a grid within a band of the surface and their distances: the dense result, filtered (m2s.h)
 //   sample_grid / raymarch_grid  client draw_raymarching.wgsl  sdf_grid / estimate_normal / sdf_3d on a finished grid (m2s.h)
+//   BandField                    (no counterpart)              the same two queries on a narrow band, no dense grid (m2s.h)
 //   grid_isosurface                                            marching-cubes mesh of a level set of a finished grid (no reference counterpart; m2s.h)
 //   band_isosurface                                            the same from a narrow band: cells and distances in, mesh and n_open out,
 //                                                              work proportional to the band (no reference counterpart; m2s.h)
@@ -587,6 +588,88 @@ BandIsosurface<V> band_isosurface(const Grid<V>& grid, const std::vector<uint64_
   r.n_open = counts[2];
   return r;
 }
+
+// ---- queries on a narrow band (m2s_band_create, m2s_band_sample, m2s_band_raymarch) ---------------------------------------
+// A band made queryable: the index of its cells, its distances and an optional sign mask stay on the device; sample and raymarch equal
+// sample_grid / raymarch_grid on the dense grid the band stands for (its values on its cells, -background_inside where `inside_bits` has
+// the cell's bit, +background_outside elsewhere) bit for bit, and that grid is never made.  m2s.h states the contract.  Move-only.
+struct BandSamples : GridSamples {
+  std::vector<uint8_t> support;   // per point: how many of the sample's 1 / 8 / 4 cell reads hit a band cell
+};
+struct BandRayMarch : RayMarch {
+  std::vector<uint8_t> support;   // per ray: the support of the last sample the march evaluated
+};
+template <class V>
+class BandField {
+ public:
+  // inside_bits: empty, or uint32[nx][ny][ceil(nz / 32)] (voxelize(solid) / narrow_band_sdf bits)
+  BandField(const Grid<V>& grid, const std::vector<uint64_t>& cells, const std::vector<float>& distances, float background_outside,
+            float background_inside, const std::vector<uint32_t>& inside_bits = {})
+      : grid_(grid) {
+    if (cells.size() != distances.size()) throw Panic(M2S_ERR_BAD_ARG, "BandField: cells and distances differ in length");
+    const auto n = grid.get_cell_count();
+    if (!inside_bits.empty() && inside_bits.size() != (size_t)(n[0] * n[1] * ((n[2] + 31) / 32)))
+      throw Panic(M2S_ERR_BAD_ARG, "BandField: inside_bits do not match the grid");
+    m2s_band_field_opts fo{};
+    fo.struct_size = sizeof(fo);
+    fo.background_outside = background_outside;
+    fo.background_inside = background_inside;
+    detail::check(m2s_band_create(&grid.raw(), cells.data(), distances.data(), cells.size(), inside_bits.empty() ? nullptr : inside_bits.data(), &fo,
+                                  nullptr, &h_));
+  }
+  BandField(const BandField&) = delete;
+  BandField& operator=(const BandField&) = delete;
+  BandField(BandField&& o) noexcept : grid_(o.grid_), h_(o.h_) { o.h_ = nullptr; }
+  BandField& operator=(BandField&& o) noexcept {
+    if (this != &o) {
+      m2s_band_destroy(h_);
+      grid_ = o.grid_;
+      h_ = o.h_;
+      o.h_ = nullptr;
+    }
+    return *this;
+  }
+  ~BandField() { m2s_band_destroy(h_); }
+
+  const Grid<V>& grid() const { return grid_; }
+  uint64_t count() const { return info(0); }
+  uint64_t device_bytes() const { return info(1); }
+  m2s_band* raw() const { return h_; }
+
+  BandSamples sample(const std::vector<V>& points, const SampleOptions& options = {}, bool normals = false) const {
+    detail::Packed<V> p(points.data(), points.size());
+    const m2s_sample_opts so = detail::sample_opts(options);
+    BandSamples r;
+    r.value.resize(points.size());
+    r.support.resize(points.size());
+    if (normals) r.normal.resize(points.size());
+    detail::check(m2s_band_sample(h_, p.ptr, points.size(), &so, r.value.data(), normals ? reinterpret_cast<float*>(r.normal.data()) : nullptr,
+                                  r.support.data(), nullptr));
+    return r;
+  }
+  BandRayMarch raymarch(const std::vector<V>& origins, const std::vector<V>& directions, const SampleOptions& options = {}, bool normals = false) const {
+    if (origins.size() != directions.size()) throw Panic(M2S_ERR_BAD_ARG, "origins and directions differ in length");
+    detail::Packed<V> o(origins.data(), origins.size()), d(directions.data(), directions.size());
+    const m2s_sample_opts so = detail::sample_opts(options);
+    BandRayMarch r;
+    r.hit.resize(origins.size());
+    r.steps.resize(origins.size());
+    r.support.resize(origins.size());
+    if (normals) r.normal.resize(origins.size());
+    detail::check(m2s_band_raymarch(h_, o.ptr, d.ptr, origins.size(), &so, reinterpret_cast<float*>(r.hit.data()), r.steps.data(),
+                                    normals ? reinterpret_cast<float*>(r.normal.data()) : nullptr, r.support.data(), nullptr));
+    return r;
+  }
+
+ private:
+  uint64_t info(int which) const {
+    uint64_t n = 0, bytes = 0;
+    detail::check(m2s_band_info(h_, nullptr, &n, &bytes));
+    return which ? bytes : n;
+  }
+  Grid<V> grid_;
+  m2s_band* h_ = nullptr;
+};
 
 // ---- serde (serde.rs:75-221) ----------------------------------------------------------------------------------------------
 namespace serde {

@@ -133,6 +133,10 @@ class M2SBandOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("exterior", C.c_float), ("interior", C.c_float)]
 
 
+class M2SBandFieldOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("background_outside", C.c_float), ("background_inside", C.c_float)]
+
+
 class M2SSampleOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("iso", C.c_float), ("outside", C.c_float), ("max_steps", C.c_uint32)]
 
@@ -187,6 +191,11 @@ EXPORTS = [
     "m2s_raymarch_grid",
     "m2s_grid_isosurface",
     "m2s_band_isosurface",
+    "m2s_band_create",
+    "m2s_band_destroy",
+    "m2s_band_info",
+    "m2s_band_sample",
+    "m2s_band_raymarch",
     "m2s_merge_instances",
     "m2s_gltf_open",
     "m2s_gltf_instances",
@@ -279,6 +288,14 @@ def _prototypes():
                                           C.POINTER(C.c_uint64), C.POINTER(M2SOpts)]),
         "m2s_band_isosurface": (C.c_int, [C.POINTER(M2SGrid), C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                           C.POINTER(C.c_uint64), C.POINTER(M2SOpts)]),
+        "m2s_band_create": (C.c_int, [C.POINTER(M2SGrid), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
+                                      C.POINTER(C.c_void_p)]),
+        "m2s_band_destroy": (None, [C.c_void_p]),
+        "m2s_band_info": (C.c_int, [C.c_void_p, C.POINTER(M2SGrid), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "m2s_band_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(M2SSampleOpts), C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(M2SOpts)]),
+        "m2s_band_raymarch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(M2SSampleOpts), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(M2SOpts)]),
         "m2s_merge_instances": (C.c_int, [C.POINTER(M2SInstance), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(M2SOpts)]),
         "m2s_gltf_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(M2SGltfInfo)]),
         "m2s_gltf_instances": (C.c_int, [C.c_void_p, C.POINTER(M2SInstance), C.c_size_t]),

@@ -647,6 +647,12 @@ class NarrowBand(NamedTuple):
         """band_isosurface on this band's own cells, distances and grid: (vertices, indices, n_open), and no dense array on the way."""
         return band_isosurface(self.grid, self.cells, self.distances, iso=iso, timings=timings)
 
+    def field(self, background=None, inside=None) -> "BandField":
+        """A BandField of this band's own cells, distances and grid: sample and ray-march it with no dense array on the way.  inside: a
+        sign mask in the layout of `bits` (or the Voxels of voxelize(solid=True, bits=True) on the same grid); Mesh.narrow_band_field
+        makes one itself."""
+        return BandField(self.grid, self.cells, self.distances, background=background, inside=inside)
+
 
 def _band_widths(band):
     """band: one width for both sides, or (interior, exterior)."""
@@ -826,7 +832,8 @@ class _GridQuery:
 
     def empty(self, shape, dtype=np.float32):
         if self.device:
-            t = self.torch.empty(shape, dtype=self.torch.int32 if dtype == np.uint32 else self.torch.float32, device=self.dev)
+            kind = self.torch.int32 if dtype == np.uint32 else (self.torch.uint8 if dtype == np.uint8 else self.torch.float32)
+            t = self.torch.empty(shape, dtype=kind, device=self.dev)
             return t, self.ptr(t)
         a = np.empty(shape, dtype)
         return a, self.ptr(a)
@@ -914,17 +921,8 @@ def grid_isosurface(grid: Grid, distances, *, iso: float = 0.0, timings: M2STimi
     return verts, idx
 
 
-def band_isosurface(grid: Grid, cells, distances, *, iso: float = 0.0, timings: M2STimings = None):
-    """Extracts the level set d = iso from a narrow band (include/m2s.h m2s_band_isosurface): `cells` are strictly ascending grid-order
-    indices L (uint64 or int64), `distances` their values.  The result is grid_isosurface of any dense grid that agrees with the band,
-    kept where the band decides it alone: the vertices whose edge has both ends in the band and the triangles whose cell has all 8 corners
-    in it, bit for bit and in the same order.  The work is proportional to the band; no array of distances sized by the grid exists.
-    Returns (vertices f32[n, 3], indices u32[m, 3], n_open).  n_open is the number of active points P that own a cell
-    (i < nx-1, j < ny-1, k < nz-1) with two properties: the cell's 8 corners are not all active; among its active corners at least one
-    is inside and at least one is outside.  A non-zero value proves the band was too narrow for this iso.  Zero does not prove the
-    opposite, because cells whose lowest corner is inactive are not visited.  CUDA tensors keep the call on their device and return
-    tensors; the call runs twice, count then fill."""
-    q = _GridQuery(distances, timings)
+def _band_cells(q: "_GridQuery", cells):
+    """A band's `cells` on the side of `q` (made from its distances) -> (pointer, n): int64 on the device, uint64 on the host."""
     if q.device:
         t = q.torch
         c = cells
@@ -943,7 +941,21 @@ def band_isosurface(grid: Grid, cells, distances, *, iso: float = 0.0, timings: 
         n = c.size
     if n != q.n_cells:
         raise M2SPanic(_lib.ERR_BAD_ARG, f"{n} cells but {q.n_cells} distances")
-    p_c = q.ptr(c)
+    return q.ptr(c), n
+
+
+def band_isosurface(grid: Grid, cells, distances, *, iso: float = 0.0, timings: M2STimings = None):
+    """Extracts the level set d = iso from a narrow band (include/m2s.h m2s_band_isosurface): `cells` are strictly ascending grid-order
+    indices L (uint64 or int64), `distances` their values.  The result is grid_isosurface of any dense grid that agrees with the band,
+    kept where the band decides it alone: the vertices whose edge has both ends in the band and the triangles whose cell has all 8 corners
+    in it, bit for bit and in the same order.  The work is proportional to the band; no array of distances sized by the grid exists.
+    Returns (vertices f32[n, 3], indices u32[m, 3], n_open).  n_open is the number of active points P that own a cell
+    (i < nx-1, j < ny-1, k < nz-1) with two properties: the cell's 8 corners are not all active; among its active corners at least one
+    is inside and at least one is outside.  A non-zero value proves the band was too narrow for this iso.  Zero does not prove the
+    opposite, because cells whose lowest corner is inactive are not visited.  CUDA tensors keep the call on their device and return
+    tensors; the call runs twice, count then fill."""
+    q = _GridQuery(distances, timings)
+    p_c, n = _band_cells(q, cells)
     L = _lib.lib()
     counts = (C.c_uint64 * 3)()
     it = float(np.float32(iso))
@@ -994,6 +1006,155 @@ def remesh(vertices, indices: Topology, grid: Grid, *, iso: float = 0.0, sign_me
     result is grid_isosurface(grid, generate_grid_sdf(...), iso) bit for bit.  Returns (vertices, indices); raises M2SError if the band
     turns out too narrow (n_open != 0)."""
     return _remesh(narrow_band_sdf(vertices, indices, grid, isosurface_band(grid, iso), sign_method), iso)
+
+
+def default_background(distances):
+    """(inside, outside) backgrounds of a band field made from `distances` alone: outside = max(distances.max(), 0) and
+    inside = max(-distances.min(), 0), the largest values known to be lower bounds of |D| beyond the band (a band holds every cell with
+    -interior <= D <= exterior, so a cell it lacks is farther than its largest value on that side).  (0, 0) for an empty band."""
+    n = distances.numel() if _is_torch(distances) else np.asarray(distances).size
+    if n == 0:
+        return 0.0, 0.0
+    hi, lo = float(distances.max()), float(distances.min())
+    return max(-lo, 0.0), max(hi, 0.0)
+
+
+def _inside_bits(inside):
+    """The sign mask of a band field: a Voxels or NarrowBand (its bits) or the bits array itself."""
+    if isinstance(inside, (Voxels, NarrowBand)):
+        if inside.bits is None:
+            raise M2SPanic(_lib.ERR_BAD_ARG, "inside: the voxelization / band was made without bits=True")
+        return inside.bits
+    if inside is True:
+        raise M2SPanic(_lib.ERR_BAD_ARG, "inside=True needs the mesh: use Mesh.narrow_band_field")
+    return inside
+
+
+class BandField:
+    """A narrow band made queryable (include/m2s.h `m2s_band`): the index of the band's cells, its distances and an optional sign mask,
+    resident on the device, built once and sampled or ray-marched many times with no dense grid anywhere.  It stands for the dense grid D'
+    that holds distances[n] at cells[n], -background_inside on the other cells whose `inside` bit is set and +background_outside on the
+    rest; `sample` and `raymarch` equal sample_grid / raymarch_grid on D' bit for bit.
+
+    cells: strictly ascending grid-order indices L (uint64 or int64); distances: their float32 values; host arrays or device tensors
+    (a CUDA tensor `distances` builds the handle on its device).  inside: uint32[nx, ny, ceil(nz / 32)] in the layout of Voxels.bits
+    (or a Voxels / NarrowBand carrying one); None: every cell beyond the band is outside.  background: a scalar or (inside, outside);
+    None means default_background(distances).  A zero background stalls a march: a ray that enters the region it fills stops there
+    (dist < eps), so give a band that has cells on one side only an explicit background for the other.
+    A context manager; `close` frees the device memory."""
+
+    def __init__(self, grid: Grid, cells, distances, *, background=None, inside=None, timings: M2STimings = None):
+        self._h = C.c_void_p()
+        q = _GridQuery(distances, timings)
+        p_c, n = _band_cells(q, cells)
+        if background is None:
+            bg_in, bg_out = default_background(distances)
+        elif np.isscalar(background):
+            bg_in = bg_out = float(background)
+        else:
+            bg_in, bg_out = (float(v) for v in background)
+        p_bits = None
+        bits = _inside_bits(inside)
+        if bits is not None:
+            nx, ny, nz = (int(v) for v in grid.get_cell_count())
+            words = nx * ny * ((nz + 31) // 32)
+            if q.device:
+                t = q.torch
+                b = bits if _is_torch(bits) else t.as_tensor(np.ascontiguousarray(np.asarray(bits)).astype(np.uint32).view(np.int32))
+                b = b.detach()
+                if b.dtype != t.int32:
+                    b = b.view(t.int32) if b.dtype == getattr(t, "uint32", None) else b.to(t.int32)
+                b = b.to(device=q.dev).contiguous().reshape(-1)
+                have = b.numel()
+            else:
+                b = bits.detach().cpu().numpy() if _is_torch(bits) else np.asarray(bits)
+                b = np.ascontiguousarray(b.reshape(-1))
+                b = b.view(np.uint32) if b.dtype in (np.uint32, np.int32) else b.astype(np.uint32)
+                have = b.size
+            if have != words:
+                raise M2SPanic(_lib.ERR_BAD_ARG, f"inside holds {have} words, the grid needs {words}")
+            p_bits = q.ptr(b)
+        fo = _lib.M2SBandFieldOpts(C.sizeof(_lib.M2SBandFieldOpts), float(np.float32(bg_out)), float(np.float32(bg_in)))
+        rc = _lib.lib().m2s_band_create(C.byref(grid._g), p_c, q.p_d, n, p_bits, C.byref(fo), C.byref(q.opts), C.byref(self._h))
+        if rc != _lib.M2S_OK:
+            self._h = C.c_void_p()
+            _raise(rc)
+        self.grid = grid
+        self.count = n
+        self.background = (float(np.float32(bg_in)), float(np.float32(bg_out)))
+        nbytes = C.c_uint64(0)
+        rc = _lib.lib().m2s_band_info(self._h, None, None, C.byref(nbytes))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        self.device_bytes = int(nbytes.value)
+
+    def _handle(self):
+        if not getattr(self, "_h", None) or not self._h.value:
+            raise M2SError(_lib.ERR_BAD_ARG, "the BandField is closed")
+        return self._h
+
+    def sample(self, points, *, mode: SampleMode = SampleMode.Trilinear, iso: float = 0.0, outside: float = 100.0, normals: bool = False,
+               support: bool = False, timings: M2STimings = None, synchronous: bool = True):
+        """sample_grid on the grid the band stands for: values f32[n], then normals f32[n, 3] with normals=True, then support u8[n] with
+        support=True (how many of the sample's 1 / 8 / 4 cell reads hit a band cell; the full number means band values only).  CUDA tensor
+        points keep the call on their device (the handle's), anything else goes through host memory."""
+        h = self._handle()
+        q = _GridQuery(points if _is_torch(points) and points.is_cuda else np.zeros(0, np.float32), timings, synchronous)
+        p_pts, n = q.points(points)
+        values, p_v = q.empty(n)
+        nrm, p_n = q.empty((n, 3)) if normals else (None, None)
+        sup, p_s = q.empty(n, np.uint8) if support else (None, None)
+        so = _sample_opts(mode, iso, outside, 100)
+        if n:                                                                # no points: the empty arrays, and no NULL outputs to explain
+            rc = _lib.lib().m2s_band_sample(h, p_pts, n, C.byref(so), p_v, p_n, p_s, C.byref(q.opts))
+            if rc != _lib.M2S_OK:
+                _raise(rc)
+        res = (values,) + ((nrm,) if normals else ()) + ((sup,) if support else ())
+        return res if len(res) > 1 else values
+
+    def raymarch(self, origins, directions, *, mode: SampleMode = SampleMode.Trilinear, iso: float = 0.0, outside: float = 100.0,
+                 max_steps: int = 100, normals: bool = False, support: bool = False, timings: M2STimings = None, synchronous: bool = True):
+        """raymarch_grid on the grid the band stands for: (positions f32[n, 3], dist f32[n], steps u32[n], hit bool[n][, normals f32[n, 3]]
+        [, support u8[n]]); support is that of the last sample the march evaluated."""
+        h = self._handle()
+        q = _GridQuery(origins if _is_torch(origins) and origins.is_cuda else np.zeros(0, np.float32), timings, synchronous)
+        p_o, n = q.points(origins)
+        p_d, n_d = q.points(directions)
+        if n != n_d:
+            raise M2SPanic(_lib.ERR_BAD_ARG, f"{n} origins but {n_d} directions")
+        out, p_out = q.empty((n, 4))
+        steps, p_s = q.empty(n, np.uint32)
+        nrm, p_n = q.empty((n, 3)) if normals else (None, None)
+        sup, p_u = q.empty(n, np.uint8) if support else (None, None)
+        so = _sample_opts(mode, iso, outside, max_steps)
+        if n:
+            rc = _lib.lib().m2s_band_raymarch(h, p_o, p_d, n, C.byref(so), p_out, p_s, p_n, p_u, C.byref(q.opts))
+            if rc != _lib.M2S_OK:
+                _raise(rc)
+        eps = np.float32(0.01) * np.float32(max(self.grid.get_cell_size()))
+        pos, dist = out[:, :3], out[:, 3]
+        miss = (steps == 0) & (dist == 1.0) & (pos == 0).all(1)   # as raymarch_grid
+        hit = (dist < float(eps)) & ~miss
+        if q.device and hasattr(q.torch, "uint32"):
+            steps = steps.view(q.torch.uint32)
+        return (pos, dist, steps, hit) + ((nrm,) if normals else ()) + ((sup,) if support else ())
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            _lib.lib().m2s_band_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class PeerMode(enum.IntEnum):
@@ -1459,6 +1620,15 @@ class Mesh:
         L = _lib.lib()
         return _band_call(lambda *r: L.m2s_mesh_narrow_band_sdf(self._h, *r), self._a, grid, band, sign_method, bits, algorithm, timings,
                           capacity, synchronous)
+
+    def narrow_band_field(self, grid: Grid, band, sign_method: SignMethod = SignMethod.Raycast, inside=True, *, background=None) -> "BandField":
+        """narrow_band_sdf and, with inside=True, voxelize(solid=True, bits=True) on the same grid, as one resident BandField: the cells
+        beyond the band take -background inside the mesh and +background outside it.  inside may also be a sign mask of the caller's, or
+        None (everything beyond the band is outside)."""
+        nb = self.narrow_band_sdf(grid, band, sign_method)
+        if inside is True:
+            inside = self.voxelize(grid, solid=True, bits=True, occupancy=False, count=False)
+        return nb.field(background, inside)
 
     def remesh(self, grid: Grid, *, iso: float = 0.0, sign_method: SignMethod = SignMethod.Raycast):
         """remesh on the resident mesh: the same bits as the one-shot function."""

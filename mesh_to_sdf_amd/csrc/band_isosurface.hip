@@ -21,7 +21,8 @@
 // places and outputs share cache lines.  Measured on k_biso_info at 1024^3: 1982 -> 299 us.
 // Every kernel after the first leaves at once when the flag is raised, so a list that is not ascending or runs past the grid is never used
 // as an index: k_biso_mask itself writes only at L < total.
-// Shared with isosurface.hip through isosurface.hip.h: the table, IsoGrid, the workgroup scan, decode, k_scan_tiles, active_index.  Copied
+// Shared with isosurface.hip through isosurface.hip.h: the table, IsoGrid, the workgroup scan, decode, k_scan_tiles, active_index; and with
+// band_query.hip (the resident index of m2s_band_create): k_biso_mask and its flags, which live there too.  Copied
 // from it, because there they are written into the bodies of kernels that read a dense grid: the vertex arithmetic of k_iso_vertices
 // (operation for operation, under the same fp contract pragma), the triangle loop of k_iso_triangles and the grid checks of iso_args.
 #include "../../include/m2s.h"
@@ -36,44 +37,6 @@
 
 namespace m2s {
 namespace {
-
-constexpr int kMaskThreads = 256;
-constexpr uint64_t kNone = ~0ull;
-constexpr uint32_t kFlagOrder = 1u, kFlagNonFinite = 2u;
-
-// hdr: [0] the flag (its low 32 bits), [1] n_vertices, [2] n_triangles, [3] n_open
-__global__ void __launch_bounds__(kMaskThreads) k_biso_mask(uint64_t total, const uint64_t* __restrict__ cells, const float* __restrict__ dist,
-                                                            uint64_t n, uint64_t* __restrict__ mask, uint64_t* __restrict__ word_off,
-                                                            uint32_t* __restrict__ flag) {
-  const uint64_t a = (uint64_t)blockIdx.x * kMaskThreads + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  uint64_t w = kNone, acc = 0;   // no word: lanes past the end and cells past the grid
-  uint32_t bad = 0;
-  bool first = false;
-  if (a < n) {
-    const uint64_t L = cells[a];
-    const uint64_t prev = a ? cells[a - 1] : 0;
-    if (L >= total || (a && prev >= L)) bad |= kFlagOrder;
-    if (!isfinite(dist[a])) bad |= kFlagNonFinite;
-    if (L < total) {
-      w = L >> 6;
-      acc = 1ull << (L & 63);
-      first = a == 0 || (prev >> 6) != w;
-    }
-  }
-  if (first) word_off[w] = a;
-  // a word has 64 points and the list ascends: the lanes of one word are a run of at most 64 neighbours
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t ow = __shfl_down(w, o, 64);
-    const uint64_t oa = __shfl_down(acc, o, 64);
-    if (lane + o < 64 && ow == w) acc |= oa;
-  }
-  const uint64_t pw = __shfl_up(w, 1, 64);
-  if (w != kNone && (lane == 0 || pw != w)) atomicOr((unsigned long long*)(mask + w), (unsigned long long)acc);
-  const uint32_t any = (__ballot(bad & kFlagOrder) ? kFlagOrder : 0u) | (__ballot(bad & kFlagNonFinite) ? kFlagNonFinite : 0u);
-  if (any && lane == 0) atomicOr(flag, any);
-}
 
 // The place of grid point L (< total) in the band list, kNone if it is not in the band.
 __device__ __forceinline__ uint64_t band_index(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ word_off, uint64_t L, uint64_t n) {

@@ -1,0 +1,593 @@
+// band_query.hip — m2s_band_create / m2s_band_sample / m2s_band_raymarch: the grid queries of grid_query.hip on a narrow band behind a
+// resident index, gfx950.  The contract is include/m2s.h's: the dense m2s_sample_grid / m2s_raymarch_grid on the grid D' the band stands
+// for (its values on the band's cells, a signed background elsewhere), bit for bit, and no array sized by 4 bytes per grid point exists.
+// tests/band_query_model.py restates it in numpy.
+//
+// The handle owns, in device memory:
+//   mask      1 bit per grid point, word L >> 6, bit L & 63            k_biso_mask (isosurface.hip.h: the index m2s_band_isosurface builds)
+//   word_off  per mask word: the list place of its first active point  k_biso_mask; zeroed first, so every word is defined
+//   dist      the band's distances, in list order                      a copy
+//   inside    the sign mask, re-laid to the mask's layout              k_bq_sign (only when the caller gave inside_bits)
+// The index costs 1 bit + 8 bytes per 64 grid points (1 GiB + 1 GiB at 2048^3, where a dense grid is 32 GiB), as in band_isosurface; the sign mask one more bit per
+// point.  The caller's inside_bits are addressed by (i, j, k); re-laid by L they are read at the mask word's own index, so a corner's
+// sign costs one more load in the first round and no division.
+//
+// The arithmetic is grid_query.hip.h's prepare / combine, shared with grid_query.hip under the same fp contract pragma.  What is new is
+// the fetch of a sample's K cell values (fetch_rounds): all addresses first, then three rounds of independent loads —
+//   1  the mask words of the corners (and the sign words),
+//   2  the word_off of the words that hold an active corner,
+//   3  the values of the active corners; an inactive corner takes its background by select.
+// A corner whose mask word is the word of its lower z-neighbour (trilinear: corner c and c + 4; tetrahedral: the corner before it)
+// reuses that word and its offset: 4 + 4 reads for a trilinear sample unless L & 63 == 63 puts the neighbour in the next word.  Both
+// corners' list places are word_off + popcount(mask below the bit), so "the next list entry" needs no special case, and the z-clamp
+// case (both reads the same cell) is the same word and the same bit.
+// A normal fetches its six samples in groups: all six at once for SNAP and TETRAHEDRAL (24 corners), two groups of three for
+// TRILINEAR — 48 corners hold 96 registers of offsets, 96 of mask words and 96 of sign words at the peak of round 1, which spills.
+// The group size sets the kernel's registers, and with them the occupancy of the whole kernel, the march loop included: measured
+// (profiles/band_query.txt), the larger groups win where normals dominate (m2s_band_sample) and the smaller ones in the march, whose loop
+// fetches one sample at a time (16 trilinear / 12 tetrahedral corners per group: 189 / 136 VGPRs against 256 / 254).  M2S_BAND_FETCH: -1
+// that choice, 0 / 2 the larger / smaller groups everywhere, 1 the per-corner chain (fetch_chain: mask, then offset, then value, corner
+// after corner), which loses from 512^3 on.
+#include "../../include/m2s.h"
+#include "capi_internal.h"
+#include "common.h"
+#include "grid_query.hip.h"
+#include "isosurface.hip.h"
+#include "tuning.h"
+
+#include <cmath>
+#include <cstring>
+
+#pragma clang fp contract(off)
+
+struct m2s_band {
+  int device = -1;
+  m2s_grid grid{};
+  uint64_t n = 0, total = 0, n_words = 0;
+  uint64_t device_bytes = 0;   // the arrays' sizes as include/m2s.h states them (the allocation adds alignment only)
+  char* block = nullptr;       // one allocation: mask, word_off, [inside], dist
+  const uint64_t* mask = nullptr;
+  const uint64_t* word_off = nullptr;
+  const uint64_t* inside = nullptr;
+  const float* dist = nullptr;
+  float bg_out = 0.0f, bg_in = 0.0f;
+};
+
+namespace m2s {
+namespace {
+
+struct BandDev {
+  const uint64_t* mask;
+  const uint64_t* word_off;
+  const uint64_t* inside;   // nullptr: no sign mask, every inactive cell is outside
+  const float* dist;        // max(n, 1) floats
+  uint64_t n;
+  float bg_out, bg_in_neg;  // +background_outside, -background_inside
+};
+
+// The sign mask from the caller's layout uint32[nx][ny][ceil(nz / 32)] to the mask's (bit L & 63 of word L >> 6).  One lane per output
+// word: the row and k of its first point by one division, then 64 steps along the list order.
+__global__ void __launch_bounds__(256) k_bq_sign(uint64_t total, uint64_t nz, uint64_t n_words, const uint32_t* __restrict__ bits,
+                                                 uint64_t* __restrict__ inside) {
+  const uint64_t nzw = (nz + 31) / 32;
+  for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < n_words; w += (uint64_t)gridDim.x * 256) {
+    const uint64_t L0 = w << 6;
+    uint64_t row = L0 / nz, k = L0 - row * nz;
+    const uint64_t cnt = total - L0 < 64 ? total - L0 : 64;
+    uint64_t acc = 0;
+    uint64_t at = ~0ull;
+    uint32_t word = 0;
+    for (uint64_t b = 0; b < cnt; ++b) {
+      const uint64_t idx = row * nzw + (k >> 5);
+      if (idx != at) { word = bits[idx]; at = idx; }
+      acc |= (uint64_t)((word >> (k & 31)) & 1u) << b;
+      if (++k == nz) { k = 0; ++row; }
+    }
+    inside[w] = acc;
+  }
+}
+
+// The K cell values of G prepared samples in three rounds of independent loads (the header comment); support[g] = the active reads of
+// sample g, 0 for a sample off the box or with a NaN coordinate.
+template <int MODE, int G, bool SIGN>
+__device__ __forceinline__ void fetch_rounds(const BandDev& b, const Prep<MODE>* p, float (*v)[Corners<MODE>::K], uint32_t* support) {
+  constexpr int K = Corners<MODE>::K;
+  constexpr int S = MODE == M2S_SAMPLE_TRILINEAR ? 4 : 1;   // corner c may share the mask word of corner c - S
+  bool same[G][K];
+  uint64_t mw[G][K], sw[G][K];
+  // round 1: the mask (and sign) word of every corner that does not share its lower neighbour's
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+      const uint64_t w = p[g].off[c] >> 6;
+      same[g][c] = c >= S && (p[g].off[c >= S ? c - S : 0] >> 6) == w;
+      mw[g][c] = 0;
+      sw[g][c] = 0;
+      if (!same[g][c]) {
+        mw[g][c] = b.mask[w];
+        if (SIGN) sw[g][c] = b.inside[w];
+      }
+    }
+  uint32_t act[G], ins[G];   // bit c: corner c is active / inside by the sign mask
+  uint32_t rank[G][K];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    act[g] = ins[g] = 0;
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+      if (same[g][c]) { mw[g][c] = mw[g][c >= S ? c - S : 0]; sw[g][c] = sw[g][c >= S ? c - S : 0]; }
+      const uint32_t bit = (uint32_t)p[g].off[c] & 63u;
+      act[g] |= (uint32_t)((mw[g][c] >> bit) & 1ull) << c;
+      if (SIGN) ins[g] |= (uint32_t)((sw[g][c] >> bit) & 1ull) << c;
+      rank[g][c] = (uint32_t)__popcll(mw[g][c] & ((1ull << bit) - 1ull));
+    }
+  }
+  // round 2: the list offset of every word with an active corner, once per word
+  uint64_t wo[G][K];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+      bool need = (act[g] >> c) & 1u;
+#pragma unroll
+      for (int f = c + S; f < K; f += S) {   // the corners that take this word's offset from here
+        if (!same[g][f]) break;
+        need = need || ((act[g] >> f) & 1u);
+      }
+      wo[g][c] = 0;
+      if (!same[g][c] && need) wo[g][c] = b.word_off[p[g].off[c] >> 6];
+    }
+  // round 3: the values
+  const float bg_out = b.bg_out, bg_in_neg = b.bg_in_neg;
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+      if (same[g][c]) wo[g][c] = wo[g][c >= S ? c - S : 0];
+      const bool a = (act[g] >> c) & 1u;
+      uint64_t at = wo[g][c] + rank[g][c];
+      at = at < b.n ? at : 0;   // at < n whenever the index is sound; the guard keeps a broken invariant in bounds
+      float x = ((ins[g] >> c) & 1u) ? bg_in_neg : bg_out;
+      if (a) x = b.dist[at];
+      v[g][c] = x;
+    }
+    support[g] = p[g].state == 0 ? (uint32_t)__popc(act[g]) : 0u;
+  }
+}
+
+// The same values corner after corner: mask word, then offset, then value (M2S_BAND_FETCH=1; the measurement's other arm).
+template <int MODE, int G, bool SIGN>
+__device__ __forceinline__ void fetch_chain(const BandDev& b, const Prep<MODE>* p, float (*v)[Corners<MODE>::K], uint32_t* support) {
+  constexpr int K = Corners<MODE>::K;
+  const float bg_out = b.bg_out, bg_in_neg = b.bg_in_neg;
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    uint32_t hits = 0;
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+      const uint64_t L = p[g].off[c];
+      const uint64_t m = b.mask[L >> 6];
+      float x = bg_out;
+      if ((m >> (L & 63)) & 1ull) {
+        uint64_t at = active_index(b.mask, b.word_off, L);
+        at = at < b.n ? at : 0;
+        x = b.dist[at];
+        ++hits;
+      } else if (SIGN) {
+        if ((b.inside[L >> 6] >> (L & 63)) & 1ull) x = bg_in_neg;
+      }
+      v[g][c] = x;
+    }
+    support[g] = p[g].state == 0 ? hits : 0u;
+  }
+}
+
+// FORM (M2S_BAND_FETCH): 0 the three rounds, a normal's samples in the larger groups; 1 the per-corner chain; 2 the three rounds, smaller groups.
+template <int MODE, int G, bool SIGN, int FORM>
+__device__ __forceinline__ void fetch(const BandDev& b, const Prep<MODE>* p, float (*v)[Corners<MODE>::K], uint32_t* support) {
+  if (FORM == 1) fetch_chain<MODE, G, SIGN>(b, p, v, support);
+  else fetch_rounds<MODE, G, SIGN>(b, p, v, support);
+}
+
+template <int MODE, bool SIGN, int FORM>
+__device__ __forceinline__ float sample(const GridQuery& q, const BandDev& b, float px, float py, float pz, uint32_t* support) {
+  const Prep<MODE> p = prepare<MODE>(q, px, py, pz);
+  float v[1][Corners<MODE>::K];
+  fetch<MODE, 1, SIGN, FORM>(b, &p, v, support);
+  return combine<MODE>(q, p, v[0]);
+}
+
+// estimate_normal as grid_query.hip's normal(): the six samples in groups of G, each group's rounds issued together.
+template <int MODE, bool SIGN, int FORM>
+__device__ __forceinline__ void normal(const GridQuery& q, const BandDev& b, float px, float py, float pz, float* nrm) {
+  // corners in flight per group: 24 (FORM 0: 3 trilinear samples, 6 tetrahedral), 16 / 12 (FORM 2: 2 trilinear, 3 tetrahedral); SNAP: all 6
+  constexpr int G = MODE == M2S_SAMPLE_SNAP ? 6 : (MODE == M2S_SAMPLE_TRILINEAR ? (FORM == 2 ? 2 : 3) : (FORM == 2 ? 3 : 6));
+  const float e = q.eps;
+  float s[6];
+#pragma unroll
+  for (int h = 0; h < 6; h += G) {
+    Prep<MODE> p[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      // px + e, px - e, ... exactly as normal() writes them: the untouched coordinates pass through unchanged
+      const int i = h + j;
+      p[j] = prepare<MODE>(q, i < 2 ? (i == 0 ? px + e : px - e) : px, (i == 2 || i == 3) ? (i == 2 ? py + e : py - e) : py,
+                           i >= 4 ? (i == 4 ? pz + e : pz - e) : pz);
+    }
+    float v[G][Corners<MODE>::K];
+    uint32_t sup[G];
+    fetch<MODE, G, SIGN, FORM>(b, p, v, sup);
+#pragma unroll
+    for (int j = 0; j < G; ++j) s[h + j] = combine<MODE>(q, p[j], v[j]);
+  }
+  const float nx = s[0] - s[1], ny = s[2] - s[3], nz = s[4] - s[5];
+  const float len = sqrtf(nx * nx + ny * ny + nz * nz);
+  if (px != px || py != py || pz != pz) {
+    nrm[0] = nrm[1] = nrm[2] = qnan();
+  } else if (len == 0.0f) {
+    nrm[0] = nrm[1] = nrm[2] = 0.0f;
+  } else {
+    nrm[0] = nx / len; nrm[1] = ny / len; nrm[2] = nz / len;
+  }
+}
+
+template <int MODE, bool SIGN, int FORM>
+__global__ __launch_bounds__(256) void k_band_sample(GridQuery q, BandDev b, const float* __restrict__ pts, uint64_t n, float* __restrict__ value_out,
+                                                     float* __restrict__ normal_out, uint8_t* __restrict__ support_out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+    const float px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
+    if (value_out || support_out) {
+      uint32_t sup;
+      const float val = sample<MODE, SIGN, FORM>(q, b, px, py, pz, &sup);
+      if (value_out) value_out[i] = val;
+      if (support_out) support_out[i] = (uint8_t)sup;
+    }
+    if (normal_out) {
+      float nrm[3];
+      normal<MODE, SIGN, FORM>(q, b, px, py, pz, nrm);
+      normal_out[3 * i] = nrm[0]; normal_out[3 * i + 1] = nrm[1]; normal_out[3 * i + 2] = nrm[2];
+    }
+  }
+}
+
+// sdf_3d as grid_query.hip's k_raymarch_grid, statement for statement; the sample is the band's.
+template <int MODE, bool SIGN, int FORM>
+__global__ __launch_bounds__(256) void k_band_raymarch(GridQuery q, BandDev b, const float* __restrict__ org, const float* __restrict__ dir, uint64_t n,
+                                                       float* __restrict__ hit_out, uint32_t* __restrict__ steps_out, float* __restrict__ normal_out,
+                                                       uint8_t* __restrict__ support_out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+    const float ox = org[3 * i], oy = org[3 * i + 1], oz = org[3 * i + 2];
+    const float dx = dir[3 * i], dy = dir[3 * i + 1], dz = dir[3 * i + 2];
+    float px = ox, py = oy, pz = oz, dist = 0.0f;
+    uint32_t steps = 0, sup = 0;
+    bool march = true;
+    if (ox != ox || oy != oy || oz != oz || dx != dx || dy != dy || dz != dz) {
+      px = py = pz = dist = qnan();
+      march = false;
+    } else if (ox < q.start[0] || oy < q.start[1] || oz < q.start[2] || ox > q.end[0] || oy > q.end[1] || oz > q.end[2]) {
+      const float t0x = (q.start[0] - ox) / dx, t0y = (q.start[1] - oy) / dy, t0z = (q.start[2] - oz) / dz;
+      const float t1x = (q.end[0] - ox) / dx, t1y = (q.end[1] - oy) / dy, t1z = (q.end[2] - oz) / dz;
+      const float nx = fminf(t0x, t1x), ny = fminf(t0y, t1y), nz = fminf(t0z, t1z);
+      const float fx = fmaxf(t0x, t1x), fy = fmaxf(t0y, t1y), fz = fmaxf(t0z, t1z);
+      const float t_near = fmaxf(fmaxf(nx, ny), nz);
+      const float t_far = fminf(fminf(fx, fy), fz);
+      if (t_near > t_far) {
+        px = py = pz = 0.0f;
+        dist = 1.0f;
+        march = false;
+      } else {
+        const float t = t_near + q.eps;
+        px = ox + t * dx; py = oy + t * dy; pz = oz + t * dz;
+      }
+    }
+    if (march) {
+      for (uint32_t s = 0; s < q.max_steps; ++s) {
+        dist = sample<MODE, SIGN, FORM>(q, b, px, py, pz, &sup);   // sup: the support of the last sample evaluated
+        if (dist < q.eps) break;
+        px = px + dx * dist; py = py + dy * dist; pz = pz + dz * dist;
+        ++steps;
+      }
+    }
+    if (hit_out) { hit_out[4 * i] = px; hit_out[4 * i + 1] = py; hit_out[4 * i + 2] = pz; hit_out[4 * i + 3] = dist; }
+    if (steps_out) steps_out[i] = steps;
+    if (support_out) support_out[i] = (uint8_t)sup;
+    if (normal_out) {
+      float nrm[3] = {0.0f, 0.0f, 0.0f};
+      if (march && dist < q.eps) normal<MODE, SIGN, FORM>(q, b, px, py, pz, nrm);
+      normal_out[3 * i] = nrm[0]; normal_out[3 * i + 1] = nrm[1]; normal_out[3 * i + 2] = nrm[2];
+    }
+  }
+}
+
+constexpr uint64_t kMaxBlocks = 1u << 20;   // beyond 2^28 lanes the grid-stride loop takes over
+unsigned blocks_for(uint64_t n) { return (unsigned)std::min<uint64_t>(kMaxBlocks, (n + 255) / 256); }
+
+template <int MODE, bool SIGN, int FORM>
+void launch_sample_as(hipStream_t st, const GridQuery& q, const BandDev& b, const float* pts, uint64_t n, float* value_out, float* normal_out,
+                      uint8_t* support_out) {
+  hipLaunchKernelGGL((k_band_sample<MODE, SIGN, FORM>), dim3(blocks_for(n)), dim3(256), 0, st, q, b, pts, n, value_out, normal_out, support_out);
+}
+
+template <int MODE, bool SIGN, int FORM>
+void launch_march_as(hipStream_t st, const GridQuery& q, const BandDev& b, const float* org, const float* dir, uint64_t n, float* hit_out,
+                     uint32_t* steps_out, float* normal_out, uint8_t* support_out) {
+  hipLaunchKernelGGL((k_band_raymarch<MODE, SIGN, FORM>), dim3(blocks_for(n)), dim3(256), 0, st, q, b, org, dir, n, hit_out, steps_out, normal_out,
+                     support_out);
+}
+
+// mode x sign mask x fetch form -> the instantiation; AUTO is the form M2S_BAND_FETCH = -1 stands for in this kernel
+#define M2S_BQ_DISPATCH(AUTO, CALL, ...)                                                         \
+  do {                                                                                      \
+    const bool sign_ = b.inside != nullptr;                                                 \
+    const int form_ = tuning().band_fetch < 0 ? AUTO : tuning().band_fetch;                 \
+    switch (mode) {                                                                         \
+      case M2S_SAMPLE_SNAP: M2S_BQ_FORMS(CALL, M2S_SAMPLE_SNAP, __VA_ARGS__); break;          \
+      case M2S_SAMPLE_TRILINEAR: M2S_BQ_FORMS(CALL, M2S_SAMPLE_TRILINEAR, __VA_ARGS__); break; \
+      default: M2S_BQ_FORMS(CALL, M2S_SAMPLE_TETRAHEDRAL, __VA_ARGS__); break;                \
+    }                                                                                       \
+  } while (0)
+#define M2S_BQ_FORMS(CALL, MODE, ...)                                      \
+  do {                                                                     \
+    if (sign_) {                                                           \
+      if (form_ == 1) CALL<MODE, true, 1>(__VA_ARGS__);                    \
+      else if (form_ == 2) CALL<MODE, true, 2>(__VA_ARGS__);               \
+      else CALL<MODE, true, 0>(__VA_ARGS__);                               \
+    } else {                                                               \
+      if (form_ == 1) CALL<MODE, false, 1>(__VA_ARGS__);                   \
+      else if (form_ == 2) CALL<MODE, false, 2>(__VA_ARGS__);              \
+      else CALL<MODE, false, 0>(__VA_ARGS__);                              \
+    }                                                                      \
+  } while (0)
+
+int launch_band_sample(hipStream_t st, const GridQuery& q, int mode, const BandDev& b, const float* pts, uint64_t n, float* value_out,
+                       float* normal_out, uint8_t* support_out) {
+  if (n == 0) return 0;
+  M2S_BQ_DISPATCH(0, launch_sample_as, st, q, b, pts, n, value_out, normal_out, support_out);
+  M2S_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_band_raymarch(hipStream_t st, const GridQuery& q, int mode, const BandDev& b, const float* org, const float* dir, uint64_t n,
+                         float* hit_out, uint32_t* steps_out, float* normal_out, uint8_t* support_out) {
+  if (n == 0) return 0;
+  M2S_BQ_DISPATCH(2, launch_march_as, st, q, b, org, dir, n, hit_out, steps_out, normal_out, support_out);
+  M2S_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+BandDev dev_of(const m2s_band* h) { return BandDev{h->mask, h->word_off, h->inside, h->dist, h->n, h->bg_out, -h->bg_in}; }
+
+// The m2s_opts fields no band call takes.
+int band_opts_args(const m2s_opts* opts, const char* what) {
+  if (!opts) return 0;
+  if (opts->algorithm != 0 || opts->x_begin != 0 || opts->x_end != 0)
+    return fail(M2S_ERR_BAD_ARG, "m2s_opts.algorithm / x_begin / x_end must be 0 for %s", what);
+  if (opts->struct_size >= sizeof(m2s_opts) && (opts->x_period != 0 || opts->n_peer_out != 0 || opts->peer_out))
+    return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_period / peer_out must be 0 for %s", what);
+  if (opts->mem_kind != M2S_MEM_HOST && opts->mem_kind != M2S_MEM_DEVICE) return fail(M2S_ERR_BAD_ARG, "bad mem_kind");
+  return 0;
+}
+
+// Options of a query on a handle: its device unless the caller names the same one (as a persistent mesh's calls).
+int band_call_opts(const m2s_band* h, const m2s_opts* opts, m2s_opts* o) {
+  *o = m2s_opts{};
+  if (opts) memcpy(o, opts, (opts->struct_size >= sizeof(m2s_opts)) ? sizeof(m2s_opts) : (size_t)M2S_OPTS_V1_SIZE);
+  else o->device = -1;
+  if (o->device < 0) o->device = h->device;
+  if (o->device != h->device) return fail(M2S_ERR_BAD_ARG, "the band lives on device %d, the call asked for %d", h->device, o->device);
+  if (!opts) o->synchronous = 1;
+  return 0;
+}
+
+}  // namespace
+
+// m2s_warmup: the first launch of a kernel of this translation unit makes the runtime load its code object (all its kernels).
+__global__ void k_warm_band_query() {}
+void warm_band_query(hipStream_t st) { hipLaunchKernelGGL(k_warm_band_query, dim3(1), dim3(64), 0, st); }
+
+}  // namespace m2s
+
+using namespace m2s;
+
+extern "C" {
+
+int m2s_band_create(const m2s_grid* grid, const uint64_t* cells, const float* distances, uint64_t n_cells, const uint32_t* inside_bits,
+                    const m2s_band_field_opts* fopts, const m2s_opts* opts, m2s_band** out) {
+  clear_error();
+  if (!out) return fail(M2S_ERR_BAD_ARG, "out is NULL");
+  *out = nullptr;
+  if (!grid) return fail(M2S_ERR_BAD_ARG, "grid is NULL");
+  if (!fopts) return fail(M2S_ERR_BAD_ARG, "m2s_band_field_opts is NULL: the backgrounds have no default");
+  if (fopts->struct_size != sizeof(m2s_band_field_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_band_field_opts.struct_size is not sizeof(m2s_band_field_opts)");
+  if (!(fopts->background_outside >= 0.0f) || !std::isfinite(fopts->background_outside) || !(fopts->background_inside >= 0.0f) ||
+      !std::isfinite(fopts->background_inside))
+    return fail(M2S_ERR_BAD_ARG, "the backgrounds (%g outside, %g inside) must be >= 0 and finite", (double)fopts->background_outside,
+                (double)fopts->background_inside);
+  if (n_cells && (!cells || !distances)) return fail(M2S_ERR_BAD_ARG, "cells / distances is NULL with n_cells > 0");
+  int rc = band_opts_args(opts, "m2s_band_create");
+  if (rc) return rc;
+  GridQuery q;
+  int mode = 0;
+  rc = grid_query_args(grid, nullptr, false, nullptr, &q, &mode);   // what m2s_sample_grid rejects of a grid
+  if (rc) return rc;
+  const uint64_t nx = grid->cell_count[0], ny = grid->cell_count[1], nz = grid->cell_count[2];
+  const uint64_t nyz = ny * nz;
+  if (nyz / ny != nz) return fail(M2S_ERR_BAD_ARG, "the grid has 2^36 or more cells");
+  const uint64_t total = nyz * nx;
+  if (total / nx != nyz || total >= ((uint64_t)1 << 36)) return fail(M2S_ERR_BAD_ARG, "the grid has 2^36 or more cells");
+  if (n_cells > total) return fail(M2S_ERR_BAD_ARG, "n_cells = %llu above the grid's %llu cells", (unsigned long long)n_cells, (unsigned long long)total);
+  const bool host = !opts || opts->mem_kind == M2S_MEM_HOST;
+  if (host) {   // host memory: the list and its values are judged here, before any device work
+    for (uint64_t a = 0; a < n_cells; ++a)
+      if (cells[a] >= total || (a && cells[a - 1] >= cells[a]))
+        return fail(M2S_ERR_BAD_ARG, "cells[%llu] = %llu is not above its predecessor or not below the grid's %llu cells", (unsigned long long)a,
+                    (unsigned long long)cells[a], (unsigned long long)total);
+    for (uint64_t a = 0; a < n_cells; ++a)
+      if (!std::isfinite(distances[a])) return fail(M2S_ERR_NAN, "distances[%llu] is NaN or infinite", (unsigned long long)a);
+  }
+  CallCtx c;
+  DeviceState* st = nullptr;
+  rc = resolve_ctx(opts, &c, &st);
+  if (rc) return rc;
+  const uint64_t n = n_cells, n_words = (total + 63) / 64;
+  const uint64_t sign_words = (nz + 31) / 32 * nx * ny;
+  // the handle's block: mask, word_off, [inside], dist (at least one float: a lane's guarded read needs an address)
+  const size_t b_mask = align_up(n_words * 8), b_sign = inside_bits ? align_up(n_words * 8) : 0, b_dist = align_up((n ? n : 1) * 4);
+  char* block = nullptr;
+  M2S_HIP_CHECK(hipMalloc((void**)&block, 2 * b_mask + b_sign + b_dist));
+  auto drop = [&](int code) { (void)hipFree(block); return code; };
+  uint64_t* mask = reinterpret_cast<uint64_t*>(block);
+  uint64_t* word_off = reinterpret_cast<uint64_t*>(block + b_mask);
+  uint64_t* inside = inside_bits ? reinterpret_cast<uint64_t*>(block + 2 * b_mask) : nullptr;
+  float* dist = reinterpret_cast<float*>(block + 2 * b_mask + b_sign);
+  // the workspace: the flag and, for host memory, the staged list and sign mask
+  size_t need = 4096 + 256;
+  if (host) need += align_up(n * 8) + (inside_bits ? align_up(sign_words * 4) : 0);
+  rc = ensure_capacity(*st, need);
+  if (rc) return drop(rc);
+  Arena ws{st->base, st->cap, 0};
+  uint32_t* d_flag = reinterpret_cast<uint32_t*>(ws.take<uint64_t>(4));
+  if (!d_flag) return drop(fail(M2S_ERR_HIP, "internal: workspace"));
+  const uint64_t* dc = cells;
+  const uint32_t* db = inside_bits;
+  if (host) {
+    if (n) {
+      char* sc = ws.take<char>(n * 8);
+      if (!sc) return drop(fail(M2S_ERR_HIP, "internal: workspace"));
+      if ((rc = staged_h2d(*st, c.stream, sc, reinterpret_cast<const char*>(cells), n * 8))) return drop(rc);
+      if ((rc = staged_h2d(*st, c.stream, reinterpret_cast<char*>(dist), reinterpret_cast<const char*>(distances), n * 4))) return drop(rc);
+      dc = reinterpret_cast<const uint64_t*>(sc);
+    }
+    if (inside_bits) {
+      char* sb = ws.take<char>(sign_words * 4);
+      if (!sb) return drop(fail(M2S_ERR_HIP, "internal: workspace"));
+      if ((rc = staged_h2d(*st, c.stream, sb, reinterpret_cast<const char*>(inside_bits), sign_words * 4))) return drop(rc);
+      db = reinterpret_cast<const uint32_t*>(sb);
+    }
+  } else if (n) {
+    if (hipMemcpyAsync(dist, distances, n * 4, hipMemcpyDeviceToDevice, c.stream) != hipSuccess) return drop(fail(M2S_ERR_HIP, "hipMemcpyAsync failed"));
+  }
+  hipError_t e = hipSuccess;
+  if (c.timings) e = hipEventRecord(st->ev[0], c.stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 32, c.stream);
+  if (e == hipSuccess) e = hipMemsetAsync(mask, 0, b_mask * 2, c.stream);   // the mask and every word's offset
+  if (e == hipSuccess && n == 0) e = hipMemsetAsync(dist, 0, 4, c.stream);
+  if (e != hipSuccess) return drop(fail(M2S_ERR_HIP, "HIP error: %s", hipGetErrorString(e)));
+  if (n)
+    hipLaunchKernelGGL(k_biso_mask, dim3((unsigned)((n + kMaskThreads - 1) / kMaskThreads)), dim3(kMaskThreads), 0, c.stream, total, dc,
+                       (const float*)dist, n, mask, word_off, d_flag);
+  if (inside_bits)
+    hipLaunchKernelGGL(k_bq_sign, dim3(blocks_for(n_words)), dim3(256), 0, c.stream, total, nz, n_words, db, inside);
+  e = hipGetLastError();
+  if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[1], c.stream);
+  uint32_t raised[2] = {0, 0};
+  if (e == hipSuccess) e = hipMemcpyAsync(raised, d_flag, 8, hipMemcpyDeviceToHost, c.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+  if (e != hipSuccess) return drop(fail(M2S_ERR_HIP, "HIP error: %s", hipGetErrorString(e)));
+  if (raised[0] & kFlagOrder) return drop(fail(M2S_ERR_BAD_ARG, "cells is not strictly ascending or holds an entry at or above the grid's cell count"));
+  if (raised[0] & kFlagNonFinite) return drop(fail(M2S_ERR_NAN, "the band holds a NaN or infinite distance"));
+  if (c.timings) {
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, st->ev[0], st->ev[1]);
+    memset(c.timings, 0, sizeof(*c.timings));
+    c.timings->seed_ms = ms;
+    c.timings->total_ms = ms;
+    c.timings->n_units = n_cells;
+  }
+  m2s_band* h = new m2s_band();
+  h->device = c.device;
+  h->grid = *grid;
+  h->n = n;
+  h->total = total;
+  h->n_words = n_words;
+  h->device_bytes = n_words * 16 + n * 4 + (inside_bits ? n_words * 8 : 0);
+  h->block = block;
+  h->mask = mask;
+  h->word_off = word_off;
+  h->inside = inside;
+  h->dist = dist;
+  h->bg_out = fopts->background_outside;
+  h->bg_in = fopts->background_inside;
+  *out = h;
+  return M2S_OK;
+}
+
+void m2s_band_destroy(m2s_band* band) {
+  if (!band) return;
+  if (band->block) {
+    int cur = -1;
+    const bool have = hipGetDevice(&cur) == hipSuccess;
+    if (hipSetDevice(band->device) == hipSuccess) {
+      (void)hipDeviceSynchronize();   // queries still in flight read the block
+      (void)hipFree(band->block);
+    }
+    if (have) (void)hipSetDevice(cur);
+  }
+  delete band;
+}
+
+int m2s_band_info(const m2s_band* band, m2s_grid* grid, uint64_t* n_cells, uint64_t* device_bytes) {
+  clear_error();
+  if (!band) return fail(M2S_ERR_BAD_ARG, "band is NULL");
+  if (grid) *grid = band->grid;
+  if (n_cells) *n_cells = band->n;
+  if (device_bytes) *device_bytes = band->device_bytes;
+  return M2S_OK;
+}
+
+int m2s_band_sample(const m2s_band* band, const float* points, size_t n_points, const m2s_sample_opts* sopts, float* value_out,
+                    float* normal_out, uint8_t* support_out, const m2s_opts* opts) {
+  clear_error();
+  if (!band) return fail(M2S_ERR_BAD_ARG, "band is NULL");
+  GridQuery q;
+  int mode = 0;
+  int rc = grid_query_args(&band->grid, sopts, false, opts, &q, &mode);
+  if (rc) return rc;
+  if (!value_out && !normal_out) return fail(M2S_ERR_BAD_ARG, "no output requested (support_out alone is none)");
+  if (n_points && !points) return fail(M2S_ERR_BAD_ARG, "points is NULL");
+  m2s_opts o;
+  rc = band_call_opts(band, opts, &o);
+  if (rc) return rc;
+  if (n_points == 0) {
+    if (opts && opts->timings) memset(opts->timings, 0, sizeof(*opts->timings));
+    return M2S_OK;
+  }
+  const BandDev b = dev_of(band);
+  QueryIo io[4] = {{points, n_points * 12, false}, {value_out, value_out ? n_points * 4 : 0, true}, {normal_out, normal_out ? n_points * 12 : 0, true},
+                   {support_out, support_out ? n_points : 0, true}};
+  return run_query(&o, io, 4, n_points, [&](hipStream_t s) {
+    return launch_band_sample(s, q, mode, b, reinterpret_cast<const float*>(io[0].dev), n_points, value_out ? reinterpret_cast<float*>(io[1].dev) : nullptr,
+                              normal_out ? reinterpret_cast<float*>(io[2].dev) : nullptr, support_out ? reinterpret_cast<uint8_t*>(io[3].dev) : nullptr);
+  });
+}
+
+int m2s_band_raymarch(const m2s_band* band, const float* origins, const float* directions, size_t n_rays, const m2s_sample_opts* sopts,
+                      float* hit_out, uint32_t* steps_out, float* normal_out, uint8_t* support_out, const m2s_opts* opts) {
+  clear_error();
+  if (!band) return fail(M2S_ERR_BAD_ARG, "band is NULL");
+  GridQuery q;
+  int mode = 0;
+  int rc = grid_query_args(&band->grid, sopts, true, opts, &q, &mode);
+  if (rc) return rc;
+  if (!hit_out && !steps_out && !normal_out) return fail(M2S_ERR_BAD_ARG, "no output requested (support_out alone is none)");
+  if (n_rays && (!origins || !directions)) return fail(M2S_ERR_BAD_ARG, "origins / directions is NULL");
+  m2s_opts o;
+  rc = band_call_opts(band, opts, &o);
+  if (rc) return rc;
+  if (n_rays == 0) {
+    if (opts && opts->timings) memset(opts->timings, 0, sizeof(*opts->timings));
+    return M2S_OK;
+  }
+  const BandDev b = dev_of(band);
+  QueryIo io[6] = {{origins, n_rays * 12, false}, {directions, n_rays * 12, false}, {hit_out, hit_out ? n_rays * 16 : 0, true},
+                   {steps_out, steps_out ? n_rays * 4 : 0, true}, {normal_out, normal_out ? n_rays * 12 : 0, true},
+                   {support_out, support_out ? n_rays : 0, true}};
+  return run_query(&o, io, 6, n_rays, [&](hipStream_t s) {
+    return launch_band_raymarch(s, q, mode, b, reinterpret_cast<const float*>(io[0].dev), reinterpret_cast<const float*>(io[1].dev), n_rays,
+                                hit_out ? reinterpret_cast<float*>(io[2].dev) : nullptr, steps_out ? reinterpret_cast<uint32_t*>(io[3].dev) : nullptr,
+                                normal_out ? reinterpret_cast<float*>(io[4].dev) : nullptr, support_out ? reinterpret_cast<uint8_t*>(io[5].dev) : nullptr);
+  });
+}
+
+}  // extern "C"

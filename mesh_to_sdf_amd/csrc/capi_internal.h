@@ -2,6 +2,7 @@
 // (capi.hip: distance path; capi_io.hip: container encode/decode, cell ordering, instance merge).
 #pragma once
 #include <cstdio>
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -85,5 +86,18 @@ int staged_h2d(DeviceState& st, hipStream_t stream, char* d_dst, const char* h_s
 int staged_d2h(DeviceState& st, hipStream_t stream, char* h_dst, const char* d_src, size_t bytes);
 int staged_d2h_to_file(DeviceState& st, hipStream_t stream, FILE* f, const char* d_src, size_t bytes);   // M2S_ERR_IO on a short write
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+
+// Grid queries (capi_io.hip), shared with the band queries (band_query.hip).
+// grid_query_args: the grid, the sample options and the m2s_opts fields a grid query does not take, into `q` and `mode`; everything
+// include/m2s.h lists as M2S_ERR_BAD_ARG for them that needs no device.  `grid` is not NULL.
+int grid_query_args(const m2s_grid* grid, const m2s_sample_opts* so, bool ray, const m2s_opts* opts, GridQuery* q, int* mode);
+// run_query runs `launch(stream)` with every io[i].dev on the device: host data is staged through the workspace, outputs copied back.
+struct QueryIo {
+  const void* src;      // caller's pointer
+  size_t bytes;
+  bool output;
+  char* dev = nullptr;  // what the kernel sees
+};
+int run_query(const m2s_opts* opts, QueryIo* io, int n_io, uint64_t n_units, const std::function<int(hipStream_t)>& launch);
 
 }  // namespace m2s

@@ -313,6 +313,13 @@ int save_impl(const char* path, const Layout& L, const float* queries, uint64_t 
 int query_args(const m2s_grid* grid, const float* distances, const m2s_sample_opts* so, bool ray, const m2s_opts* opts, GridQuery* q,
                int* mode) {
   if (!grid || !distances) return fail(M2S_ERR_BAD_ARG, "grid / distances is NULL");
+  return grid_query_args(grid, so, ray, opts, q, mode);
+}
+
+}  // namespace
+
+// The same without the distances: the band queries (band_query.hip) take theirs from a handle.  `grid` is not NULL.
+int grid_query_args(const m2s_grid* grid, const m2s_sample_opts* so, bool ray, const m2s_opts* opts, GridQuery* q, int* mode) {
   if (opts) {
     if (opts->algorithm != 0 || opts->x_begin != 0 || opts->x_end != 0)
       return fail(M2S_ERR_BAD_ARG, "m2s_opts.algorithm / x_begin / x_end must be 0 for grid queries");
@@ -350,16 +357,6 @@ int query_args(const m2s_grid* grid, const float* distances, const m2s_sample_op
   }
   return 0;
 }
-
-uint64_t grid_cells(const m2s_grid* g) { return g->cell_count[0] * g->cell_count[1] * g->cell_count[2]; }
-
-// Runs `launch(d_grid, d_in0, d_in1, d_out...)` with every pointer on the device: host data is staged through the workspace.
-struct QueryIo {
-  const float* src;     // caller's pointer
-  size_t bytes;
-  bool output;
-  char* dev = nullptr;  // what the kernel sees
-};
 
 int run_query(const m2s_opts* opts, QueryIo* io, int n_io, uint64_t n_units, const std::function<int(hipStream_t)>& launch) {
   CallCtx c;
@@ -406,6 +403,8 @@ int run_query(const m2s_opts* opts, QueryIo* io, int n_io, uint64_t n_units, con
   return M2S_OK;
 }
 
+namespace {
+uint64_t grid_cells(const m2s_grid* g) { return g->cell_count[0] * g->cell_count[1] * g->cell_count[2]; }
 }  // namespace
 }  // namespace m2s
 

@@ -52,6 +52,7 @@ const Entry TABLE[] = {
     M2S_KNOB("M2S_DEFER", K_INT, defer),
     M2S_KNOB("M2S_GATHER_AHEAD", K_INT, gather_ahead),
     M2S_KNOB("M2S_BAND_CHUNK", K_U32, band_chunk),
+    M2S_KNOB("M2S_BAND_FETCH", K_INT, band_fetch),
     M2S_KNOB("M2S_HOST_PIECE_MB", K_U32, host_piece_mb),
     M2S_KNOB("M2S_PUSH_PIECES", K_U32, push_pieces),
     M2S_KNOB("M2S_PUSH_BLOCKS", K_U32, push_blocks),
@@ -89,6 +90,8 @@ void sanitise(Tuning& t) {
   if (t.band_chunk > (1u << 30)) t.band_chunk = 1u << 30;
   if (t.gather_ahead > 1) t.gather_ahead = 1;     // -1, 0, 1 and nothing else
   if (t.gather_ahead < -1) t.gather_ahead = -1;
+  if (t.band_fetch > 2) t.band_fetch = 2;
+  if (t.band_fetch < -1) t.band_fetch = -1;
   if (t.leaf_max > 16) t.leaf_max = 16;   // the tree's limit (bvh.hip): a larger wish would differ from every resident tree's size for ever
 }
 

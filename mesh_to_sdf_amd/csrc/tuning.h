@@ -48,6 +48,8 @@ struct Tuning {
   int gather_ahead = -1;            // M2S_GATHER_AHEAD the DEFER 3 walk's pre-test gathers: 0 issued where they are used, 1 issued a leaf ahead of their use (k_packet's GA form; the split walk, the packet groups and the other DEFER forms have none), -1 automatic: ahead for the grid walk of the unsigned distance and the queries' walk with the three-ray sign, where it is measured to win; other values are clamped to -1 .. 1
   // ---- narrow bands (band.hip)
   uint32_t band_chunk = 1u << 24;   // M2S_BAND_CHUNK      candidates per pass of the query walk in a narrow-band call (1 .. 2^30); every chunk pays the query path's sort and seed passes again (DESIGN.md section 4.13 has the sweep), and the workspace grows by about 100 bytes per candidate of a chunk
+  // ---- band queries (band_query.hip)
+  int band_fetch = -1;              // M2S_BAND_FETCH      how a band sample reads its cells: 0 three rounds of independent loads (mask words, list offsets, values) with a normal's six samples in groups of 24 corners, 2 the same in groups of 16 / 12 corners, 1 corner after corner, -1 automatic: 0 in m2s_band_sample, 2 in m2s_band_raymarch, where each is measured to win (the same bits in every form); other values are clamped to -1 .. 2
   // ---- host-pointer calls and peer delivery (capi.hip, multi.hip, peer_push.hip)
   uint32_t host_piece_mb = 32;      // M2S_HOST_PIECE_MB   x-pieces of the result streamed to the host while the next is walked
   uint32_t push_pieces = 4;         // M2S_PUSH_PIECES     x-pieces of a slab pushed to the peers while the next is walked
