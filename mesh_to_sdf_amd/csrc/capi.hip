@@ -431,6 +431,7 @@ int run_grid_distance_push(Arena& ws, const CallCtx& c, DeviceState& st, const D
     gp.xe = gp.xb + (uint32_t)std::min<uint64_t>(lpp, layers - i * lpp);
     gp.chunk_log = 31;
     gp.period = 0;
+    set_super_brick_magic(gp);                                       // the piece's own per-call constants (its super-bricks may be narrower)
     rc = launch_grid_walk(c.stream, mesh, gp, mode, plane, plan, (uint32_t)((i * lpp) >> g.bl[0]), d_out, d_err);
     if (rc) return rc;
     if (i + 1 == pieces) M2S_HIP_CHECK(hipEventRecord(st.ev[3], c.stream));
@@ -656,6 +657,7 @@ int run_grid_distance_to_host(Arena& ws, const CallCtx& c, DeviceState& st, cons
     GridParams gp = g;
     gp.xb = g.xb + (uint32_t)(i * lpp);
     gp.xe = (uint32_t)std::min<uint64_t>(g.xe, gp.xb + lpp);
+    set_super_brick_magic(gp);
     rc = launch_grid_walk(c.stream, mesh, gp, mode, plane, plan, (uint32_t)((i * lpp) >> g.bl[0]), d_slab, d_err);
     if (rc) { cleanup(); return rc; }
     if (hipEventRecord(done[i], c.stream) != hipSuccess) { cleanup(); return fail(M2S_ERR_HIP, "hipEventRecord failed"); }
@@ -3071,6 +3073,29 @@ int m2s_debug_cut_code(uint32_t n_nodes, uint32_t start, uint32_t len, uint32_t 
   g_err[0] = 0;
   if (!out || n_nodes == 0 || n_nodes > (1u << 26) || len == 0 || start >= n_nodes || len > n_nodes - start) return fail(M2S_ERR_BAD_ARG, "bad range");
   cut_word_roundtrip(n_nodes, start, len, &out[0], &out[1], &out[2]);
+  return M2S_OK;
+}
+
+// Test hook (not part of include/m2s.h): the per-call constants the host resolves for the walks' kernels — for the slab `opts` names of
+// `grid` (as every grid call fills its GridParams: fill_grid_params), with super-bricks capped as a trailing push caps them (xl_cap, 0: no
+// cap), and for a tree of n_nodes records.  out = {sb_xl, nby, nbz, sy, sz, sz_magic, sy_magic, start bits of the list words, bl[0], bl[1],
+// bl[2], bricks along x of the slab}.  Host arithmetic only; tests/test_walk_consts_cpu.py restates the rules.
+int m2s_debug_walk_consts(const m2s_grid* grid, const m2s_opts* opts, uint32_t xl_cap, uint32_t n_nodes, uint32_t out[12]) {
+  g_err[0] = 0;
+  if (!grid || !out) return fail(M2S_ERR_BAD_ARG, "NULL argument");
+  if (xl_cap > 4u) return fail(M2S_ERR_BAD_ARG, "xl_cap = %u (0 .. 4)", xl_cap);
+  GridParams g;
+  size_t slab_cells = 0;
+  const int rc = fill_grid_params(grid, opts, &g, &slab_cells);
+  if (rc) return rc;
+  if (xl_cap != 0u) {          // as run_grid_distance_trail does
+    g.xl_cap = xl_cap;
+    set_super_brick_magic(g);
+  }
+  if (!grid_consts_set(g)) return fail(M2S_ERR_HIP, "internal: the grid's per-call constants are not resolved");
+  const uint32_t v[12] = {g.sb_xl, g.nby, g.nbz, g.sy, g.sz, g.sz_magic, g.sy_magic, cut_list_start_bits(n_nodes), g.bl[0], g.bl[1], g.bl[2],
+                          bricks_along(g.xe - g.xb, g.bl[0])};
+  memcpy(out, v, sizeof(v));
   return M2S_OK;
 }
 

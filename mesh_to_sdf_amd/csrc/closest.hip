@@ -127,6 +127,7 @@ int launch_closest_grid(hipStream_t st, const DeviceMesh& mesh, const GridParams
                         const ClosestOut& out) {
   const uint32_t packets = host_packet_bricks(g);
   if (packets == 0) return 0;
+  M2S_REQUIRE_GRID_CONSTS(g);
   if (algorithm == 1) hipLaunchKernelGGL(k_closest_grid<true>, dim3(packets), dim3(64), 0, st, mesh, g, d_dist, dist_off, out);
   else hipLaunchKernelGGL(k_closest_grid<false>, dim3(packets), dim3(64), 0, st, mesh, g, d_dist, dist_off, out);
   M2S_HIP_CHECK(hipGetLastError());

@@ -113,29 +113,65 @@ struct GridParams {
   // index by them: one multiply-high instead of a 30-instruction u32 division per wave); 0 = divide (d == 1, or a grid so
   // large that the product could be off by one)
   uint32_t sz_magic, sy_magic;
-  uint32_t xl_cap;   // 0: super-bricks up to 8 bricks wide in x (walk.hip.h super_brick_xlog); k: at most 2^(k-1) bricks wide, so
+  uint32_t xl_cap;   // 0: super-bricks up to 8 bricks wide in x (super_brick_xlog below); k: at most 2^(k-1) bricks wide, so
                      // that the x-layers of a slab are finished in order at that granularity (M2S_PEER_TRAIL)
   // Interleaved slab (m2s_opts.x_period): the call owns the chunks [xb + j * period, xb + j * period + 2^chunk_log), j = 0, 1, ...
   // [xb, xe) then is the VIRTUAL slab — the chunks laid end to end — which is what bricks, seeds and cut lists are numbered
   // by; slab_x() turns a virtual layer into the grid's x.  chunk_log = 31: one contiguous slab (slab_x(v) = xb + v).
   uint32_t chunk_log, period;
+  // What brick_coords (walk.hip.h) needs of the above, resolved ONCE per call on the host (set_super_brick_magic) instead of by every
+  // packet: sb_xl = super_brick_xlog of the slab's bricks along x under xl_cap, nby / nbz = packet bricks along y / z, sy / sz =
+  // super-bricks along y / z.  They follow from n, bl, xb, xe and xl_cap: whoever changes one of those resolves them again, and
+  // every launcher of a kernel that decodes bricks checks them first (grid_consts_set).
+  uint32_t sb_xl, nby, nbz, sy, sz;
 };
 // Grid x of virtual layer `v` (0-based) of the slab.
 __host__ __device__ __forceinline__ uint32_t slab_x(const GridParams& g, uint32_t v) {
   return g.xb + (v >> g.chunk_log) * g.period + (v & ((1u << g.chunk_log) - 1u));
 }
 
-// Brick shape for a cell size: minimises max/min of the world extents |size[k]| * 2^bl[k] over all splits of 6.
+// Bricks are walked in 8x8x8 super-bricks (walk.hip.h brick_coords).  A thin x-slab (multi-GPU pieces are 16 layers = 4 bricks at
+// 8 GPUs x 4 chunks) uses super-bricks that are 4, 2 or 1 bricks wide in x instead, so that at most 1/8 of the launched packets
+// are padding.  The rule's single definition: the host resolves it once per call (GridParams::sb_xl), no kernel runs the loop.
+__host__ __device__ __forceinline__ uint32_t bricks_along(uint32_t cells, uint32_t log2_extent) {
+  return (cells + (1u << log2_extent) - 1u) >> log2_extent;
+}
+__host__ __device__ __forceinline__ uint32_t super_brick_xlog(uint32_t nbx, uint32_t xl_cap = 0) {
+  for (uint32_t xl = xl_cap ? xl_cap - 1u : 3u; xl > 0; --xl) {
+    const uint32_t padded = ((nbx + (1u << xl) - 1u) >> xl) << xl;
+    if ((padded - nbx) * 8u <= nbx) return xl;
+  }
+  return 0;
+}
+// The slab's per-call constants (GridParams::sb_xl ... sz) as the rules give them; grid_consts_set: g carries exactly these.
+struct GridConsts { uint32_t sb_xl, nby, nbz, sy, sz; };
+inline GridConsts resolve_grid_consts(const GridParams& g) {
+  GridConsts c;
+  c.nby = bricks_along(g.n[1], g.bl[1]);
+  c.nbz = bricks_along(g.n[2], g.bl[2]);
+  c.sy = (c.nby + 7) >> 3;
+  c.sz = (c.nbz + 7) >> 3;
+  c.sb_xl = super_brick_xlog(bricks_along(g.xe - g.xb, g.bl[0]), g.xl_cap);
+  return c;
+}
+inline bool grid_consts_set(const GridParams& g) {
+  const GridConsts c = resolve_grid_consts(g);
+  return g.sb_xl == c.sb_xl && g.nby == c.nby && g.nbz == c.nbz && g.sy == c.sy && g.sz == c.sz;
+}
+// Everything of g that is derived from its grid, slab and xl_cap: the per-call constants above and the two division magics.
 // Exact for n * d < 2^32 (Granlund-Montgomery with a 32-bit multiplier): q = mulhi(n, ceil(2^32 / d)).
 inline void set_super_brick_magic(GridParams& g) {
-  const uint64_t nbx = (g.n[0] + (1u << g.bl[0]) - 1u) >> g.bl[0], nby = (g.n[1] + (1u << g.bl[1]) - 1u) >> g.bl[1],
-                 nbz = (g.n[2] + (1u << g.bl[2]) - 1u) >> g.bl[2];
-  const uint64_t sy = (nby + 7) >> 3, sz = (nbz + 7) >> 3, n_max = (nbx + 1) * sy * sz;   // super-brick indices stay below this
+  const GridConsts c = resolve_grid_consts(g);
+  g.sb_xl = c.sb_xl; g.nby = c.nby; g.nbz = c.nbz; g.sy = c.sy; g.sz = c.sz;
+  const uint64_t nbx = (g.n[0] + (1u << g.bl[0]) - 1u) >> g.bl[0];
+  const uint64_t sy = c.sy, sz = c.sz, n_max = (nbx + 1) * sy * sz;   // super-brick indices stay below this
   const uint64_t d_max = sy > sz ? sy : sz;
   const bool safe = n_max * d_max < (1ull << 32);
   g.sz_magic = (safe && sz > 1) ? (uint32_t)(((1ull << 32) + sz - 1) / sz) : 0u;
   g.sy_magic = (safe && sy > 1) ? (uint32_t)(((1ull << 32) + sy - 1) / sy) : 0u;
 }
+
+// Brick shape for a cell size: minimises max/min of the world extents |size[k]| * 2^bl[k] over all splits of 6.
 
 inline void choose_brick_shape(const float size[3], uint32_t bl[3]) {
   bl[0] = bl[1] = bl[2] = 2;
@@ -198,6 +234,15 @@ enum : int {
 
 constexpr int M2S_ERR_HIP_INTERNAL = -4;
 void set_error(const char* fmt, ...);
+// In front of every launch of a kernel that decodes bricks (brick_coords): the grid's per-call constants are the resolved ones.  A
+// GridParams whose slab was changed without set_super_brick_magic would decode other bricks than the launch covers, silently.
+#define M2S_REQUIRE_GRID_CONSTS(g)                                            \
+  do {                                                                        \
+    if (!::m2s::grid_consts_set(g)) {                                         \
+      ::m2s::set_error("internal: the grid's per-call constants are not resolved (%s:%d)", __FILE__, __LINE__); \
+      return M2S_ERR_HIP_INTERNAL;                                            \
+    }                                                                         \
+  } while (0)
 
 // Bump allocator over one device block per device (kept between calls; see capi.hip).
 struct Arena {
@@ -359,6 +404,7 @@ int launch_grid_distance(Arena& ws, hipStream_t st, const DeviceMesh& mesh, cons
                          const SeedLattice* raw_seeds = nullptr, hipEvent_t wait_raw_seeds = nullptr,
                          const PeerOut* peers = nullptr);
 void cut_word_roundtrip(uint32_t n_nodes, uint32_t start, uint32_t len, uint32_t* word, uint32_t* first, uint32_t* end);   // cut.hip: test hook
+uint32_t cut_list_start_bits(uint32_t n_nodes);   // cut.hip: test hook — the start bits a walk over a tree of n_nodes records is handed (CutList)
 size_t query_workspace_bytes(size_t n_q);   // query_order.hip
 // brute.hip
 bool query_is_tiny(size_t n_q, size_t n_tris, int algorithm, int sign_src);   // small query sets: all queries x all triangles, no tree

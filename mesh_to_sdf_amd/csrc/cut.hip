@@ -54,7 +54,7 @@ __global__ __launch_bounds__(64) void k_cut(DeviceMesh mesh, GridParams g, const
                                             uint32_t seed_ny, uint32_t seed_nz, uint32_t nbx, uint32_t nby, uint32_t nbz,
                                             uint32_t* __restrict__ lists, float emit_near, float emit_far, uint32_t budget, uint32_t wave_cap,
                                             const float4* __restrict__ centres, const uint32_t* __restrict__ table,
-                                            const GridParams* __restrict__ seed_lattice, const uint32_t* __restrict__ coarse = nullptr) {
+                                            const GridParams* __restrict__ seed_lattice, uint32_t start_bits, const uint32_t* __restrict__ coarse = nullptr) {
   static_assert(GRID || LEVEL == 0, "the two-level form is the grid's");
   // LEVEL 1: the "bricks" of this launch are blocks of 4 x 4 x 4 packet bricks (nbx, nby, nbz count blocks), eight waves per 4 x 4 x 4 of them
   constexpr uint32_t UL = LEVEL == 1 ? 2u : 0u;               // log2 packet bricks per lane unit and axis
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(64) void k_cut(DeviceMesh mesh, GridParams g, const
   const uint32_t tree_end = mesh.n_nodes * NB;
   uint32_t* out = lists + ((size_t)(in_grid ? (GRID ? (bk[0] * nby + bk[1]) * nbz + bk[2] : pk) : 0u)) * (LEVEL == 1 ? CUTC_S * CUTC_WORDS : OUT_WORDS)
                   + sub * CUTC_WORDS;
-  const uint32_t cut_S = cut_start_bits(mesh.n_nodes);
+  const uint32_t cut_S = start_bits;   // cut_start_bits(mesh.n_nodes), resolved by the launch
   auto cut_word = [cut_S](uint32_t start, uint32_t stop) {   // byte offsets -> list word (see CUT_WORDS)
     return (start / NB_CUT) | (cut_encode_len((stop - start) / NB_CUT, 27u - cut_S) << cut_S);
   };
@@ -280,16 +280,17 @@ void launch_grid_cut(hipStream_t st, const DeviceMesh& mesh, const GridParams& g
   const uint32_t nbx = bc.nb[0], nby = bc.nb[1], nbz = bc.nb[2];
   const uint32_t cbx = bricks_along(nbx, 2), cby = bricks_along(nby, 2), cbz = bricks_along(nbz, 2);   // blocks of 4 x 4 x 4 bricks = fine waves
   const size_t waves = cut_blocks(g, 2);
+  const uint32_t S = cut_start_bits(mesh.n_nodes);   // the list words' start field: once per call, for k_cut and (CutList) the walk
   if (coarse != nullptr) {
     const size_t groups = cut_blocks(g, 4);   // 4 x 4 x 4 blocks
     const uint32_t coarse_cap = tn.cut_coarse_cap ? tn.cut_coarse_cap : cp.wave_cap;
     hipLaunchKernelGGL((k_cut<true, 1>), dim3((unsigned)(groups * CUTC_S)), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, cbx, cby, cbz, coarse, 1.0f, cp.emit_far, cp.budget,
-                       coarse_cap, (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, (const uint32_t*)nullptr);
+                       coarse_cap, (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, S, (const uint32_t*)nullptr);
     hipLaunchKernelGGL((k_cut<true, 2>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap,
-                       (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, (const uint32_t*)coarse);
+                       (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, S, (const uint32_t*)coarse);
   } else
   hipLaunchKernelGGL((k_cut<true, 0>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap,
-                     (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, (const uint32_t*)nullptr);
+                     (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, S, (const uint32_t*)nullptr);
 }
 
 // k_cut<false> for the packets of a query set: one list per packet of the `launched` the walk will be launched with.
@@ -298,7 +299,7 @@ void launch_query_cut(hipStream_t st, const DeviceMesh& mesh, const uint32_t* se
   GridParams g{};
   const CutParams cp = cut_params(mesh.n_tris, tuning());
   hipLaunchKernelGGL((k_cut<false, 0>), dim3((launched + 63) / 64), dim3(64), 0, st, mesh, g, seeds, 0u, 0u, 0u, launched, 1u, 1u, lists,
-                     cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap, centres, table, d_lat);
+                     cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap, centres, table, d_lat, cut_start_bits(mesh.n_nodes));
 }
 
 // Test hook (capi.hip m2s_debug_cut_code): the list word k_cut writes for the range [start, start + len) of a tree of n_nodes records,
@@ -312,6 +313,9 @@ void cut_word_roundtrip(uint32_t n_nodes, uint32_t start, uint32_t len, uint32_t
   *first = f;
   *end = std::min(f + l, n_nodes);
 }
+
+// Test hook (capi.hip m2s_debug_walk_consts): the start bits the host resolves for a tree of n_nodes records, as every launch gets them.
+uint32_t cut_list_start_bits(uint32_t n_nodes) { return cut_list_for(n_nodes, nullptr, 0, 0, 0, 0, nullptr).start_bits; }
 
 // m2s_warmup: this unit's code object, and the kernel functions of it that a first call uses (see warm_distance).
 __global__ void k_warm_cut() {}

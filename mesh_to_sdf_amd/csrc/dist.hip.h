@@ -56,7 +56,12 @@ struct CutList {
   uint32_t bx_off;         // grid: this launch covers a piece of the slab the seed lattice and the lists were built for,
                            // starting bx_off bricks into it along x (a multiple of 2^log)
   const float4* centres;   // generic queries: (centre, radius) of every packet's bounding box (k_qpacket_bounds); one list per packet
+  uint32_t start_bits;     // S of the list words: cut_start_bits of the tree's node count, resolved once on the host (cut_list_for); 0: not set
 };
+// The lists of a tree of n_nodes records: the ONE place that fills a CutList (no lists: `lists` null, nothing is decoded).
+inline CutList cut_list_for(uint32_t n_nodes, const uint32_t* lists, uint32_t log, uint32_t ny, uint32_t nz, uint32_t bx_off, const float4* centres) {
+  return {lists, log, ny, nz, bx_off, centres, cut_start_bits(n_nodes)};
+}
 // The coarse level of two-level lists (cut.hip k_cut, LEVEL 1): CUTC_S sub-lists of at most CUTC_MAX ranges per block of 4 x 4 x 4 bricks.
 constexpr uint32_t CUTC_S_LOG = 3, CUTC_S = 1u << CUTC_S_LOG, CUTC_WORDS = 8, CUTC_MAX = CUTC_WORDS - 1;   // 64 words = 256 B per block
 static_assert(CUTC_S * CUTC_WORDS == 64, "a fine wave fetches its block's coarse record with one load, lane = word");
@@ -79,15 +84,21 @@ __device__ __forceinline__ bool query_packet_range(const uint32_t* __restrict__ 
   return true;
 }
 // Cell of the generic path's seed lattice that holds x (k_qlattice).
+__device__ __forceinline__ uint32_t query_lattice_coord(const GridParams& L, int k, float q) {
+  float f = (q - L.first[k]) / L.size[k] + 0.5f;
+  f = (f == f) ? fminf(fmaxf(f, 0.0f), (float)(L.n[k] - 1)) : 0.0f;
+  return min((uint32_t)f, L.n[k] - 1);
+}
 __device__ __forceinline__ uint32_t query_lattice_cell(const GridParams& L, float x, float y, float z) {
-  const float q0[3] = {x, y, z};
-  uint32_t cell[3];
-  for (int k = 0; k < 3; ++k) {
-    float f = (q0[k] - L.first[k]) / L.size[k] + 0.5f;
-    f = (f == f) ? fminf(fmaxf(f, 0.0f), (float)(L.n[k] - 1)) : 0.0f;
-    cell[k] = min((uint32_t)f, L.n[k] - 1);
-  }
-  return (cell[0] * L.n[1] + cell[1]) * L.n[2] + cell[2];
+  return (query_lattice_coord(L, 0, x) * L.n[1] + query_lattice_coord(L, 1, y)) * L.n[2] + query_lattice_coord(L, 2, z);
+}
+// The same cell for a point that is the same in every lane, its index formed on the scalar unit.  (Formed on the vector unit the
+// multiply-adds are 64-bit ones whose unused upper half the compiler pairs with any register at hand — in k_packet the one the list
+// word is being loaded into, which put the wait for that load in front of the seed's loads.)
+__device__ __forceinline__ uint32_t query_lattice_cell_uniform(const GridParams& L, float x, float y, float z) {
+  const uint32_t cx = __builtin_amdgcn_readfirstlane(query_lattice_coord(L, 0, x)), cy = __builtin_amdgcn_readfirstlane(query_lattice_coord(L, 1, y)),
+                 cz = __builtin_amdgcn_readfirstlane(query_lattice_coord(L, 2, z));
+  return (cx * L.n[1] + cy) * L.n[2] + cz;
 }
 constexpr uint32_t QL = 64;   // generic queries: QL^3 cells of the seed lattice over the query bounding box (query_order.hip k_qlattice)
 

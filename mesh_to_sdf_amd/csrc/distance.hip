@@ -585,7 +585,7 @@ __device__ __forceinline__ void store_grid_result(float* __restrict__ out, size_
     // and the packet that completes a row counts the row on the unit's own counter, the only address the copy kernel polls
     if (lane == 0) {
       const uint32_t unit = vox.bx >> peers.unit_log;
-      const uint32_t nbx = bricks_along(g.xe - g.xb, g.bl[0]), nbz = bricks_along(g.n[2], g.bl[2]);
+      const uint32_t nbx = bricks_along(g.xe - g.xb, g.bl[0]), nbz = g.nbz;
       const uint32_t bricks = min((unit + 1u) << peers.unit_log, nbx) - (unit << peers.unit_log);
       const uint32_t old = __hip_atomic_fetch_add(&peers.progress[peers.units + unit * peers.rows + vox.by], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (old + 1u == bricks * nbz) __hip_atomic_fetch_add(&peers.progress[unit], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -652,6 +652,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   WalkStats st;
   uint32_t st_ranges = 0, st_band = 0, st_rbytes = 0;
   if (mesh.n_nodes) {
+    // Placement of the headline form's node loop.  The prologue below lost 960 bytes when the call's constants moved to the host, and the
+    // node loop of walk_span — the same instructions as before — came to start 16 bytes into a 64-byte line of the instruction cache
+    // instead of 36: the headline still gained (distance 6.42 -> 6.31 ms) but 512^3 x blob-1M, whose packets spend 2.8 times as long in
+    // that loop, LOST 0.5 % (17.78 -> 17.85 ms).  Twelve bytes of padding put the loop back at 36: 6.42 -> 6.29 and 17.78 -> 17.65 ms, same
+    // box, alternating runs (profiles/prologue_ab.txt).  A change of the code in front of the loop moves it again: tools/isa_kernel_diff.py
+    // shows the change, llvm-objdump -d the loop's address (the backward branch over ~1 860 bytes), and the two configs decide.
+    // (Side effect, part of what was measured: behind an asm statement the compiler reads mesh_scale — a global load, "may be clobbered" —
+    // through the vector unit, one VMEM instruction more per packet; the seed index and the records stay scalar loads.)
+    if (GRID && MODE == MODE_UNSIGNED && SIGN == SIGN_GRID_PLANE && DEFER == 3 && GA) asm volatile("s_nop 0\n s_nop 0\n s_nop 0");
     const float scale = fmaxf(mesh_scale(mesh), fmaxf(fabsf(p.x), fmaxf(fabsf(p.y), fabsf(p.z))));
     const float slack = 4.0e-6f * scale + (MODE == MODE_NORMAL_FOLD ? 2.5e-6f : 0.0f);
     SplitState sp;
@@ -663,26 +672,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     ga.pending = false;
 
     // pre-order ranges to walk: the brick's cut list (grid path), or the whole tree.  The list is 64 bytes that nobody has
-    // touched before (written by k_cut, read once): it is requested here, in front of the seed evaluation, so that the ~1 us of
-    // the miss passes under its 120 instructions instead of in front of the walk.
+    // touched before (written by k_cut, read once), and the seed is a chain of two more cold loads (its index, then its record).
+    // The list word is REQUESTED here and first USED behind the seed evaluation: nothing in between reads it, so the compiler's
+    // s_waitcnt vmcnt(0) stands at the decode below and the list's miss passes under the seed chain and its ~140 instructions.
+    // (Decoded right here, as it was, the wait stood directly behind the load, in front of the seed's loads: three misses in a row.)
     constexpr uint32_t NB = (uint32_t)sizeof(NodeExt);
-    const uint32_t* cl = nullptr;
+    uint32_t cw = 0;
     uint32_t n_ranges = 1, cut_off_v = 0, cut_end_v = (lane == 1) ? mesh.n_nodes * NB : 0u;   // no list: lane 1 holds the whole tree
     if (SPLIT) sp.n_ranges = &n_ranges;
+    // generic queries: the packet's centre (its seed cell below) is a vector load too.  Requested in FRONT of the list word: vmcnt counts
+    // in order, so the seed chain can then wait for the centre alone (behind the list word it would wait for both).
+    float4 centre = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!GRID && seed_in != nullptr && cut.centres != nullptr) centre = cut.centres[packet];
     if (cut.lists != nullptr) {
       const uint32_t cb = GRID ? __builtin_amdgcn_readfirstlane((((vox.bx + cut.bx_off) >> cut.log) * cut.ny + (vox.by >> cut.log)) * cut.nz + (vox.bz >> cut.log))
                                : packet;
-      cl = cut.lists + (size_t)cb * CUT_WORDS;
-      // The whole 64-byte record with ONE vector load — lane l takes word l — requested here, in front of the seed evaluation;
-      // lanes 1..15 then decode their range side by side (eight VALU instructions for the whole list), and the range loop below
-      // fetches (start, end) of range k from lane 1 + k with two v_readlane: no load and no scalar arithmetic per range.  (Decoding
-      // on the scalar unit, one range at a time, cost the Normal-sign walk of 1024^3 1.3 %: 9 SALU x ~10 ranges per packet.)
-      const uint32_t cw = cl[(uint32_t)lane & 15u];
-      const uint32_t cS = cut_start_bits(mesh.n_nodes), cfirst = cw & ((1u << cS) - 1u);
-      const uint32_t clen = ((cw >> cS) & ((1u << (27u - cS)) - 1u)) << (cw >> 27);
-      cut_off_v = cfirst * NB;
-      cut_end_v = min(cfirst + clen, mesh.n_nodes) * NB;
-      n_ranges = __builtin_amdgcn_readfirstlane(cw);
+      // The whole 64-byte record with ONE vector load — lane l takes word l.
+      cw = cut.lists[(size_t)cb * CUT_WORDS + ((uint32_t)lane & 15u)];
     }
     if (seed_in != nullptr) {
       // seed: a triangle near this packet's centre, from the seed pass
@@ -693,10 +699,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         const GridParams L = *seed_lattice;
         float q0[3] = {__shfl(p.x, 0), __shfl(p.y, 0), __shfl(p.z, 0)};
         if (cut.centres != nullptr) {      // the same cell k_cut<false> took this packet's seed from
-          const float4 c = cut.centres[packet];
-          q0[0] = c.x; q0[1] = c.y; q0[2] = c.z;
+          q0[0] = centre.x; q0[1] = centre.y; q0[2] = centre.z;
         }
-        sidx = __builtin_amdgcn_readfirstlane(query_lattice_cell(L, q0[0], q0[1], q0[2]));
+        sidx = query_lattice_cell_uniform(L, q0[0], q0[1], q0[2]);
       }
       // one seed per packet: wave-uniform, so the 96-byte record comes through scalar loads
       const uint32_t slot = __builtin_amdgcn_readfirstlane(min(seed_in[sidx], mesh.n_tris - 1));
@@ -720,6 +725,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       }
       const TriRec tr = mesh.tris[nr.tri];
       eval_triangle<MODE>(best, p, tr);
+    }
+    if (cut.lists != nullptr) {
+      // The list word's first use.  Lanes 1..15 decode their range side by side (eight VALU instructions for the whole list), and the
+      // range loop below fetches (start, end) of range k from lane 1 + k with two v_readlane: no load and no scalar arithmetic per range.
+      // (Decoding on the scalar unit, one range at a time, cost the Normal-sign walk of 1024^3 1.3 %: 9 SALU x ~10 ranges per packet.)
+      const uint32_t cS = cut.start_bits, cfirst = cw & ((1u << cS) - 1u);
+      const uint32_t clen = ((cw >> cS) & ((1u << (27u - cS)) - 1u)) << (cw >> 27);
+      cut_off_v = cfirst * NB;
+      cut_end_v = min(cfirst + clen, mesh.n_nodes) * NB;
+      n_ranges = __builtin_amdgcn_readfirstlane(cw);
     }
 
     float thr = prune_bound(best.d2, slack);
@@ -939,7 +954,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       if (cut.lists != nullptr) {
         const uint32_t cb = __builtin_amdgcn_readfirstlane((((vox.bx + cut.bx_off) >> cut.log) * cut.ny + (vox.by >> cut.log)) * cut.nz + (vox.bz >> cut.log));
         const uint32_t cw = cut.lists[(size_t)cb * CUT_WORDS + ((uint32_t)lane & 15u)];
-        const uint32_t cS = cut_start_bits(mesh.n_nodes), cfirst = cw & ((1u << cS) - 1u);
+        const uint32_t cS = cut.start_bits, cfirst = cw & ((1u << cS) - 1u);
         const uint32_t clen = ((cw >> cS) & ((1u << (27u - cS)) - 1u)) << (cw >> 27);
         cut_off_v = cfirst * NB;
         cut_end_v = min(cfirst + clen, mesh.n_nodes) * NB;
@@ -1289,7 +1304,7 @@ struct PacketArgs {
   const uint32_t* seed_in = nullptr;
   uint32_t seed_shift = 0, seed_ny = 0, seed_nz = 0;
   const GridParams* seed_lattice = nullptr;
-  CutList cut = {nullptr, 0, 0, 0, 0, nullptr};
+  CutList cut = {nullptr, 0, 0, 0, 0, nullptr, 0};
   PeerOut peers{};
   SplitCtl split{};
 };
@@ -1501,6 +1516,7 @@ int prepare_grid_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const G
   const GridWalkChoice ch = choose_grid_walk(g, mesh.n_tris, mesh.n_nodes, mesh.leaf_max, mesh.stats != nullptr, algorithm, tn);
   plan->choice = ch;
   if (ch.path == GridWalkChoice::NOTHING) return 0;
+  M2S_REQUIRE_GRID_CONSTS(g);
   const BrickCounts bc = brick_counts(g);
   const uint32_t packets = bc.padded;
   if (ch.path == GridWalkChoice::ALL_PAIRS_SPLIT) {
@@ -1565,7 +1581,8 @@ int launch_grid_walk(hipStream_t st, const DeviceMesh& mesh, const GridParams& g
   const BrickCounts bc = brick_counts(g);
   const uint32_t packets = bc.padded, real = (uint32_t)bc.real;   // (no super-brick padding for k_brute_split)
   const uint32_t* plane = mode == MODE_UNSIGNED ? d_inside_plane : nullptr;   // the Normal fold carries its own sign
-  const CutList cut = {plan.cut_lists, plan.cut_log, plan.cut_ny, plan.cut_nz, bx_off, nullptr};
+  const CutList cut = cut_list_for(mesh.n_nodes, plan.cut_lists, plan.cut_log, plan.cut_ny, plan.cut_nz, bx_off, nullptr);
+  M2S_REQUIRE_GRID_CONSTS(g);
   if (ch.path == GridWalkChoice::ALL_PAIRS_SPLIT) {
     M2S_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)plan.brute_acc, 0x7f800000, (size_t)packets * 64 * 2, st));   // +inf: where every search starts (Best<>)
     return launch_grid_brute_split(st, mesh, g, mode, plane, plan.brute_acc, real, d_out, d_err, pz);
@@ -1686,12 +1703,12 @@ int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const f
     seeds = pre->ids;
     d_lat = plan.lat;
   }
-  CutList cut = {nullptr, 0, 0, 0, 0, nullptr};
+  CutList cut = {nullptr, 0, 0, 0, 0, nullptr, 0};
   if (plan.centres != nullptr && seeds != nullptr) {
     uint32_t* lists = ws.take<uint32_t>((size_t)launched * CUT_WORDS);
     if (!lists) { set_error("internal: query workspace too small"); return M2S_ERR_HIP_INTERNAL; }
     launch_query_cut(st, mesh, seeds, launched, lists, plan.centres, plan.table, d_lat);
-    cut = {lists, 0, 0, 0, 0, plan.centres};
+    cut = cut_list_for(mesh.n_nodes, lists, 0, 0, 0, 0, plan.centres);
   }
   PacketArgs a;
   a.mesh = mesh; a.g = g; a.qsorted = plan.sorted; a.perm = plan.perm; a.n_q = nq; a.plane = plan.table; a.out = d_out; a.err = d_err; a.n_packets = launched;

@@ -69,28 +69,13 @@ struct GridBrick {
 // Brick sequence number -> brick coordinates.  Bricks are walked in 8x8x8 super-bricks (z fastest inside
 // and between them), so that consecutive packets of an XCD keep touching the same part of the BVH while
 // its 4 MiB L2 still holds it; a plain z-y-x sweep returns to a node only after a whole z column.
-// A thin x-slab (multi-GPU pieces are 16 layers = 4 bricks at 8 GPUs x 4 chunks) uses super-bricks that are
-// 4, 2 or 1 bricks wide in x instead, so that at most 1/8 of the launched packets are padding.
-__host__ __device__ __forceinline__ uint32_t bricks_along(uint32_t cells, uint32_t log2_extent) {
-  return (cells + (1u << log2_extent) - 1u) >> log2_extent;
-}
-__host__ __device__ __forceinline__ uint32_t super_brick_xlog(uint32_t nbx, uint32_t xl_cap = 0) {
-  // (the compiler also emits an eight-wide "vectorised" form of this loop for trip counts >= 16, which never runs: xl starts at 3 or below.
-  // A straight-line rewrite — round 6 — executed the same handful of scalar instructions and moved the packet walk's code by 1 400 bytes:
-  // 6.44 -> 6.48 ms on the headline, same box, three runs each.  Left as it was.)
-  for (uint32_t xl = xl_cap ? xl_cap - 1u : 3u; xl > 0; --xl) {
-    const uint32_t padded = ((nbx + (1u << xl) - 1u) >> xl) << xl;
-    if ((padded - nbx) * 8u <= nbx) return xl;
-  }
-  return 0;
-}
+// A thin x-slab uses super-bricks that are 4, 2 or 1 bricks wide in x instead (common.h super_brick_xlog).  The width's log and the
+// super-brick counts are the call's constants, resolved on the host (GridParams::sb_xl, sy, sz: common.h set_super_brick_magic).
 __device__ __forceinline__ uint32_t div_magic(uint32_t n, uint32_t d, uint32_t magic) {
   return magic ? __umulhi(n, magic) : n / d;   // common.h set_super_brick_magic
 }
 __device__ __forceinline__ void brick_coords(const GridParams& g, uint32_t brick, uint32_t* bx, uint32_t* by, uint32_t* bz) {
-  const uint32_t nby = bricks_along(g.n[1], g.bl[1]), nbz = bricks_along(g.n[2], g.bl[2]);
-  const uint32_t sy = (nby + 7) >> 3, sz = (nbz + 7) >> 3;
-  const uint32_t xl = super_brick_xlog(bricks_along(g.xe - g.xb, g.bl[0]), g.xl_cap);
+  const uint32_t sy = g.sy, sz = g.sz, xl = g.sb_xl;
   const uint32_t sb = brick >> (6 + xl), in = brick & ((64u << xl) - 1u);   // super-brick index, position inside (padded grid)
   const uint32_t t = div_magic(sb, sz, g.sz_magic), sbz = sb - t * sz;
   const uint32_t sbx = div_magic(t, sy, g.sy_magic), sby = t - sbx * sy;
@@ -124,7 +109,7 @@ __device__ __forceinline__ uint32_t grid_brick_count(const GridParams& g) {
 
 // Bricks in plain z-y-x order, no padding to super-bricks (k_brute_split: every packet costs the same, order is irrelevant).
 __device__ __forceinline__ GridBrick grid_lane_voxel_plain(const GridParams& g, uint32_t brick, int lane) {
-  const uint32_t nby = bricks_along(g.n[1], g.bl[1]), nbz = bricks_along(g.n[2], g.bl[2]);
+  const uint32_t nby = g.nby, nbz = g.nbz;
   const uint32_t bz = brick % nbz, t = brick / nbz, by = t % nby, bx = t / nby;
   GridBrick v;
   const uint32_t lx = g.bl[0], ly = g.bl[1], lz = g.bl[2], l = (uint32_t)lane;

@@ -267,6 +267,7 @@ int launch_winding_grid(hipStream_t st, const DeviceMesh& mesh, const NodeMom* m
                         const float* d_dist, uint64_t dist_off, int algorithm, const WindingOut& out) {
   const uint32_t packets = host_packet_bricks(g);
   if (packets == 0) return 0;
+  M2S_REQUIRE_GRID_CONSTS(g);
   if (algorithm == 1) hipLaunchKernelGGL(k_winding_grid<true>, dim3(packets), dim3(64), 0, st, mesh, moms, g, beta, threshold, d_dist, dist_off, out);
   else hipLaunchKernelGGL(k_winding_grid<false>, dim3(packets), dim3(64), 0, st, mesh, moms, g, beta, threshold, d_dist, dist_off, out);
   M2S_HIP_CHECK(hipGetLastError());
