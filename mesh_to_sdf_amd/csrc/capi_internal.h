@@ -1,5 +1,7 @@
 // capi_internal.h — per-device state and call context shared by the C-ABI translation units
-// (capi.hip: distance path; capi_io.hip: container encode/decode, cell ordering, instance merge).
+// (capi.hip: contexts, staging, the distance path and the m2s_mesh lifecycle; capi_features.hip: closest points, winding numbers,
+// rays, surface sampling, voxelization, narrow bands; capi_io.hip: container encode/decode, cell ordering, instance merge, grid
+// queries).  The m2s_mesh handle itself is in capi_mesh.h.
 #pragma once
 #include <cstdio>
 #include <functional>
@@ -86,6 +88,22 @@ int staged_h2d(DeviceState& st, hipStream_t stream, char* d_dst, const char* h_s
 int staged_d2h(DeviceState& st, hipStream_t stream, char* h_dst, const char* d_src, size_t bytes);
 int staged_d2h_to_file(DeviceState& st, hipStream_t stream, FILE* f, const char* d_src, size_t bytes);   // M2S_ERR_IO on a short write
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+
+// Steps of a mesh call (capi.hip) that the feature entry points (capi_features.hip) take as the distance calls do.
+int check_mesh_args(const float* vertices, size_t n_vertices, const void* indices, size_t n_indices, int index_bytes, int topology);
+struct StagedMesh {
+  const float* d_verts = nullptr;
+  const void* d_indices = nullptr;
+};
+// Copies the mesh to the device when the caller passed host pointers.
+int stage_mesh(Arena& ws, const CallCtx& c, const float* vertices, size_t n_vertices, const void* indices, size_t n_indices,
+               int index_bytes, StagedMesh* out);
+// The grid, and the x-slab `opts` names (NULL: the whole grid), into `g`; *slab_cells = the cells of the slab.
+int fill_grid_params(const m2s_grid* grid, const m2s_opts* opts, GridParams* g, size_t* slab_cells);
+// Ends a synchronous call (an asynchronous one returns at once): waits, fills `t` from ev[0] .. ev[4], reports the device's error word.
+// (capi.hip's own calls may leave had_seed_event out: its definition defaults it to false.)
+int finish_call(const CallCtx& c, DeviceState& st, int* d_err, m2s_timings* t, size_t n_tris, size_t n_units, bool had_sign,
+                bool had_seed_event);
 
 // Grid queries (capi_io.hip), shared with the band queries (band_query.hip).
 // grid_query_args: the grid, the sample options and the m2s_opts fields a grid query does not take, into `q` and `mode`; everything
