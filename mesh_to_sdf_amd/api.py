@@ -1679,6 +1679,36 @@ class Mesh:
         out["leaf_max"] = int(fetch(len(self.DEBUG_ARRAYS))[0])
         return out
 
+    def debug_cut_lists(self, grid: Grid = None, *, x_slab: Sequence[int] = None, x_period: int = 0, coarse: bool = False, queries=None):
+        """The cut lists k_cut leaves for a call on this mesh (test hook `m2s_debug_cut_lists`), as uint32 words, 16 per list: of a grid call
+        over `grid` (its slab `x_slab`, interleaved with `x_period`), one list per packet brick of the slab — `coarse`: the coarse records of
+        a two-level plan instead, 64 words per block: 8 sub-lists of 8 —, or of a query call over `queries` (host array), one list per packet.
+        An empty array where the call takes no lists.  The list format is csrc/dist.hip.h: word 0 the number of ranges, one word per range;
+        the words behind a list's last range, which k_cut never writes, come back as 0."""
+        L = _lib.lib()
+        L.m2s_debug_cut_lists.argtypes = [C.c_void_p, C.c_int, C.POINTER(_lib.M2SGrid), C.POINTER(_lib.M2SOpts), C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.m2s_debug_cut_lists.restype = C.c_int
+        xb, xe = (0, 0) if x_slab is None else (int(x_slab[0]), int(x_slab[1]))
+        o = self._a.opts(x_begin=xb, x_end=xe, x_period=x_period)
+        if queries is not None:
+            q = np.ascontiguousarray(np.asarray(queries, np.float32)).reshape(-1, 3)
+            args = (self._h, 2, None, C.byref(o), q.ctypes.data if q.size else None, q.shape[0])
+        else:
+            args = (self._h, 1 if coarse else 0, C.byref(grid._g), C.byref(o), None, 0)
+        n = C.c_size_t(0)
+        rc = L.m2s_debug_cut_lists(*args, None, 0, C.byref(n))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        words = np.zeros(n.value, np.uint32)
+        if n.value:
+            rc = L.m2s_debug_cut_lists(*args, words.ctypes.data, words.size, C.byref(n))
+            if rc != _lib.M2S_OK:
+                _raise(rc)
+        per = words.reshape(-1, 8 if coarse and queries is None else 16)
+        per[np.arange(per.shape[1])[None, :] > per[:, :1]] = 0
+        return words
+
     def drain_timings(self) -> M2STimings:
         t = M2STimings()
         rc = _lib.lib().m2s_mesh_drain_timings(self._h, C.byref(t))

@@ -1739,6 +1739,93 @@ int m2s_debug_mesh_arrays(m2s_mesh* m, int which, void* dst, size_t capacity, si
   return M2S_OK;
 }
 
+// Test hook (not part of include/m2s.h): the cut lists k_cut (cut.hip) leaves for a call on a resident mesh, copied to host memory.  `which`
+// 0: the lists of a grid call over the slab `opts` names of `grid` (x_begin, x_end, x_period as m2s_mesh_generate_grid_sdf takes them) — the
+// call's own steps up to and including launch_grid_cut (remark_leaves by grid_leaf_max, then prepare_grid_walk: choose_grid_walk, the seed
+// lattice, the lists), CUT_WORDS words per packet brick of the slab, brick (bx, by, bz) at ((bx * nby) + by) * nbz + bz; 1: the same call's
+// coarse records (64 words per block of 4 x 4 x 4 bricks) where the plan is two-level, else nothing; 2: the lists of a query call
+// (m2s_mesh_generate_sdf, RtreeBvh, Raycast) over the n_queries points of `queries` (host memory) — prepare_query_walk and
+// prepare_query_lists, CUT_WORDS words per packet of the set.  The words of a list past its last range are whatever the workspace held.  A call that takes no lists (another path, too few packets) has none: 0 words.
+// *words (optional unless dst is NULL) receives the count; dst == NULL asks for the count alone (the work is done either way).  No distance is
+// computed.  tests/test_gpu_cut_lists.py compares the lists word for word with those recorded by tools/record_cut_lists.py.
+int m2s_debug_cut_lists(m2s_mesh* m, int which, const m2s_grid* grid, const m2s_opts* opts, const float* queries, size_t n_queries,
+                        uint32_t* dst, size_t capacity_words, size_t* words) {
+  g_err[0] = 0;
+  if (!m) return fail(M2S_ERR_BAD_ARG, "m2s_debug_cut_lists: NULL mesh");
+  if (which < 0 || which > 2) return fail(M2S_ERR_BAD_ARG, "m2s_debug_cut_lists: which = %d (0 .. 2)", which);
+  if (!dst && !words) return fail(M2S_ERR_BAD_ARG, "m2s_debug_cut_lists: NULL dst and NULL words");
+  if (which < 2 ? !grid : (!queries && n_queries)) return fail(M2S_ERR_BAD_ARG, "m2s_debug_cut_lists: NULL %s", which < 2 ? "grid" : "queries");
+  if (n_queries >= 0xffffffc0ull) return fail(M2S_ERR_BAD_ARG, "too many queries for one call");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  if (words) *words = 0;
+  GridParams g{};
+  size_t slab_cells = 0;
+  int rc = which < 2 ? fill_grid_params(grid, opts, &g, &slab_cells) : 0;
+  if (rc) return rc;
+  if (m->n_tris == 0 || (which < 2 ? slab_cells == 0 : n_queries == 0)) return M2S_OK;
+  m2s_opts o{};
+  if (opts) memcpy(&o, opts, (opts->struct_size >= sizeof(m2s_opts)) ? sizeof(m2s_opts) : (size_t)M2S_OPTS_V1_SIZE);
+  o.device = m->device;
+  o.synchronous = 1;
+  o.timings = nullptr;
+  o.n_peer_out = 0;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  rc = resolve_ctx(&o, &c, &st);
+  if (rc) return rc;
+  rc = ensure_capacity(*st, which < 2 ? grid_distance_workspace_bytes(g, m->n_tris) + 8192 : query_workspace_bytes(n_queries) + align_up(n_queries * 12) + 8192);
+  if (rc) return rc;
+  Arena ws{st->base, st->cap, 0};
+  const uint32_t* d_words = nullptr;
+  const uint32_t* d_table = nullptr;   // queries: word 0 = the packets the set really has (the launch has room for more)
+  uint32_t launched = 0;
+  size_t count = 0;
+  if (which < 2) {
+    rc = remark_leaves(m, c, grid_leaf_max(g, m->n_tris));
+    if (rc) return rc;
+    GridWalkPlan plan;
+    rc = prepare_grid_walk(ws, c.stream, m->dm, g, c.algorithm, false, &plan, nullptr);
+    if (rc) return rc;
+    if (which == 0 && plan.cut_lists) {
+      d_words = plan.cut_lists;
+      count = plan.cut_words;
+    } else if (which == 1 && plan.cut_coarse) {
+      d_words = plan.cut_coarse;
+      count = plan.cut_coarse_words;
+    }
+  } else {
+    int mode, sign_src, algorithm;
+    select_generic_mode(M2S_ACCEL_RTREE_BVH, M2S_SIGN_RAYCAST, c.algorithm, &mode, &sign_src, &algorithm);
+    if (algorithm == 1 || query_is_tiny(n_queries, m->n_tris, algorithm, sign_src)) return M2S_OK;
+    float* dq = ws.take<float>(n_queries * 3);
+    if (!dq) return fail(M2S_ERR_HIP, "internal: workspace");
+    M2S_HIP_CHECK(hipMemcpyAsync(dq, queries, n_queries * 12, hipMemcpyHostToDevice, c.stream));
+    rc = remark_leaves(m, c, query_leaf_max(n_queries, m->n_tris, sign_src));
+    if (rc) return rc;
+    QueryPlan plan;
+    rc = prepare_query_walk(ws, c.stream, dq, n_queries, m->n_tris, sign_src, algorithm, &plan, nullptr);
+    if (rc) return rc;
+    const uint32_t* seeds = nullptr;
+    const GridParams* d_lat = nullptr;
+    rc = prepare_query_lists(ws, c.stream, m->dm, plan, nullptr, &seeds, &d_lat, &d_words, &count);
+    if (rc) return rc;
+    d_table = plan.table;
+    launched = plan.launched;
+  }
+  M2S_HIP_CHECK(hipGetLastError());
+  M2S_HIP_CHECK(hipStreamSynchronize(c.stream));
+  if (count && d_table && launched) {   // k_cut<false> leaves the lists of the packets past the table's count unwritten
+    uint32_t packets = 0;
+    M2S_HIP_CHECK(hipMemcpy(&packets, d_table, 4, hipMemcpyDeviceToHost));
+    count = std::min<size_t>(packets, launched) * (count / launched);
+  }
+  if (words) *words = count;
+  if (!dst || !count) return M2S_OK;
+  if (capacity_words < count) return fail(M2S_ERR_BAD_ARG, "m2s_debug_cut_lists: capacity %zu < %zu words", capacity_words, count);
+  M2S_HIP_CHECK(hipMemcpy(dst, d_words, count * 4, hipMemcpyDeviceToHost));
+  return M2S_OK;
+}
+
 // Test hook (not part of include/m2s.h): the cut-list word of one range and what the walk decodes from it (dist.hip.h CutList) —
 // host arithmetic only, no device needed.  tests/test_capi_cpu.py checks the superset property for every tree size.
 int m2s_debug_cut_code(uint32_t n_nodes, uint32_t start, uint32_t len, uint32_t out[3]) {

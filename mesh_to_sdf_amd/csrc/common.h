@@ -350,6 +350,8 @@ struct GridWalkPlan {
   uint32_t seed_shift = 0, seed_ny = 0, seed_nz = 0;
   const uint32_t* cut_lists = nullptr;
   uint32_t cut_log = 0, cut_ny = 0, cut_nz = 0;
+  const uint32_t* cut_coarse = nullptr;   // two-level lists: the coarse records the fine level started from
+  size_t cut_words = 0, cut_coarse_words = 0;   // words behind cut_lists and cut_coarse (both read back by m2s_debug_cut_lists only)
   SplitCtl split;                     // choice.split
   const uint2* group_top = nullptr;   // GROUP: the tree's top subtrees (k_tree_top)
   uint32_t* brute_acc = nullptr;      // ALL_PAIRS_SPLIT: per-voxel minima of k_brute_split; no seeds, no lists, no tree
@@ -430,7 +432,10 @@ struct QuerySeeds {
 int prepare_query_walk(Arena& ws, hipStream_t st, const float* d_queries, size_t n_q, size_t n_tris, int sign_src, int algorithm, QueryPlan* plan,
                        hipEvent_t after_lattice = nullptr);
 int launch_query_seeds(Arena& ws, hipStream_t st, const float4* cen, uint32_t n_tris, const QueryPlan& plan, bool raw, QuerySeeds* out);   // seeds.hip
-// distance.hip
+// distance.hip.  prepare_query_lists: the seeds (`pre`: computed beside the build, else here) and the cut lists (*lists null: the set walks
+// without; *list_words: their size) of a prepared query set — the first half of launch_query_walk, which m2s_debug_cut_lists stops after.
+int prepare_query_lists(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const QueryPlan& plan, const QuerySeeds* pre, const uint32_t** seeds,
+                        const GridParams** d_lat, const uint32_t** lists, size_t* list_words = nullptr);
 int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const float* d_queries, const QueryPlan& plan,
                       int mode, int sign_src, int algorithm, float* d_out, int* d_err, const QuerySeeds* pre = nullptr);
 int launch_query_distance(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const float* d_queries, size_t n_q,

@@ -8,6 +8,7 @@
 #include "tuning.h"
 #include "walk.hip.h"
 #include "dist.hip.h"
+#include "cut_size.hip.h"
 
 namespace m2s {
 
@@ -39,7 +40,6 @@ namespace {
 // GRID = false (generic queries): "brick" = packet of sorted queries, lane = packet, 64 consecutive packets (neighbours in
 // the Morton order) per wave; centre and radius from `centres` (k_qpacket_bounds), the seed from the lattice cell of the
 // centre (as k_packet<false> does), `nbx` = the number of wave slots the packet walk was launched with.
-constexpr uint32_t NB_CUT = (uint32_t)sizeof(NodeExt);
 // Two levels (round 6; grids only).  Of a fine wave's node visits on 512^3 x blob-100k 44 % fall on nodes larger than the wave's own block
 // of 4 x 4 x 4 bricks (16 % on nodes larger than four blocks; 1024^3 x sheet-100k: 61 % / 29 %; counted, profiles/r06_kcut_visits.txt),
 // and its 63 neighbours inside a 64^3-voxel region repeat them with the same outcome.  LEVEL 1 walks that top ONCE per region: lane =
@@ -49,10 +49,13 @@ constexpr uint32_t NB_CUT = (uint32_t)sizeof(NodeExt);
 // and leaves CUTC_S sub-lists of <= CUTC_MAX ranges per block.  LEVEL 2 is the fine walk started from its block's ranges instead of
 // the root.  A subtree the coarse level drops holds nothing a voxel of the block can need, whatever the fine level's own seeds say,
 // so the fine lists can only get shorter; the packets' results cannot change (parity suite, soaks).
+// A lane condition as the wave's 64-bit mask, and this lane's bit of such a mask as a condition again: neither costs a vector instruction.
+__device__ __forceinline__ unsigned long long wave_mask(bool lane_condition) { return __builtin_amdgcn_ballot_w64(lane_condition); }
+__device__ __forceinline__ bool lane_of(unsigned long long mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
 template <bool GRID, int LEVEL = 0>
 __global__ __launch_bounds__(64) void k_cut(DeviceMesh mesh, GridParams g, const uint32_t* __restrict__ seeds, uint32_t seed_shift,
                                             uint32_t seed_ny, uint32_t seed_nz, uint32_t nbx, uint32_t nby, uint32_t nbz,
-                                            uint32_t* __restrict__ lists, float emit_near, float emit_far, uint32_t budget, uint32_t wave_cap,
+                                            uint32_t* __restrict__ lists, float emit_near, float emit_far, uint32_t wave_cap,
                                             const float4* __restrict__ centres, const uint32_t* __restrict__ table,
                                             const GridParams* __restrict__ seed_lattice, uint32_t start_bits, const uint32_t* __restrict__ coarse = nullptr) {
   static_assert(GRID || LEVEL == 0, "the two-level form is the grid's");
@@ -122,15 +125,17 @@ __global__ __launch_bounds__(64) void k_cut(DeviceMesh mesh, GridParams g, const
   const float emit_radius = fmaxf(emit_near * r, R * emit_far);
 
   constexpr uint32_t NB = (uint32_t)sizeof(NodeExt);
-  const uint32_t tree_end = mesh.n_nodes * NB;
   uint32_t* out = lists + ((size_t)(in_grid ? (GRID ? (bk[0] * nby + bk[1]) * nbz + bk[2] : pk) : 0u)) * (LEVEL == 1 ? CUTC_S * CUTC_WORDS : OUT_WORDS)
                   + sub * CUTC_WORDS;
   const uint32_t cut_S = start_bits;   // cut_start_bits(mesh.n_nodes), resolved by the launch
-  auto cut_word = [cut_S](uint32_t start, uint32_t stop) {   // byte offsets -> list word (see CUT_WORDS)
-    return (start / NB_CUT) | (cut_encode_len((stop - start) / NB_CUT, 27u - cut_S) << cut_S);
+  auto cut_word = [cut_S](uint32_t start, uint32_t stop) {   // records [start, stop) -> list word (see CUT_WORDS)
+    return start | (cut_encode_len(stop - start, 27u - cut_S) << cut_S);
   };
-  uint32_t n = 0, last_start = 0, last_end = 0, resume = 0, opened = 0;   // per lane
-  uint32_t off = 0, end = tree_end, steps = 0;                // wave-uniform
+  // The walk's own positions (off, end, the lanes' resume) are byte offsets, as the records' `skip` is; the ranges a lane collects
+  // (last_start, last_end) are RECORD indices, divided once on the scalar unit where a range is emitted, so that a list word needs no
+  // per-lane division by the record size.
+  uint32_t n = 0, last_start = 0, last_end = 0, resume = 0;   // per lane
+  uint32_t off = 0, end = mesh.n_nodes * NB, steps = 0;       // wave-uniform
   if (LEVEL == 1) {
     // this wave's subtree: CUTC_S_LOG levels down from the root, left or right by the bits of `sub`.  A leaf met on the way belongs to
     // the wave whose remaining bits are zero; the others have nothing to walk.
@@ -184,7 +189,11 @@ __global__ __launch_bounds__(64) void k_cut(DeviceMesh mesh, GridParams g, const
       st_above4 += ext > 4.0f * st_block ? 1u : 0u;
     }
 #endif
-    const bool active = off >= resume;                        // this brick has not dropped / emitted an ancestor
+    // The lanes' conditions live as 64-bit wave masks in scalar registers from the compare that forms them (the ballot of ONE compare is
+    // that compare's own result) and are combined there with AND / OR / ANDN2; a lane's state changes under the final mask (lane_of).
+    // Kept as per-lane booleans they were turned into 0 / 1 values and back (v_cndmask + v_cmp) at every ballot of a combined
+    // condition and in the loop's tail: some twenty vector instructions of every visit held no arithmetic of the brick.
+    const unsigned long long active = wave_mask(off >= resume);   // bricks that have not dropped / emitted an ancestor
     // closest point of the disc-slab to q:  q - c = ax * n_s + lat * l / |l|   (common.h NodeExt, ext_dist2)
     const float vx = q.x - nr.cx, vy = q.y - nr.cy, vz = q.z - nr.cz;
     const float t = __builtin_fmaf(nr.nz, vz, __builtin_fmaf(nr.ny, vy, nr.nx * vx));
@@ -196,8 +205,8 @@ __global__ __launch_bounds__(64) void k_cut(DeviceMesh mesh, GridParams g, const
     const float dt = t - nr.mid;
     const float ax = copysignf(fmaxf(fabsf(dt) - nr.half, 0.0f), dt);
     const float L2 = __builtin_fmaf(ax, ax, lat * lat);
-    bool keep = active & !(L2 > R2);                          // sphere test; NaN keeps the node
-    if (__ballot(keep) == 0ull) { off = nr.skip; continue; }
+    unsigned long long kept = active & wave_mask(!(L2 > R2));    // sphere test; NaN keeps the node
+    if (kept == 0ull) { off = nr.skip; continue; }
     {
       // gradient test (lanes without it carry grad_c0 = inf: never dropped).  rcp / rsq instead of IEEE divisions: their
       // 1-ulp error is nothing beside the 2e-5 added under the root
@@ -210,27 +219,29 @@ __global__ __launch_bounds__(64) void k_cut(DeviceMesh mesh, GridParams g, const
       const float cosne = fminf(num * inv_L, 1.0f);                                                      // n . e (NaN / inf if L == 0: kept)
       const float nme2 = fmaxf(2.0f - 2.0f * cosne, 0.0f) + 2.0e-5f;                                     // >= |n - e|^2
       const float A = __builtin_fmaf(L2 * inv_L, 0.9999f, -grad_c0);                                     // L (1 - 1e-4) - c0
-      const bool drop = (A > 0.0f) & (A * A > grad_c1sq * nme2);                                         // A > c1 |n - e| without the root; false on NaN
-      keep = keep & !drop;
+      kept &= ~(wave_mask(A > 0.0f) & wave_mask(A * A > grad_c1sq * nme2));                              // drop if A > c1 |n - e|, without the root; false on NaN
     }
-    const unsigned long long bal = __ballot(keep);
-    if (bal == 0ull) { off = nr.skip; continue; }
+    if (kept == 0ull) { off = nr.skip; continue; }
     // Where many triangles are (nearly) equidistant — towards the medial axis, e.g. deep inside a round body — the brick-level
-    // test keeps a large part of the tree however far it descends: a brick that has already opened `budget` nodes emits what
-    // it meets next as it is and leaves the rest to the packet's per-voxel tests (which are 200 times sharper there).
+    // test keeps a large part of the tree however far it descends: past wave_cap visits (cut_params) the wave's bricks emit what
+    // they meet next as it is and leave the rest to the packet's per-voxel tests (which are 200 times sharper there).
     // (a saturated list — NMAX ranges — only grows its last range over every gap from here on: nothing finer can be said)
-    const bool emit = keep & (nr.tri >= 0 || fmaxf(nr.R, nr.half) <= emit_radius || opened >= budget || n == NMAX || steps >= wave_cap);
-    if (emit) {
-      // keep this subtree: [off, skip).  Adjacent subtrees merge; past NMAX ranges the last one grows over the gap
-      if (n > 0 && (last_end == off || n == NMAX)) last_end = nr.skip;
+    // The leaf mark and the cap are the wave's, the size test's left side too (cut_size.hip.h): one compare per lane each for the size
+    // and the saturated list.
+    const unsigned long long emit_all = ((nr.tri >= 0) | (steps >= wave_cap)) ? ~0ull : 0ull;
+    const unsigned long long emitted = kept & (emit_all | wave_mask(cut_small_enough(nr.R, nr.half, emit_radius)) | wave_mask(n == NMAX));
+    const unsigned long long open = kept & ~emitted;          // bricks that still have to look inside
+    if (lane_of(emitted)) {
+      // keep this subtree: the records [at, to).  Adjacent subtrees merge; past NMAX ranges the last one grows over the gap
+      const uint32_t at = off / NB, to = nr.skip / NB;        // (wave-uniform: one multiply-high each on the scalar unit)
+      if (n > 0 && (last_end == at || n == NMAX)) last_end = to;
       else {
         if (n > 0) out[n] = cut_word(last_start, last_end);
-        ++n; last_start = off; last_end = nr.skip;
+        ++n; last_start = at; last_end = to;
       }
     }
-    opened += (keep & !emit) ? 1u : 0u;
-    if (active & (emit | !keep)) resume = nr.skip;            // done with this subtree either way
-    off = (__ballot(keep & !emit) != 0ull) ? off + NB : nr.skip;   // some brick still has to look inside
+    if (lane_of(active & ~open)) resume = nr.skip;            // dropped or emitted: done with this subtree either way
+    off = open != 0ull ? off + NB : nr.skip;
   }
     if (LEVEL != 2) break;
   }
@@ -250,7 +261,7 @@ __global__ __launch_bounds__(64) void k_cut(DeviceMesh mesh, GridParams g, const
     out[0] = n;
     return;
   }
-  if (n == 0) { n = 1; last_start = 0; last_end = tree_end; }    // cannot happen with finite input; never walk nothing
+  if (n == 0) { n = 1; last_start = 0; last_end = mesh.n_nodes; }    // cannot happen with finite input; never walk nothing
   out[n] = cut_word(last_start, last_end);
   out[0] = n;
 }
@@ -258,7 +269,7 @@ __global__ __launch_bounds__(64) void k_cut(DeviceMesh mesh, GridParams g, const
 }  // namespace
 
 // What k_cut is launched with, for grids and for queries.
-struct CutParams { float emit_near, emit_far; uint32_t budget, wave_cap; };   // emission radius of a list entry: emit_near brick radii next to the surface, emit_far of the distance far from it
+struct CutParams { float emit_near, emit_far; uint32_t wave_cap; };   // emission radius of a list entry: emit_near brick radii next to the surface, emit_far of the distance far from it
 static CutParams cut_params(uint32_t n_tris, const Tuning& tn) {
   // A wave that has visited wave_cap nodes lets its bricks emit whatever they meet next: the long union walks of the
   // regions with many near-ties (deep inside a round body) are the tail of the launch — on the 64-layer slab of an 8-GPU
@@ -267,7 +278,10 @@ static CutParams cut_params(uint32_t n_tris, const Tuning& tn) {
   uint32_t depth = 1;
   while ((1ull << depth) < (unsigned long long)n_tris + 1ull) ++depth;
   // (emit_far 1/32: re-tuned at the end of round 3 (1/16 before): headline 9.19 -> 9.11 ms, 1024^3 x sheet-100k 92.95 -> 89.33 ms)
-  return {tn.cut_near, tn.cut_far, 100000u, tn.cut_wave_cap ? tn.cut_wave_cap : std::max(120u, 20u * depth)};
+  // (k_cut once also counted the nodes each brick had opened and let a brick past a budget of 100 000 emit what it met.  A brick opens at
+  // most one node per visit, so its count never exceeds the wave's visits, and the cap — at most 99 999 whatever M2S_CUT_WAVE_CAP or
+  // M2S_CUT_COARSE_CAP asks for: tuning.cpp — is always met first: the term could never decide and is gone.)
+  return {tn.cut_near, tn.cut_far, tn.cut_wave_cap ? tn.cut_wave_cap : std::max(120u, 20u * depth)};
 }
 
 // k_cut over the slab [g.xb, g.xe): one list of CUT_WORDS words per packet brick into `lists`, from the seed lattice the walk will use.
@@ -284,12 +298,12 @@ void launch_grid_cut(hipStream_t st, const DeviceMesh& mesh, const GridParams& g
   if (coarse != nullptr) {
     const size_t groups = cut_blocks(g, 4);   // 4 x 4 x 4 blocks
     const uint32_t coarse_cap = tn.cut_coarse_cap ? tn.cut_coarse_cap : cp.wave_cap;
-    hipLaunchKernelGGL((k_cut<true, 1>), dim3((unsigned)(groups * CUTC_S)), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, cbx, cby, cbz, coarse, 1.0f, cp.emit_far, cp.budget,
+    hipLaunchKernelGGL((k_cut<true, 1>), dim3((unsigned)(groups * CUTC_S)), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, cbx, cby, cbz, coarse, 1.0f, cp.emit_far,
                        coarse_cap, (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, S, (const uint32_t*)nullptr);
-    hipLaunchKernelGGL((k_cut<true, 2>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap,
+    hipLaunchKernelGGL((k_cut<true, 2>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, cp.emit_near, cp.emit_far, cp.wave_cap,
                        (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, S, (const uint32_t*)coarse);
   } else
-  hipLaunchKernelGGL((k_cut<true, 0>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap,
+  hipLaunchKernelGGL((k_cut<true, 0>), dim3((unsigned)waves), dim3(64), 0, st, mesh, g, seed1, sh1, s1ny, s1nz, nbx, nby, nbz, lists, cp.emit_near, cp.emit_far, cp.wave_cap,
                      (const float4*)nullptr, (const uint32_t*)nullptr, (const GridParams*)nullptr, S, (const uint32_t*)nullptr);
 }
 
@@ -299,7 +313,7 @@ void launch_query_cut(hipStream_t st, const DeviceMesh& mesh, const uint32_t* se
   GridParams g{};
   const CutParams cp = cut_params(mesh.n_tris, tuning());
   hipLaunchKernelGGL((k_cut<false, 0>), dim3((launched + 63) / 64), dim3(64), 0, st, mesh, g, seeds, 0u, 0u, 0u, launched, 1u, 1u, lists,
-                     cp.emit_near, cp.emit_far, cp.budget, cp.wave_cap, centres, table, d_lat, cut_start_bits(mesh.n_nodes));
+                     cp.emit_near, cp.emit_far, cp.wave_cap, centres, table, d_lat, cut_start_bits(mesh.n_nodes));
 }
 
 // Test hook (capi.hip m2s_debug_cut_code): the list word k_cut writes for the range [start, start + len) of a tree of n_nodes records,

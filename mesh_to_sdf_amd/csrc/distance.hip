@@ -1544,7 +1544,8 @@ int prepare_grid_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const G
       if (!coarse) { set_error("internal: cut-list workspace too small"); return M2S_ERR_HIP_INTERNAL; }
     }
     launch_grid_cut(st, mesh, g, plan->seeds, plan->seed_shift, plan->seed_ny, plan->seed_nz, lists, coarse);
-    plan->cut_lists = lists; plan->cut_log = 0; plan->cut_ny = bc.nb[1]; plan->cut_nz = bc.nb[2];
+    plan->cut_lists = lists; plan->cut_log = 0; plan->cut_ny = bc.nb[1]; plan->cut_nz = bc.nb[2]; plan->cut_coarse = coarse;
+    plan->cut_words = (size_t)bc.real * CUT_WORDS; plan->cut_coarse_words = coarse ? cut_blocks(g, 2) * CUTC_S * CUTC_WORDS : 0;
   }
   if (ch.path == GridWalkChoice::GROUP) {
     uint2* top = ws.take<uint2>(TOP_SUBTREES);
@@ -1680,14 +1681,10 @@ uint32_t grid_leaf_max(const GridParams& g, size_t n_tris) {
   return per_brick >= 40.0 ? 16u : per_brick >= 3.0 ? 8u : per_brick >= 0.6 ? 4u : 2u;   // (16: blob-100k 32^3, 195 per brick, 1.31 -> 1.11 ms; blob-1M 80^3 3.14 -> 2.53)
 }
 
-int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const float* d_queries, const QueryPlan& plan,
-                      int mode, int sign_src, int algorithm, float* d_out, int* d_err, const QuerySeeds* pre) {
-  const size_t n_q = plan.n_q;
-  if (n_q == 0) return 0;
-  GridParams g{};
-  const uint32_t nq = (uint32_t)n_q;
-  if (algorithm == 1) return launch_query_brute(st, mesh, d_queries, nq, mode, sign_src, d_out, d_err);
-  const uint32_t launched = plan.launched;
+int prepare_query_lists(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const QueryPlan& plan, const QuerySeeds* pre, const uint32_t** seeds_out,
+                        const GridParams** d_lat_out, const uint32_t** lists_out, size_t* list_words) {
+  *seeds_out = nullptr; *d_lat_out = nullptr; *lists_out = nullptr;
+  if (list_words) *list_words = 0;
   // seeds: jump flooding over a QL^3 lattice on the query bounding box (as for the grid path) — here, or beside the build (`pre`)
   const uint32_t* seeds = nullptr;
   const GridParams* d_lat = nullptr;
@@ -1703,13 +1700,31 @@ int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const f
     seeds = pre->ids;
     d_lat = plan.lat;
   }
-  CutList cut = {nullptr, 0, 0, 0, 0, nullptr, 0};
   if (plan.centres != nullptr && seeds != nullptr) {
-    uint32_t* lists = ws.take<uint32_t>((size_t)launched * CUT_WORDS);
+    uint32_t* lists = ws.take<uint32_t>((size_t)plan.launched * CUT_WORDS);
     if (!lists) { set_error("internal: query workspace too small"); return M2S_ERR_HIP_INTERNAL; }
-    launch_query_cut(st, mesh, seeds, launched, lists, plan.centres, plan.table, d_lat);
-    cut = cut_list_for(mesh.n_nodes, lists, 0, 0, 0, 0, plan.centres);
+    launch_query_cut(st, mesh, seeds, plan.launched, lists, plan.centres, plan.table, d_lat);
+    *lists_out = lists;
+    if (list_words) *list_words = (size_t)plan.launched * CUT_WORDS;
   }
+  *seeds_out = seeds; *d_lat_out = d_lat;
+  return 0;
+}
+
+int launch_query_walk(Arena& ws, hipStream_t st, const DeviceMesh& mesh, const float* d_queries, const QueryPlan& plan,
+                      int mode, int sign_src, int algorithm, float* d_out, int* d_err, const QuerySeeds* pre) {
+  const size_t n_q = plan.n_q;
+  if (n_q == 0) return 0;
+  GridParams g{};
+  const uint32_t nq = (uint32_t)n_q;
+  if (algorithm == 1) return launch_query_brute(st, mesh, d_queries, nq, mode, sign_src, d_out, d_err);
+  const uint32_t launched = plan.launched;
+  const uint32_t *seeds = nullptr, *lists = nullptr;
+  const GridParams* d_lat = nullptr;
+  const int rc = prepare_query_lists(ws, st, mesh, plan, pre, &seeds, &d_lat, &lists);
+  if (rc) return rc;
+  CutList cut = {nullptr, 0, 0, 0, 0, nullptr, 0};
+  if (lists != nullptr) cut = cut_list_for(mesh.n_nodes, lists, 0, 0, 0, 0, plan.centres);
   PacketArgs a;
   a.mesh = mesh; a.g = g; a.qsorted = plan.sorted; a.perm = plan.perm; a.n_q = nq; a.plane = plan.table; a.out = d_out; a.err = d_err; a.n_packets = launched;
   a.seed_in = seeds; a.seed_lattice = d_lat; a.cut = cut;

@@ -1,10 +1,11 @@
-// geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h, sample.hip.h, voxel.hip.h and band.hip.h, for CPU unit tests only
-// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py, tests/test_narrow_band_cpu.py).  Not linked into libm2s_hip.so.
+// geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h, sample.hip.h, voxel.hip.h, band.hip.h and cut_size.hip.h, for CPU unit tests only
+// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py, tests/test_narrow_band_cpu.py, tests/test_cut_size_cpu.py).  Not linked into libm2s_hip.so.
 #include "geo.hip.h"
 #include "ray.hip.h"
 #include "sample.hip.h"
 #include "voxel.hip.h"
 #include "band.hip.h"
+#include "cut_size.hip.h"
 
 using namespace m2s;
 
@@ -28,6 +29,12 @@ void probe_closest_point(const float* p, const float* a, const float* b, const f
 int probe_ray(int axis, const float* o, const float* a, const float* b, const float* c, float* t) {
   return ray_triangle_aligned_rt(axis, mk3(o[0], o[1], o[2]), mk3(a[0], a[1], a[2]), mk3(b[0], b[1], b[2]),
                                  mk3(c[0], c[1], c[2]), t) ? 1 : 0;
+}
+// cut_size.hip.h: k_cut's size test, 1 where the node is small enough for the list
+int probe_cut_small_enough(float R, float half, float emit_radius) { return cut_small_enough(R, half, emit_radius) ? 1 : 0; }
+// ... for n triples at once (out: one byte each)
+void probe_cut_small_enough_n(size_t n, const float* R, const float* half, const float* emit_radius, unsigned char* out) {
+  for (size_t i = 0; i < n; ++i) out[i] = cut_small_enough(R[i], half[i], emit_radius[i]) ? 1 : 0;
 }
 float probe_normal_fold_result(float d2_all, float d2_pos) { return normal_fold_result(d2_all, d2_pos); }
 int probe_approx_eq_abs(float a, float b) { return approx_eq_abs(a, b) ? 1 : 0; }

@@ -92,6 +92,8 @@ void sanitise(Tuning& t) {
   if (t.gather_ahead < -1) t.gather_ahead = -1;
   if (t.band_fetch > 2) t.band_fetch = 2;
   if (t.band_fetch < -1) t.band_fetch = -1;
+  if (t.cut_wave_cap > 99999) t.cut_wave_cap = 99999;   // k_cut's visit caps stay below the per-brick budget of 100 000 opened nodes the kernel
+  if (t.cut_coarse_cap > 99999) t.cut_coarse_cap = 99999;   // once had beside them, so that no setting brings back a case where that budget decided (cut.hip cut_params)
   if (t.leaf_max > 16) t.leaf_max = 16;   // the tree's limit (bvh.hip): a larger wish would differ from every resident tree's size for ever
 }
 

@@ -35,7 +35,7 @@ struct Tuning {
   int cut_coarse = -1;              // M2S_CUT_COARSE   grid cut lists in two levels (a coarse pass per 4 x 4 x 4 bricks first): -1 automatic (from M2S_CUT_COARSE_MIN_WAVES fine waves on), 0 never, 1 always
   uint32_t cut_coarse_min_waves = 40000;   // M2S_CUT_COARSE_MIN_WAVES   fine k_cut waves (blocks of 4 x 4 x 4 bricks) from which the automatic choice takes two levels (512^3: 32 768 waves, a wash; 1024^3: 262 144, - 1.5 %)
   uint32_t cut_coarse_cap = 0;      // M2S_CUT_COARSE_CAP   node visits after which a coarse-level wave emits what it meets; 0: as M2S_CUT_WAVE_CAP
-  uint32_t cut_wave_cap = 0;        // M2S_CUT_WAVE_CAP node visits after which a k_cut wave emits what it meets; 0: max(120, 20 x tree depth)
+  uint32_t cut_wave_cap = 0;        // M2S_CUT_WAVE_CAP node visits after which a k_cut wave emits what it meets; 0: max(120, 20 x tree depth); at most 99 999 (as M2S_CUT_COARSE_CAP: tuning.cpp sanitise)
   // ---- heavy packets (distance.hip "split walk")
   int split = -1;                   // M2S_SPLIT        -1 automatic, 0 never, 1 on, 2 on with the "out of work" flags raised from the start (tests): walks still running when the launch runs dry hand subtrees to other waves
   uint32_t split_budget = 0;        // M2S_SPLIT_BUDGET work units (3 per leaf + 1 per pre-test + 4 per exact evaluation) a walk does before it first looks whether its XCD is running dry; 0: 128
