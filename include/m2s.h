@@ -49,7 +49,7 @@ extern "C" {
 #endif
 
 #define M2S_VERSION_MAJOR 0
-#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface, m2s_band_create / destroy / info / sample / raymarch); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
+#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface, m2s_band_create / destroy / info / sample / raymarch, m2s_band_csg, m2s_band_export, m2s_band_field_info); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
 
 /* Return codes.  The reference panics where this ABI returns a negative code; the Rust shim
  * turns a negative code back into panic!(m2s_last_error()). */
@@ -849,6 +849,61 @@ int m2s_band_sample(const m2s_band* band, const float* points, size_t n_points, 
                     float* normal_out, uint8_t* support_out, const m2s_opts* opts);
 int m2s_band_raymarch(const m2s_band* band, const float* origins, const float* directions, size_t n_rays, const m2s_sample_opts* sopts,
                       float* hit_out, uint32_t* steps_out, float* normal_out, uint8_t* support_out, const m2s_opts* opts);
+
+/* ---- CSG on narrow bands: union, intersection, difference; a handle's lists back out ---------------------------------------------------
+ * m2s_band_csg combines two resident bands on the same grid into a new one without a dense grid: what csgUnion, csgIntersection and
+ * csgDifference are in OpenVDB.  m2s_band_export is the inverse of m2s_band_create, so a combined band reaches m2s_band_isosurface
+ * (mesh booleans: mesh -> band -> CSG -> band isosurface -> mesh).  The result is DEFINED per grid point, to the bit
+ * (tests/band_csg_model.py restates it in numpy).
+ * A handle X stands for the dense grid D'_X above.  Per grid point L:
+ *   actX[L]   its mask bit: L is one of X's cells.
+ *   x         D'_X[L]: the band's value if active, else -X.background_inside if X's inside bit is set, else +X.background_outside.
+ *   sX[L]     actX ? (x < 0) : insideX[L]; the inside bit counts as 0 everywhere when X has no sign mask.
+ * The negation -X (used only to define the difference): values -x (the sign bit flipped), the same active set,
+ *   s_{-X}[L] = actX ? (-x < 0) : !insideX[L], the backgrounds swapped (outside = X's inside, inside = X's outside); D'_{-X} = -D'_X.
+ * With a = D'_A[L] and b = D'_B[L] (all finite; comparisons are IEEE, so -0 == +0):
+ *   M2S_CSG_UNION         pickB = (b < a) || (a == b && !actA[L]);   r = pickB ? b : a   (every bit)
+ *                         active = (actA && !(b < a)) || (actB && !(a < b));   s = sA | sB
+ *   M2S_CSG_INTERSECTION  pickB = (b > a) || (a == b && !actA[L]);   r = pickB ? b : a
+ *                         active = (actA && !(b > a)) || (actB && !(a > b));   s = sA & sB
+ *   M2S_CSG_DIFFERENCE    A \ B = INTERSECTION(A, -B)
+ * A cell is active in the result exactly when an operand that supplies its value is active there; on a tie an active operand
+ * supplies the bits.
+ * The result is a new immutable m2s_band on the same grid and device: the active points ascending, their r, a sign mask equal to s on
+ *   EVERY grid point (a result always has a sign mask), and the backgrounds of `fopts`.  fopts == NULL: the min rule,
+ *   outside = min(A.outside, B*.outside) and inside = min(A.inside, B*.inside), where B* = B, or -B for the difference.  With it
+ *   |D'_R| <= |op(D'_A, D'_B)| on the inactive cells, so sphere tracing stays safe.
+ * Consequence 1: if A and B* have the same two backgrounds, both > 0, and the result gets them too, then D'_R == op(D'_A, D'_B) on
+ *   every grid point, bit for bit (op = the select above, min or max, on the dense grids): an inactive result cell had its value
+ *   supplied by an inactive operand, that is one of the two backgrounds with the sign that s repeats.
+ * Consequence 2: let the true fields D_A, D_B be 1-Lipschitz, each band contain [-W, W] with W above one cell diagonal, and all
+ *   backgrounds be W.  Then D'_X = clamp(D_X, -W, W), and op of the two is clamp(op(D_A, D_B), -W, W), because clamping is monotone.
+ *   op(D_A, D_B) is 1-Lipschitz too, so in a cell its zero level cuts every corner is within one diagonal of a zero: |op| < W there.
+ *   Such a corner's value is not a background, so the operand that supplies it is active: all 8 corners are active in the result.
+ *   m2s_band_isosurface of the exported result therefore equals m2s_grid_isosurface of the dense op(D'_A, D'_B), with n_open == 0.
+ * Caveat: min / max of distance fields has the right zero set and is a lower bound of the distance to it; it is NOT the exact distance
+ *   field of the combined solid (near the seams of a union's inside, of an intersection's outside).  The usual level-set CSG.
+ * m2s_band_csg: always synchronous (one stream synchronisation, for the count).  a == b is legal.  *out = NULL on every failure.
+ *   M2S_ERR_BAD_ARG before any device work: a NULL handle or out; a bad op; handles on different devices; grids that differ in any bit
+ *   of first_cell, cell_size or cell_count; fopts with a struct_size other than sizeof or a negative or non-finite background; an
+ *   m2s_opts.device that is not the handles' (-1 means theirs); algorithm, x_begin, x_end, x_period or peer_out not zero; a bad mem_kind.
+ *   m2s_opts: device, stream / stream_mode, lane.  timings: seed_ms = the call's kernels, n_units = the result's cells.
+ *   m2s_band_info of the result: device_bytes by the formula above for a handle with a sign mask; the allocation itself is sized by
+ *   the bound min(nA + nB, cells) of the result's count.  Nothing sized 4 bytes per grid point is allocated: the work is the index
+ *   words of the operands plus their band cells.
+ * m2s_band_export writes cells_out (ascending L) and distances_out (every bit), `capacity` entries each at least, and inside_bits_out
+ *   in the caller's layout uint32[nx][ny][ceil(nz / 32)] with the bits at k >= nz zero; all zero for a handle without a sign mask.
+ *   Any output may be NULL, not all.  A capacity below the handle's n_cells (m2s_band_info) is M2S_ERR_BAD_ARG and nothing is
+ *   written.  Also M2S_ERR_BAD_ARG before any device work: a NULL handle, and the m2s_opts fields above.  mem_kind covers the three
+ *   outputs.  Always synchronous.  timings: distance_ms = the call's kernels, n_units = n_cells.  Round trips hold bit for bit:
+ *   export(create(lists)) == lists, and a handle recreated from an export answers every query identically.
+ * m2s_band_field_info: the handle's backgrounds (struct_size set to sizeof) and whether it has a sign mask; either output may be NULL. */
+enum m2s_csg_op { M2S_CSG_UNION = 0, M2S_CSG_INTERSECTION = 1, M2S_CSG_DIFFERENCE = 2 };
+int m2s_band_csg(const m2s_band* a, const m2s_band* b, int op, const m2s_band_field_opts* fopts /* NULL = the min rule */,
+                 const m2s_opts* opts, m2s_band** out);
+int m2s_band_export(const m2s_band* band, uint64_t* cells_out, float* distances_out, uint64_t capacity,
+                    uint32_t* inside_bits_out, const m2s_opts* opts);
+int m2s_band_field_info(const m2s_band* band, m2s_band_field_opts* fopts_out, int* has_inside);
 
 /* glTF 2.0 / GLB ingestion (host side) — what the reference client extracts from a file before the merge:
  * mesh_to_sdf_client/src/gltf/mod.rs:56-174 (models keyed by mesh index, one primitive per mesh survives;

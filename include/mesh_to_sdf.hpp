@@ -18,6 +18,7 @@
 //   narrow_band_sdf                 the cells of a grid within a band of the surface and their distances: the dense result, filtered (m2s.h)
 //   sample_grid / raymarch_grid  client draw_raymarching.wgsl  sdf_grid / estimate_normal / sdf_3d on a finished grid (m2s.h)
 //   BandField                    (no counterpart)              the same two queries on a narrow band, no dense grid (m2s.h)
+//   BandField::csg / export_band (no counterpart)              union, intersection, difference of two band fields on the device; a field's lists back out (m2s.h)
 //   grid_isosurface                                            marching-cubes mesh of a level set of a finished grid (no reference counterpart; m2s.h)
 //   band_isosurface                                            the same from a narrow band: cells and distances in, mesh and n_open out,
 //                                                              work proportional to the band (no reference counterpart; m2s.h)
@@ -599,6 +600,8 @@ struct BandSamples : GridSamples {
 struct BandRayMarch : RayMarch {
   std::vector<uint8_t> support;   // per ray: the support of the last sample the march evaluated
 };
+// How BandField::csg combines two fields (m2s_csg_op); Difference is this minus the other.
+enum class CsgOp : int { Union = M2S_CSG_UNION, Intersection = M2S_CSG_INTERSECTION, Difference = M2S_CSG_DIFFERENCE };
 template <class V>
 class BandField {
  public:
@@ -661,7 +664,44 @@ class BandField {
     return r;
   }
 
+  // The union, intersection or difference of two fields on the same grid as a new resident field (m2s_band_csg: min / max of the grids
+  // the bands stand for, per grid point and to the bit; no dense grid, nothing leaves the device).  Without backgrounds the result takes
+  // the smaller of the operands' on each side.  The zero set is the combined solid's; the values are a lower bound of its distance.
+  BandField csg(const BandField& other, CsgOp op) const { return csg_as(other, op, nullptr); }
+  BandField csg(const BandField& other, CsgOp op, float background_outside, float background_inside) const {
+    m2s_band_field_opts fo{};
+    fo.struct_size = sizeof(fo);
+    fo.background_outside = background_outside;
+    fo.background_inside = background_inside;
+    return csg_as(other, op, &fo);
+  }
+  // The field's lists back out (m2s_band_export): cells ascending, distances bit for bit, and `bits` the sign mask in the layout of
+  // Voxels::bits (all zero for a field made without one).  band_isosurface(grid, b.cells, b.distances) meshes it.
+  NarrowBand export_band() const {
+    NarrowBand r;
+    r.count = count();
+    const auto n = grid_.get_cell_count();
+    r.cells.resize(r.count);
+    r.distances.resize(r.count);
+    r.bits.resize(n[0] * n[1] * ((n[2] + 31) / 32));
+    detail::check(m2s_band_export(h_, r.count ? r.cells.data() : nullptr, r.count ? r.distances.data() : nullptr, r.count, r.bits.data(), nullptr));
+    return r;
+  }
+  float background_outside() const { return field_info().background_outside; }
+  float background_inside() const { return field_info().background_inside; }
+
  private:
+  BandField(const Grid<V>& grid, m2s_band* h) : grid_(grid), h_(h) {}
+  BandField csg_as(const BandField& other, CsgOp op, const m2s_band_field_opts* fo) const {
+    m2s_band* h = nullptr;
+    detail::check(m2s_band_csg(h_, other.h_, (int)op, fo, nullptr, &h));
+    return BandField(grid_, h);
+  }
+  m2s_band_field_opts field_info() const {
+    m2s_band_field_opts fo{};
+    detail::check(m2s_band_field_info(h_, &fo, nullptr));
+    return fo;
+  }
   uint64_t info(int which) const {
     uint64_t n = 0, bytes = 0;
     detail::check(m2s_band_info(h_, nullptr, &n, &bytes));

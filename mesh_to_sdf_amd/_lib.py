@@ -15,6 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 M2S_OK = 0
 ERR_BAD_ARG, ERR_NAN, ERR_EMPTY_MESH, ERR_HIP, ERR_IO = -1, -2, -3, -4, -5
 MEM_HOST, MEM_DEVICE = 0, 1
+CSG_UNION, CSG_INTERSECTION, CSG_DIFFERENCE = 0, 1, 2
 
 
 class M2SGrid(C.Structure):
@@ -196,6 +197,9 @@ EXPORTS = [
     "m2s_band_info",
     "m2s_band_sample",
     "m2s_band_raymarch",
+    "m2s_band_csg",
+    "m2s_band_export",
+    "m2s_band_field_info",
     "m2s_merge_instances",
     "m2s_gltf_open",
     "m2s_gltf_instances",
@@ -296,6 +300,9 @@ def _prototypes():
                                       C.POINTER(M2SOpts)]),
         "m2s_band_raymarch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(M2SSampleOpts), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(M2SOpts)]),
+        "m2s_band_csg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts), C.POINTER(C.c_void_p)]),
+        "m2s_band_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(M2SOpts)]),
+        "m2s_band_field_info": (C.c_int, [C.c_void_p, C.POINTER(M2SBandFieldOpts), C.POINTER(C.c_int)]),
         "m2s_merge_instances": (C.c_int, [C.POINTER(M2SInstance), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(M2SOpts)]),
         "m2s_gltf_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(M2SGltfInfo)]),
         "m2s_gltf_instances": (C.c_int, [C.c_void_p, C.POINTER(M2SInstance), C.c_size_t]),

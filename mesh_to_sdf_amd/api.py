@@ -832,7 +832,7 @@ class _GridQuery:
 
     def empty(self, shape, dtype=np.float32):
         if self.device:
-            kind = self.torch.int32 if dtype == np.uint32 else (self.torch.uint8 if dtype == np.uint8 else self.torch.float32)
+            kind = {np.uint32: self.torch.int32, np.uint8: self.torch.uint8, np.uint64: self.torch.int64}.get(dtype, self.torch.float32)
             t = self.torch.empty(shape, dtype=kind, device=self.dev)
             return t, self.ptr(t)
         a = np.empty(shape, dtype)
@@ -1008,6 +1008,27 @@ def remesh(vertices, indices: Topology, grid: Grid, *, iso: float = 0.0, sign_me
     return _remesh(narrow_band_sdf(vertices, indices, grid, isosurface_band(grid, iso), sign_method), iso)
 
 
+def _boolean(mesh_a: "Mesh", mesh_b: "Mesh", op, grid: Grid, sign_method):
+    op = _csg_op(op)
+    w = isosurface_band(grid, 0.0)                    # (interior, exterior): the same width w on both sides at iso = 0
+    with mesh_a.narrow_band_field(grid, w, sign_method, True, background=w) as fa, \
+            mesh_b.narrow_band_field(grid, w, sign_method, True, background=w) as fb, fa.csg(fb, op) as fr:
+        verts, idx, n_open = fr.isosurface(0.0)
+    if n_open != 0:
+        raise M2SError(_lib.ERR_BAD_ARG, f"boolean: the bands are too narrow: {n_open} cells are cut but incomplete")
+    return verts, idx
+
+
+def boolean(vertices_a, indices_a: Topology, vertices_b, indices_b: Topology, op, grid: Grid, *, sign_method: SignMethod = SignMethod.Raycast):
+    """A mesh boolean through level sets, without a dense grid: both meshes to narrow band fields on `grid` (the widths of
+    isosurface_band(grid, 0), both backgrounds that width, the Raycast sign beyond the band), BandField.csg with `op` (a CsgOp or its
+    name: union, intersection, difference = a minus b), then the isosurface at 0.  Where the distance fields are exact the result is
+    grid_isosurface of min / max of the two dense grids clamped to the band width, bit for bit.  Returns (vertices, indices); raises
+    M2SError if a band turns out too narrow (n_open != 0).  The surface is that of the grid's resolution: features below a cell are lost."""
+    with Mesh(vertices_a, indices_a) as ma, Mesh(vertices_b, indices_b) as mb:
+        return _boolean(ma, mb, op, grid, sign_method)
+
+
 def default_background(distances):
     """(inside, outside) backgrounds of a band field made from `distances` alone: outside = max(distances.max(), 0) and
     inside = max(-distances.min(), 0), the largest values known to be lower bounds of |D| beyond the band (a band holds every cell with
@@ -1030,6 +1051,29 @@ def _inside_bits(inside):
     return inside
 
 
+class CsgOp(enum.IntEnum):
+    """include/m2s.h `m2s_csg_op`: how BandField.csg combines two bands."""
+    Union = 0
+    Intersection = 1
+    Difference = 2
+
+
+def _csg_op(op) -> CsgOp:
+    """A CsgOp, its number or its name in any case."""
+    try:
+        return CsgOp[op.capitalize()] if isinstance(op, str) else CsgOp(int(op))
+    except (KeyError, ValueError, TypeError):
+        raise M2SPanic(_lib.ERR_BAD_ARG, f"op = {op!r} is not a CsgOp (union, intersection, difference)") from None
+
+
+def _backgrounds(background):
+    """background: a scalar for both sides, or (inside, outside) -> (inside, outside)."""
+    if np.isscalar(background):
+        return float(background), float(background)
+    bg_in, bg_out = (float(v) for v in background)
+    return bg_in, bg_out
+
+
 class BandField:
     """A narrow band made queryable (include/m2s.h `m2s_band`): the index of the band's cells, its distances and an optional sign mask,
     resident on the device, built once and sampled or ray-marched many times with no dense grid anywhere.  It stands for the dense grid D'
@@ -1041,18 +1085,20 @@ class BandField:
     (or a Voxels / NarrowBand carrying one); None: every cell beyond the band is outside.  background: a scalar or (inside, outside);
     None means default_background(distances).  A zero background stalls a march: a ray that enters the region it fills stops there
     (dist < eps), so give a band that has cells on one side only an explicit background for the other.
+    Two fields on the same grid combine on the device into a third (`csg`, `union`, `intersection`, `difference`, or `a | b`, `a & b`,
+    `a - b`); `to_band` hands a field's lists back as a NarrowBand and `isosurface` meshes it.  `background` is (inside, outside) and
+    `count` the number of cells, for a combined field as the library reports them.
     A context manager; `close` frees the device memory."""
 
     def __init__(self, grid: Grid, cells, distances, *, background=None, inside=None, timings: M2STimings = None):
         self._h = C.c_void_p()
         q = _GridQuery(distances, timings)
+        self._dev = q.dev if q.device else None     # the side the lists came from: where to_band puts them again
         p_c, n = _band_cells(q, cells)
         if background is None:
             bg_in, bg_out = default_background(distances)
-        elif np.isscalar(background):
-            bg_in = bg_out = float(background)
         else:
-            bg_in, bg_out = (float(v) for v in background)
+            bg_in, bg_out = _backgrounds(background)
         p_bits = None
         bits = _inside_bits(inside)
         if bits is not None:
@@ -1138,6 +1184,89 @@ class BandField:
         if q.device and hasattr(q.torch, "uint32"):
             steps = steps.view(q.torch.uint32)
         return (pos, dist, steps, hit) + ((nrm,) if normals else ()) + ((sup,) if support else ())
+
+    @classmethod
+    def _adopt(cls, h, grid: Grid, dev):
+        """A BandField around a handle the library made (a CSG result): count, background and device_bytes as it reports them."""
+        self = cls.__new__(cls)
+        self._h, self.grid, self._dev = h, grid, dev
+        L = _lib.lib()
+        n, nbytes, fo = C.c_uint64(0), C.c_uint64(0), _lib.M2SBandFieldOpts()
+        for rc in (L.m2s_band_info(h, None, C.byref(n), C.byref(nbytes)), L.m2s_band_field_info(h, C.byref(fo), None)):
+            if rc != _lib.M2S_OK:
+                _raise(rc)
+        self.count, self.device_bytes = int(n.value), int(nbytes.value)
+        self.background = (float(fo.background_inside), float(fo.background_outside))
+        return self
+
+    def _side(self, timings=None) -> "_GridQuery":
+        """The options and buffers of a call with no input array, on the side this field's lists came from."""
+        if self._dev is None:
+            return _GridQuery(np.zeros(0, np.float32), timings)
+        import torch
+
+        return _GridQuery(torch.empty(0, dtype=torch.float32, device=self._dev), timings)
+
+    def csg(self, other: "BandField", op, background=None, *, timings: M2STimings = None) -> "BandField":
+        """The union, intersection or difference (self minus other) of two fields on the same grid as a new resident BandField
+        (include/m2s.h m2s_band_csg states the result per grid point, to the bit): min / max of the two grids the bands stand for, active
+        where an active operand supplies the value, with a sign mask on every point.  No dense grid exists on the way and nothing
+        leaves the device.  background: a scalar or (inside, outside); None takes the smaller of the operands' on each side, which keeps
+        sphere tracing safe.  The zero set is the combined solid's; away from it the values are a lower bound of its distance, not
+        the exact distance (the usual level-set CSG)."""
+        op = _csg_op(op)
+        if not isinstance(other, BandField):
+            raise M2SPanic(_lib.ERR_BAD_ARG, "csg: the other operand is not a BandField")
+        q = self._side(timings)
+        fo = None
+        if background is not None:
+            bg_in, bg_out = _backgrounds(background)
+            fo = C.byref(_lib.M2SBandFieldOpts(C.sizeof(_lib.M2SBandFieldOpts), float(np.float32(bg_out)), float(np.float32(bg_in))))
+        h = C.c_void_p()
+        rc = _lib.lib().m2s_band_csg(self._handle(), other._handle(), int(op), fo, C.byref(q.opts), C.byref(h))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        return BandField._adopt(h, self.grid, self._dev)
+
+    def union(self, other: "BandField", background=None) -> "BandField":
+        return self.csg(other, CsgOp.Union, background)
+
+    def intersection(self, other: "BandField", background=None) -> "BandField":
+        return self.csg(other, CsgOp.Intersection, background)
+
+    def difference(self, other: "BandField", background=None) -> "BandField":
+        return self.csg(other, CsgOp.Difference, background)
+
+    def __or__(self, other):
+        return self.csg(other, CsgOp.Union) if isinstance(other, BandField) else NotImplemented
+
+    def __and__(self, other):
+        return self.csg(other, CsgOp.Intersection) if isinstance(other, BandField) else NotImplemented
+
+    def __sub__(self, other):
+        return self.csg(other, CsgOp.Difference) if isinstance(other, BandField) else NotImplemented
+
+    def to_band(self, *, timings: M2STimings = None) -> NarrowBand:
+        """The field's lists back out (include/m2s.h m2s_band_export, the inverse of creating it): a NarrowBand of its cells (ascending),
+        their distances bit for bit and, as `bits`, its sign mask in the layout of Voxels.bits (all zero for a field made without
+        one).  Device tensors for a field made from device tensors, host arrays otherwise."""
+        h = self._handle()
+        q = self._side(timings)
+        nx, ny, nz = (int(v) for v in self.grid.get_cell_count())
+        n = self.count
+        cells, p_c = q.empty(n, np.uint64)
+        dist, p_d = q.empty(n)
+        bits, p_b = q.empty((nx, ny, (nz + 31) // 32), np.uint32)
+        rc = _lib.lib().m2s_band_export(h, p_c, p_d, n, p_b, C.byref(q.opts))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        if q.device and hasattr(q.torch, "uint32"):
+            bits = bits.view(q.torch.uint32)
+        return NarrowBand(cells, dist, bits, n, self.grid)
+
+    def isosurface(self, iso: float = 0.0, *, timings: M2STimings = None):
+        """band_isosurface of the field's own cells and distances: (vertices, indices, n_open)."""
+        return self.to_band().isosurface(iso, timings=timings)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -1633,6 +1762,10 @@ class Mesh:
     def remesh(self, grid: Grid, *, iso: float = 0.0, sign_method: SignMethod = SignMethod.Raycast):
         """remesh on the resident mesh: the same bits as the one-shot function."""
         return _remesh(self.narrow_band_sdf(grid, isosurface_band(grid, iso), sign_method), iso)
+
+    def boolean(self, other: "Mesh", op, grid: Grid, *, sign_method: SignMethod = SignMethod.Raycast):
+        """boolean on two resident meshes: the same bits as the one-shot function."""
+        return _boolean(self, other, op, grid, sign_method)
 
     def sample_sdf_near_surface(self, n: int, sigmas=None, uniform_fraction: float = 0.05, sign: str = "winding", seed: int = 0):
         """sample_sdf_near_surface on this mesh."""

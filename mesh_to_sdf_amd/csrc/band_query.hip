@@ -3,7 +3,7 @@
 // for (its values on the band's cells, a signed background elsewhere), bit for bit, and no array sized by 4 bytes per grid point exists.
 // tests/band_query_model.py restates it in numpy.
 //
-// The handle owns, in device memory:
+// The handle (band_handle.h, shared with band_csg.hip) owns, in device memory:
 //   mask      1 bit per grid point, word L >> 6, bit L & 63            k_biso_mask (isosurface.hip.h: the index m2s_band_isosurface builds)
 //   word_off  per mask word: the list place of its first active point  k_biso_mask; zeroed first, so every word is defined
 //   dist      the band's distances, in list order                      a copy
@@ -29,6 +29,7 @@
 // that choice, 0 / 2 the larger / smaller groups everywhere, 1 the per-corner chain (fetch_chain: mask, then offset, then value, corner
 // after corner), which loses from 512^3 on.
 #include "../../include/m2s.h"
+#include "band_handle.h"
 #include "capi_internal.h"
 #include "common.h"
 #include "grid_query.hip.h"
@@ -40,30 +41,8 @@
 
 #pragma clang fp contract(off)
 
-struct m2s_band {
-  int device = -1;
-  m2s_grid grid{};
-  uint64_t n = 0, total = 0, n_words = 0;
-  uint64_t device_bytes = 0;   // the arrays' sizes as include/m2s.h states them (the allocation adds alignment only)
-  char* block = nullptr;       // one allocation: mask, word_off, [inside], dist
-  const uint64_t* mask = nullptr;
-  const uint64_t* word_off = nullptr;
-  const uint64_t* inside = nullptr;
-  const float* dist = nullptr;
-  float bg_out = 0.0f, bg_in = 0.0f;
-};
-
 namespace m2s {
 namespace {
-
-struct BandDev {
-  const uint64_t* mask;
-  const uint64_t* word_off;
-  const uint64_t* inside;   // nullptr: no sign mask, every inactive cell is outside
-  const float* dist;        // max(n, 1) floats
-  uint64_t n;
-  float bg_out, bg_in_neg;  // +background_outside, -background_inside
-};
 
 // The sign mask from the caller's layout uint32[nx][ny][ceil(nz / 32)] to the mask's (bit L & 63 of word L >> 6).  One lane per output
 // word: the row and k of its first point by one division, then 64 steps along the list order.
@@ -353,30 +332,6 @@ int launch_band_raymarch(hipStream_t st, const GridQuery& q, int mode, const Ban
   if (n == 0) return 0;
   M2S_BQ_DISPATCH(2, launch_march_as, st, q, b, org, dir, n, hit_out, steps_out, normal_out, support_out);
   M2S_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-BandDev dev_of(const m2s_band* h) { return BandDev{h->mask, h->word_off, h->inside, h->dist, h->n, h->bg_out, -h->bg_in}; }
-
-// The m2s_opts fields no band call takes.
-int band_opts_args(const m2s_opts* opts, const char* what) {
-  if (!opts) return 0;
-  if (opts->algorithm != 0 || opts->x_begin != 0 || opts->x_end != 0)
-    return fail(M2S_ERR_BAD_ARG, "m2s_opts.algorithm / x_begin / x_end must be 0 for %s", what);
-  if (opts->struct_size >= sizeof(m2s_opts) && (opts->x_period != 0 || opts->n_peer_out != 0 || opts->peer_out))
-    return fail(M2S_ERR_BAD_ARG, "m2s_opts.x_period / peer_out must be 0 for %s", what);
-  if (opts->mem_kind != M2S_MEM_HOST && opts->mem_kind != M2S_MEM_DEVICE) return fail(M2S_ERR_BAD_ARG, "bad mem_kind");
-  return 0;
-}
-
-// Options of a query on a handle: its device unless the caller names the same one (as a persistent mesh's calls).
-int band_call_opts(const m2s_band* h, const m2s_opts* opts, m2s_opts* o) {
-  *o = m2s_opts{};
-  if (opts) memcpy(o, opts, (opts->struct_size >= sizeof(m2s_opts)) ? sizeof(m2s_opts) : (size_t)M2S_OPTS_V1_SIZE);
-  else o->device = -1;
-  if (o->device < 0) o->device = h->device;
-  if (o->device != h->device) return fail(M2S_ERR_BAD_ARG, "the band lives on device %d, the call asked for %d", h->device, o->device);
-  if (!opts) o->synchronous = 1;
   return 0;
 }
 
