@@ -4,7 +4,7 @@
 // exact minimum comes from launch_query_distance (bit-identical to the grid walks) and the Raycast sign from sign.hip's majority plane.
 //   k_band_count    per triangle: the box of its finite vertices, its reach (band.hip.h) and the three intervals of cells whose axis gap is
 //                   within reach (band_interval: binary searches on the predicate itself); the number of (i, j) columns in them.
-//   the scan        exclusive running sums of the column counts in uint64 (the pattern of voxelize.hip).
+//   the scan        exclusive running sums of the column counts in uint64 (scan.hip.h, as in voxelize.hip).
 //   k_band_raster   one column per lane, grid-stride over the device-resident total.  A lane finds its triangle by a binary search in the
 //                   sums, drops the column if its x and y gaps alone are out of reach, tightens the z interval by what they have spent
 //                   (band_interval again) and by the distance to the triangle's plane (band_plane_interval), and sets that run of bits: one atomicOr per touched word.
@@ -12,13 +12,14 @@
 //   k_band_emit     candidates of rank [begin, end) in ascending L, from the per-tile offsets of launch_voxel_count: their L and centres
 //                   (cell_center: the dense walk's own expression).  Tiles outside the range leave at once.
 //   k_band_filter   per candidate: the plane bit applied (Raycast), -interior <= d <= exterior, the active bit, a flag.
-//   compaction      k_band_flag_sums + k_band_scan_tiles + k_band_compact: flagged cells and distances to a running offset kept on the device,
+//   compaction      k_band_flag_sums + k_scan_tiles + k_band_compact: flagged cells and distances to a running offset kept on the device,
 //                   stable, so ascending chunks give ascending output.
 //   algorithm 1     k_band_dense_mask (one mask word per lane over the dense grid) and k_band_gather.
 #include <algorithm>
 
 #include "common.h"
 #include "geo.hip.h"
+#include "scan.hip.h"
 #include "band.hip.h"
 
 namespace m2s {
@@ -27,36 +28,8 @@ namespace {
 
 __global__ void k_warm_band() {}
 
-constexpr int kThreads = 256;
-constexpr int kScanItems = 16;
-constexpr int kScanTile = kThreads * kScanItems;
-static_assert(kScanTile == MASK_SCAN_TILE, "k_band_emit reads launch_voxel_count's per-tile offsets");
+constexpr int kThreads = kTileThreads;
 constexpr unsigned kRasterBlocks = 4096;
-
-// Exclusive scan over a workgroup of NT threads (64-wide waves); *total = the sum of all.  (voxelize.hip, sample.hip and isosurface.hip have the same.)
-template <int NT>
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t* total) {
-  __shared__ uint64_t wave_sum[NT / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wave_sum[wave] = x;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < NT / 64; ++w) {
-    const uint64_t s = wave_sum[w];
-    if (w < wave) before += s;
-    all += s;
-  }
-  __syncthreads();
-  *total = all;
-  return before + x - v;
-}
 
 __device__ __forceinline__ BandBox load_band_box(const TriRec* __restrict__ tris, uint32_t t) {
   const TriRec& r = tris[t];
@@ -86,55 +59,6 @@ __global__ __launch_bounds__(kThreads) void k_band_count(const TriRec* __restric
     iv[6 * (size_t)t + 2 * m + 1] = hi[m];
   }
   cols[t] = any ? (uint64_t)(hi[0] - lo[0]) * (uint64_t)(hi[1] - lo[1]) : 0;   // < 2^32: a grid face has fewer lines (fill_grid_params)
-}
-
-__device__ __forceinline__ uint64_t tile_items_u64(const uint64_t* __restrict__ src, size_t n, uint64_t (&w)[kScanItems]) {
-  const size_t first = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kScanItems;
-  uint64_t s = 0;
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    w[k] = first + k < n ? src[first + k] : 0;
-    s += w[k];
-  }
-  return s;
-}
-
-__global__ __launch_bounds__(kThreads) void k_band_col_sums(const uint64_t* __restrict__ cols, size_t n, uint64_t* __restrict__ tile_sum) {
-  uint64_t w[kScanItems], all;
-  const uint64_t s = tile_items_u64(cols, n, w);
-  (void)block_exclusive_scan<kThreads>(s, &all);
-  if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
-}
-
-// In-place exclusive scan of the n tile sums in one workgroup; *total = their sum.
-__global__ __launch_bounds__(kThreads) void k_band_scan_tiles(uint64_t* __restrict__ v, uint32_t n, uint64_t* __restrict__ total) {
-  const uint32_t chunk = (n + kThreads - 1) / kThreads;
-  const uint32_t b = min(threadIdx.x * chunk, n), e = min(b + chunk, n);
-  uint64_t s = 0;
-  for (uint32_t i = b; i < e; ++i) s += v[i];
-  uint64_t all;
-  uint64_t run = block_exclusive_scan<kThreads>(s, &all);
-  for (uint32_t i = b; i < e; ++i) {
-    const uint64_t x = v[i];
-    v[i] = run;
-    run += x;
-  }
-  if (threadIdx.x == 0) *total = all;
-}
-
-// S[t] = cols[0] + ... + cols[t - 1];  S[n] is written by the thread that holds the last triangle.
-__global__ __launch_bounds__(kThreads) void k_band_col_scan(const uint64_t* __restrict__ cols, uint32_t n, const uint64_t* __restrict__ tile_off,
-                                                            uint64_t* __restrict__ S) {
-  uint64_t w[kScanItems], all;
-  const uint64_t s = tile_items_u64(cols, n, w);
-  uint64_t run = tile_off[blockIdx.x] + block_exclusive_scan<kThreads>(s, &all);
-  const size_t first = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kScanItems;
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    if (first + k < n) S[first + k] = run;
-    run += w[k];
-    if (first + k + 1 == n) S[n] = run;
-  }
 }
 
 // What bounds this kernel is what bounds k_vox_raster: the binary search in S, the record gather and the scattered
@@ -321,7 +245,6 @@ __global__ __launch_bounds__(kThreads) void k_band_gather(const float* __restric
   if (q < n) d_out[q] = dense[cells[q]];
 }
 
-inline uint32_t tiles_of(size_t n) { return (uint32_t)((n + kScanTile - 1) / kScanTile); }
 inline size_t mask_words(const GridParams& g) { return (size_t)g.n[0] * g.n[1] * g.nzw; }
 
 }  // namespace
@@ -365,9 +288,9 @@ int launch_band_candidates(hipStream_t st, const TriRec* tris, uint32_t n_tris, 
   const uint32_t tiles = tiles_of(n_tris);
   const float gs = band_grid_scale(g);
   hipLaunchKernelGGL(k_band_count, dim3((n_tris + kThreads - 1) / kThreads), dim3(kThreads), 0, st, tris, n_tris, g, r, gs, s.iv, s.cols);
-  hipLaunchKernelGGL(k_band_col_sums, dim3(tiles), dim3(kThreads), 0, st, (const uint64_t*)s.cols, (size_t)n_tris, s.tile_sum);
-  hipLaunchKernelGGL(k_band_scan_tiles, dim3(1), dim3(kThreads), 0, st, s.tile_sum, tiles, s.hdr + 1);
-  hipLaunchKernelGGL(k_band_col_scan, dim3(tiles), dim3(kThreads), 0, st, (const uint64_t*)s.cols, n_tris, (const uint64_t*)s.tile_sum, s.S);
+  hipLaunchKernelGGL(k_tile_sums<false>, dim3(tiles), dim3(kThreads), 0, st, (const void*)s.cols, (size_t)n_tris, s.tile_sum);
+  hipLaunchKernelGGL((k_scan_tiles<kThreads, uint32_t>), dim3(1), dim3(kThreads), 0, st, s.tile_sum, tiles, s.hdr + 1);
+  hipLaunchKernelGGL(k_col_scan<uint32_t>, dim3(tiles), dim3(kThreads), 0, st, (const uint64_t*)s.cols, n_tris, (const uint64_t*)s.tile_sum, s.S);
   hipLaunchKernelGGL(k_band_raster, dim3(kRasterBlocks), dim3(kThreads), 0, st, tris, n_tris, g, r, gs, (const uint32_t*)s.iv, (const uint64_t*)s.S, bits);
   M2S_HIP_CHECK(hipGetLastError());
   return 0;
@@ -389,7 +312,7 @@ int launch_band_filter(hipStream_t st, const GridParams& g, const BandChunk& c, 
   hipLaunchKernelGGL(k_band_filter, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, st, (const uint64_t*)c.cells, c.dist, n, plane, g.nzw, g.n[2],
                      interior, exterior, bits, c.flags);
   hipLaunchKernelGGL(k_band_flag_sums, dim3(tiles), dim3(kThreads), 0, st, (const uint8_t*)c.flags, n, c.tile_sum);
-  hipLaunchKernelGGL(k_band_scan_tiles, dim3(1), dim3(kThreads), 0, st, c.tile_sum, tiles, c.hdr);
+  hipLaunchKernelGGL((k_scan_tiles<kThreads, uint32_t>), dim3(1), dim3(kThreads), 0, st, c.tile_sum, tiles, c.hdr);
   if (cells_out || d_out)
     hipLaunchKernelGGL(k_band_compact, dim3(tiles), dim3(kThreads), 0, st, (const uint8_t*)c.flags, (const uint64_t*)c.cells, (const float*)c.dist, n,
                        (const uint64_t*)c.tile_sum, (const uint64_t*)running, capacity, cells_out, d_out);

@@ -10,7 +10,7 @@
 //                values at word_off + popcount(mask below t) — contiguous runs —, takes the backgrounds by select and evaluates the
 //                rules; two ballots are the result's mask word and sign word.  The unit's popcount goes to unit_cnt, and by one
 //                atomic add to the sum of its GROUP of 16 units.
-//   k_scan_tiles the group sums, one workgroup (isosurface.hip.h); the total is the result's cell count, read by the host.
+//   k_scan_tiles the group sums, one workgroup (scan.hip.h); the total is the result's cell count, read by the host.
 //   k_csg_emit   the same units: the group's base plus the counts of the units before it in the group, then a wave scan of the
 //                result's popcounts, is the result's word_off; the words with active points are taken one at a time as above and
 //                lane t stores r at word_off + rank.
@@ -255,7 +255,7 @@ void launch_csg_as(hipStream_t st, const BandDev& A, const BandDev& B, uint64_t 
   const uint64_t n_groups = (n_units + kCsgGroup - 1) / kCsgGroup;
   hipLaunchKernelGGL((k_csg_mask<OP, NEG>), dim3(blocks), dim3(kCsgThreads), 0, st, A, B, A.bg_out, A.bg_in_neg, B.bg_out, B.bg_in_neg, n_words, total,
                      mask, inside, unit_cnt, group_sum);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kScanThreads), 0, st, group_sum, n_groups, d_total);
+  hipLaunchKernelGGL((k_scan_tiles<kScanThreads, uint64_t>), dim3(1), dim3(kScanThreads), 0, st, group_sum, n_groups, d_total);
   hipLaunchKernelGGL((k_csg_emit<OP, NEG>), dim3(blocks), dim3(kCsgThreads), 0, st, A, B, A.bg_out, A.bg_in_neg, B.bg_out, B.bg_in_neg, n_words,
                      (const uint64_t*)mask, (const uint32_t*)unit_cnt, (const uint64_t*)group_sum, word_off, dist, cap);
 }

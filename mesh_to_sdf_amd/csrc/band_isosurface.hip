@@ -21,7 +21,7 @@
 // places and outputs share cache lines.  Measured on k_biso_info at 1024^3: 1982 -> 299 us.
 // Every kernel after the first leaves at once when the flag is raised, so a list that is not ascending or runs past the grid is never used
 // as an index: k_biso_mask itself writes only at L < total.
-// Shared with isosurface.hip through isosurface.hip.h: the table, IsoGrid, the workgroup scan, decode, k_scan_tiles, active_index; and with
+// Shared with isosurface.hip through isosurface.hip.h: the table, IsoGrid, decode, active_index, and scan.hip.h's workgroup scan and k_scan_tiles; and with
 // band_query.hip (the resident index of m2s_band_create): k_biso_mask and its flags, which live there too.  Copied
 // from it, because there they are written into the bodies of kernels that read a dense grid: the vertex arithmetic of k_iso_vertices
 // (operation for operation, under the same fp contract pragma), the triangle loop of k_iso_triangles and the grid checks of iso_args.
@@ -278,8 +278,8 @@ int m2s_band_isosurface(const m2s_grid* grid, const uint64_t* cells, const float
                        word_off, reinterpret_cast<uint32_t*>(d_hdr));
     hipLaunchKernelGGL(k_biso_info, dim3((unsigned)n_blk), dim3(kItemThreads), 0, c.stream, g, dc, dd, n, (const uint64_t*)mask, (const uint64_t*)word_off,
                        flag, info, vsum, tsum, reinterpret_cast<unsigned long long*>(d_hdr + 3));
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kScanThreads), 0, c.stream, vsum, n_blk, d_hdr + 1);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kScanThreads), 0, c.stream, tsum, n_blk, d_hdr + 2);
+    hipLaunchKernelGGL((k_scan_tiles<kScanThreads, uint64_t>), dim3(1), dim3(kScanThreads), 0, c.stream, vsum, n_blk, d_hdr + 1);
+    hipLaunchKernelGGL((k_scan_tiles<kScanThreads, uint64_t>), dim3(1), dim3(kScanThreads), 0, c.stream, tsum, n_blk, d_hdr + 2);
     M2S_HIP_CHECK(hipGetLastError());
     M2S_HIP_CHECK(hipMemcpyAsync(hdr, d_hdr, 32, hipMemcpyDeviceToHost, c.stream));
     M2S_HIP_CHECK(hipStreamSynchronize(c.stream));

@@ -15,7 +15,8 @@
 //   k_iso_triangles  per active cell: its triangles; an edge owned by another point finds that point's index from the mask word
 //                    offsets, and its vertex id is the owner's first id plus the axis's rank among the owner's flags.
 // 64-bit point indices throughout (a 1040 x 1024 x 1024 grid has byte offsets beyond 2^32).
-// The table, IsoGrid, the workgroup scan, decode, k_scan_tiles and active_index live in isosurface.hip.h, which band_isosurface.hip shares.
+// The table, IsoGrid, decode and active_index live in isosurface.hip.h, which band_isosurface.hip shares; the workgroup scan and
+// k_scan_tiles in scan.hip.h.
 #include "../../include/m2s.h"
 #include "capi_internal.h"
 #include "common.h"
@@ -307,7 +308,7 @@ int m2s_grid_isosurface(const m2s_grid* grid, const float* distances, float iso,
     M2S_HIP_CHECK(hipMemsetAsync(d_hdr, 0, 32, c.stream));
     hipLaunchKernelGGL(k_iso_classify, dim3((unsigned)n_tiles), dim3(kClassifyThreads), 0, c.stream, g, d, mask, tiles,
                        reinterpret_cast<uint32_t*>(d_hdr + 1));
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kScanThreads), 0, c.stream, tiles, n_tiles, d_hdr);
+    hipLaunchKernelGGL((k_scan_tiles<kScanThreads, uint64_t>), dim3(1), dim3(kScanThreads), 0, c.stream, tiles, n_tiles, d_hdr);
     M2S_HIP_CHECK(hipGetLastError());
     M2S_HIP_CHECK(hipMemcpyAsync(hdr, d_hdr, 16, hipMemcpyDeviceToHost, c.stream));
     M2S_HIP_CHECK(hipStreamSynchronize(c.stream));
@@ -327,8 +328,8 @@ int m2s_grid_isosurface(const m2s_grid* grid, const float* distances, float iso,
     if (n_act) {
       hipLaunchKernelGGL(k_iso_compact, dim3((unsigned)n_tiles), dim3(kTile / 64), 0, c.stream, mask, n_words, tiles, act, word_off);
       hipLaunchKernelGGL(k_iso_info, dim3((unsigned)n_blk), dim3(kItemThreads), 0, c.stream, g, d, act, n_act, info, vsum, tsum);
-      hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kScanThreads), 0, c.stream, vsum, n_blk, d_hdr + 2);
-      hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kScanThreads), 0, c.stream, tsum, n_blk, d_hdr + 3);
+      hipLaunchKernelGGL((k_scan_tiles<kScanThreads, uint64_t>), dim3(1), dim3(kScanThreads), 0, c.stream, vsum, n_blk, d_hdr + 2);
+      hipLaunchKernelGGL((k_scan_tiles<kScanThreads, uint64_t>), dim3(1), dim3(kScanThreads), 0, c.stream, tsum, n_blk, d_hdr + 3);
       M2S_HIP_CHECK(hipGetLastError());
       M2S_HIP_CHECK(hipMemcpyAsync(hdr + 2, d_hdr + 2, 16, hipMemcpyDeviceToHost, c.stream));
       M2S_HIP_CHECK(hipStreamSynchronize(c.stream));

@@ -1,11 +1,13 @@
 // isosurface.hip.h — what the two marching-cubes extractors share: isosurface.hip (m2s_grid_isosurface, a dense grid) and
 // band_isosurface.hip (m2s_band_isosurface, a narrow band).  Moved here from isosurface.hip unchanged: the table, the grid
-// description, the workgroup scan, the point decode, the scan of block sums and the rank of an active point from the mask.
+// description, the point decode and the rank of an active point from the mask; the workgroup scan and the scan of block sums
+// (k_scan_tiles<kScanThreads, uint64_t>) come from scan.hip.h.
 // band_query.hip (m2s_band_create) builds the same index of a band as band_isosurface.hip: k_biso_mask and its flags are here for both.
 // Everything is in an unnamed namespace: each translation unit that includes this has its own copy (of the __constant__ table too).
 #pragma once
 #include "../../include/m2s.h"
 #include "common.h"
+#include "scan.hip.h"
 
 #define M2S_ISO_TABLE static __constant__ const
 #include "isosurface_table.h"
@@ -13,7 +15,7 @@
 namespace m2s {
 namespace {
 
-constexpr int kScanThreads = 1024;
+constexpr int kScanThreads = 1024;   // the one workgroup that scans block sums
 constexpr int kItemThreads = 256;
 constexpr int kItemsPerThread = 16;
 constexpr int kItemBlock = kItemThreads * kItemsPerThread;   // active points per k_iso_info / vertices / triangles workgroup
@@ -26,31 +28,6 @@ struct IsoGrid {
   float iso;
 };
 
-// Exclusive scan over a workgroup of NT threads (64-wide waves); *total = the sum of all.
-template <int NT>
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t* total) {
-  __shared__ uint64_t wave_sum[NT / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wave_sum[wave] = x;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < NT / 64; ++w) {
-    const uint64_t s = wave_sum[w];
-    if (w < wave) before += s;
-    all += s;
-  }
-  __syncthreads();   // wave_sum may be reused by the caller's next scan
-  *total = all;
-  return before + x - v;
-}
-
 struct Pt {
   uint64_t i, j, k;
 };
@@ -62,22 +39,6 @@ __device__ __forceinline__ Pt decode(const IsoGrid& g, uint64_t L) {
   p.j = r / g.n[2];
   p.k = r - p.j * g.n[2];
   return p;
-}
-
-// In-place exclusive scan of n counts in one workgroup; *total = their sum.
-__global__ void __launch_bounds__(kScanThreads) k_scan_tiles(uint64_t* __restrict__ v, uint64_t n, uint64_t* __restrict__ total) {
-  const uint64_t chunk = (n + kScanThreads - 1) / kScanThreads;
-  const uint64_t b = threadIdx.x * chunk, e = b + chunk < n ? b + chunk : n;
-  uint64_t s = 0;
-  for (uint64_t i = b; i < e; ++i) s += v[i];
-  uint64_t all;
-  uint64_t run = block_exclusive_scan<kScanThreads>(s, &all);
-  for (uint64_t i = b; i < e; ++i) {
-    const uint64_t x = v[i];
-    v[i] = run;
-    run += x;
-  }
-  if (threadIdx.x == 0) *total = all;
 }
 
 // The index of active point L in the active list: its mask word's offset plus the active points before it in that word.

@@ -7,7 +7,7 @@
 //                   one-shot call reads the caller's vertices and indices (no tree is built), a persistent mesh reads its resident
 //                   `corners` through `slot_of`.
 //   the table       w_t = floor(A_t 2^(37 - e)) and C = their inclusive running sums in uint64, by the two-level pattern of
-//                   isosurface.hip: k_weight_sums (one sum per tile of 4096 triangles), k_scan_tiles (the tile sums, one workgroup;
+//                   scan.hip.h: k_weight_sums (one sum per tile of 4096 triangles), k_weight_scan_tiles (the tile sums, one workgroup;
 //                   its total is W), k_weight_scan (each tile again, now with its offset).  At the limit of 2^25 triangles that is
 //                   8192 tiles, 32 per thread of the middle pass.  k_table_top then copies an evenly strided SAMPLE_TOP entries of C.
 //                   The sums are integers: any order gives the same table.
@@ -26,6 +26,7 @@
 #include "common.h"
 #include "geo.hip.h"
 #include "sample.hip.h"
+#include "scan.hip.h"
 
 namespace m2s {
 
@@ -35,35 +36,8 @@ namespace {
 
 __global__ void k_warm_sample() {}
 
-constexpr int kThreads = 256;
-constexpr int kScanItems = 16;
-constexpr int kScanTile = kThreads * kScanItems;   // triangles per tile of the table's two outer passes
+constexpr int kThreads = kTileThreads;
 constexpr int kSampleIters = 8;                    // samples per lane of k_sample: one copy of `top` serves 2048 samples
-
-// Exclusive scan over a workgroup of NT threads (64-wide waves); *total = the sum of all.  (isosurface.hip has the same.)
-template <int NT>
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t* total) {
-  __shared__ uint64_t wave_sum[NT / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wave_sum[wave] = x;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < NT / 64; ++w) {
-    const uint64_t s = wave_sum[w];
-    if (w < wave) before += s;
-    all += s;
-  }
-  __syncthreads();
-  *total = all;
-  return before + x - v;
-}
 
 __device__ __forceinline__ uint32_t load_index(const void* idx, int index_bytes, size_t i) {
   if (idx == nullptr) return (uint32_t)i;
@@ -93,7 +67,7 @@ __device__ __forceinline__ bool load_triangle(const SampleSrc& s, uint32_t t, f3
   return true;
 }
 
-// hdr[0]: the bits of Amax (cleared by the launcher);  hdr[2], hdr[3]: W, written by k_scan_tiles.
+// hdr[0]: the bits of Amax (cleared by the launcher);  hdr[2], hdr[3]: W, written by k_weight_scan_tiles.
 __global__ __launch_bounds__(kThreads) void k_tri_area(SampleSrc src, float* __restrict__ A, uint32_t* __restrict__ hdr, int* __restrict__ err) {
   __shared__ uint32_t wave_max[kThreads / 64];
   const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
@@ -138,20 +112,11 @@ __global__ __launch_bounds__(kThreads) void k_weight_sums(const float* __restric
   if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
 }
 
-// In-place exclusive scan of the n tile sums in one workgroup; their total is W.
-__global__ __launch_bounds__(kThreads) void k_scan_tiles(uint64_t* __restrict__ v, uint32_t n, uint32_t* __restrict__ hdr) {
+// The tile sums scanned in place by one workgroup; their total is W.
+__global__ __launch_bounds__(kThreads) void k_weight_scan_tiles(uint64_t* __restrict__ v, uint32_t n, uint32_t* __restrict__ hdr) {
   if (hdr[0] == 0u) return;
-  const uint32_t chunk = (n + kThreads - 1) / kThreads;
-  const uint32_t b = min(threadIdx.x * chunk, n), e = min(b + chunk, n);
-  uint64_t s = 0;
-  for (uint32_t i = b; i < e; ++i) s += v[i];
   uint64_t all;
-  uint64_t run = block_exclusive_scan<kThreads>(s, &all);
-  for (uint32_t i = b; i < e; ++i) {
-    const uint64_t x = v[i];
-    v[i] = run;
-    run += x;
-  }
+  scan_tiles_in_place<kThreads, uint32_t>(v, n, &all);
   if (threadIdx.x == 0) *reinterpret_cast<uint64_t*>(hdr + 2) = all;
 }
 
@@ -265,12 +230,12 @@ uint32_t sample_top_shift(size_t n_tris) {
 
 size_t sample_table_bytes(size_t n_tris) { return (n_tris * 8 + 255) / 256 * 256 + SAMPLE_TOP * 8 + 256; }
 size_t sample_scratch_bytes(size_t n_tris) {
-  const size_t tiles = (n_tris + kScanTile - 1) / kScanTile;
+  const size_t tiles = tiles_of(n_tris);
   return (n_tris * 4 + 255) / 256 * 256 + (tiles * 8 + 255) / 256 * 256 + 512;
 }
 
 int sample_table_carve(Arena& table, Arena& scratch, size_t n_tris, SampleTable* tb) {
-  const size_t tiles = (n_tris + kScanTile - 1) / kScanTile;
+  const size_t tiles = tiles_of(n_tris);
   tb->C = table.take<uint64_t>(n_tris);
   tb->top = table.take<uint64_t>(SAMPLE_TOP);
   tb->hdr = table.take<uint32_t>(4);
@@ -280,12 +245,12 @@ int sample_table_carve(Arena& table, Arena& scratch, size_t n_tris, SampleTable*
 }
 
 int launch_sample_table(hipStream_t st, const SampleSrc& src, const SampleTable& tb, int* d_err) {
-  const uint32_t n = src.n_tris, tiles = (n + kScanTile - 1) / kScanTile, shift = sample_top_shift(n);
+  const uint32_t n = src.n_tris, tiles = tiles_of(n), shift = sample_top_shift(n);
   const uint32_t n_top = (uint32_t)(((size_t)n + ((size_t)1 << shift) - 1) >> shift);
   M2S_HIP_CHECK(hipMemsetAsync(tb.hdr, 0, 16, st));
   hipLaunchKernelGGL(k_tri_area, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, st, src, tb.A, tb.hdr, d_err);
   hipLaunchKernelGGL(k_weight_sums, dim3(tiles), dim3(kThreads), 0, st, tb.A, n, tb.hdr, tb.tile_sum);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kThreads), 0, st, tb.tile_sum, tiles, tb.hdr);
+  hipLaunchKernelGGL(k_weight_scan_tiles, dim3(1), dim3(kThreads), 0, st, tb.tile_sum, tiles, tb.hdr);
   hipLaunchKernelGGL(k_weight_scan, dim3(tiles), dim3(kThreads), 0, st, tb.A, n, tb.hdr, tb.tile_sum, tb.C);
   hipLaunchKernelGGL(k_table_top, dim3((n_top + kThreads - 1) / kThreads), dim3(kThreads), 0, st, tb.C, n, shift, n_top, tb.hdr, tb.top);
   M2S_HIP_CHECK(hipGetLastError());

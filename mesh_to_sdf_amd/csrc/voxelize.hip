@@ -6,7 +6,7 @@
 //                   the clause's own operations, so the candidate box is exact however far the mesh is from the origin) and the number
 //                   of (i, j) columns in them, 0 when any interval is empty or a coordinate is not finite.
 //   the scan        exclusive running sums S of the column counts in uint64: k_tile_sums, k_scan_tiles, k_col_scan (the two-level
-//                   pattern of sample.hip); S[n_tris] = the number of columns.
+//                   pattern of scan.hip.h); S[n_tris] = the number of columns.
 //   k_vox_raster    one column per lane, grid-stride over S[n_tris] (read on the device: no trip to the host).  A lane finds its triangle by
 //                   a binary search in S — neighbouring lanes take neighbouring columns of the same few triangles, so the loads coalesce —
 //                   evaluates the three cross axes with m = z once (the x and y box clauses hold by construction of the intervals), and on
@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "geo.hip.h"
+#include "scan.hip.h"
 #include "voxel.hip.h"
 
 namespace m2s {
@@ -30,36 +31,8 @@ namespace {
 
 __global__ void k_warm_voxelize() {}
 
-constexpr int kThreads = 256;
-constexpr int kScanItems = 16;
-constexpr int kScanTile = kThreads * kScanItems;
-static_assert(kScanTile == MASK_SCAN_TILE, "common.h names the tile of launch_voxel_count's offsets");
+constexpr int kThreads = kTileThreads;
 constexpr unsigned kRasterBlocks = 4096;   // 16 workgroups per CU's worth of grid-stride lanes
-
-// Exclusive scan over a workgroup of NT threads (64-wide waves); *total = the sum of all.  (sample.hip and isosurface.hip have the same.)
-template <int NT>
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t* total) {
-  __shared__ uint64_t wave_sum[NT / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wave_sum[wave] = x;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < NT / 64; ++w) {
-    const uint64_t s = wave_sum[w];
-    if (w < wave) before += s;
-    all += s;
-  }
-  __syncthreads();
-  *total = all;
-  return before + x - v;
-}
 
 __device__ __forceinline__ VoxTri load_vox_tri(const TriRec* __restrict__ tris, uint32_t t) {
   const TriRec& r = tris[t];
@@ -85,62 +58,6 @@ __global__ __launch_bounds__(kThreads) void k_vox_count(const TriRec* __restrict
     iv[6 * (size_t)t + 2 * m + 1] = hi[m];
   }
   cols[t] = any ? (uint64_t)(hi[0] - lo[0]) * (uint64_t)(hi[1] - lo[1]) : 0;   // < 2^32: a grid face has fewer lines (fill_grid_params)
-}
-
-// What the two scans add up: column counts, or the set bits of mask words.
-template <bool POPC>
-__device__ __forceinline__ uint64_t scan_item(const void* __restrict__ src, size_t i) {
-  return POPC ? (uint64_t)__popc(static_cast<const uint32_t*>(src)[i]) : static_cast<const uint64_t*>(src)[i];
-}
-template <bool POPC>
-__device__ __forceinline__ uint64_t tile_items(const void* __restrict__ src, size_t n, uint64_t (&w)[kScanItems]) {
-  const size_t first = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kScanItems;
-  uint64_t s = 0;
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    w[k] = first + k < n ? scan_item<POPC>(src, first + k) : 0;
-    s += w[k];
-  }
-  return s;
-}
-
-template <bool POPC>
-__global__ __launch_bounds__(kThreads) void k_tile_sums(const void* __restrict__ src, size_t n, uint64_t* __restrict__ tile_sum) {
-  uint64_t w[kScanItems], all;
-  const uint64_t s = tile_items<POPC>(src, n, w);
-  (void)block_exclusive_scan<kThreads>(s, &all);
-  if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
-}
-
-// In-place exclusive scan of the n tile sums in one workgroup; *total = their sum.
-__global__ __launch_bounds__(kThreads) void k_scan_tiles(uint64_t* __restrict__ v, uint32_t n, uint64_t* __restrict__ total) {
-  const uint32_t chunk = (n + kThreads - 1) / kThreads;
-  const uint32_t b = min(threadIdx.x * chunk, n), e = min(b + chunk, n);
-  uint64_t s = 0;
-  for (uint32_t i = b; i < e; ++i) s += v[i];
-  uint64_t all;
-  uint64_t run = block_exclusive_scan<kThreads>(s, &all);
-  for (uint32_t i = b; i < e; ++i) {
-    const uint64_t x = v[i];
-    v[i] = run;
-    run += x;
-  }
-  if (threadIdx.x == 0) *total = all;
-}
-
-// S[t] = cols[0] + ... + cols[t - 1];  S[n] is written by the thread that holds the last triangle.
-__global__ __launch_bounds__(kThreads) void k_col_scan(const uint64_t* __restrict__ cols, uint32_t n, const uint64_t* __restrict__ tile_off,
-                                                       uint64_t* __restrict__ S) {
-  uint64_t w[kScanItems], all;
-  const uint64_t s = tile_items<false>(cols, n, w);
-  uint64_t run = tile_off[blockIdx.x] + block_exclusive_scan<kThreads>(s, &all);
-  const size_t first = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kScanItems;
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    if (first + k < n) S[first + k] = run;
-    run += w[k];
-    if (first + k + 1 == n) S[n] = run;
-  }
 }
 
 __global__ __launch_bounds__(kThreads) void k_vox_raster(const TriRec* __restrict__ tris, uint32_t n_tris, GridParams g,
@@ -253,7 +170,6 @@ __global__ __launch_bounds__(kThreads) void k_emit_cells(const uint32_t* __restr
   }
 }
 
-inline uint32_t tiles_of(size_t n) { return (uint32_t)((n + kScanTile - 1) / kScanTile); }
 inline size_t mask_words(const GridParams& g) { return (size_t)g.n[0] * g.n[1] * g.nzw; }
 inline uint64_t grid_cells(const GridParams& g) { return (uint64_t)g.n[0] * g.n[1] * g.n[2]; }
 
@@ -289,8 +205,8 @@ int launch_voxelize_surface(hipStream_t st, const TriRec* tris, uint32_t n_tris,
     const uint32_t tiles = tiles_of(n_tris);
     hipLaunchKernelGGL(k_vox_count, dim3((n_tris + kThreads - 1) / kThreads), dim3(kThreads), 0, st, tris, n_tris, g, s.iv, s.cols);
     hipLaunchKernelGGL(k_tile_sums<false>, dim3(tiles), dim3(kThreads), 0, st, (const void*)s.cols, (size_t)n_tris, s.tile_sum);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kThreads), 0, st, s.tile_sum, tiles, s.hdr + 1);
-    hipLaunchKernelGGL(k_col_scan, dim3(tiles), dim3(kThreads), 0, st, (const uint64_t*)s.cols, n_tris, (const uint64_t*)s.tile_sum, s.S);
+    hipLaunchKernelGGL((k_scan_tiles<kThreads, uint32_t>), dim3(1), dim3(kThreads), 0, st, s.tile_sum, tiles, s.hdr + 1);
+    hipLaunchKernelGGL(k_col_scan<uint32_t>, dim3(tiles), dim3(kThreads), 0, st, (const uint64_t*)s.cols, n_tris, (const uint64_t*)s.tile_sum, s.S);
     hipLaunchKernelGGL(k_vox_raster, dim3(kRasterBlocks), dim3(kThreads), 0, st, tris, n_tris, g, (const uint32_t*)s.iv, (const uint64_t*)s.S, bits);
   }
   M2S_HIP_CHECK(hipGetLastError());
@@ -309,7 +225,7 @@ int launch_voxel_count(hipStream_t st, const GridParams& g, const uint32_t* bits
   const size_t words = mask_words(g);
   const uint32_t tiles = tiles_of(words);
   hipLaunchKernelGGL(k_tile_sums<true>, dim3(tiles), dim3(kThreads), 0, st, (const void*)bits, words, s.tile_sum);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kThreads), 0, st, s.tile_sum, tiles, s.hdr);
+  hipLaunchKernelGGL((k_scan_tiles<kThreads, uint32_t>), dim3(1), dim3(kThreads), 0, st, s.tile_sum, tiles, s.hdr);
   M2S_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -244,6 +244,27 @@ def test_blob_100k_against_the_dense_filter(blob100k, sign):
         _check(m.narrow_band_sdf(grid, band, sign), D, band, grid, "blob-100k, Mesh")
 
 
+def test_more_scan_tiles_than_threads():
+    """1040 x 1010 x 8 cells are 1 050 400 mask words, 257 scan tiles: every thread of the one workgroup that scans the candidates' tile
+    sums walks two of them, and the emit kernel reads the offsets of all 257.  Algorithm 1 takes its mask from the dense grid."""
+    v, idx = meshes.blob(12, 9)
+    dv, di = _dev(v, idx)
+    shape = (1040, 1010, 8)
+    grid = _grid_of(v, shape)
+    topo = Topology.TriangleList(di)
+    band = _band(grid, (1.0, 1.0))
+    fast = narrow_band_sdf(dv, topo, grid, band, SignMethod.Raycast)
+    slow = narrow_band_sdf(dv, topo, grid, band, SignMethod.Raycast, algorithm=1)
+    cells = _np(fast.cells).astype(np.uint64)
+    n_tiles, held = vm.scan_tiles(cells, shape)
+    assert n_tiles > 256, n_tiles
+    even = held[held % 2 == 0]
+    assert np.isin(even + 1, held).any(), "no thread of the scan holds two tiles with candidates"
+    assert fast.count == slow.count == cells.size > 0
+    assert np.array_equal(cells, _np(slow.cells).astype(np.uint64))
+    assert np.array_equal(_np(fast.distances).view(np.uint32), _np(slow.distances).view(np.uint32))
+
+
 def test_suzanne_96_leaves_the_all_pairs_branch(cases):
     """96^3 cells: a chunk of candidates times suzanne's triangles is past the all-pairs limit of the query path (M2S_BRUTE_MAX: 1.2e8 pairs
     without rays), so the tree is walked; with the limit forced to 0 and with the lane walk forced the outputs are the same."""

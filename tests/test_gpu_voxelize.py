@@ -129,6 +129,29 @@ def test_default_equals_all_pairs(blob100k, name, count):
     assert torch.equal(fast.occupancy, slow.occupancy) and torch.equal(fast.bits.view(torch.int32), slow.bits.view(torch.int32))
 
 
+BIG = (1040, 1010, 8)                                                          # one mask word per row: 1 050 400 words, 257 scan tiles
+
+
+def test_more_scan_tiles_than_threads():
+    """The scan of the tile sums is one workgroup of 256 threads: with 257 tiles every thread walks two sums.  The cells come through the
+    tile offsets and the occupancy does not, so the two check each other; algorithm 1 checks both."""
+    v, idx = meshes.blob(12, 9)
+    dv, di = _dev(v, idx)
+    grid = _grid_of(v, BIG)
+    topo = Topology.TriangleList(di)
+    fast = voxelize(dv, topo, grid, bits=True, cells=True)
+    slow = voxelize(dv, topo, grid, bits=True, algorithm=1)
+    occ = _np(fast.occupancy).reshape(-1)
+    want_cells = np.flatnonzero(occ).astype(np.uint64)
+    n_tiles, held = vm.scan_tiles(want_cells, BIG)
+    assert n_tiles > 256, n_tiles
+    even = held[held % 2 == 0]
+    assert np.isin(even + 1, held).any(), "no thread of the scan holds two tiles with set cells"
+    assert torch.equal(fast.occupancy, slow.occupancy) and torch.equal(fast.bits.view(torch.int32), slow.bits.view(torch.int32))
+    assert np.array_equal(_np(fast.cells).astype(np.uint64), want_cells)
+    assert fast.count == slow.count == int(occ.sum()) > 0
+
+
 # ---- 2. the outputs agree with each other -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("solid", [False, True], ids=["surface", "solid"])
 def test_outputs_agree_with_each_other(cases, solid):

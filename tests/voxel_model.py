@@ -125,6 +125,16 @@ def unpack_bits(bits, nz):
     return b.reshape(bits.shape[0], bits.shape[1], -1)[:, :, :nz].astype(np.uint8)
 
 
+def scan_tiles(cells, count, tile=4096):
+    """(the number of tiles of `tile` mask words in a grid of `count` cells, the sorted tiles that hold any of the flat cell indices
+    `cells`): the tiles whose sums the library scans when it counts or lists the set cells of a mask."""
+    cells = np.asarray(cells).astype(np.int64)
+    nz = int(count[2])
+    nzw = (nz + 31) // 32
+    words = int(count[0]) * int(count[1]) * nzw
+    return -(-words // tile), np.unique(((cells // nz) * nzw + (cells % nz) // 32) // tile)
+
+
 def classify64(tris, first, size, count, rel=2.0 ** -20):
     """(sure_in, sure_out) bool[nx, ny, nz]: the clauses in float64 on the exact products, each compared with a margin of `rel` times
     the magnitude of its terms.  sure_in: some triangle passes every clause by the margin; sure_out: every triangle misses some clause by

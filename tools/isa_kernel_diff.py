@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Compares the per-kernel gfx950 instruction streams of hipcc -S listings, kernel by kernel, by symbol name.
 
-usage: tools/isa_kernel_diff.py <before.s> <after.s>
-       tools/isa_kernel_diff.py <before.s> ... -- <after.s> ...
+usage: tools/isa_kernel_diff.py [--map OLD=NEW]... <before.s> <after.s>
+       tools/isa_kernel_diff.py [--map OLD=NEW]... <before.s> ... -- <after.s> ...
 
 Each side is one listing or several (code that moved between translation units: a kernel's symbol does not depend on the
 file that defines it); the kernels of a side's listings are taken together.
@@ -11,7 +11,12 @@ A kernel's body is every instruction from its symbol to its .Lfunc_end label, wi
 local labels (.LBB*, .Ltmp*) renamed by order of appearance, so that code that only moved inside the file
 compares equal; its .amdhsa_* descriptor (registers, LDS, scratch) is compared as well.  Prints one line per
 kernel that differs, one per kernel present on one side only, and a summary; exit status 1 when anything
-differs.  Listings are made with the Makefile's FLAGS, e.g.
+differs.
+
+--map OLD=NEW pairs a renamed kernel: OLD is a substring of exactly one symbol before, NEW of exactly one after (mangled names:
+"k_scan_tilesILi256EjE" picks k_scan_tiles<256, uint32_t>), and the two are compared as one kernel, body and descriptor.
+
+Listings are made with the Makefile's FLAGS, e.g.
 
   hipcc $(FLAGS) --cuda-device-only -S distance.hip -o distance.s
 """
@@ -41,7 +46,7 @@ def kernels(path):
             if ".end_amdhsa_kernel" in l:
                 break
             desc.append(l.strip())
-        out[name] = (body, desc)
+        out[name] = (body, desc)   # desc starts after the .amdhsa_kernel line: it does not hold the name
     return out
 
 
@@ -55,13 +60,31 @@ def side(paths):
     return out
 
 
+def one_symbol(names, sub, which):
+    hits = [n for n in names if sub in n]
+    if len(hits) != 1:
+        sys.exit("--map: '%s' matches %d symbols %s, not one: %s" % (sub, len(hits), which, ", ".join(hits)))
+    return hits[0]
+
+
 def main():
     args = sys.argv[1:]
+    maps = []
+    while "--map" in args:
+        i = args.index("--map")
+        if i + 1 >= len(args) or "=" not in args[i + 1]:
+            sys.exit(__doc__)
+        maps.append(args[i + 1].split("=", 1))
+        del args[i:i + 2]
     cut = args.index("--") if "--" in args else 1
     before, after = args[:cut], [p for p in args[cut:] if p != "--"]
     if not before or not after:
         sys.exit(__doc__)
     a, b = side(before), side(after)
+    for was, now in [(one_symbol(a, old, "before"), one_symbol(b, new, "after")) for old, new in maps]:
+        if now in a and now != was:
+            sys.exit("--map: %s exists before as well" % now)
+        a[now] = a.pop(was)
     differ = 0
     for name in sorted(set(a) | set(b)):
         if name not in a or name not in b:
