@@ -49,7 +49,7 @@ extern "C" {
 #endif
 
 #define M2S_VERSION_MAJOR 0
-#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface, m2s_band_create / destroy / info / sample / raymarch, m2s_band_csg, m2s_band_export, m2s_band_field_info); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
+#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface, m2s_band_create / destroy / info / sample / raymarch, m2s_band_csg, m2s_band_export, m2s_band_field_info, m2s_band_redistance); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
 
 /* Return codes.  The reference panics where this ABI returns a negative code; the Rust shim
  * turns a negative code back into panic!(m2s_last_error()). */
@@ -904,6 +904,62 @@ int m2s_band_csg(const m2s_band* a, const m2s_band* b, int op, const m2s_band_fi
 int m2s_band_export(const m2s_band* band, uint64_t* cells_out, float* distances_out, uint64_t capacity,
                     uint32_t* inside_bits_out, const m2s_opts* opts);
 int m2s_band_field_info(const m2s_band* band, m2s_band_field_opts* fopts_out, int* has_inside);
+
+/* ---- Redistancing a narrow band: true distances after CSG, wider or narrower bands ----------------------------------------------------
+ * m2s_band_redistance takes a resident band and returns a resident band with the same zero set, values that are distances again and
+ * the half-widths the caller asks for: what LevelSetFilter::normalize / dilate are to csgUnion in OpenVDB.  It closes the chain
+ * mesh -> band -> CSG -> redistance -> offset / isosurface / march / CSG again with no dense grid anywhere.  The result is DEFINED per
+ * grid point, to the bit (tests/band_redistance_model.py restates it in numpy).
+ * Input: a handle X, widths exterior >= 0 and interior >= 0 (finite), max_sweeps.  act, x = D'_X and s = act ? (x < 0) : inside bit
+ *   are those of the CSG definition above; h = (hx, hy, hz) is the grid's cell_size; W(L) = s[L] ? interior : exterior.
+ *   All arithmetic is IEEE binary32 with no FMA, each operation in the order written; `/` and sqrt are correctly rounded.
+ * Frozen set F: an active point L with an axis neighbour M (+-1 in i, j or k, inside the grid) that is active and has s[M] != s[L].
+ *   Frozen points keep x[L] in every bit, so the zero level's mesh is untouched.  n_open counts the ordered pairs (L active, M an
+ *   inactive axis neighbour, s[M] != s[L]): n_open > 0 proves that the input does not bracket its own zero set there (the idea of
+ *   m2s_band_isosurface's n_open).  The call still succeeds; those pairs freeze nothing.  Sign changes between two inactive points
+ *   are not looked for: the sign bits are taken as given.
+ * Candidate region C: L is in C if it lies in the box |di| <= Kx, |dj| <= Ky, |dk| <= Kz of some frozen point, with
+ *   K_a = min(ceil(W(L) / h_a) + 1, n_a): the division in binary32, the ceil of that quotient, computed on the host; K is taken per
+ *   side, so two box dilations of F are selected by s.  Points outside C have u = +inf for ever, by definition: this is what makes
+ *   the work proportional to the band without a causality argument.
+ * Start: u0[L] = |x[L]| on F, +inf elsewhere.
+ * One sweep, Jacobi: every u(n+1) is computed from u(n) only.  For L in C \ F:
+ *   c(v, M) = v <= W(M) ? v : +inf (the cut-off applies to frozen values too).
+ *   Per axis a, m_a = the min over the two axis neighbours M inside the grid with s[M] == s[L] of c(u(n)[M], M); +inf if there is none.
+ *   The three (m_a, h_a) sorted ascending by m, stably in the axis order i, j, k (swap on a strict < only: (i,j), (j,k), (i,j)):
+ *   a1 <= a2 <= a3 with h1, h2, h3 and w_n = 1 / (h_n * h_n).
+ *     t = a1 + h1
+ *     if (t > a2) { d2 = a2 - a1;  A = w1 + w2;  B = w2 * d2;  q2 = B * d2;  C = q2 - 1;  D = B * B - A * C;  D = D > 0 ? D : 0;
+ *                   t = a1 + (B + sqrt(D)) / A;
+ *       if (t > a3) { d3 = a3 - a1;  A = A + w3;  B = B + w3 * d3;  C = (q2 + (w3 * d3) * d3) - 1;  D = B * B - A * C;  D = D > 0 ? D : 0;
+ *                     t = a1 + (B + sqrt(D)) / A; } }
+ *   A +inf neighbour never enters the arithmetic (the branches exclude it), and a point with a1 = +inf stays +inf.
+ *   u(n+1)[L] = t < u(n)[L] ? t : u(n)[L]   (a NaN t, which needs a cell size whose square underflows, changes nothing).
+ * Sweeps run until one changes no bit or max_sweeps have run.  sweeps = the number of sweeps that changed something; converged = the
+ *   last one run changed nothing.  Further sweeps after convergence change nothing, so the library reads its change flags every few
+ *   sweeps.  max_sweeps == 0: the default 2 * (Kx + Ky + Kz) + 8 with the larger side's K; a cap, not a target.
+ * IT MUST BE JACOBI.  With asynchronous, in-place updates the iteration converges to DIFFERENT BITS, because the binary32 update is not
+ *   monotone across its branches: a Gauss-Seidel sweep, a multi-sweep LDS tile, a fast iterative method or anything else that lets a
+ *   point see a value of the same sweep cannot meet this definition.  The library keeps two value buffers.
+ * Result: a new immutable m2s_band on the same grid and device.  Active set: F and the L in C with u[L] <= W(L).  Values: x[L] on F,
+ *   otherwise s[L] ? -u : +u.  Sign mask: s on EVERY grid point.  Backgrounds: fopts', or by default outside = exterior and inside =
+ *   interior.  Input cells that are neither frozen nor reached are dropped: their values were not distances.  F empty: an empty band
+ *   with the sign mask.
+ * Accuracy (first order; measured with the numpy model): a sphere of radius 0.6 on cells (0.05, 0.04, 0.0625), max
+ *   error 0.14 / 0.30 cells of 0.0625 at widths of 3 / 5 such cells; the seam of a union of two spheres 0.21 cells where the min rule of
+ *   m2s_band_csg is off by 1.20.
+ * Always synchronous.  *out = NULL on every failure.  M2S_ERR_BAD_ARG before any device work: a NULL handle, ropts or out; a
+ *   struct_size other than sizeof (ropts, fopts, info_out); negative or non-finite widths or backgrounds; an m2s_opts.device that is not
+ *   the handle's (-1 means its own); algorithm, x_begin, x_end, x_period or peer_out not zero; a bad mem_kind.
+ *   m2s_opts: device, stream / stream_mode, lane.  timings: seed_ms = the topology (s, F, C and its index), distance_ms = the sweeps,
+ *   total_ms = the whole call, n_units = the result's cells.  m2s_band_info of the result: device_bytes by the formula for a handle
+ *   with a sign mask.  Nothing sized 4 bytes per grid point is allocated: during the call six or seven words per 64 grid points and
+ *   33 bytes per candidate (two values, six 32-bit neighbour places, a byte); 2^32 - 1 or more candidates are M2S_ERR_BAD_ARG.
+ *   info_out (may be NULL; set struct_size): the figures above and n_candidates = |C|. */
+typedef struct m2s_band_redistance_opts { uint32_t struct_size; float exterior, interior; uint32_t max_sweeps; } m2s_band_redistance_opts;
+typedef struct m2s_band_redistance_info { uint32_t struct_size, sweeps, converged, reserved; uint64_t n_frozen, n_open, n_candidates; } m2s_band_redistance_info;
+int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ropts, const m2s_band_field_opts* fopts /* NULL = the widths */,
+                        const m2s_opts* opts, m2s_band** out, m2s_band_redistance_info* info_out /* may be NULL */);
 
 /* glTF 2.0 / GLB ingestion (host side) — what the reference client extracts from a file before the merge:
  * mesh_to_sdf_client/src/gltf/mod.rs:56-174 (models keyed by mesh index, one primitive per mesh survives;

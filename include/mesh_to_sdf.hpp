@@ -602,6 +602,14 @@ struct BandRayMarch : RayMarch {
 };
 // How BandField::csg combines two fields (m2s_csg_op); Difference is this minus the other.
 enum class CsgOp : int { Union = M2S_CSG_UNION, Intersection = M2S_CSG_INTERSECTION, Difference = M2S_CSG_DIFFERENCE };
+// What BandField::redistance reports (m2s_band_redistance_info): the sweeps that changed a value, whether the last one run changed none,
+// the frozen cells next to the zero set, the sign changes towards an inactive cell (> 0: the band does not bracket its zero set there),
+// the candidate cells the sweeps ran over.
+struct RedistanceInfo {
+  uint32_t sweeps = 0;
+  bool converged = false;
+  uint64_t n_frozen = 0, n_open = 0, n_candidates = 0;
+};
 template <class V>
 class BandField {
  public:
@@ -674,6 +682,28 @@ class BandField {
     fo.background_outside = background_outside;
     fo.background_inside = background_inside;
     return csg_as(other, op, &fo);
+  }
+  // The field with the same zero set, values that are distances again and the half-widths asked for, as a new resident field
+  // (m2s_band_redistance: Jacobi sweeps of the first-order update from the cells next to the zero set, per grid point and to the bit;
+  // no dense grid).  The cells next to the zero set keep their values in every bit; the backgrounds become the two widths.
+  BandField redistance(float exterior, float interior, uint32_t max_sweeps = 0, RedistanceInfo* info = nullptr) const {
+    m2s_band_redistance_opts ro{};
+    ro.struct_size = sizeof(ro);
+    ro.exterior = exterior;
+    ro.interior = interior;
+    ro.max_sweeps = max_sweeps;
+    m2s_band_redistance_info ri{};
+    ri.struct_size = sizeof(ri);
+    m2s_band* h = nullptr;
+    detail::check(m2s_band_redistance(h_, &ro, nullptr, nullptr, &h, &ri));
+    if (info) {
+      info->sweeps = ri.sweeps;
+      info->converged = ri.converged != 0;
+      info->n_frozen = ri.n_frozen;
+      info->n_open = ri.n_open;
+      info->n_candidates = ri.n_candidates;
+    }
+    return BandField(grid_, h);
   }
   // The field's lists back out (m2s_band_export): cells ascending, distances bit for bit, and `bits` the sign mask in the layout of
   // Voxels::bits (all zero for a field made without one).  band_isosurface(grid, b.cells, b.distances) meshes it.

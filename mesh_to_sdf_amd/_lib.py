@@ -138,6 +138,15 @@ class M2SBandFieldOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("background_outside", C.c_float), ("background_inside", C.c_float)]
 
 
+class M2SBandRedistanceOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("exterior", C.c_float), ("interior", C.c_float), ("max_sweeps", C.c_uint32)]
+
+
+class M2SBandRedistanceInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sweeps", C.c_uint32), ("converged", C.c_uint32), ("reserved", C.c_uint32),
+                ("n_frozen", C.c_uint64), ("n_open", C.c_uint64), ("n_candidates", C.c_uint64)]
+
+
 class M2SSampleOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("iso", C.c_float), ("outside", C.c_float), ("max_steps", C.c_uint32)]
 
@@ -200,6 +209,7 @@ EXPORTS = [
     "m2s_band_csg",
     "m2s_band_export",
     "m2s_band_field_info",
+    "m2s_band_redistance",
     "m2s_merge_instances",
     "m2s_gltf_open",
     "m2s_gltf_instances",
@@ -303,6 +313,8 @@ def _prototypes():
         "m2s_band_csg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts), C.POINTER(C.c_void_p)]),
         "m2s_band_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(M2SOpts)]),
         "m2s_band_field_info": (C.c_int, [C.c_void_p, C.POINTER(M2SBandFieldOpts), C.POINTER(C.c_int)]),
+        "m2s_band_redistance": (C.c_int, [C.c_void_p, C.POINTER(M2SBandRedistanceOpts), C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
+                                          C.POINTER(C.c_void_p), C.POINTER(M2SBandRedistanceInfo)]),
         "m2s_merge_instances": (C.c_int, [C.POINTER(M2SInstance), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(M2SOpts)]),
         "m2s_gltf_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(M2SGltfInfo)]),
         "m2s_gltf_instances": (C.c_int, [C.c_void_p, C.POINTER(M2SInstance), C.c_size_t]),

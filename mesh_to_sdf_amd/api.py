@@ -1074,6 +1074,17 @@ def _backgrounds(background):
     return bg_in, bg_out
 
 
+class RedistanceInfo(NamedTuple):
+    """include/m2s.h `m2s_band_redistance_info`: the sweeps that changed a value, whether the last one run changed none, the frozen
+    cells next to the zero set, the sign changes towards an inactive cell (> 0: the band does not bracket its own zero set there), the
+    candidate cells the sweeps ran over."""
+    sweeps: int
+    converged: bool
+    n_frozen: int
+    n_open: int
+    n_candidates: int
+
+
 class BandField:
     """A narrow band made queryable (include/m2s.h `m2s_band`): the index of the band's cells, its distances and an optional sign mask,
     resident on the device, built once and sampled or ray-marched many times with no dense grid anywhere.  It stands for the dense grid D'
@@ -1086,7 +1097,8 @@ class BandField:
     None means default_background(distances).  A zero background stalls a march: a ray that enters the region it fills stops there
     (dist < eps), so give a band that has cells on one side only an explicit background for the other.
     Two fields on the same grid combine on the device into a third (`csg`, `union`, `intersection`, `difference`, or `a | b`, `a & b`,
-    `a - b`); `to_band` hands a field's lists back as a NarrowBand and `isosurface` meshes it.  `background` is (inside, outside) and
+    `a - b`); `redistance` turns a combined field back into distances at any width and `offset` grows or shrinks the solid;
+    `to_band` hands a field's lists back as a NarrowBand and `isosurface` meshes it.  `background` is (inside, outside) and
     `count` the number of cells, for a combined field as the library reports them.
     A context manager; `close` frees the device memory."""
 
@@ -1245,6 +1257,68 @@ class BandField:
 
     def __sub__(self, other):
         return self.csg(other, CsgOp.Difference) if isinstance(other, BandField) else NotImplemented
+
+    def redistance(self, band, background=None, max_sweeps: int = 0, *, timings: M2STimings = None) -> "BandField":
+        """A new resident BandField with the same zero set, values that are distances again and the half-widths `band` (a scalar or
+        (interior, exterior)), narrower or wider than this one (include/m2s.h m2s_band_redistance states the result per grid point, to
+        the bit).  The cells next to the zero set keep their values in every bit; from them Jacobi sweeps of the first-order update
+        run over the cells within reach, and what they do not reach within the widths is dropped.  Use it after `csg`, whose values
+        are only a lower bound of the distance, and before anything that reads the band as a distance: isosurface(iso != 0), a march,
+        a second csg after an offset.  background: a scalar or (inside, outside); None is the two widths.  max_sweeps 0 is the
+        library's cap.  The result carries `.redistance_info` (a RedistanceInfo)."""
+        interior, exterior = _band_widths(band)
+        q = self._side(timings)
+        ro = _lib.M2SBandRedistanceOpts(C.sizeof(_lib.M2SBandRedistanceOpts), float(np.float32(exterior)), float(np.float32(interior)), int(max_sweeps))
+        fo = None
+        if background is not None:
+            bg_in, bg_out = _backgrounds(background)
+            fo = C.byref(_lib.M2SBandFieldOpts(C.sizeof(_lib.M2SBandFieldOpts), float(np.float32(bg_out)), float(np.float32(bg_in))))
+        info = _lib.M2SBandRedistanceInfo(C.sizeof(_lib.M2SBandRedistanceInfo))
+        h = C.c_void_p()
+        rc = _lib.lib().m2s_band_redistance(self._handle(), C.byref(ro), fo, C.byref(q.opts), C.byref(h), C.byref(info))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        out = BandField._adopt(h, self.grid, self._dev)
+        out.redistance_info = RedistanceInfo(int(info.sweeps), bool(info.converged), int(info.n_frozen), int(info.n_open), int(info.n_candidates))
+        return out
+
+    def offset(self, distance: float, band, max_sweeps: int = 0) -> "BandField":
+        """The solid grown (distance > 0) or shrunk (distance < 0) by `distance`, as a new BandField of half-widths `band`: the lists
+        out, `distance` subtracted from the values, the sign mask rebuilt from the shifted values on the band's cells and kept
+        elsewhere, a field of them with this one's backgrounds, then `redistance`.  Raises if the shifted zero set leaves what the
+        band brackets (n_open > 0): redistance to a band wider than |distance| first."""
+        nb = self.to_band()
+        d = np.float32(distance)
+        nx, ny, nz = (int(v) for v in self.grid.get_cell_count())
+        nzw = (nz + 31) // 32
+        if _is_torch(nb.cells):
+            import torch as t
+
+            moved = nb.distances - float(d)
+            L = nb.cells
+            word = (L // nz) * nzw + (L % nz) // 32
+            bit = t.ones_like(L) << ((L % nz) % 32)
+            bits = nb.bits.view(t.int32).reshape(-1).to(t.int64) & 0xffffffff
+            clear = t.zeros_like(bits).scatter_add_(0, word, bit)                      # the cells of a word are distinct bits: a sum is an OR
+            setb = t.zeros_like(bits).scatter_add_(0, word, t.where(moved < 0, bit, t.zeros_like(bit)))
+            bits = (bits & ~clear) | setb
+            bits = t.where(bits >= 2 ** 31, bits - 2 ** 32, bits).to(t.int32).reshape(nx, ny, nzw)
+        else:
+            moved = (np.asarray(nb.distances, np.float32) - d).astype(np.float32)
+            L = np.asarray(nb.cells).astype(np.int64)
+            word = (L // nz) * nzw + (L % nz) // 32
+            bit = np.uint32(1) << ((L % nz) % 32).astype(np.uint32)
+            bits = np.array(nb.bits, np.uint32).reshape(-1)
+            np.bitwise_and.at(bits, word, ~bit)
+            np.bitwise_or.at(bits, word[moved < 0], bit[moved < 0])
+            bits = bits.reshape(nx, ny, nzw)
+        with BandField(self.grid, nb.cells, moved, background=self.background, inside=bits) as shifted:
+            out = shifted.redistance(band, max_sweeps=max_sweeps)
+        if out.redistance_info.n_open:
+            n_open = out.redistance_info.n_open
+            out.close()
+            raise M2SError(_lib.ERR_BAD_ARG, f"offset: the zero set moved by {float(d)} leaves the band at {n_open} cell faces; redistance to a wider band first")
+        return out
 
     def to_band(self, *, timings: M2STimings = None) -> NarrowBand:
         """The field's lists back out (include/m2s.h m2s_band_export, the inverse of creating it): a NarrowBand of its cells (ascending),
