@@ -60,11 +60,12 @@ __global__ __launch_bounds__(256) void k_tri_setup(const float* __restrict__ ver
                                                    const void* __restrict__ indices, int index_bytes, int topology,
                                                    uint32_t n_tris, TriRec* __restrict__ raw, Box* __restrict__ boxes,
                                                    float4* __restrict__ cen_raw,
-                                                   int* __restrict__ scene /*final values, then 6 per block from part_base on*/, int part_base,
+                                                   int* __restrict__ scene /*final values, then SCENE_PARTIAL_WORDS per block from part_base on*/, int part_base,
                                                    int* __restrict__ err, uint32_t* __restrict__ aux, uint32_t aux_words) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (aux && blockIdx.x == 0 && threadIdx.x < aux_words) aux[threadIdx.x] = 0u;   // the build's counters
   int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+  float vmax = 0.0f;   // largest finite |coordinate| of the box: of the vertices, for the walks' slack (common.h mesh_scale)
   if (t < n_tris) {
     const size_t base = topology == 0 ? (size_t)t * 3 : (size_t)t;  // list: tuples(); strip: tuple_windows()
     uint32_t i0 = load_index(indices, index_bytes, base), i1 = load_index(indices, index_bytes, base + 1),
@@ -99,10 +100,13 @@ __global__ __launch_bounds__(256) void k_tri_setup(const float* __restrict__ ver
     const float cen[3] = {sx, sy, sz};
     for (int k = 0; k < 3; ++k)
       if (cen[k] == cen[k] && fabsf(cen[k]) < 3.0e38f) { lo[k] = ord(cen[k]); hi[k] = lo[k]; }
+    const float box[6] = {mn.x, mn.y, mn.z, mx.x, mx.y, mx.z};
+    for (int k = 0; k < 6; ++k)
+      if (fabsf(box[k]) < 3.0e38f) vmax = fmaxf(vmax, fabsf(box[k]));   // (false for a NaN)
   }
   // block reduce (wave shuffles, then LDS); one partial per block, folded by k_morton_keys:
   // no atomics, no serialisation on six hot addresses
-  __shared__ int part[6][4];
+  __shared__ int part[SCENE_PARTIAL_WORDS][4];
   const int wv = threadIdx.x >> 6;
   for (int k = 0; k < 3; ++k) {
     int l = lo[k], h = hi[k];
@@ -112,12 +116,15 @@ __global__ __launch_bounds__(256) void k_tri_setup(const float* __restrict__ ver
     }
     if ((threadIdx.x & 63) == 0) { part[k][wv] = l; part[3 + k][wv] = h; }
   }
+  int vm = __float_as_int(vmax);   // not negative: its bits order as the floats do
+  for (int off = 32; off > 0; off >>= 1) vm = max(vm, __shfl_xor(vm, off));
+  if ((threadIdx.x & 63) == 0) part[6][wv] = vm;
   __syncthreads();
-  if (threadIdx.x < 6) {
+  if (threadIdx.x < SCENE_PARTIAL_WORDS) {
     const int k = threadIdx.x;
     int v = part[k][0];
     for (int w = 1; w < 4; ++w) v = k < 3 ? min(v, part[k][w]) : max(v, part[k][w]);
-    scene[part_base + blockIdx.x * 6 + k] = v;   // partials live behind the final values
+    scene[part_base + blockIdx.x * SCENE_PARTIAL_WORDS + k] = v;   // partials live behind the final values
   }
 }
 
@@ -909,19 +916,23 @@ constexpr size_t AUX_WORDS = 16;   // [0]: k_hierarchy's finished segment-tree b
 
 // 63-bit Morton key of every triangle's box centre (21 bits per axis over the scene's box of centres) and the identity permutation.
 // One block per tile; every block folds the per-block scene partials of k_tri_setup itself, block 0 publishes the final values
-// (scene[0..5]: order-encoded min xyz / max xyz; scene[6]: largest finite |coordinate| as float bits; scene[7]: treelet root counter).
+// (scene[0..5]: order-encoded min xyz / max xyz; scene[6]: their largest finite |coordinate| as float bits; scene[7]: treelet root
+// counter; scene[SCENE_VERTEX_SCALE]: the largest finite |coordinate| of the triangle boxes as float bits).
 __global__ __launch_bounds__(KEY_THREADS) void k_morton_keys(const Box* __restrict__ boxes, uint32_t n_tris, int* __restrict__ scene,
                                                               uint32_t n_partials, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                               uint32_t tile_pairs) {
-  __shared__ int s_part[6][KEY_THREADS / 64];
-  __shared__ int s_scene[6];
+  __shared__ int s_part[SCENE_PARTIAL_WORDS][KEY_THREADS / 64];
+  __shared__ int s_scene[SCENE_PARTIAL_WORDS];
   const uint32_t tid = threadIdx.x;
-  int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
-  for (uint32_t b = tid; b < n_partials; b += KEY_THREADS)   // a few KB out of L2
+  int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN}, vm = 0;
+  for (uint32_t b = tid; b < n_partials; b += KEY_THREADS) {   // a few KB out of L2
+    const int* part = scene + SCENE_PARTIALS + b * SCENE_PARTIAL_WORDS;
     for (int k = 0; k < 3; ++k) {
-      lo[k] = min(lo[k], scene[8 + b * 6 + k]);
-      hi[k] = max(hi[k], scene[8 + b * 6 + 3 + k]);
+      lo[k] = min(lo[k], part[k]);
+      hi[k] = max(hi[k], part[3 + k]);
     }
+    vm = max(vm, part[6]);
+  }
   for (int k = 0; k < 3; ++k) {
     int l = lo[k], h = hi[k];
     for (int off = 32; off > 0; off >>= 1) {
@@ -930,8 +941,10 @@ __global__ __launch_bounds__(KEY_THREADS) void k_morton_keys(const Box* __restri
     }
     if ((tid & 63u) == 0) { s_part[k][tid >> 6] = l; s_part[3 + k][tid >> 6] = h; }
   }
+  for (int off = 32; off > 0; off >>= 1) vm = max(vm, __shfl_xor(vm, off));
+  if ((tid & 63u) == 0) s_part[6][tid >> 6] = vm;
   __syncthreads();
-  if (tid < 6) {
+  if (tid < SCENE_PARTIAL_WORDS) {
     int v = s_part[tid][0];
     for (int w = 1; w < KEY_THREADS / 64; ++w) v = tid < 3 ? min(v, s_part[tid][w]) : max(v, s_part[tid][w]);
     s_scene[tid] = v;
@@ -946,6 +959,7 @@ __global__ __launch_bounds__(KEY_THREADS) void k_morton_keys(const Box* __restri
     }
     scene[6] = __float_as_int(s);
     scene[7] = 0;
+    scene[SCENE_VERTEX_SCALE] = s_scene[6];
   }
   float slo[3], shi[3];
   for (int k = 0; k < 3; ++k) { slo[k] = unord(s_scene[k]); shi[k] = unord(s_scene[3 + k]); }
@@ -1123,7 +1137,7 @@ size_t bvh_workspace_bytes(size_t n_tris) {
   size_t b = AUX_WORDS * 4 + 256;
   b += n * 48 + 256 + n * sizeof(TriRec) * 2 + n * 16 + 256 + n * 16 + 256 + n * 16 + 256 + n * 4 + 256 + n * sizeof(TriPlanes) + 256 + n * sizeof(Box) * 3 + n * (8 + 4) * 2 + sort_tmp;
   b += n * (sizeof(int2) * 2) + n * 16 + 2 * (n / 512 + 2) * 16 + 768 + 2 * n * sizeof(NodeRec) + 2 * n * (sizeof(NodeExt) + 4);
-  return b + 64 * 256 + 4096 + 24 * ((n + 255) / 256) + 256 + sample_sort_bytes(n);
+  return b + 64 * 256 + 4096 + 4 * SCENE_PARTIAL_WORDS * ((n + 255) / 256) + 256 + sample_sort_bytes(n);
 }
 
 int build_device_mesh(Arena& ws, hipStream_t st, const float* d_verts, size_t n_verts, const void* d_indices,
@@ -1173,7 +1187,7 @@ int build_device_mesh(Arena& ws, hipStream_t st, const float* d_verts, size_t n_
   NodeRec* nodes = ws.take<NodeRec>(2 * n_tris);
   NodeExt* ext = ws.take<NodeExt>(2 * n_tris);
   uint32_t* slot_first = ws.take<uint32_t>(2 * n_tris);
-  int* scene = ws.take<int>(8 + 6 * ((n_tris + 255) / 256));
+  int* scene = ws.take<int>(SCENE_PARTIALS + SCENE_PARTIAL_WORDS * ((n_tris + 255) / 256));
   uint32_t* aux = ws.take<uint32_t>(AUX_WORDS);   // [0]: k_hierarchy's finished segment-tree blocks
   size_t sort_tmp = 0;
   (void)sort_pairs_u64(nullptr, sort_tmp, keys, keys2, vals, order, n_tris, 0, 64, st);
@@ -1205,7 +1219,7 @@ int build_device_mesh(Arena& ws, hipStream_t st, const float* d_verts, size_t n_
   leaf_max = std::min(std::max(leaf_max, 1u), 16u);
   out->leaf_max = leaf_max;
   hipLaunchKernelGGL(k_tri_setup, dim3(cdiv(n_tris, B)), dim3(B), 0, st, d_verts, (uint32_t)n_verts, d_indices,
-                     index_bytes, topology, (uint32_t)n_tris, raw, boxes, cen_raw, scene, 8, d_err, records_only ? nullptr : aux, (uint32_t)AUX_WORDS);
+                     index_bytes, topology, (uint32_t)n_tris, raw, boxes, cen_raw, scene, SCENE_PARTIALS, d_err, records_only ? nullptr : aux, (uint32_t)AUX_WORDS);
   if (records_only) {
     // a tiny problem (grid_is_tiny): all voxels x all triangles needs the triangle records and nothing else — no keys, no sort, no tree
     M2S_HIP_CHECK(hipGetLastError());

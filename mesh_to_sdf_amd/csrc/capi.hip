@@ -1714,7 +1714,7 @@ int m2s_debug_mesh_digest(m2s_mesh* m, uint64_t out[8]) {
 
 // Test hook (not part of include/m2s.h): one resident array of a mesh copied to host memory as it stands — `which` 0 triangle records,
 // 1 pre-test planes, 2 box nodes, 3 oriented bounds, 4 slot table (input triangle -> slot), 5 slot_first (pre-order slot -> first
-// triangle), 6 scene words, 7 the tree's current leaf_max (one uint32, host state).  *bytes (optional unless dst is NULL) receives the
+// triangle), 6 scene words (the eight of the digest and the vertex scale), 7 the tree's current leaf_max (one uint32, host state).  *bytes (optional unless dst is NULL) receives the
 // array's size; dst == NULL asks for the size alone.  tests/test_gpu_bounds.py checks the tree and its bounds against an f64 model with it.
 int m2s_debug_mesh_arrays(m2s_mesh* m, int which, void* dst, size_t capacity, size_t* bytes) {
   g_err[0] = 0;
@@ -1724,7 +1724,7 @@ int m2s_debug_mesh_arrays(m2s_mesh* m, int which, void* dst, size_t capacity, si
   std::lock_guard<std::mutex> mlk(m->mu);
   const size_t n = m->n_tris, nn = n ? 2 * n - 1 : 0;
   const void* ptr[8] = {m->dm.tris, m->dm.planes, m->dm.nodes, m->dm.ext, m->dm.slot_of, m->dm.slot_first, m->dm.scene, nullptr};
-  const size_t size[8] = {n * sizeof(TriRec), n * sizeof(TriPlanes), nn * sizeof(NodeRec), nn * sizeof(NodeExt), n * 4, nn * 4, n ? 32u : 0u, 4u};
+  const size_t size[8] = {n * sizeof(TriRec), n * sizeof(TriPlanes), nn * sizeof(NodeRec), nn * sizeof(NodeExt), n * 4, nn * 4, n ? 4u * (SCENE_VERTEX_SCALE + 1) : 0u, 4u};
   const size_t need = (which == 7 || ptr[which]) ? size[which] : 0;   // an array the mesh does not hold is empty
   if (bytes) *bytes = need;
   if (!dst) return M2S_OK;

@@ -91,12 +91,22 @@ struct DeviceMesh {
   uint32_t n_nodes;
   uint32_t leaf_max;    // subtrees of at most this many triangles are walked as one leaf (a grid call chooses by its grid: grid_leaf_max; set_leaf_size re-marks a resident tree)
   const uint32_t* slot_first;   // pre-order slot -> first triangle of its subtree (what a collapsed leaf's `tri` holds)
-  const int* scene;     // 6 order-encoded ints: min xyz / max xyz of the triangle box centres (see bvh.hip)
+  const int* scene;     // 6 order-encoded ints: min xyz / max xyz of the triangle box centres, then the scales below (see bvh.hip)
 };
 
-// Largest finite |coordinate| of the mesh's triangle-box centres; feeds the pruning slack.  k_scene_reduce
-// (bvh.hip) leaves it as float bits in scene[6], so a walk pays one wave-uniform load for it.
-__device__ __forceinline__ float mesh_scale(const DeviceMesh& m) { return __int_as_float(m.scene[6]); }
+// Words of `scene` behind the eight the build has always published: the vertex scale, then (from SCENE_PARTIALS on) the per-block
+// partials of k_tri_setup, SCENE_PARTIAL_WORDS each (min xyz / max xyz of the box centres, the largest |box coordinate|).
+constexpr int SCENE_VERTEX_SCALE = 8;
+constexpr int SCENE_PARTIALS = 16;
+constexpr int SCENE_PARTIAL_WORDS = 7;
+
+// Largest finite |coordinate| of the mesh's triangle boxes, i.e. of its vertices (+ the boxes' 1e-4 padding); feeds the walks' pruning
+// slack, which has to cover the cancellation in coordinates of that size (the box centres of long triangles about the origin are far
+// smaller than their vertices).  The build (bvh.hip k_morton_keys, lbvh_sort.hip.h fold_scene) leaves it as float bits in
+// scene[SCENE_VERTEX_SCALE], so a walk pays one wave-uniform load for it.
+__device__ __forceinline__ float mesh_scale(const DeviceMesh& m) { return __int_as_float(m.scene[SCENE_VERTEX_SCALE]); }
+// Largest finite |coordinate| of the triangle-box centres (scene[6]): the first term of k_cut's margin (cut.hip).
+__device__ __forceinline__ float mesh_centre_scale(const DeviceMesh& m) { return __int_as_float(m.scene[6]); }
 
 struct GridParams {
   float first[3];

@@ -90,8 +90,11 @@ __global__ __launch_bounds__(64) void k_cut(DeviceMesh mesh, GridParams g, const
     if (!(r < 3.0e37f)) r = __builtin_inff();
   }
   const f3 q = mk3(qq[0], qq[1], qq[2]);
-  const float scale = fmaxf(mesh_scale(mesh), fmaxf(fabsf(q.x), fmaxf(fabsf(q.y), fabsf(q.z))) + r);
-  const float abs_margin = 6.4e-5f * scale + 4.0e-5f;        // the packet walk's own slack is <= 4e-6 * scale + 2.5e-6
+  const float scale = fmaxf(mesh_centre_scale(mesh), fmaxf(fabsf(q.x), fmaxf(fabsf(q.y), fabsf(q.z))) + r);
+  // 16 x the packet walk's own slack, which is 4e-6 * vscale + 2.5e-6 with the scale of the VERTICES (common.h mesh_scale): the first
+  // term is the larger one unless the vertices exceed the box centres and the unit by 0.625, as those of long triangles about the origin do
+  const float vscale = fmaxf(mesh_scale(mesh), scale);
+  const float abs_margin = fmaxf(6.4e-5f * scale + 4.0e-5f, 6.4e-5f * vscale);
   float R2 = -1.0f, R = 0.0f, D = 0.0f;                      // unit outside the grid: never keeps anything
   f3 e = mk3(0.0f, 0.0f, 0.0f);
   float grad_c0 = __builtin_inff(), grad_c1 = 0.0f;          // gradient test: drop if L * (1 - 1e-4) - grad_c0 > grad_c1 * |n - e|

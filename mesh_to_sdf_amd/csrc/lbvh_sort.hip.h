@@ -116,18 +116,21 @@ __device__ __forceinline__ uint64_t morton_key_of_box(const Box& bx, const float
 }
 
 // Folds the per-block scene partials of k_tri_setup (every workgroup does it for itself: a few KB out of L2); block 0 publishes
-// the final values (scene[0..5] order-encoded min xyz / max xyz, scene[6] the largest finite |coordinate| as float bits, scene[7] the
-// treelet root counter, cleared).
+// the final values (scene[0..5] order-encoded min xyz / max xyz, scene[6] their largest finite |coordinate| as float bits, scene[7] the
+// treelet root counter, cleared, scene[SCENE_VERTEX_SCALE] the largest finite |coordinate| of the triangle boxes as float bits).
 template <uint32_t THREADS>
 __device__ __forceinline__ void fold_scene(int* __restrict__ scene, uint32_t n_partials, uint32_t tid, float slo[3], float shi[3]) {
-  __shared__ int s_part[6][THREADS / 64];
-  __shared__ int s_scene[6];
-  int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
-  for (uint32_t b = tid; b < n_partials; b += THREADS)
+  __shared__ int s_part[SCENE_PARTIAL_WORDS][THREADS / 64];
+  __shared__ int s_scene[SCENE_PARTIAL_WORDS];
+  int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN}, vm = 0;
+  for (uint32_t b = tid; b < n_partials; b += THREADS) {
+    const int* part = scene + SCENE_PARTIALS + b * SCENE_PARTIAL_WORDS;
     for (int k = 0; k < 3; ++k) {
-      lo[k] = min(lo[k], scene[8 + b * 6 + k]);
-      hi[k] = max(hi[k], scene[8 + b * 6 + 3 + k]);
+      lo[k] = min(lo[k], part[k]);
+      hi[k] = max(hi[k], part[3 + k]);
     }
+    vm = max(vm, part[6]);
+  }
   for (int k = 0; k < 3; ++k) {
     int l = lo[k], h = hi[k];
     for (int off = 32; off > 0; off >>= 1) {
@@ -136,8 +139,10 @@ __device__ __forceinline__ void fold_scene(int* __restrict__ scene, uint32_t n_p
     }
     if ((tid & 63u) == 0) { s_part[k][tid >> 6] = l; s_part[3 + k][tid >> 6] = h; }
   }
+  for (int off = 32; off > 0; off >>= 1) vm = max(vm, __shfl_xor(vm, off));
+  if ((tid & 63u) == 0) s_part[6][tid >> 6] = vm;
   __syncthreads();
-  if (tid < 6) {
+  if (tid < SCENE_PARTIAL_WORDS) {
     int v = s_part[tid][0];
     for (uint32_t w = 1; w < THREADS / 64; ++w) v = tid < 3 ? min(v, s_part[tid][w]) : max(v, s_part[tid][w]);
     s_scene[tid] = v;
@@ -152,6 +157,7 @@ __device__ __forceinline__ void fold_scene(int* __restrict__ scene, uint32_t n_p
     }
     scene[6] = __float_as_int(s);
     scene[7] = 0;
+    scene[SCENE_VERTEX_SCALE] = s_scene[6];
   }
   for (int k = 0; k < 3; ++k) { slo[k] = unord(s_scene[k]); shi[k] = unord(s_scene[3 + k]); }
 }

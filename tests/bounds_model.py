@@ -23,7 +23,8 @@ TRI_REGULAR = 0                                                    # geo.hip.h t
 
 
 def mesh_scale(scene):
-    """scene[6]: the largest finite |coordinate| of the triangle-box centres, as float bits."""
+    """scene[6]: the largest finite |coordinate| of the triangle-box centres, as float bits.  (The walks' slack takes the scale of the
+    vertices, csrc/common.h mesh_scale, which is never smaller: a comparison that prunes nothing with this scale prunes nothing with theirs.)"""
     return float(np.asarray(scene, np.uint32)[6:7].view(F)[0])
 
 

@@ -233,7 +233,7 @@ def test_hook_argument_checks_with_a_mesh():
         fn = L.m2s_debug_mesh_arrays
         nbytes = C.c_size_t(0)
         n = idx.size // 3
-        for which, size in enumerate((96 * n, 64 * n, 32 * (2 * n - 1), 48 * (2 * n - 1), 4 * n, 4 * (2 * n - 1), 32, 4)):
+        for which, size in enumerate((96 * n, 64 * n, 32 * (2 * n - 1), 48 * (2 * n - 1), 4 * n, 4 * (2 * n - 1), 36, 4)):
             assert fn(m._h, which, None, 0, C.byref(nbytes)) == 0 and nbytes.value == size, which
             buf = np.full(size // 4, 0xDEADBEEF, np.uint32)
             assert fn(m._h, which, buf.ctypes.data, size - 1, None) == _lib.ERR_BAD_ARG
