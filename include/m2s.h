@@ -49,7 +49,7 @@ extern "C" {
 #endif
 
 #define M2S_VERSION_MAJOR 0
-#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface, m2s_band_create / destroy / info / sample / raymarch, m2s_band_csg, m2s_band_export, m2s_band_field_info, m2s_band_redistance); 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
+#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface, m2s_band_create / destroy / info / sample / raymarch, m2s_band_csg, m2s_band_export, m2s_band_field_info, m2s_band_redistance); additive within 0.5 too: m2s_band_filter; 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
 
 /* Return codes.  The reference panics where this ABI returns a negative code; the Rust shim
  * turns a negative code back into panic!(m2s_last_error()). */
@@ -960,6 +960,70 @@ typedef struct m2s_band_redistance_opts { uint32_t struct_size; float exterior, 
 typedef struct m2s_band_redistance_info { uint32_t struct_size, sweeps, converged, reserved; uint64_t n_frozen, n_open, n_candidates; } m2s_band_redistance_info;
 int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ropts, const m2s_band_field_opts* fopts /* NULL = the widths */,
                         const m2s_opts* opts, m2s_band** out, m2s_band_redistance_info* info_out /* may be NULL */);
+
+/* ---- Smoothing a narrow band: mean, Laplacian, mean-curvature flow, everywhere or inside a region -------------------------------------
+ * m2s_band_filter takes a resident band and returns a resident band on the same cells whose values have been smoothed: what
+ * LevelSetFilter::mean / gaussian / laplacian / meanCurvature are in OpenVDB.  It rounds the crease a CSG leaves into a fillet, fairs a
+ * re-meshed surface and removes the staircase of a coarse band, with no dense grid and nothing leaving the device.  The result is
+ * DEFINED per grid point, to the bit (tests/band_filter_model.py restates it in numpy).
+ * Input: a handle X, a kind, iterations, and optionally a region handle `where` on the same grid.  act, x = D'_X[L] and
+ *   s = act ? (x < 0) : inside bit are those of the CSG definition above; h = (h_i, h_j, h_k) is the grid's cell_size.
+ *   All arithmetic is IEEE binary32 with no FMA, each operation in the order written; `/` is correctly rounded.
+ * Host constants, computed in binary32 and handed to the kernels as values: r_a = 1 / h_a, w_a = r_a * r_a,
+ *   dt = 1 / (2 * ((w_i + w_j) + w_k)); for cubic cells dt = h^2 / 6.
+ * The field a pass reads: v[L] is the current value where L is active; elsewhere it is D'_X[L], that is +background_outside, or
+ *   -background_inside when X's inside bit is set (X's own backgrounds, not the result's).  Inactive points never change.
+ * Neighbour reads: N(di, dj, dk) is v at (clamp(i + di, 0, nx - 1), clamp(j + dj, 0, ny - 1), clamp(k + dk, 0, nz - 1)): the box faces
+ *   use clamped reads, as in m2s_sample_grid.  N(+a) steps +1 along axis a alone, N(+a-b) steps +1 along a and -1 along b.  c = N(0,0,0).
+ * One pass, for an active L, computes a candidate:
+ *   M2S_FILTER_LAPLACIAN       t_a = ((N(+a) - c) + (N(-a) - c)) * w_a
+ *                              cand = c + dt * ((t_i + t_j) + t_k)
+ *   M2S_FILTER_MEAN            one iteration is three passes, axis i, then j, then k.  Pass a:
+ *                              cand = ((N(-a) + c) + N(+a)) / 3
+ *                              The separable 3 x 3 x 3 box, as in OpenVDB.  `width` must be 1; the field exists so that the struct can
+ *                              grow.  Four iterations of M2S_FILTER_MEAN approximate OpenVDB's Gaussian.
+ *   M2S_FILTER_MEAN_CURVATURE  g_a = (N(+a) - N(-a)) * (0.5f * r_a);   t_a as for M2S_FILTER_LAPLACIAN
+ *                              for ab in ij, ik, jk:  x_ab = ((N(+a+b) - N(+a-b)) - (N(-a+b) - N(-a-b))) * (0.25f * (r_a * r_b))
+ *                              q_a = g_a * g_a
+ *                              num = ((t_i*(q_j+q_k) + t_j*(q_i+q_k)) + t_k*(q_i+q_j)) - 2 * (((g_i*g_j)*x_ij + (g_i*g_k)*x_ik) + (g_j*g_k)*x_jk)
+ *                              g2 = (q_i + q_j) + q_k
+ *                              cand = g2 > 0 ? c + dt * (num / g2) : c
+ *                              One explicit step of phi_t = kappa |grad phi|, kappa the sum of the principal curvatures; 19 points.
+ *   next[L] = (W[L] && isfinite(cand)) ? cand : c.  W[L] is 1 when `where` is NULL, else s_where[L]: the CSG definition's s of the
+ *   `where` handle, read as "inside the region".  A cell outside the region evaluates no candidate and keeps every bit through every
+ *   pass.  A non-finite cand of a cell inside the region keeps c and counts once, per cell and pass, in n_nonfinite; values of
+ *   +-f32::MAX in a band are legal and make this reachable.  (A NaN g2 fails g2 > 0, so that cand is c: finite, not counted.)
+ * IT MUST BE JACOBI.  Every pass reads the previous pass's values only; the library keeps two value buffers, as for redistancing.
+ *   An in-place pass ends in different bits, and so does a tile that runs several passes in local memory.
+ * Result: a new immutable m2s_band on the same grid and device.  The active set is X's.  The values r are those after `iterations`
+ *   iterations.  Sign mask: on EVERY grid point, act ? (r < 0) : s.  Backgrounds: fopts', or X's by default.  m2s_band_info's
+ *   device_bytes follows the formula for a handle with a sign mask.  An empty band gives an empty band with the sign mask.
+ * info_out (may be NULL; set struct_size): passes = iterations, or 3 * iterations for M2S_FILTER_MEAN; n_changed = the active cells
+ *   whose final bits differ from x; n_sign_flips = the active cells with (r < 0) != (x < 0); max_change = the largest fabsf(r - x)
+ *   over the active cells (0 for an empty band; it may be +inf); n_nonfinite as above.  All are deterministic: integer sums and a maximum.
+ * What the definition does NOT promise: the result is not a distance field, follow it with m2s_band_redistance.  Cells at the band's
+ *   rim read the backgrounds, that is the clamped field, so their stencils see a kink.  The band should hold the zero set with two
+ *   cells to spare, plus the distance it is meant to move.
+ * Accuracy (measured with the numpy model): on a sphere the zero set follows R^2 = R0^2 - 4 n dt under
+ *   M2S_FILTER_MEAN_CURVATURE and M2S_FILTER_LAPLACIAN to a few hundredths of a cell over 8 iterations.
+ * Always synchronous: one synchronisation at the end, for the info, none between passes.  *out = NULL on every failure.
+ *   M2S_ERR_BAD_ARG before any device work: a NULL band, fl or out; a struct_size other than sizeof (fl, fopts, info_out); a bad kind;
+ *   iterations == 0 or above 65 536; width != 1; a negative or non-finite background; a `where` on another device, or on a grid that
+ *   differs in any bit of first_cell, cell_size or cell_count; n_cells + 2 >= 2^32; an m2s_opts.device that is not the handle's (-1
+ *   means its own); algorithm, x_begin, x_end, x_period or peer_out not zero; a bad mem_kind.  band == where is legal.
+ *   m2s_opts: device, stream / stream_mode, lane.  timings: seed_ms = the neighbour table, distance_ms = the passes, total_ms = the
+ *   whole call, n_units = the cell count.
+ * Memory during the call: per active cell two values and 24 (M2S_FILTER_MEAN, M2S_FILTER_LAPLACIAN) or 72 (M2S_FILTER_MEAN_CURVATURE)
+ *   bytes of 32-bit neighbour places plus a byte, 33 or 81 bytes in all; per 64 grid points the result's sign word (with the copies of
+ *   the mask and its offsets, the result itself).  Nothing sized 4 bytes per grid point is allocated.  An inactive neighbour is one of
+ *   two extra places behind the values, which is why n_cells + 2 must stay below 2^32. */
+enum m2s_filter_kind { M2S_FILTER_MEAN = 0, M2S_FILTER_LAPLACIAN = 1, M2S_FILTER_MEAN_CURVATURE = 2 };
+typedef struct m2s_band_filter_opts { uint32_t struct_size; int32_t kind; uint32_t iterations; uint32_t width; } m2s_band_filter_opts;
+typedef struct m2s_band_filter_info { uint32_t struct_size, passes; float max_change; uint32_t reserved;
+                                      uint64_t n_changed, n_sign_flips, n_nonfinite; } m2s_band_filter_info;
+int m2s_band_filter(const m2s_band* band, const m2s_band* where /* may be NULL = everywhere */, const m2s_band_filter_opts* fl,
+                    const m2s_band_field_opts* fopts /* NULL = the input's backgrounds */, const m2s_opts* opts,
+                    m2s_band** out, m2s_band_filter_info* info_out /* may be NULL */);
 
 /* glTF 2.0 / GLB ingestion (host side) — what the reference client extracts from a file before the merge:
  * mesh_to_sdf_client/src/gltf/mod.rs:56-174 (models keyed by mesh index, one primitive per mesh survives;

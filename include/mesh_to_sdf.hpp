@@ -610,6 +610,16 @@ struct RedistanceInfo {
   bool converged = false;
   uint64_t n_frozen = 0, n_open = 0, n_candidates = 0;
 };
+// What BandField::filter runs (m2s_filter_kind): the separable 3 x 3 x 3 box (four iterations approximate a Gaussian), one explicit step of
+// the heat equation, one explicit step of the mean-curvature flow.
+enum class FilterKind : int { Mean = M2S_FILTER_MEAN, Laplacian = M2S_FILTER_LAPLACIAN, MeanCurvature = M2S_FILTER_MEAN_CURVATURE };
+// What BandField::filter reports (m2s_band_filter_info): the passes run, the largest |result - input| over the cells, the cells whose bits
+// changed, the cells whose sign changed, the candidates that were not finite and were dropped (per cell and pass).
+struct FilterInfo {
+  uint32_t passes = 0;
+  float max_change = 0.0f;
+  uint64_t n_changed = 0, n_sign_flips = 0, n_nonfinite = 0;
+};
 template <class V>
 class BandField {
  public:
@@ -702,6 +712,29 @@ class BandField {
       info->n_frozen = ri.n_frozen;
       info->n_open = ri.n_open;
       info->n_candidates = ri.n_candidates;
+    }
+    return BandField(grid_, h);
+  }
+  // The field on the same cells with its values smoothed by `iterations` iterations of `kind`, as a new resident field (m2s_band_filter:
+  // Jacobi passes over the band's cells, per grid point and to the bit; no dense grid).  where: a field on the same grid whose inside is the
+  // region to smooth; the cells outside it keep every bit.  The backgrounds are kept.  The result is not a distance field: follow it
+  // with redistance.
+  BandField filter(FilterKind kind, uint32_t iterations = 1, const BandField* where = nullptr, FilterInfo* info = nullptr) const {
+    m2s_band_filter_opts fl{};
+    fl.struct_size = sizeof(fl);
+    fl.kind = (int32_t)kind;
+    fl.iterations = iterations;
+    fl.width = 1;
+    m2s_band_filter_info fi{};
+    fi.struct_size = sizeof(fi);
+    m2s_band* h = nullptr;
+    detail::check(m2s_band_filter(h_, where ? where->h_ : nullptr, &fl, nullptr, nullptr, &h, &fi));
+    if (info) {
+      info->passes = fi.passes;
+      info->max_change = fi.max_change;
+      info->n_changed = fi.n_changed;
+      info->n_sign_flips = fi.n_sign_flips;
+      info->n_nonfinite = fi.n_nonfinite;
     }
     return BandField(grid_, h);
   }

@@ -147,6 +147,15 @@ class M2SBandRedistanceInfo(C.Structure):
                 ("n_frozen", C.c_uint64), ("n_open", C.c_uint64), ("n_candidates", C.c_uint64)]
 
 
+class M2SBandFilterOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("iterations", C.c_uint32), ("width", C.c_uint32)]
+
+
+class M2SBandFilterInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("passes", C.c_uint32), ("max_change", C.c_float), ("reserved", C.c_uint32),
+                ("n_changed", C.c_uint64), ("n_sign_flips", C.c_uint64), ("n_nonfinite", C.c_uint64)]
+
+
 class M2SSampleOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("iso", C.c_float), ("outside", C.c_float), ("max_steps", C.c_uint32)]
 
@@ -210,6 +219,7 @@ EXPORTS = [
     "m2s_band_export",
     "m2s_band_field_info",
     "m2s_band_redistance",
+    "m2s_band_filter",
     "m2s_merge_instances",
     "m2s_gltf_open",
     "m2s_gltf_instances",
@@ -315,6 +325,8 @@ def _prototypes():
         "m2s_band_field_info": (C.c_int, [C.c_void_p, C.POINTER(M2SBandFieldOpts), C.POINTER(C.c_int)]),
         "m2s_band_redistance": (C.c_int, [C.c_void_p, C.POINTER(M2SBandRedistanceOpts), C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
                                           C.POINTER(C.c_void_p), C.POINTER(M2SBandRedistanceInfo)]),
+        "m2s_band_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(M2SBandFilterOpts), C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
+                                      C.POINTER(C.c_void_p), C.POINTER(M2SBandFilterInfo)]),
         "m2s_merge_instances": (C.c_int, [C.POINTER(M2SInstance), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(M2SOpts)]),
         "m2s_gltf_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(M2SGltfInfo)]),
         "m2s_gltf_instances": (C.c_int, [C.c_void_p, C.POINTER(M2SInstance), C.c_size_t]),

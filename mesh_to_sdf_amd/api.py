@@ -1085,6 +1085,35 @@ class RedistanceInfo(NamedTuple):
     n_candidates: int
 
 
+class FilterKind(enum.IntEnum):
+    """include/m2s.h `m2s_filter_kind`: what BandField.filter runs.  Mean is the separable 3 x 3 x 3 box (four iterations approximate a
+    Gaussian), Laplacian one explicit step of the heat equation, MeanCurvature one explicit step of the mean-curvature flow."""
+    Mean = 0
+    Laplacian = 1
+    MeanCurvature = 2
+
+
+_FILTER_NAMES = {"mean": FilterKind.Mean, "laplacian": FilterKind.Laplacian, "meancurvature": FilterKind.MeanCurvature}
+
+
+def _filter_kind(kind) -> FilterKind:
+    """A FilterKind, its number or its name in any case (mean, laplacian, mean_curvature)."""
+    try:
+        return _FILTER_NAMES[kind.replace("_", "").replace(" ", "").lower()] if isinstance(kind, str) else FilterKind(int(kind))
+    except (KeyError, ValueError, TypeError):
+        raise M2SPanic(_lib.ERR_BAD_ARG, f"kind = {kind!r} is not a FilterKind (mean, laplacian, mean_curvature)") from None
+
+
+class FilterInfo(NamedTuple):
+    """include/m2s.h `m2s_band_filter_info`: the passes run, the largest |result - input| over the cells, the cells whose bits changed,
+    the cells whose sign changed, and the candidates that were not finite and were therefore dropped (per cell and pass)."""
+    passes: int
+    max_change: float
+    n_changed: int
+    n_sign_flips: int
+    n_nonfinite: int
+
+
 class BandField:
     """A narrow band made queryable (include/m2s.h `m2s_band`): the index of the band's cells, its distances and an optional sign mask,
     resident on the device, built once and sampled or ray-marched many times with no dense grid anywhere.  It stands for the dense grid D'
@@ -1098,6 +1127,7 @@ class BandField:
     (dist < eps), so give a band that has cells on one side only an explicit background for the other.
     Two fields on the same grid combine on the device into a third (`csg`, `union`, `intersection`, `difference`, or `a | b`, `a & b`,
     `a - b`); `redistance` turns a combined field back into distances at any width and `offset` grows or shrinks the solid;
+    `filter` and `smooth` fair it (mean, Laplacian, mean-curvature flow), everywhere or inside a region;
     `to_band` hands a field's lists back as a NarrowBand and `isosurface` meshes it.  `background` is (inside, outside) and
     `count` the number of cells, for a combined field as the library reports them.
     A context manager; `close` frees the device memory."""
@@ -1280,6 +1310,40 @@ class BandField:
             _raise(rc)
         out = BandField._adopt(h, self.grid, self._dev)
         out.redistance_info = RedistanceInfo(int(info.sweeps), bool(info.converged), int(info.n_frozen), int(info.n_open), int(info.n_candidates))
+        return out
+
+    def filter(self, kind, iterations: int = 1, *, where: "BandField" = None, background=None, timings: M2STimings = None) -> "BandField":
+        """A new resident BandField on the same cells whose values have been smoothed by `iterations` iterations of `kind` (a
+        FilterKind, its number or its name; include/m2s.h m2s_band_filter states the result per grid point, to the bit).  where: a
+        BandField on the same grid whose inside is the region to smooth; the cells outside it keep every bit, which is how a
+        union's seam becomes a fillet while the rest of the surface stays put.  background: a scalar or (inside, outside); None
+        keeps this field's.  The result is not a distance field: follow it with `redistance`, or call `smooth`.  It carries
+        `.filter_info` (a FilterInfo)."""
+        kind = _filter_kind(kind)
+        if where is not None and not isinstance(where, BandField):
+            raise M2SPanic(_lib.ERR_BAD_ARG, "filter: where is not a BandField")
+        q = self._side(timings)
+        fl = _lib.M2SBandFilterOpts(C.sizeof(_lib.M2SBandFilterOpts), int(kind), int(iterations), 1)
+        fo = None
+        if background is not None:
+            bg_in, bg_out = _backgrounds(background)
+            fo = C.byref(_lib.M2SBandFieldOpts(C.sizeof(_lib.M2SBandFieldOpts), float(np.float32(bg_out)), float(np.float32(bg_in))))
+        info = _lib.M2SBandFilterInfo(C.sizeof(_lib.M2SBandFilterInfo))
+        h = C.c_void_p()
+        rc = _lib.lib().m2s_band_filter(self._handle(), where._handle() if where is not None else None, C.byref(fl), fo, C.byref(q.opts),
+                                        C.byref(h), C.byref(info))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        out = BandField._adopt(h, self.grid, self._dev)
+        out.filter_info = FilterInfo(int(info.passes), float(info.max_change), int(info.n_changed), int(info.n_sign_flips), int(info.n_nonfinite))
+        return out
+
+    def smooth(self, kind, iterations: int, band, *, where: "BandField" = None) -> "BandField":
+        """`filter(kind, iterations, where=where)` followed by `redistance(band)`: a smoothed field that is a distance field again.
+        The result carries both `.filter_info` and `.redistance_info`."""
+        with self.filter(kind, iterations, where=where) as filtered:
+            out = filtered.redistance(band)
+            out.filter_info = filtered.filter_info
         return out
 
     def offset(self, distance: float, band, max_sweeps: int = 0) -> "BandField":

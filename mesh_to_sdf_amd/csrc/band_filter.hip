@@ -1,0 +1,413 @@
+// band_filter.hip — m2s_band_filter: the values of a resident band smoothed by a mean, a Laplacian or a mean-curvature flow, on the whole
+// band or inside a region, gfx950.  The contract is include/m2s.h's (per grid point, to the bit); tests/band_filter_model.py restates it in
+// numpy.  Nothing sized 4 bytes per grid point exists: the arrays are per mask word (the result's sign word) or per active cell.
+//
+// The two kernels that walk the mask words use band_walk.hip.h, band_redistance.hip's form: a wave owns 256 words; a
+// word with no active point is settled by its own lane, the others are taken one at a time by the whole wave and lane t owns the point
+// L = 64 w + t.
+//   k_bf_table   per active cell, once: the list places of its 6 or 18 clamped neighbours as 32-bit slots (a rank look-up each: mask word,
+//                word_off, popcount below); an inactive neighbour becomes one of the two places n and n + 1 behind the values, which hold
+//                +background_outside and -background_inside; the cell's `where` bit; its value into the first value buffer.
+//   k_bf_pass    one Jacobi pass, one lane per active cell: the slots, their values from the pass's input buffer, the arithmetic of the
+//                header, a store to the OTHER buffer; non-finite candidates counted by one atomic add per wave.  It reads no index word,
+//                takes no branch per neighbour and divides nothing but what the definition divides.
+//   k_bf_final   the result's sign words (a ballot per mask word), its values, n_changed, n_sign_flips and max_change.
+// All stores are plain vector stores; the ballot loops are wave-uniform; no LDS is used.
+#include "../../include/m2s.h"
+#include "band_handle.h"
+#include "band_walk.hip.h"
+#include "capi_internal.h"
+#include "common.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#pragma clang fp contract(off)
+
+namespace m2s {
+namespace {
+
+constexpr int kBfAxisSlots = 6, kBfAllSlots = 18;
+
+// The host constants of the definition, computed in binary32 on the host.
+struct BfConst {
+  float w[3];     // w_a = r_a * r_a
+  float gs[3];    // 0.5f * r_a
+  float xs[3];    // 0.25f * (r_a * r_b) for ab = ij, ik, jk
+  float dt;       // 1 / (2 * ((w_i + w_j) + w_k))
+};
+
+// The place in the value buffers of the grid point M (inside the grid): its rank in X's list if it is active, else n (outside) or n + 1
+// (its inside bit is set).  Always below n + 2.
+__device__ __forceinline__ uint32_t bf_slot(const BandDev& X, uint64_t M) {
+  const uint64_t w = M >> 6;
+  const int b = (int)(M & 63);
+  const uint64_t m = X.mask[w];
+  if ((m >> b) & 1ull) {
+    const uint64_t r = X.word_off[w] + (uint64_t)__popcll(m & walk_below(b));
+    return (uint32_t)(r < X.n ? r : X.n);   // r < n whenever the index is sound
+  }
+  const uint64_t in = X.inside ? (X.inside[w] >> b) & 1ull : 0ull;
+  return (uint32_t)(X.n + in);
+}
+
+// Per active cell r, once: slots[s * n + r], s = 0 .. NSLOT - 1 in the order i+, i-, j+, j-, k+, k-, then for ab = ij, ik, jk the four
+// diagonals +a+b, +a-b, -a+b, -a-b; in_region[r]; v0[r] = x.  A clamped step is a step of 0, so a clamped neighbour is the clamped point.
+// The first lane of the grid also fills the two background places of both value buffers.
+template <int NSLOT>
+__global__ void __launch_bounds__(kWalkThreads) k_bf_table(BandDev X, BandDev Wh, int has_where, WalkGrid g, uint32_t* __restrict__ slots,
+                                                         uint8_t* __restrict__ in_region, float* __restrict__ v0, float* __restrict__ v1) {
+  WALK_UNIT_HEAD
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    v0[X.n] = X.bg_out;
+    v0[X.n + 1] = X.bg_in_neg;
+    v1[X.n] = X.bg_out;
+    v1[X.n + 1] = X.bg_in_neg;
+  }
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD
+    const uint64_t m = in_range ? X.mask[w] : 0;
+    const uint64_t wo = m ? X.word_off[w] : 0;
+    const uint64_t wm = (m && has_where) ? Wh.mask[w] : 0;
+    const uint64_t win = (m && has_where && Wh.inside) ? Wh.inside[w] : 0;
+    const uint64_t wwo = wm ? Wh.word_off[w] : 0;
+    WalkIjk base{0, 0, 0};
+    if (m) base = walk_base(w << 6, g);
+    uint64_t todo = __ballot(m != 0);
+    while (todo) {   // wave-uniform
+      const int j = __ffsll((unsigned long long)todo) - 1;
+      todo &= todo - 1;
+      const uint64_t mj = walk_lane(m, j), woj = walk_lane(wo, j), wmj = walk_lane(wm, j), winj = walk_lane(win, j), wwoj = walk_lane(wwo, j);
+      const WalkIjk p = walk_step(walk_bcast(base, j), (uint32_t)lane, g);
+      const uint64_t L = ((wb + (uint64_t)j) << 6) + (uint64_t)lane;
+      const uint64_t r = woj + (uint64_t)__popcll(mj & walk_below(lane));
+      if (((mj >> lane) & 1ull) && r < X.n) {   // an active point is inside the grid
+        const int64_t d[3][2] = {{p.i + 1 < g.nx ? (int64_t)g.si : 0, p.i > 0 ? -(int64_t)g.si : 0},
+                                 {p.j + 1 < g.ny ? (int64_t)g.sj : 0, p.j > 0 ? -(int64_t)g.sj : 0},
+                                 {p.k + 1 < g.nz ? (int64_t)1 : 0, p.k > 0 ? (int64_t)-1 : 0}};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          slots[(uint64_t)(2 * a) * X.n + r] = bf_slot(X, (uint64_t)((int64_t)L + d[a][0]));
+          slots[(uint64_t)(2 * a + 1) * X.n + r] = bf_slot(X, (uint64_t)((int64_t)L + d[a][1]));
+        }
+        if (NSLOT == kBfAllSlots) {
+          int s = kBfAxisSlots;
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = a + 1; b < 3; ++b)
+#pragma unroll
+              for (int sa = 0; sa < 2; ++sa)
+#pragma unroll
+                for (int sb = 0; sb < 2; ++sb) slots[(uint64_t)(s++) * X.n + r] = bf_slot(X, (uint64_t)((int64_t)L + d[a][sa] + d[b][sb]));
+        }
+        bool in = true;
+        if (has_where) {
+          in = (winj >> lane) & 1ull;
+          if ((wmj >> lane) & 1ull) {
+            uint64_t at = wwoj + (uint64_t)__popcll(wmj & walk_below(lane));
+            at = at < Wh.n ? at : 0;
+            in = Wh.dist[at] < 0.0f;
+          }
+        }
+        in_region[r] = in ? 1 : 0;
+        v0[r] = X.dist[r];
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ bool bf_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// t_a = ((N(+a) - c) + (N(-a) - c)) * w_a
+__device__ __forceinline__ float bf_second(float np, float nm, float c, float w) { return ((np - c) + (nm - c)) * w; }
+
+// One Jacobi pass, one lane per active cell: v_out[r] = in the region and finite ? cand : c, from v_in only (v_out is the other buffer).
+// KIND: m2s_filter_kind; AXIS: the axis of a M2S_FILTER_MEAN pass.  counters[0] += the candidates that were not finite.
+template <int KIND, int AXIS>
+__global__ void __launch_bounds__(256) k_bf_pass(const uint32_t* __restrict__ slots, const uint8_t* __restrict__ in_region, const float* __restrict__ v_in,
+                                                 float* __restrict__ v_out, uint64_t n, BfConst k, uint64_t* __restrict__ counters) {
+  uint32_t bad = 0;
+  for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (uint64_t)gridDim.x * 256) {
+    const float c = v_in[r];
+    float next = c;
+    if (in_region[r]) {
+      float cand;
+      if (KIND == M2S_FILTER_MEAN) {
+        const float np = v_in[slots[(uint64_t)(2 * AXIS) * n + r]], nm = v_in[slots[(uint64_t)(2 * AXIS + 1) * n + r]];
+        cand = ((nm + c) + np) / 3.0f;
+      } else {
+        float N[kBfAllSlots];
+#pragma unroll
+        for (int s = 0; s < (KIND == M2S_FILTER_LAPLACIAN ? kBfAxisSlots : kBfAllSlots); ++s) N[s] = v_in[slots[(uint64_t)s * n + r]];
+        const float ti = bf_second(N[0], N[1], c, k.w[0]), tj = bf_second(N[2], N[3], c, k.w[1]), tk = bf_second(N[4], N[5], c, k.w[2]);
+        if (KIND == M2S_FILTER_LAPLACIAN) {
+          cand = c + k.dt * ((ti + tj) + tk);
+        } else {
+          const float gi = (N[0] - N[1]) * k.gs[0], gj = (N[2] - N[3]) * k.gs[1], gk = (N[4] - N[5]) * k.gs[2];
+          const float xij = ((N[6] - N[7]) - (N[8] - N[9])) * k.xs[0];
+          const float xik = ((N[10] - N[11]) - (N[12] - N[13])) * k.xs[1];
+          const float xjk = ((N[14] - N[15]) - (N[16] - N[17])) * k.xs[2];
+          const float qi = gi * gi, qj = gj * gj, qk = gk * gk;
+          const float num = ((ti * (qj + qk) + tj * (qi + qk)) + tk * (qi + qj)) - 2.0f * (((gi * gj) * xij + (gi * gk) * xik) + (gj * gk) * xjk);
+          const float g2 = (qi + qj) + qk;
+          cand = g2 > 0.0f ? c + k.dt * (num / g2) : c;
+        }
+      }
+      if (bf_finite(cand)) next = cand;
+      else ++bad;
+    }
+    v_out[r] = next;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd((unsigned long long*)counters, (unsigned long long)bad);
+}
+
+// The result: S = act ? (r < 0) : inside bit on every grid point (bits past the grid zero), out[r] = the last pass's values, and
+// counters[1] += n_changed, counters[2] += n_sign_flips, counters[3] = max(the bits of fabsf(r - x)): non-negative floats order as their bits.
+__global__ void __launch_bounds__(kWalkThreads) k_bf_final(BandDev X, WalkGrid g, const float* __restrict__ v, uint64_t* __restrict__ S, float* __restrict__ out,
+                                                         uint64_t* __restrict__ counters) {
+  WALK_UNIT_HEAD
+  uint32_t n_changed = 0, n_flips = 0, top = 0;
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD
+    const uint64_t m = in_range ? X.mask[w] : 0;
+    const uint64_t in = in_range && X.inside ? X.inside[w] : 0;
+    const uint64_t wo = m ? X.word_off[w] : 0;
+    const uint64_t valid = walk_valid(w, in_range, g.total);
+    uint64_t s = in & valid;
+    uint64_t todo = __ballot(m != 0);
+    while (todo) {   // wave-uniform
+      const int j = __ffsll((unsigned long long)todo) - 1;
+      todo &= todo - 1;
+      const uint64_t mj = walk_lane(m, j), inj = walk_lane(in, j), woj = walk_lane(wo, j);
+      const uint64_t r = woj + (uint64_t)__popcll(mj & walk_below(lane));
+      bool sb = (inj >> lane) & 1ull;
+      if (((mj >> lane) & 1ull) && r < X.n) {
+        const float x = X.dist[r], y = v[r];
+        out[r] = y;
+        sb = y < 0.0f;
+        n_changed += __float_as_uint(x) != __float_as_uint(y) ? 1u : 0u;
+        n_flips += sb != (x < 0.0f) ? 1u : 0u;
+        const uint32_t ch = __float_as_uint(fabsf(y - x));   // finite operands: a number or +inf, never a NaN
+        top = ch > top ? ch : top;
+      }
+      const uint64_t sm = __ballot(sb);
+      if (lane == j) s = sm & valid;
+    }
+    if (in_range) S[w] = s;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    n_changed += __shfl_xor(n_changed, o, 64);
+    n_flips += __shfl_xor(n_flips, o, 64);
+    const uint32_t other = __shfl_xor(top, o, 64);
+    top = other > top ? other : top;
+  }
+  if (lane == 0) {
+    if (n_changed) atomicAdd((unsigned long long*)(counters + 1), (unsigned long long)n_changed);
+    if (n_flips) atomicAdd((unsigned long long*)(counters + 2), (unsigned long long)n_flips);
+    if (top) atomicMax((unsigned int*)(counters + 3), top);
+  }
+}
+
+bool good_background(float v) { return v >= 0.0f && std::isfinite(v); }
+
+template <int KIND, int AXIS>
+void launch_pass(hipStream_t st, unsigned blocks, const uint32_t* slots, const uint8_t* in_region, const float* v_in, float* v_out, uint64_t n,
+                 const BfConst& k, uint64_t* counters) {
+  hipLaunchKernelGGL((k_bf_pass<KIND, AXIS>), dim3(blocks), dim3(256), 0, st, slots, in_region, v_in, v_out, n, k, counters);
+}
+
+}  // namespace
+
+// m2s_warmup: the first launch of a kernel of this translation unit makes the runtime load its code object (all its kernels).
+__global__ void k_warm_band_filter() {}
+void warm_band_filter(hipStream_t st) { hipLaunchKernelGGL(k_warm_band_filter, dim3(1), dim3(64), 0, st); }
+
+}  // namespace m2s
+
+using namespace m2s;
+
+extern "C" {
+
+int m2s_band_filter(const m2s_band* band, const m2s_band* where, const m2s_band_filter_opts* fl, const m2s_band_field_opts* fopts,
+                    const m2s_opts* opts, m2s_band** out, m2s_band_filter_info* info_out) {
+  clear_error();
+  if (!out) return fail(M2S_ERR_BAD_ARG, "out is NULL");
+  *out = nullptr;
+  if (!band) return fail(M2S_ERR_BAD_ARG, "band is NULL");
+  if (!fl) return fail(M2S_ERR_BAD_ARG, "m2s_band_filter_opts is NULL");
+  if (fl->struct_size != sizeof(m2s_band_filter_opts))
+    return fail(M2S_ERR_BAD_ARG, "m2s_band_filter_opts.struct_size is not sizeof(m2s_band_filter_opts)");
+  if (fl->kind != M2S_FILTER_MEAN && fl->kind != M2S_FILTER_LAPLACIAN && fl->kind != M2S_FILTER_MEAN_CURVATURE)
+    return fail(M2S_ERR_BAD_ARG, "bad m2s_filter_kind %d", fl->kind);
+  if (fl->iterations == 0 || fl->iterations > 65536) return fail(M2S_ERR_BAD_ARG, "iterations = %u: must be 1 .. 65536", fl->iterations);
+  if (fl->width != 1) return fail(M2S_ERR_BAD_ARG, "width = %u: must be 1", fl->width);
+  if (fopts) {
+    if (fopts->struct_size != sizeof(m2s_band_field_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_band_field_opts.struct_size is not sizeof(m2s_band_field_opts)");
+    if (!good_background(fopts->background_outside) || !good_background(fopts->background_inside))
+      return fail(M2S_ERR_BAD_ARG, "the backgrounds (%g outside, %g inside) must be >= 0 and finite", (double)fopts->background_outside,
+                  (double)fopts->background_inside);
+  }
+  if (info_out && info_out->struct_size != sizeof(m2s_band_filter_info))
+    return fail(M2S_ERR_BAD_ARG, "m2s_band_filter_info.struct_size is not sizeof(m2s_band_filter_info)");
+  int rc = band_opts_args(opts, "m2s_band_filter");
+  if (rc) return rc;
+  if (where) {
+    if (where->device != band->device) return fail(M2S_ERR_BAD_ARG, "the band and the region live on devices %d and %d", band->device, where->device);
+    if (memcmp(band->grid.first_cell, where->grid.first_cell, sizeof(band->grid.first_cell)) != 0 ||
+        memcmp(band->grid.cell_size, where->grid.cell_size, sizeof(band->grid.cell_size)) != 0 ||
+        memcmp(band->grid.cell_count, where->grid.cell_count, sizeof(band->grid.cell_count)) != 0)
+      return fail(M2S_ERR_BAD_ARG, "the band's and the region's grids differ (first_cell, cell_size and cell_count must agree in every bit)");
+  }
+  const uint64_t n = band->n;
+  if (n + 2 >= (1ull << 32))
+    return fail(M2S_ERR_BAD_ARG, "%llu cells: the neighbour table holds 32-bit places, and two more are the backgrounds", (unsigned long long)n);
+  m2s_opts o;
+  rc = band_call_opts(band, opts, &o);
+  if (rc) return rc;
+  CallCtx c;
+  DeviceState* st = nullptr;
+  rc = resolve_ctx(&o, &c, &st);
+  if (rc) return rc;
+
+  const int kind = fl->kind;
+  const uint64_t passes = (uint64_t)fl->iterations * (kind == M2S_FILTER_MEAN ? 3 : 1);
+  const int n_slots = kind == M2S_FILTER_MEAN_CURVATURE ? kBfAllSlots : kBfAxisSlots;
+  BfConst k;
+  float r[3];
+  for (int a = 0; a < 3; ++a) {
+    r[a] = 1.0f / band->grid.cell_size[a];
+    k.w[a] = r[a] * r[a];
+    k.gs[a] = 0.5f * r[a];
+  }
+  k.xs[0] = 0.25f * (r[0] * r[1]);
+  k.xs[1] = 0.25f * (r[0] * r[2]);
+  k.xs[2] = 0.25f * (r[1] * r[2]);
+  k.dt = 1.0f / (2.0f * ((k.w[0] + k.w[1]) + k.w[2]));
+  WalkGrid g;
+  g.total = band->total;
+  g.n_words = band->n_words;
+  g.nx = band->grid.cell_count[0];
+  g.ny = band->grid.cell_count[1];
+  g.nz = band->grid.cell_count[2];
+  g.sj = g.nz;
+  g.si = g.ny * g.nz;
+
+  const uint64_t n_words = g.n_words;
+  const uint64_t n_units = (n_words + kWalkUnit - 1) / kWalkUnit;   // below 2^22: a grid has fewer than 2^36 cells
+  const unsigned blocks = (unsigned)((n_units + kWalkWaves - 1) / kWalkWaves);
+  const size_t b_words = align_up(n_words * 8);
+  const size_t b_v = align_up((n + 2) * 4), b_slots = align_up((uint64_t)n_slots * n * 4 + 4), b_region = align_up(n + 1);
+  const uint64_t cap = std::max<uint64_t>(n, 1);   // at least one float
+  char* tmp = nullptr;     // two value buffers, the table, the region bytes: 33 or 81 bytes per active cell
+  char* block = nullptr;   // the result
+  auto drop = [&](int code) {
+    (void)hipFree(tmp);
+    (void)hipFree(block);
+    return code;
+  };
+  auto hip_fail = [&](hipError_t e) { return drop(fail(M2S_ERR_HIP, "HIP error: %s", hipGetErrorString(e))); };
+  rc = ensure_capacity(*st, 4096);
+  if (rc) return rc;
+  Arena ws{st->base, st->cap, 0};
+  uint64_t* d_hdr = ws.take<uint64_t>(4);   // [0] n_nonfinite, [1] n_changed, [2] n_sign_flips, [3] the bits of max_change
+  if (!d_hdr) return fail(M2S_ERR_HIP, "internal: workspace");
+  hipError_t e = hipMalloc((void**)&tmp, 2 * b_v + b_slots + b_region);
+  if (e == hipSuccess) e = hipMalloc((void**)&block, 3 * b_words + align_up(cap * 4));
+  if (e != hipSuccess) return hip_fail(e);
+  float* v[2] = {reinterpret_cast<float*>(tmp), reinterpret_cast<float*>(tmp + b_v)};
+  uint32_t* slots = reinterpret_cast<uint32_t*>(tmp + 2 * b_v);
+  uint8_t* in_region = reinterpret_cast<uint8_t*>(tmp + 2 * b_v + b_slots);
+  uint64_t* mask = reinterpret_cast<uint64_t*>(block);
+  uint64_t* word_off = reinterpret_cast<uint64_t*>(block + b_words);
+  uint64_t* inside = reinterpret_cast<uint64_t*>(block + 2 * b_words);
+  float* dist = reinterpret_cast<float*>(block + 3 * b_words);
+  const BandDev X = dev_of(band);
+  const BandDev Wh = where ? dev_of(where) : X;
+  hipStream_t s = c.stream;
+
+  // ---- the table ----
+  if (c.timings) e = hipEventRecord(st->ev[0], s);
+  if (e == hipSuccess) e = hipMemsetAsync(d_hdr, 0, 32, s);
+  if (e == hipSuccess) e = hipMemsetAsync(dist, 0, 4, s);   // an empty result still has one defined float
+  if (e == hipSuccess) e = hipMemcpyAsync(mask, band->mask, n_words * 8, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(word_off, band->word_off, n_words * 8, hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return hip_fail(e);
+  if (n_slots == kBfAllSlots)
+    hipLaunchKernelGGL((k_bf_table<kBfAllSlots>), dim3(blocks), dim3(kWalkThreads), 0, s, X, Wh, where ? 1 : 0, g, slots, in_region, v[0], v[1]);
+  else
+    hipLaunchKernelGGL((k_bf_table<kBfAxisSlots>), dim3(blocks), dim3(kWalkThreads), 0, s, X, Wh, where ? 1 : 0, g, slots, in_region, v[0], v[1]);
+  e = hipGetLastError();
+  if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[1], s);
+  if (e != hipSuccess) return hip_fail(e);
+
+  // ---- the passes, back to back: pass p reads v[p & 1] and writes the other buffer ----
+  const unsigned pass_blocks = (unsigned)std::min<uint64_t>(1u << 20, (n + 255) / 256);
+  if (n) {
+    for (uint64_t p = 0; p < passes; ++p) {
+      const float* v_in = v[p & 1];
+      float* v_out = v[(p + 1) & 1];
+      if (kind == M2S_FILTER_LAPLACIAN) launch_pass<M2S_FILTER_LAPLACIAN, 0>(s, pass_blocks, slots, in_region, v_in, v_out, n, k, d_hdr);
+      else if (kind == M2S_FILTER_MEAN_CURVATURE) launch_pass<M2S_FILTER_MEAN_CURVATURE, 0>(s, pass_blocks, slots, in_region, v_in, v_out, n, k, d_hdr);
+      else if (p % 3 == 0) launch_pass<M2S_FILTER_MEAN, 0>(s, pass_blocks, slots, in_region, v_in, v_out, n, k, d_hdr);
+      else if (p % 3 == 1) launch_pass<M2S_FILTER_MEAN, 1>(s, pass_blocks, slots, in_region, v_in, v_out, n, k, d_hdr);
+      else launch_pass<M2S_FILTER_MEAN, 2>(s, pass_blocks, slots, in_region, v_in, v_out, n, k, d_hdr);
+    }
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[2], s);
+  if (e != hipSuccess) return hip_fail(e);
+
+  // ---- the result ----
+  hipLaunchKernelGGL(k_bf_final, dim3(blocks), dim3(kWalkThreads), 0, s, X, g, (const float*)v[passes & 1], inside, dist, d_hdr);
+  e = hipGetLastError();
+  uint64_t hdr[4] = {0, 0, 0, 0};
+  if (e == hipSuccess) e = hipMemcpyAsync(hdr, d_hdr, 32, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[3], s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);   // the call's one synchronisation
+  if (e != hipSuccess) return hip_fail(e);
+  if (c.timings) {
+    float table_ms = 0.0f, pass_ms = 0.0f, total = 0.0f;
+    (void)hipEventElapsedTime(&table_ms, st->ev[0], st->ev[1]);
+    (void)hipEventElapsedTime(&pass_ms, st->ev[1], st->ev[2]);
+    (void)hipEventElapsedTime(&total, st->ev[0], st->ev[3]);
+    memset(c.timings, 0, sizeof(*c.timings));
+    c.timings->seed_ms = table_ms;
+    c.timings->distance_ms = pass_ms;
+    c.timings->total_ms = total;
+    c.timings->n_units = n;
+    c.timings->distance_launches = (uint32_t)(n ? passes : 0);
+  }
+  (void)hipFree(tmp);
+  if (info_out) {
+    const uint32_t top = (uint32_t)hdr[3];
+    info_out->passes = (uint32_t)passes;
+    memcpy(&info_out->max_change, &top, 4);
+    info_out->reserved = 0;
+    info_out->n_changed = hdr[1];
+    info_out->n_sign_flips = hdr[2];
+    info_out->n_nonfinite = hdr[0];
+  }
+  m2s_band* h = new m2s_band();
+  h->device = band->device;
+  h->grid = band->grid;
+  h->n = n;
+  h->total = g.total;
+  h->n_words = n_words;
+  h->device_bytes = n_words * 24 + n * 4;
+  h->block = block;
+  h->mask = mask;
+  h->word_off = word_off;
+  h->inside = inside;
+  h->dist = dist;
+  h->bg_out = fopts ? fopts->background_outside : band->bg_out;
+  h->bg_in = fopts ? fopts->background_inside : band->bg_in;
+  *out = h;
+  return M2S_OK;
+}
+
+}  // extern "C"

@@ -24,6 +24,7 @@
 // All stores are plain vector stores; the ballot loops are wave-uniform.
 #include "../../include/m2s.h"
 #include "band_handle.h"
+#include "band_walk.hip.h"
 #include "capi_internal.h"
 #include "common.h"
 #include "scan.hip.h"
@@ -37,99 +38,29 @@
 namespace m2s {
 namespace {
 
-constexpr int kRdThreads = 256;
-constexpr int kRdWaves = kRdThreads / 64;
-constexpr int kRdSteps = 4;                                // steps of 64 words per wave
-constexpr uint64_t kRdUnit = 64 * kRdSteps;                // 256 words per wave
 constexpr int kRdGroup = 16;                               // units per scanned sum (at most 64: one lane each in k_rd_offsets)
 constexpr int kRdScanThreads = 1024;
 constexpr int kRdBatch = 4;                                // sweeps between two reads of the change flags
 
-struct RdGrid {
-  uint64_t total, n_words;
-  uint64_t nx, ny, nz;
-  uint64_t sj, si;   // the strides of j and i in L: nz, ny * nz
-};
-
-struct RdIjk {
-  uint64_t i, j, k;
-};
-
-__device__ __forceinline__ uint64_t rd_lane(uint64_t v, int j) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t rd_below(int t) { return (1ull << t) - 1ull; }
-__device__ __forceinline__ uint64_t rd_valid(uint64_t w, bool in_range, uint64_t total) {
-  const uint64_t left = in_range ? total - (w << 6) : 0;
-  return left >= 64 ? ~0ull : ((1ull << left) - 1ull);
-}
-// (i, j, k) of a word's first point: the two 64-bit divisions of a word, taken only by lanes whose word has work.
-__device__ __forceinline__ RdIjk rd_base(uint64_t L0, const RdGrid& g) {
-  RdIjk b;
-  const uint64_t row = L0 / g.nz;
-  b.k = L0 - row * g.nz;
-  b.i = row / g.ny;
-  b.j = row - b.i * g.ny;
-  return b;
-}
-__device__ __forceinline__ RdIjk rd_bcast(const RdIjk& b, int j) { return RdIjk{rd_lane(b.i, j), rd_lane(b.j, j), rd_lane(b.k, j)}; }
-// The base stepped by t < 64 points.  The branches are wave-uniform: with 64 or more points per row a step crosses one row end at most.
-__device__ __forceinline__ RdIjk rd_step(const RdIjk& b, uint32_t t, const RdGrid& g) {
-  RdIjk p;
-  uint64_t kk = b.k + t, q;
-  if (g.nz >= 64) {
-    q = kk >= g.nz ? 1 : 0;
-    kk -= q ? g.nz : 0;
-  } else {
-    const uint32_t q32 = (uint32_t)kk / (uint32_t)g.nz;   // kk < nz + 64 < 128
-    q = q32;
-    kk -= (uint64_t)q32 * g.nz;
-  }
-  uint64_t jj = b.j + q, q2;   // q <= 63
-  if (g.ny >= 64) {
-    q2 = jj >= g.ny ? 1 : 0;
-    jj -= q2 ? g.ny : 0;
-  } else {
-    const uint32_t q32 = (uint32_t)jj / (uint32_t)g.ny;   // jj < ny + 64 < 128
-    q2 = q32;
-    jj -= (uint64_t)q32 * g.ny;
-  }
-  p.k = kk;
-  p.j = jj;
-  p.i = b.i + q2;
-  return p;
-}
 __device__ __forceinline__ bool rd_bit(const uint64_t* __restrict__ a, uint64_t L) { return (a[L >> 6] >> (L & 63)) & 1ull; }
 
-#define RD_UNIT_HEAD                                                                                                              \
-  const int lane = threadIdx.x & 63;                                                                                              \
-  const uint64_t unit = (uint64_t)blockIdx.x * kRdWaves + (uint64_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);             \
-  const uint64_t w0 = unit * kRdUnit;                                                                                             \
-  if (w0 >= g.n_words) return; /* the whole wave: the last workgroup's spare units */
-#define RD_STEP_HEAD                                                                                                              \
-  const uint64_t wb = w0 + (uint64_t)step * 64; /* wave-uniform */                                                                \
-  if (wb >= g.n_words) break;                                                                                                     \
-  const uint64_t w = wb + lane;                                                                                                   \
-  const bool in_range = w < g.n_words;
-
 // s on every grid point, bits past the grid zero.
-__global__ void __launch_bounds__(kRdThreads) k_rd_sign(BandDev X, RdGrid g, uint64_t* __restrict__ S) {
-  RD_UNIT_HEAD
-  for (int step = 0; step < kRdSteps; ++step) {
-    RD_STEP_HEAD
+__global__ void __launch_bounds__(kWalkThreads) k_rd_sign(BandDev X, WalkGrid g, uint64_t* __restrict__ S) {
+  WALK_UNIT_HEAD
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD
     const uint64_t m = in_range ? X.mask[w] : 0;
     const uint64_t in = in_range && X.inside ? X.inside[w] : 0;
     const uint64_t wo = m ? X.word_off[w] : 0;
-    const uint64_t valid = rd_valid(w, in_range, g.total);
+    const uint64_t valid = walk_valid(w, in_range, g.total);
     uint64_t s = in & valid;
     uint64_t todo = __ballot(m != 0);
     while (todo) {   // wave-uniform
       const int j = __ffsll((unsigned long long)todo) - 1;
       todo &= todo - 1;
-      const uint64_t mj = rd_lane(m, j), inj = rd_lane(in, j), woj = rd_lane(wo, j);
+      const uint64_t mj = walk_lane(m, j), inj = walk_lane(in, j), woj = walk_lane(wo, j);
       const bool act = (mj >> lane) & 1ull;
-      uint64_t at = woj + (uint64_t)__popcll(mj & rd_below(lane));
+      uint64_t at = woj + (uint64_t)__popcll(mj & walk_below(lane));
       at = at < X.n ? at : 0;
       bool sb = (inj >> lane) & 1ull;
       if (act) sb = X.dist[at] < 0.0f;
@@ -141,23 +72,23 @@ __global__ void __launch_bounds__(kRdThreads) k_rd_sign(BandDev X, RdGrid g, uin
 }
 
 // F, and counters[0] += n_frozen, counters[1] += n_open.
-__global__ void __launch_bounds__(kRdThreads) k_rd_frozen(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ S, RdGrid g,
+__global__ void __launch_bounds__(kWalkThreads) k_rd_frozen(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ S, WalkGrid g,
                                                           uint64_t* __restrict__ Fm, uint64_t* __restrict__ counters) {
-  RD_UNIT_HEAD
+  WALK_UNIT_HEAD
   uint64_t n_frozen = 0, n_open = 0;
-  for (int step = 0; step < kRdSteps; ++step) {
-    RD_STEP_HEAD
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD
     const uint64_t m = in_range ? mask[w] : 0;
     const uint64_t sw = m ? S[w] : 0;
-    RdIjk base{0, 0, 0};
-    if (m) base = rd_base(w << 6, g);
+    WalkIjk base{0, 0, 0};
+    if (m) base = walk_base(w << 6, g);
     uint64_t f = 0;
     uint64_t todo = __ballot(m != 0);
     while (todo) {   // wave-uniform
       const int j = __ffsll((unsigned long long)todo) - 1;
       todo &= todo - 1;
-      const uint64_t mj = rd_lane(m, j), sj = rd_lane(sw, j);
-      const RdIjk p = rd_step(rd_bcast(base, j), (uint32_t)lane, g);
+      const uint64_t mj = walk_lane(m, j), sj = walk_lane(sw, j);
+      const WalkIjk p = walk_step(walk_bcast(base, j), (uint32_t)lane, g);
       const uint64_t L = ((wb + (uint64_t)j) << 6) + (uint64_t)lane;
       const bool act = (mj >> lane) & 1ull, sL = (sj >> lane) & 1ull;
       bool frozen = false;
@@ -210,12 +141,12 @@ __device__ __forceinline__ uint64_t rd_window(const uint64_t* __restrict__ src, 
 // dst = src dilated along one axis (AXIS 0: i, 1: j, 2: k) by the taps d * hop, |d| <= K, clipped to the grid.  hop == 1: the box
 // dilation by K.
 template <int AXIS>
-__global__ void __launch_bounds__(kRdThreads) k_rd_dilate(const uint64_t* __restrict__ src, RdGrid g, int64_t K, int64_t hop, uint64_t* __restrict__ dst) {
-  RD_UNIT_HEAD
+__global__ void __launch_bounds__(kWalkThreads) k_rd_dilate(const uint64_t* __restrict__ src, WalkGrid g, int64_t K, int64_t hop, uint64_t* __restrict__ dst) {
+  WALK_UNIT_HEAD
   const int64_t stride = (AXIS == 0 ? (int64_t)g.si : AXIS == 1 ? (int64_t)g.sj : 1) * hop;
   const int64_t n_axis = (int64_t)(AXIS == 0 ? g.nx : AXIS == 1 ? g.ny : g.nz);
-  for (int step = 0; step < kRdSteps; ++step) {
-    RD_STEP_HEAD
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD
     uint64_t any = 0;
     if (in_range) {
       if (AXIS == 2 && hop == 1 && K < 64) {   // the windows overlap: the word, the K bits before it and the K bits after it
@@ -226,15 +157,15 @@ __global__ void __launch_bounds__(kRdThreads) k_rd_dilate(const uint64_t* __rest
         for (int64_t d = -K; d <= K; ++d) any |= rd_window(src, (int64_t)(w << 6) + d * stride, g.n_words);
       }
     }
-    RdIjk base{0, 0, 0};
-    if (any) base = rd_base(w << 6, g);
-    const uint64_t valid = rd_valid(w, in_range, g.total);
+    WalkIjk base{0, 0, 0};
+    if (any) base = walk_base(w << 6, g);
+    const uint64_t valid = walk_valid(w, in_range, g.total);
     uint64_t out = 0;
     uint64_t todo = __ballot(any != 0);
     while (todo) {   // wave-uniform
       const int j = __ffsll((unsigned long long)todo) - 1;
       todo &= todo - 1;
-      const RdIjk p = rd_step(rd_bcast(base, j), (uint32_t)lane, g);
+      const WalkIjk p = walk_step(walk_bcast(base, j), (uint32_t)lane, g);
       const int64_t L = (int64_t)(((wb + (uint64_t)j) << 6) + (uint64_t)lane);
       const int64_t c = (int64_t)(AXIS == 0 ? p.i : AXIS == 1 ? p.j : p.k);
       bool hit = false;
@@ -258,12 +189,12 @@ __global__ void __launch_bounds__(256) k_rd_select(const uint64_t* DE, const uin
 }
 
 // A mask's popcounts per unit, and by one atomic add per unit the sum of its group (zeroed by the launcher).
-__global__ void __launch_bounds__(kRdThreads) k_rd_count(const uint64_t* __restrict__ mask, RdGrid g, uint32_t* __restrict__ unit_cnt,
+__global__ void __launch_bounds__(kWalkThreads) k_rd_count(const uint64_t* __restrict__ mask, WalkGrid g, uint32_t* __restrict__ unit_cnt,
                                                          uint64_t* __restrict__ group_sum) {
-  RD_UNIT_HEAD
+  WALK_UNIT_HEAD
   uint64_t cnt = 0;
-  for (int step = 0; step < kRdSteps; ++step) {
-    RD_STEP_HEAD
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD
     cnt += in_range ? (uint64_t)__popcll(mask[w]) : 0;
   }
 #pragma unroll
@@ -275,16 +206,16 @@ __global__ void __launch_bounds__(kRdThreads) k_rd_count(const uint64_t* __restr
 }
 
 // word_off of a mask from the scanned group sums and the unit counts.
-__global__ void __launch_bounds__(kRdThreads) k_rd_offsets(const uint64_t* __restrict__ mask, RdGrid g, const uint32_t* __restrict__ unit_cnt,
+__global__ void __launch_bounds__(kWalkThreads) k_rd_offsets(const uint64_t* __restrict__ mask, WalkGrid g, const uint32_t* __restrict__ unit_cnt,
                                                            const uint64_t* __restrict__ group_base, uint64_t* __restrict__ word_off) {
-  RD_UNIT_HEAD
+  WALK_UNIT_HEAD
   const uint64_t first = unit - unit % kRdGroup;   // the group's first unit: every unit from there to this one exists
   uint64_t before = first + lane < unit ? unit_cnt[first + lane] : 0;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
   uint64_t base = group_base[unit / kRdGroup] + before;
-  for (int step = 0; step < kRdSteps; ++step) {
-    RD_STEP_HEAD
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD
     const uint64_t c = in_range ? (uint64_t)__popcll(mask[w]) : 0;
     uint64_t incl = c;
 #pragma unroll
@@ -293,13 +224,13 @@ __global__ void __launch_bounds__(kRdThreads) k_rd_offsets(const uint64_t* __res
       if (lane >= o) incl += y;
     }
     if (in_range) word_off[w] = base + incl - c;
-    base += rd_lane(incl, 63);
+    base += walk_lane(incl, 63);
   }
 }
 
 // x of an active point of X: bit t of word w.
 __device__ __forceinline__ float rd_x(const BandDev& X, uint64_t mX, uint64_t woX, int t) {
-  uint64_t at = woX + (uint64_t)__popcll(mX & rd_below(t));
+  uint64_t at = woX + (uint64_t)__popcll(mX & walk_below(t));
   at = at < X.n ? at : 0;   // at < n whenever the index is sound
   return X.dist[at];
 }
@@ -321,7 +252,7 @@ __device__ __forceinline__ uint32_t rd_slot(const RdField& p, uint64_t M, bool s
   const uint64_t cm = p.C[w];
   uint32_t slot = kRdNone;
   if (((cm >> b) & 1ull) && (((p.S[w] >> b) & 1ull) != 0) == sL) {
-    const uint64_t r = p.Coff[w] + (uint64_t)__popcll(cm & rd_below(b));
+    const uint64_t r = p.Coff[w] + (uint64_t)__popcll(cm & walk_below(b));
     if (r < p.n_cand) slot = (uint32_t)r;   // n_cand < kRdNone (the host checks)
   }
   return slot;
@@ -330,27 +261,27 @@ __device__ __forceinline__ uint32_t rd_slot(const RdField& p, uint64_t M, bool s
 // Per candidate, once: its six neighbour slots (i+, i-, j+, j-, k+, k-; slots[n * n_cand + r]), meta (bit 0: frozen, bit 1: s) and the
 // start value u = |x| on F, +inf elsewhere, into both value buffers.  The in-grid test, the same-sign test and the membership in C
 // fold into kRdNone, so a sweep needs no index word and no coordinate.
-__global__ void __launch_bounds__(kRdThreads) k_rd_table(BandDev X, RdGrid g, const uint64_t* __restrict__ Fm, RdField fld, uint32_t* __restrict__ slots,
+__global__ void __launch_bounds__(kWalkThreads) k_rd_table(BandDev X, WalkGrid g, const uint64_t* __restrict__ Fm, RdField fld, uint32_t* __restrict__ slots,
                                                          uint8_t* __restrict__ meta, float* __restrict__ u0, float* __restrict__ u1) {
-  RD_UNIT_HEAD
-  for (int step = 0; step < kRdSteps; ++step) {
-    RD_STEP_HEAD
+  WALK_UNIT_HEAD
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD
     const uint64_t c = in_range ? fld.C[w] : 0;
     const uint64_t co = c ? fld.Coff[w] : 0;
     const uint64_t f = c ? Fm[w] : 0;
     const uint64_t sw = c ? fld.S[w] : 0;
     const uint64_t mX = f ? X.mask[w] : 0;
     const uint64_t woX = f ? X.word_off[w] : 0;
-    RdIjk base{0, 0, 0};
-    if (c) base = rd_base(w << 6, g);
+    WalkIjk base{0, 0, 0};
+    if (c) base = walk_base(w << 6, g);
     uint64_t todo = __ballot(c != 0);
     while (todo) {   // wave-uniform
       const int j = __ffsll((unsigned long long)todo) - 1;
       todo &= todo - 1;
-      const uint64_t cj = rd_lane(c, j), coj = rd_lane(co, j), fj = rd_lane(f, j), sj = rd_lane(sw, j), mXj = rd_lane(mX, j), woXj = rd_lane(woX, j);
-      const RdIjk p = rd_step(rd_bcast(base, j), (uint32_t)lane, g);
+      const uint64_t cj = walk_lane(c, j), coj = walk_lane(co, j), fj = walk_lane(f, j), sj = walk_lane(sw, j), mXj = walk_lane(mX, j), woXj = walk_lane(woX, j);
+      const WalkIjk p = walk_step(walk_bcast(base, j), (uint32_t)lane, g);
       const uint64_t L = ((wb + (uint64_t)j) << 6) + (uint64_t)lane;
-      const uint64_t r = coj + (uint64_t)__popcll(cj & rd_below(lane));
+      const uint64_t r = coj + (uint64_t)__popcll(cj & walk_below(lane));
       if (((cj >> lane) & 1ull) && r < fld.n_cand) {   // a point of C is inside the grid
         const bool sL = (sj >> lane) & 1ull, frozen = (fj >> lane) & 1ull;
         uint32_t s0 = kRdNone, s1 = kRdNone, s2 = kRdNone, s3 = kRdNone, s4 = kRdNone, s5 = kRdNone;
@@ -447,11 +378,11 @@ __global__ void __launch_bounds__(256) k_rd_sweep(const uint32_t* __restrict__ s
 }
 
 // The result's mask: F, or in C with u <= W.
-__global__ void __launch_bounds__(kRdThreads) k_rd_final(RdGrid g, const uint64_t* __restrict__ Fm, RdField fld, float w_out, float w_in,
+__global__ void __launch_bounds__(kWalkThreads) k_rd_final(WalkGrid g, const uint64_t* __restrict__ Fm, RdField fld, float w_out, float w_in,
                                                          uint64_t* __restrict__ R) {
-  RD_UNIT_HEAD
-  for (int step = 0; step < kRdSteps; ++step) {
-    RD_STEP_HEAD
+  WALK_UNIT_HEAD
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD
     const uint64_t c = in_range ? fld.C[w] : 0;
     const uint64_t f = c ? Fm[w] : 0;
     const uint64_t co = c ? fld.Coff[w] : 0;
@@ -461,8 +392,8 @@ __global__ void __launch_bounds__(kRdThreads) k_rd_final(RdGrid g, const uint64_
     while (todo) {   // wave-uniform
       const int j = __ffsll((unsigned long long)todo) - 1;
       todo &= todo - 1;
-      const uint64_t cj = rd_lane(c, j), fj = rd_lane(f, j), coj = rd_lane(co, j), sj = rd_lane(sw, j);
-      uint64_t r = coj + (uint64_t)__popcll(cj & rd_below(lane));
+      const uint64_t cj = walk_lane(c, j), fj = walk_lane(f, j), coj = walk_lane(co, j), sj = walk_lane(sw, j);
+      uint64_t r = coj + (uint64_t)__popcll(cj & walk_below(lane));
       r = r < fld.n_cand ? r : 0;
       bool keep = false;
       if ((cj >> lane) & 1ull) keep = ((fj >> lane) & 1ull) || fld.u[r] <= (((sj >> lane) & 1ull) ? w_in : w_out);
@@ -474,11 +405,11 @@ __global__ void __launch_bounds__(kRdThreads) k_rd_final(RdGrid g, const uint64_
 }
 
 // The result's values at Roff + rank: x on F, else -u or +u by s.  cap: the floats out holds.
-__global__ void __launch_bounds__(kRdThreads) k_rd_emit(BandDev X, RdGrid g, const uint64_t* __restrict__ Fm, RdField fld, const uint64_t* __restrict__ R,
+__global__ void __launch_bounds__(kWalkThreads) k_rd_emit(BandDev X, WalkGrid g, const uint64_t* __restrict__ Fm, RdField fld, const uint64_t* __restrict__ R,
                                                         const uint64_t* __restrict__ Roff, float* __restrict__ out, uint64_t cap) {
-  RD_UNIT_HEAD
-  for (int step = 0; step < kRdSteps; ++step) {
-    RD_STEP_HEAD
+  WALK_UNIT_HEAD
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD
     const uint64_t rm = in_range ? R[w] : 0;
     const uint64_t ro = rm ? Roff[w] : 0;
     const uint64_t c = rm ? fld.C[w] : 0;
@@ -491,19 +422,19 @@ __global__ void __launch_bounds__(kRdThreads) k_rd_emit(BandDev X, RdGrid g, con
     while (todo) {   // wave-uniform
       const int j = __ffsll((unsigned long long)todo) - 1;
       todo &= todo - 1;
-      const uint64_t rj = rd_lane(rm, j), roj = rd_lane(ro, j), cj = rd_lane(c, j), coj = rd_lane(co, j), sj = rd_lane(sw, j), fj = rd_lane(f, j);
-      const uint64_t mXj = rd_lane(mX, j), woXj = rd_lane(woX, j);
+      const uint64_t rj = walk_lane(rm, j), roj = walk_lane(ro, j), cj = walk_lane(c, j), coj = walk_lane(co, j), sj = walk_lane(sw, j), fj = walk_lane(f, j);
+      const uint64_t mXj = walk_lane(mX, j), woXj = walk_lane(woX, j);
       if ((rj >> lane) & 1ull) {
         float v;
         if ((fj >> lane) & 1ull) {
           v = rd_x(X, mXj, woXj, lane);
         } else {
-          uint64_t r = coj + (uint64_t)__popcll(cj & rd_below(lane));
+          uint64_t r = coj + (uint64_t)__popcll(cj & walk_below(lane));
           r = r < fld.n_cand ? r : 0;
           const float u = fld.u[r];
           v = ((sj >> lane) & 1ull) ? -u : u;
         }
-        const uint64_t pos = roj + (uint64_t)__popcll(rj & rd_below(lane));
+        const uint64_t pos = roj + (uint64_t)__popcll(rj & walk_below(lane));
         if (pos < cap) out[pos] = v;
       }
     }
@@ -519,13 +450,13 @@ int64_t reach(float width, float h, uint64_t n) {
 }
 
 template <int AXIS>
-void dilate_axis(hipStream_t st, unsigned blocks, const RdGrid& g, int64_t K, int64_t hop, const uint64_t* src, uint64_t* dst) {
-  hipLaunchKernelGGL((k_rd_dilate<AXIS>), dim3(blocks), dim3(kRdThreads), 0, st, src, g, K, hop, dst);
+void dilate_axis(hipStream_t st, unsigned blocks, const WalkGrid& g, int64_t K, int64_t hop, const uint64_t* src, uint64_t* dst) {
+  hipLaunchKernelGGL((k_rd_dilate<AXIS>), dim3(blocks), dim3(kWalkThreads), 0, st, src, g, K, hop, dst);
 }
 
 // dst = src dilated by the box K.  One gather per axis over its 2K + 1 windows.  M2S_RD_DILATE (an A/B build, tools/build_ab.sh) selects
 // what it was measured against: 1: K single steps per axis, 2: steps of 1, 2, 4, ... (three taps each), both through t1 and t2 and a copy.
-void dilate(hipStream_t st, unsigned blocks, const RdGrid& g, const int64_t K[3], const uint64_t* src, uint64_t* t1, uint64_t* t2, uint64_t* dst) {
+void dilate(hipStream_t st, unsigned blocks, const WalkGrid& g, const int64_t K[3], const uint64_t* src, uint64_t* t1, uint64_t* t2, uint64_t* dst) {
 #if defined(M2S_RD_DILATE) && M2S_RD_DILATE > 0
   const uint64_t* cur = src;
   uint64_t* bufs[2] = {t1, t2};
@@ -594,7 +525,7 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   const float w_out = ropts->exterior, w_in = ropts->interior;
   const float hx = band->grid.cell_size[0], hy = band->grid.cell_size[1], hz = band->grid.cell_size[2];
   const float wx = 1.0f / (hx * hx), wy = 1.0f / (hy * hy), wz = 1.0f / (hz * hz);
-  RdGrid g;
+  WalkGrid g;
   g.total = band->total;
   g.n_words = band->n_words;
   g.nx = band->grid.cell_count[0];
@@ -615,9 +546,9 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   const bool one_reach = memcmp(k_out, k_in, sizeof(k_out)) == 0;
 
   const uint64_t n_words = g.n_words;
-  const uint64_t n_units = (n_words + kRdUnit - 1) / kRdUnit;   // below 2^22: a grid has fewer than 2^36 cells
+  const uint64_t n_units = (n_words + kWalkUnit - 1) / kWalkUnit;   // below 2^22: a grid has fewer than 2^36 cells
   const uint64_t n_groups = (n_units + kRdGroup - 1) / kRdGroup;
-  const unsigned blocks = (unsigned)((n_units + kRdWaves - 1) / kRdWaves);
+  const unsigned blocks = (unsigned)((n_units + kWalkWaves - 1) / kWalkWaves);
   const size_t b_words = align_up(n_words * 8);
   const int n_arrays = one_reach ? 6 : 7;   // S, F, T1, T2, DE (then C), Coff[, DI]
   char* tmp = nullptr;
@@ -653,7 +584,7 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   auto count_and_scan = [&](const uint64_t* mask) {
     hipError_t r = hipMemsetAsync(group_sum, 0, n_groups * 8, s);
     if (r != hipSuccess) return r;
-    hipLaunchKernelGGL(k_rd_count, dim3(blocks), dim3(kRdThreads), 0, s, mask, g, unit_cnt, group_sum);
+    hipLaunchKernelGGL(k_rd_count, dim3(blocks), dim3(kWalkThreads), 0, s, mask, g, unit_cnt, group_sum);
     hipLaunchKernelGGL((k_scan_tiles<kRdScanThreads, uint64_t>), dim3(1), dim3(kRdScanThreads), 0, s, group_sum, n_groups, d_hdr + 2);
     return hipGetLastError();
   };
@@ -662,8 +593,8 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   if (c.timings) e = hipEventRecord(st->ev[0], s);
   if (e == hipSuccess) e = hipMemsetAsync(d_hdr, 0, 32, s);
   if (e != hipSuccess) return hip_fail(e);
-  hipLaunchKernelGGL(k_rd_sign, dim3(blocks), dim3(kRdThreads), 0, s, X, g, S);
-  hipLaunchKernelGGL(k_rd_frozen, dim3(blocks), dim3(kRdThreads), 0, s, X.mask, (const uint64_t*)S, g, Fm, d_hdr);
+  hipLaunchKernelGGL(k_rd_sign, dim3(blocks), dim3(kWalkThreads), 0, s, X, g, S);
+  hipLaunchKernelGGL(k_rd_frozen, dim3(blocks), dim3(kWalkThreads), 0, s, X.mask, (const uint64_t*)S, g, Fm, d_hdr);
   dilate(s, blocks, g, k_out, Fm, T1, T2, Cm);
   if (!one_reach) dilate(s, blocks, g, k_in, Fm, T1, T2, DI);
   hipLaunchKernelGGL(k_rd_select, dim3((unsigned)std::min<uint64_t>(1u << 20, (n_words + 255) / 256)), dim3(256), 0, s, (const uint64_t*)Cm,
@@ -686,8 +617,8 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   uint32_t* slots = reinterpret_cast<uint32_t*>(ubuf + 2 * b_u);
   uint8_t* meta = reinterpret_cast<uint8_t*>(ubuf + 2 * b_u + align_up(6 * n_cand * 4 + 4));
   RdField fld{Cm, Coff, S, u[0], n_cand};
-  hipLaunchKernelGGL(k_rd_offsets, dim3(blocks), dim3(kRdThreads), 0, s, (const uint64_t*)Cm, g, (const uint32_t*)unit_cnt, (const uint64_t*)group_sum, Coff);
-  hipLaunchKernelGGL(k_rd_table, dim3(blocks), dim3(kRdThreads), 0, s, X, g, (const uint64_t*)Fm, fld, slots, meta, u[0], u[1]);
+  hipLaunchKernelGGL(k_rd_offsets, dim3(blocks), dim3(kWalkThreads), 0, s, (const uint64_t*)Cm, g, (const uint32_t*)unit_cnt, (const uint64_t*)group_sum, Coff);
+  hipLaunchKernelGGL(k_rd_table, dim3(blocks), dim3(kWalkThreads), 0, s, X, g, (const uint64_t*)Fm, fld, slots, meta, u[0], u[1]);
   e = hipGetLastError();
   if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[1], s);
   if (e != hipSuccess) return hip_fail(e);
@@ -721,7 +652,7 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
 
   // ---- the result ----
   uint64_t* R = T1;
-  hipLaunchKernelGGL(k_rd_final, dim3(blocks), dim3(kRdThreads), 0, s, g, (const uint64_t*)Fm, fld, w_out, w_in, R);
+  hipLaunchKernelGGL(k_rd_final, dim3(blocks), dim3(kWalkThreads), 0, s, g, (const uint64_t*)Fm, fld, w_out, w_in, R);
   e = hipGetLastError();
   if (e == hipSuccess) e = count_and_scan(R);
   uint64_t n = 0;
@@ -740,8 +671,8 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   if (e == hipSuccess) e = hipMemcpyAsync(mask, R, n_words * 8, hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(inside, S, n_words * 8, hipMemcpyDeviceToDevice, s);
   if (e != hipSuccess) return hip_fail(e);
-  hipLaunchKernelGGL(k_rd_offsets, dim3(blocks), dim3(kRdThreads), 0, s, (const uint64_t*)R, g, (const uint32_t*)unit_cnt, (const uint64_t*)group_sum, word_off);
-  hipLaunchKernelGGL(k_rd_emit, dim3(blocks), dim3(kRdThreads), 0, s, X, g, (const uint64_t*)Fm, fld, (const uint64_t*)R, (const uint64_t*)word_off, dist, cap);
+  hipLaunchKernelGGL(k_rd_offsets, dim3(blocks), dim3(kWalkThreads), 0, s, (const uint64_t*)R, g, (const uint32_t*)unit_cnt, (const uint64_t*)group_sum, word_off);
+  hipLaunchKernelGGL(k_rd_emit, dim3(blocks), dim3(kWalkThreads), 0, s, X, g, (const uint64_t*)Fm, fld, (const uint64_t*)R, (const uint64_t*)word_off, dist, cap);
   e = hipGetLastError();
   if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[3], s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
