@@ -312,6 +312,13 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+// The owner lane's value of a queued pair: ds_bpermute takes the source lane as a byte address (lane << 2), formed ONCE per batch by
+// owner_addr and shared by the batch's three or four fetches.  (__shfl forms it as ((self & 64) | lane) << 2: the compiler cannot see that a
+// wave has no lane >= 64, and `self & 64` cost the walk a VGPR for its whole length.)  Pair words keep the lane in bits 0..5.
+__device__ __forceinline__ uint32_t owner_addr(uint32_t pair) { return (pair & 63u) << 2; }
+__device__ __forceinline__ float owner_fetch(uint32_t addr, float x) {
+  return __int_as_float(__builtin_amdgcn_ds_bpermute((int)addr, __float_as_int(x)));
+}
 template <int MODE>
 __device__ __forceinline__ unsigned long long defer_key(const Best<MODE>& x) {
   return ((unsigned long long)__float_as_uint(x.d2) << 32) | ((unsigned long long)(x.idx & 0x7fffffffu) << 1) | (x.pos ? 0ull : 1ull);
@@ -335,8 +342,8 @@ __device__ __forceinline__ void defer_flush(const DeviceMesh& mesh, f3 p, DeferQ
   const uint32_t take = min(dq.n, 64u);
   const bool valid = lane < take;
   const uint32_t e = valid ? dq.q[(dq.head + lane) & 127u] : 0u;
-  const uint32_t v = e & 63u, t = e >> 6;
-  const f3 pv = mk3(__shfl(p.x, (int)v), __shfl(p.y, (int)v), __shfl(p.z, (int)v));
+  const uint32_t v = e & 63u, t = e >> 6, va = owner_addr(e);
+  const f3 pv = mk3(owner_fetch(va, p.x), owner_fetch(va, p.y), owner_fetch(va, p.z));
   Best<MODE> one;
   eval_triangle<MODE>(one, pv, mesh.tris[t]);
   if (valid) {
@@ -385,9 +392,9 @@ __device__ __forceinline__ bool defer_pretest(const DeviceMesh& mesh, f3 p, floa
   const uint32_t take = min(dq.n1, 64u);
   const bool valid = lane < take;
   const uint32_t e = valid ? dq.q1[(dq.head1 + lane) & 127u] : 0u;
-  const uint32_t v = e & 63u, t = e >> 6;
-  const f3 pv = mk3(__shfl(p.x, (int)v), __shfl(p.y, (int)v), __shfl(p.z, (int)v));
-  const float tv = __shfl(thr, (int)v);
+  const uint32_t t = e >> 6, va = owner_addr(e);
+  const f3 pv = mk3(owner_fetch(va, p.x), owner_fetch(va, p.y), owner_fetch(va, p.z));
+  const float tv = owner_fetch(va, thr);
   const bool pass = valid & !(planes_dist2(pv, mesh.planes[t]) > tv);
   dq.head1 = (dq.head1 + take) & 127u;
   dq.n1 -= take;
@@ -427,16 +434,16 @@ __device__ __forceinline__ void pretest_issue(const DeviceMesh& mesh, DeferQueue
 __device__ __forceinline__ void pretest_forget(PretestAhead& ga) {
   float* f = reinterpret_cast<float*>(&ga.tp);
   static_assert(sizeof(TriPlanes) == 64, "sixteen words");
-#pragma unroll
-  for (int i = 0; i < 16; ++i) asm volatile("" : "=v"(f[i]));
-  asm volatile("" : "=v"(ga.e));
+  // ONE statement: seventeen separate ones came out with a hazard s_nop between each where the in-leaf consume stands, 16 issue slots a time.
+  asm volatile("" : "=v"(f[0]), "=v"(f[1]), "=v"(f[2]), "=v"(f[3]), "=v"(f[4]), "=v"(f[5]), "=v"(f[6]), "=v"(f[7]), "=v"(f[8]), "=v"(f[9]),
+                    "=v"(f[10]), "=v"(f[11]), "=v"(f[12]), "=v"(f[13]), "=v"(f[14]), "=v"(f[15]), "=v"(ga.e));
 }
 // Returns true if the second ring was flushed (the lanes' bounds have moved).
 template <int MODE>
 __device__ __forceinline__ bool pretest_consume(const DeviceMesh& mesh, f3 p, float thr, DeferQueue& dq, Best<MODE>& best, PretestAhead& ga) {
-  const uint32_t e = ga.e, v = e & 63u;
-  const f3 pv = mk3(__shfl(p.x, (int)v), __shfl(p.y, (int)v), __shfl(p.z, (int)v));
-  const float tv = __shfl(thr, (int)v);
+  const uint32_t e = ga.e, va = owner_addr(e);
+  const f3 pv = mk3(owner_fetch(va, p.x), owner_fetch(va, p.y), owner_fetch(va, p.z));
+  const float tv = owner_fetch(va, thr);
   const bool pass = !(planes_dist2(pv, ga.tp) > tv);
   ga.pending = false;
   return pretest_pass_on<MODE>(mesh, p, dq, best, e, pass);
@@ -457,9 +464,15 @@ __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float sl
                                           PretestAhead* gap = nullptr) {
   // The walk addresses NodeExt by BYTE offset (its skip links are stored that way): the scalar loads then take
   // the offset operand directly and the loop carries no address arithmetic.
+  // `off` is wave-uniform at every caller (a v_readlane / v_readfirstlane result) and stays so: it only ever takes nr.skip or off + NB.
+  // The three outcomes of a visit — pruned, interior, leaf — each set `off` and go on to the loop test.  `below`, the
+  // record behind this one, is formed in FRONT of the leaf test because both sides use it (the interior's next record, the start of a leaf's
+  // cursor): with the addition on the interior side alone, that side was a block of its own, the join in front of the loop test was compiled
+  // through a pair of wave-mask flags, and "add 48 and loop" cost nine scalar instructions and four branches; now six and three.  (An early
+  // `continue` for the interior WITHOUT the shared addition moved the gather-ahead batch's 17 registers to other registers inside the leaf and
+  // back — 50 more v_mov and 52 bytes of scratch.  profiles/walk_isa.txt.)
   constexpr uint32_t NB = (uint32_t)sizeof(NodeExt);
   while (off < end) {
-    off = __builtin_amdgcn_readfirstlane(off);
     const NodeExt nr = record_at_bytes<NodeExt>(mesh.ext, off);
     if (STATS) ++st.box;
     const float ed2 = ext_dist2(p, nr);
@@ -474,8 +487,18 @@ __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float sl
       if (__ballot(!(sq * sq > thr)) == 0ull) ++st.sphere;
     }
     if (__ballot(!(ed2 > thr)) == 0ull) { off = nr.skip; continue; }   // a NaN bound keeps the node
+    const uint32_t below = off + NB;                            // the first child's record; a leaf's cursor starts there too
+    // Which side stands first in the source decides how the register allocator lays the loop out, and the two kinds of form want it differently
+    // (tools/kernel_resources.py): the plain forms take the interior visit first — the headline form is 26 scalar instructions and 8 branches
+    // shorter that way, statically, most of them in the node loop —, the split forms (BUDGET, EMIT; k_split_round inlines this function three times at the SGPR cap) the leaf, as
+    // they always had it: interior first costs k_split_round<1> 16 bytes of scratch more and k_split_round<0> a VGPR.
+    if (!(BUDGET || EMIT) && nr.tri < 0) { off = below; continue; }   // interior: on to its first child
     if (nr.tri >= 0) {
-      const uint32_t cnt = (nr.skip - off + NB) / (2u * NB);    // triangles of this (possibly collapsed) leaf
+      // A leaf.  Its subtree's records [off, nr.skip) are 2 cnt - 1 of them for the cnt triangles nr.tri, nr.tri + 1, ... (a collapsed leaf; cnt = 1: the
+      // record alone), so a byte cursor that starts at `below` and steps over two records at a time is at or below nr.skip exactly cnt times, the
+      // first time always: leaf_cursor_steps of geo.hip.h, held against cnt = (nr.skip - off + NB) / (2 NB) by
+      // tests/test_walk_leaf_count_cpu.py.  No division, no count and no guard in front of the loop.
+      uint32_t tri = (uint32_t)nr.tri, cur = below;
       if (DEFER == 3) {
         // GA: the batch pending from an earlier leaf is taken first — one scalar branch per leaf is all the node loop pays —, one issued by
         // this leaf when the ring fills again inside it (long leaves; rare); the ring never holds 128 pairs.
@@ -489,9 +512,19 @@ __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float sl
         const unsigned long long wb = __ballot(want);
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(wb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wb, 0u));
         const uint32_t wn = (uint32_t)__popcll(wb);
-        for (uint32_t k = 0; k < cnt; ++k) {
-          if (want) dq.q1[(dq.head1 + dq.n1 + rank) & 127u] = (threadIdx.x & 63u) | (((uint32_t)nr.tri + k) << 6);
+        // This lane's ring slot as a byte offset, formed once per leaf; per triangle it moves on by the wn pairs just queued (one add, the mask at
+        // the store) and the pair word by one triangle.  A batch taken out of the ring (head1 + 64, n1 - 64) leaves head1 + n1 where it was.
+        // (Measured and not kept: no exec region around the store — the lanes that do not want the leaf all write the free slot BEHIND the wn wanted
+        // ones, two scalar instructions fewer per triangle.  64 - wn lanes storing to one address are not free: headline distance 6.110 -> 6.136 ms,
+        // 512^3 x blob-1M 17.20 -> 17.32.  profiles/walk_diet_ab.txt, series 1.)
+        uint32_t slot4 = (dq.head1 + dq.n1 + rank) << 2, pair = (threadIdx.x & 63u) | (tri << 6);
+        const uint32_t step4 = wn << 2;
+        do {
+          if (want) *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(dq.q1) + (slot4 & 0x1fcu)) = pair;
+          slot4 += step4;
+          pair += 64u;
           dq.n1 += wn;
+          if (BUDGET) ++sp.units;
           if (dq.n1 >= 64u) {
             if (BUDGET) sp.units += 4u;
             if (GA) {
@@ -502,11 +535,13 @@ __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float sl
               pretest_issue(mesh, dq, *gap);
             } else if (defer_pretest<MODE>(mesh, p, thr, dq, best)) thr = prune_bound(best.d2, slack);
           }
-        }
+          cur += 2u * NB;
+        } while (cur <= nr.skip);
       } else
-      for (uint32_t k = 0; k < cnt; ++k) {
+      do {
         if (STATS) { ++st.ext; st.pre_lanes += (uint32_t)__popcll(__ballot(!(ed2 > thr))); }
-        const TriPlanes tp = record_at(mesh.planes, (uint32_t)nr.tri + k);   // scalar: small, needed for every leaf triangle
+        if (BUDGET) ++sp.units;
+        const TriPlanes tp = record_at(mesh.planes, tri);   // scalar: small, needed for every leaf triangle
         const bool reach = !(planes_dist2(p, tp) > thr);
         const unsigned long long rb = __ballot(reach);
         if (rb != 0ull) {   // some lane's bound reaches the triangle itself
@@ -514,7 +549,7 @@ __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float sl
           if (DEFER != 0 && !(DEFER == 2 && (uint32_t)__popcll(rb) >= DEFER_DIRECT_LANES)) {
             DeferQueue& dq = *dqp;
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(rb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rb, 0u));
-            if (reach) dq.q[(dq.head + dq.n + rank) & 127u] = (threadIdx.x & 63u) | (((uint32_t)nr.tri + k) << 6);
+            if (reach) dq.q[(dq.head + dq.n + rank) & 127u] = (threadIdx.x & 63u) | (tri << 6);
             dq.n += (uint32_t)__popcll(rb);
             if (dq.n >= 64u) {
               if (BUDGET) sp.units += 4u;
@@ -523,15 +558,17 @@ __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float sl
             }
           } else {
             if (BUDGET) sp.units += 4u;
-            const TriRec tr = record_at_vec(mesh.tris, (uint32_t)nr.tri + k);
+            const TriRec tr = record_at_vec(mesh.tris, tri);
             eval_triangle_leaf<MODE>(best, p, tr, reach);
             thr = prune_bound(best.d2, slack);
           }
         }
-      }
+        ++tri;
+        cur += 2u * NB;
+      } while (cur <= nr.skip);
       off = nr.skip;
       if (BUDGET) {
-        sp.units += 3u + cnt;
+        sp.units += 3u;                                           // (+ 1 per leaf triangle, counted above: 3 + cnt as ever, looked at here only)
         if (sp.units >= sp.next_check) {
           // (no exit of its own: a second way out of this loop cost the walk 11 % although it was never taken; the loop ends by its
           // own condition)
@@ -553,22 +590,23 @@ __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float sl
           }
         }
       }
-    } else {
-      if (EMIT) {
-        EmitState& em = *emp;
-        const uint32_t bytes = nr.skip - off;
-        if (bytes >= em.min_bytes && bytes <= em.max_bytes) {
-          if (em.used == em.room) emit_reserve(em);
-          if (em.used < em.room) {
-            if ((threadIdx.x & 63u) == 0u) em.list[em.base + em.used] = make_uint4(em.packet, off, nr.skip, em.slot);
-            ++em.used;
-            off = nr.skip;                                      // somebody else's from here
-            continue;
-          }
+      continue;
+    }
+    // (the split forms' interior visit)
+    if (EMIT) {
+      EmitState& em = *emp;
+      const uint32_t bytes = nr.skip - off;
+      if (bytes >= em.min_bytes && bytes <= em.max_bytes) {
+        if (em.used == em.room) emit_reserve(em);
+        if (em.used < em.room) {
+          if ((threadIdx.x & 63u) == 0u) em.list[em.base + em.used] = make_uint4(em.packet, off, nr.skip, em.slot);
+          ++em.used;
+          off = nr.skip;                                      // somebody else's from here
+          continue;
         }
       }
-      off = off + NB;
     }
+    off = below;
   }
 }
 
@@ -660,7 +698,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     // shows the change, llvm-objdump -d the loop's address (the backward branch over ~1 860 bytes), and the two configs decide.
     // (Side effect, part of what was measured: behind an asm statement the compiler reads mesh_scale — a global load, "may be clobbered" —
     // through the vector unit, one VMEM instruction more per packet; the seed index and the records stay scalar loads.)
-    if (GRID && MODE == MODE_UNSIGNED && SIGN == SIGN_GRID_PLANE && DEFER == 3 && GA) asm volatile("s_nop 0\n s_nop 0\n s_nop 0");
+    // Decided again when the node loop's bookkeeping was trimmed and the loop moved: with the three s_nop its loop test (three instructions in
+    // front of the record load, where the backward branches land) stood at byte 8 of a line and the load at byte 20.  Measured, loop test at byte 52
+    // of the line before / 60 / 8 / 24 / 36 by no asm statement at all, 0, 3, 7 and 10 s_nop: headline distance 6.154 / 6.186 / 6.137 / 6.136 / 6.137 ms,
+    // 512^3 x blob-1M 17.32 / 17.34 / 17.20 / 17.17 / 17.16 (parent 6.263 and 17.62; profiles/walk_diet_ab.txt, series 2).  A record load in the first
+    // bytes of a line costs blob-1M 0.7 %; ten s_nop put the loop test back at byte 36, where it has stood since the padding was introduced.
+    // Among 3, 7 and 10 s_nop nothing is measured to matter (the headline is level; blob-1M's 0.04 ms between 3 and 10 is one series of four
+    // runs, two of its spreads): what IS measured is that the load must not stand in the first bytes of a line.  Ten are seven issue slots per
+    // packet more than three; the position the parent had was kept so that the A/B against it compares the loop and not its placement.
+    if (GRID && MODE == MODE_UNSIGNED && SIGN == SIGN_GRID_PLANE && DEFER == 3 && GA) asm volatile(".rept 10\n s_nop 0\n .endr");
     const float scale = fmaxf(mesh_scale(mesh), fmaxf(fabsf(p.x), fmaxf(fabsf(p.y), fabsf(p.z))));
     const float slack = 4.0e-6f * scale + (MODE == MODE_NORMAL_FOLD ? 2.5e-6f : 0.0f);
     SplitState sp;
@@ -792,7 +838,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     atomicAdd(&q[7], (unsigned long long)(st_rbytes <= 4096u ? 1u : 0u));
     // histogram of the packets' work units (node tests + pre-tests + 4 x exact evaluations) in octaves: stats[80 + log2]
     const uint32_t units = st.box + st.ext + 4u * st.leaf;
-    atomicAdd(&mesh.stats[80 + (31 - __builtin_clz(units | 1u))], 1ull);
+    // (octaves 0..23: the words from stats[104] on are k_cut's visit counters)
+    atomicAdd(&mesh.stats[80 + min(31u - (uint32_t)__builtin_clz(units | 1u), 23u)], 1ull);
   }
 
   bool negate = false;

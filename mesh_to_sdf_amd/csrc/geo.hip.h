@@ -240,4 +240,15 @@ M2S_HD float normal_fold_result(float d2_all, float d2_pos) {
 // Grid::get_cell_center for one axis (grid.rs:135-141): first + (i as f32) * size, mul then add.
 M2S_HD float cell_center(float first, float size, uint32_t i) { return first + (float)i * size; }
 
+// The packet walk's leaf loop (distance.hip walk_span), its control alone: a byte cursor that starts at the record behind the leaf's own,
+// off + nb, and moves on by two records of `nb` bytes per triangle, the first triangle taken unconditionally; returns how many triangles it
+// takes before it has passed `skip`, the end of the leaf's subtree.  A leaf of cnt triangles owns the 2 cnt - 1 records [off, skip), so this
+// is cnt — what (skip - off + nb) / (2 nb) gave, without the division (1 where that is 0, a link no tree has: the counted loop took no
+// triangle there).  tests/test_walk_leaf_count_cpu.py, through the CPU probe library.
+M2S_HD uint32_t leaf_cursor_steps(uint32_t off, uint32_t skip, uint32_t nb) {
+  uint32_t n = 0, cur = off + nb;
+  do { ++n; cur += 2u * nb; } while (cur <= skip);
+  return n;
+}
+
 }  // namespace m2s

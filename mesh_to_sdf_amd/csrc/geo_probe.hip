@@ -1,5 +1,5 @@
 // geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h, sample.hip.h, voxel.hip.h, band.hip.h and cut_size.hip.h, for CPU unit tests only
-// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py, tests/test_narrow_band_cpu.py, tests/test_cut_size_cpu.py).  Not linked into libm2s_hip.so.
+// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py, tests/test_narrow_band_cpu.py, tests/test_cut_size_cpu.py, tests/test_walk_leaf_count_cpu.py).  Not linked into libm2s_hip.so.
 #include "geo.hip.h"
 #include "ray.hip.h"
 #include "sample.hip.h"
@@ -35,6 +35,10 @@ int probe_cut_small_enough(float R, float half, float emit_radius) { return cut_
 // ... for n triples at once (out: one byte each)
 void probe_cut_small_enough_n(size_t n, const float* R, const float* half, const float* emit_radius, unsigned char* out) {
   for (size_t i = 0; i < n; ++i) out[i] = cut_small_enough(R[i], half[i], emit_radius[i]) ? 1 : 0;
+}
+// geo.hip.h: the leaf loop's trip count for n (off, skip) pairs of records of nb bytes
+void probe_leaf_cursor_steps_n(size_t n, const uint32_t* off, const uint32_t* skip, uint32_t nb, uint32_t* out) {
+  for (size_t i = 0; i < n; ++i) out[i] = leaf_cursor_steps(off[i], skip[i], nb);
 }
 float probe_normal_fold_result(float d2_all, float d2_pos) { return normal_fold_result(d2_all, d2_pos); }
 int probe_approx_eq_abs(float a, float b) { return approx_eq_abs(a, b) ? 1 : 0; }
