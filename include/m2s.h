@@ -49,7 +49,7 @@ extern "C" {
 #endif
 
 #define M2S_VERSION_MAJOR 0
-#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface, m2s_band_create / destroy / info / sample / raymarch, m2s_band_csg, m2s_band_export, m2s_band_field_info, m2s_band_redistance); additive within 0.5 too: m2s_band_filter; 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
+#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface, m2s_band_create / destroy / info / sample / raymarch, m2s_band_csg, m2s_band_export, m2s_band_field_info, m2s_band_redistance); additive within 0.5 too: m2s_band_filter, m2s_band_resample; 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
 
 /* Return codes.  The reference panics where this ABI returns a negative code; the Rust shim
  * turns a negative code back into panic!(m2s_last_error()). */
@@ -1024,6 +1024,65 @@ typedef struct m2s_band_filter_info { uint32_t struct_size, passes; float max_ch
 int m2s_band_filter(const m2s_band* band, const m2s_band* where /* may be NULL = everywhere */, const m2s_band_filter_opts* fl,
                     const m2s_band_field_opts* fopts /* NULL = the input's backgrounds */, const m2s_opts* opts,
                     m2s_band** out, m2s_band_filter_info* info_out /* may be NULL */);
+
+/* ---- Resampling a narrow band onto another grid under a similarity: crop, pad, move, turn, scale, refine --------------------------------
+ * m2s_band_resample evaluates a resident band at the cell centres of another grid, under an optional map from target space to source
+ * space, and returns a new resident band on that grid with its sign mask on every point: what GridTransformer / resampleToMatch are
+ * in OpenVDB.  It lets a field leave the grid it was born on: two parts voxelised on their own boxes meet in m2s_band_csg, a band is
+ * cropped to a region, a finished field is placed somewhere else, a band goes to finer cells before m2s_band_isosurface.  Follow it
+ * with m2s_band_redistance, as OpenVDB follows its resampling with a renormalisation.  The result is DEFINED per target grid point, to
+ * the bit (tests/band_resample_model.py restates it in numpy).
+ * Input: a handle X on its grid Gs, a target grid T, a mode (m2s_sample_mode), to_source = m, the row-major 3 x 4 map from target
+ *   space to source space, and value_scale > 0.  The library takes m as given and inverts nothing.  All arithmetic is IEEE binary32
+ *   with no FMA, each operation in the order written.
+ * Per target point L = k + j*nz + i*ny*nz of T:
+ *   Centre        p = m2s_grid_cell_center(T, (i, j, k)), that is first_cell + (float)idx * cell_size per axis.
+ *   Source point  q_a = ((m[4a] * p.x + m[4a+1] * p.y) + m[4a+2] * p.z) + m[4a+3] for a = 0, 1, 2.
+ *   Sample        (v, support) = m2s_band_sample(X, q) with `mode`, iso = 0 and outside = X.background_outside, exactly as defined
+ *                 above: the clamped reads between the last centre and `end`, the `outside` and NaN rules, support counted after
+ *                 clamping.  K = 1 (SNAP), 8 (TRILINEAR), 4 (TETRAHEDRAL).
+ *   Value         r = v * value_scale.
+ *   Active set    active[L] = (support == K) && isfinite(r).  A point with support == K and a non-finite r is inactive and counts in
+ *                 n_nonfinite; cells of +-f32::MAX and a scale above 1 make this reachable.
+ *   Sign          s[L] = active ? (r < 0) : sX[c].  c is the cell the SNAP rule of m2s_sample_grid reads for q, and sX is the CSG
+ *                 definition's s of X: act ? (x < 0) : inside bit.  s[L] = 0 when q is off the source box or has a NaN coordinate.
+ *                 It is the SNAP rule and not v < 0: a zero background is legal and has no sign.
+ * Result: a new immutable m2s_band on T and on X's device.  The active points ascending with their r; a sign mask equal to s on EVERY
+ *   target point; the backgrounds of `fopts`, or by default X.background_outside * value_scale and X.background_inside * value_scale
+ *   (a default that comes out non-finite is M2S_ERR_BAD_ARG).  m2s_band_info's device_bytes follows the formula for a handle with a
+ *   sign mask.
+ * info_out (may be NULL; set struct_size): n_cells = the result's cell count.  n_partial = the points on the source box with
+ *   0 < support < K: the rim the interpolation loses.  n_nonfinite as above.  n_open = the ordered pairs (L active, M an inactive axis
+ *   neighbour inside T, s[M] != s[L]), with the meaning it has in m2s_band_redistance: the result does not bracket its own zero set
+ *   there, which is what happens when the target cells outgrow the source band.
+ * Consequence 1: SNAP, the identity map and T == Gs give X back: the cells and values keep every bit and the sign mask is sX on every
+ *   point.  This holds on any grid, not only dyadic ones, because the SNAP index has half a cell of slack.  TRILINEAR has no such
+ *   property: (first + i*cs - first) / cs need not be i, and a point needs all 8 corners active.
+ * Consequence 2: SNAP with a target grid that is the source grid shifted by whole cells is crop and pad.  A target centre that falls
+ *   exactly on the source box's `end` face (one cell past the last centre) is still on the box and repeats the last cell: the clamped
+ *   reads.  Cropping the padded result back to Gs drops that layer, so pad and crop return X in every bit.
+ * Consequence 3: for a similarity p = s R q + t (the map from source space to target space, of which m is the inverse) with
+ *   value_scale = s, and a distance field, r is the moved solid's distance within the interpolation error.  Measured with the numpy
+ *   model: a sphere on cells of about 0.03 turned, scaled by 0.75 and moved onto cells (0.05, 0.04, 0.0625) is off by
+ *   at most 0.0075 cells of 0.0625 under TRILINEAR, 0.0101 under TETRAHEDRAL and 0.311 under SNAP.
+ * What the definition does NOT promise: the result is not a distance field after TRILINEAR or TETRAHEDRAL, follow it with
+ *   m2s_band_redistance.  A map that is not a similarity is accepted and gives something that is not a distance at all.  In the outer
+ *   half cell of the source box the field is constant extrapolation, because of the clamped reads: pad the source.  Resampling to much
+ *   coarser cells aliases, as OpenVDB's point samplers do.
+ * Always synchronous, with one synchronisation inside the call, for the count: the values are allocated at their true size.  *out =
+ *   NULL on every failure.  M2S_ERR_BAD_ARG before any device work: a NULL band, target or out; a struct_size other than sizeof (ropts,
+ *   fopts, info_out); a bad mode; a non-finite entry of to_source; a value_scale that is not finite or not > 0; what m2s_band_create
+ *   rejects of a grid, 2^36 or more cells included; negative or non-finite backgrounds; an m2s_opts.device that is not the handle's (-1
+ *   means its own); algorithm, x_begin, x_end, x_period or peer_out not zero; a bad mem_kind.
+ *   m2s_opts: device, stream / stream_mode, lane.  timings: seed_ms = the mask pass and the scan, distance_ms = the value pass,
+ *   total_ms = the whole call, n_units = the result's cells.
+ * Memory during the call: per 64 target points the result's three index words plus 4 bytes per 64 words and 8 per 4096 words of
+ *   counts; per result cell its value.  Nothing sized 4 bytes per point of either grid is allocated. */
+typedef struct m2s_band_resample_opts { uint32_t struct_size; int32_t mode; float to_source[12]; float value_scale; } m2s_band_resample_opts;   /* 60 bytes */
+typedef struct m2s_band_resample_info { uint32_t struct_size, reserved; uint64_t n_cells, n_partial, n_nonfinite, n_open; } m2s_band_resample_info;   /* 40 bytes */
+int m2s_band_resample(const m2s_band* band, const m2s_grid* target, const m2s_band_resample_opts* ropts /* NULL = identity, TRILINEAR, 1 */,
+                      const m2s_band_field_opts* fopts /* NULL = the input's backgrounds times value_scale */, const m2s_opts* opts,
+                      m2s_band** out, m2s_band_resample_info* info_out /* may be NULL */);
 
 /* glTF 2.0 / GLB ingestion (host side) — what the reference client extracts from a file before the merge:
  * mesh_to_sdf_client/src/gltf/mod.rs:56-174 (models keyed by mesh index, one primitive per mesh survives;

@@ -620,6 +620,12 @@ struct FilterInfo {
   float max_change = 0.0f;
   uint64_t n_changed = 0, n_sign_flips = 0, n_nonfinite = 0;
 };
+// What BandField::resample reports (m2s_band_resample_info): the result's cells, the points on the source box with some but not all of
+// their reads in the band (the rim the interpolation loses), the points whose value came out non-finite and were dropped, the sign changes
+// towards an inactive cell (> 0: the result does not bracket its zero set there).
+struct ResampleInfo {
+  uint64_t n_cells = 0, n_partial = 0, n_nonfinite = 0, n_open = 0;
+};
 template <class V>
 class BandField {
  public:
@@ -737,6 +743,29 @@ class BandField {
       info->n_nonfinite = fi.n_nonfinite;
     }
     return BandField(grid_, h);
+  }
+  // The field evaluated at the cell centres of another grid, as a new resident field on that grid (m2s_band_resample, per target grid
+  // point and to the bit; no dense grid): crop, pad, move, turn, scale, refine.  to_source: 12 floats, the row-major 3 x 4 map from TARGET
+  // space to SOURCE space (the inverse of the placement; nullptr is the identity); the library inverts nothing.  value_scale: the
+  // placement's uniform scale, which the values are multiplied by; the backgrounds are this field's times it.  After an interpolating mode
+  // the result is not a distance field: follow it with redistance.
+  BandField resample(const Grid<V>& target, const float* to_source = nullptr, float value_scale = 1.0f, SampleMode mode = SampleMode::Trilinear, ResampleInfo* info = nullptr) const {
+    m2s_band_resample_opts ro{};
+    ro.struct_size = sizeof(ro);
+    ro.mode = (int32_t)mode;
+    for (int a = 0; a < 12; ++a) ro.to_source[a] = to_source ? to_source[a] : (a % 5 == 0 ? 1.0f : 0.0f);
+    ro.value_scale = value_scale;
+    m2s_band_resample_info ri{};
+    ri.struct_size = sizeof(ri);
+    m2s_band* h = nullptr;
+    detail::check(m2s_band_resample(h_, &target.raw(), &ro, nullptr, nullptr, &h, &ri));
+    if (info) {
+      info->n_cells = ri.n_cells;
+      info->n_partial = ri.n_partial;
+      info->n_nonfinite = ri.n_nonfinite;
+      info->n_open = ri.n_open;
+    }
+    return BandField(target, h);
   }
   // The field's lists back out (m2s_band_export): cells ascending, distances bit for bit, and `bits` the sign mask in the layout of
   // Voxels::bits (all zero for a field made without one).  band_isosurface(grid, b.cells, b.distances) meshes it.

@@ -156,6 +156,15 @@ class M2SBandFilterInfo(C.Structure):
                 ("n_changed", C.c_uint64), ("n_sign_flips", C.c_uint64), ("n_nonfinite", C.c_uint64)]
 
 
+class M2SBandResampleOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("to_source", C.c_float * 12), ("value_scale", C.c_float)]
+
+
+class M2SBandResampleInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_cells", C.c_uint64), ("n_partial", C.c_uint64),
+                ("n_nonfinite", C.c_uint64), ("n_open", C.c_uint64)]
+
+
 class M2SSampleOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("iso", C.c_float), ("outside", C.c_float), ("max_steps", C.c_uint32)]
 
@@ -220,6 +229,7 @@ EXPORTS = [
     "m2s_band_field_info",
     "m2s_band_redistance",
     "m2s_band_filter",
+    "m2s_band_resample",
     "m2s_merge_instances",
     "m2s_gltf_open",
     "m2s_gltf_instances",
@@ -327,6 +337,8 @@ def _prototypes():
                                           C.POINTER(C.c_void_p), C.POINTER(M2SBandRedistanceInfo)]),
         "m2s_band_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(M2SBandFilterOpts), C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
                                       C.POINTER(C.c_void_p), C.POINTER(M2SBandFilterInfo)]),
+        "m2s_band_resample": (C.c_int, [C.c_void_p, C.POINTER(M2SGrid), C.POINTER(M2SBandResampleOpts), C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
+                                        C.POINTER(C.c_void_p), C.POINTER(M2SBandResampleInfo)]),
         "m2s_merge_instances": (C.c_int, [C.POINTER(M2SInstance), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(M2SOpts)]),
         "m2s_gltf_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(M2SGltfInfo)]),
         "m2s_gltf_instances": (C.c_int, [C.c_void_p, C.POINTER(M2SInstance), C.c_size_t]),

@@ -1114,6 +1114,35 @@ class FilterInfo(NamedTuple):
     n_nonfinite: int
 
 
+class ResampleInfo(NamedTuple):
+    """include/m2s.h `m2s_band_resample_info`: the result's cells, the points on the source box that had some but not all of their
+    reads in the band (the rim the interpolation loses), the points whose value came out non-finite and were dropped, and the sign
+    changes towards an inactive cell (> 0: the result does not bracket its own zero set there; the target cells outgrew the band)."""
+    n_cells: int
+    n_partial: int
+    n_nonfinite: int
+    n_open: int
+
+
+def _similarity(transform):
+    """A 3 x 4 or 4 x 4 map p = A q + t from source space to target space -> (to_source float32[12], value_scale float32): checked in
+    float64 to be a similarity (A^T A = s^2 I to a relative 1e-5; reflections pass), inverted as [A^T / s^2, -A^T t / s^2]."""
+    M = np.asarray(transform.detach().cpu().numpy() if _is_torch(transform) else transform, np.float64)
+    if M.shape == (4, 4):
+        if not np.array_equal(M[3], (0.0, 0.0, 0.0, 1.0)):
+            raise ValueError("resample: the last row of a 4 x 4 transform must be (0, 0, 0, 1)")
+        M = M[:3]
+    if M.shape != (3, 4) or not np.isfinite(M).all():
+        raise ValueError("resample: the transform must be a finite 3 x 4 or 4 x 4 array")
+    A, t = M[:, :3], M[:, 3]
+    G = A.T @ A
+    s2 = np.trace(G) / 3.0
+    if not s2 > 0 or np.abs(G - s2 * np.eye(3)).max() > 1e-5 * s2:
+        raise ValueError("resample: the transform is not a similarity (rotation, uniform scale, reflection, translation)")
+    inv = A.T / s2
+    return np.concatenate([inv, (-inv @ t)[:, None]], 1).astype(np.float32).reshape(12), np.float32(np.sqrt(s2))
+
+
 class BandField:
     """A narrow band made queryable (include/m2s.h `m2s_band`): the index of the band's cells, its distances and an optional sign mask,
     resident on the device, built once and sampled or ray-marched many times with no dense grid anywhere.  It stands for the dense grid D'
@@ -1128,6 +1157,7 @@ class BandField:
     Two fields on the same grid combine on the device into a third (`csg`, `union`, `intersection`, `difference`, or `a | b`, `a & b`,
     `a - b`); `redistance` turns a combined field back into distances at any width and `offset` grows or shrinks the solid;
     `filter` and `smooth` fair it (mean, Laplacian, mean-curvature flow), everywhere or inside a region;
+    `resample` takes it to another grid, moved, turned or scaled on the way, so that fields born on different grids can be combined;
     `to_band` hands a field's lists back as a NarrowBand and `isosurface` meshes it.  `background` is (inside, outside) and
     `count` the number of cells, for a combined field as the library reports them.
     A context manager; `close` frees the device memory."""
@@ -1336,6 +1366,41 @@ class BandField:
             _raise(rc)
         out = BandField._adopt(h, self.grid, self._dev)
         out.filter_info = FilterInfo(int(info.passes), float(info.max_change), int(info.n_changed), int(info.n_sign_flips), int(info.n_nonfinite))
+        return out
+
+    def resample(self, grid, transform=None, *, mode: SampleMode = SampleMode.Trilinear, background=None,
+                 timings: M2STimings = None) -> "BandField":
+        """This field evaluated at the cell centres of another grid, as a new resident BandField on that grid (include/m2s.h
+        m2s_band_resample states the result per target grid point, to the bit): crop, pad, move, turn, scale, refine.  grid: a Grid, or
+        another BandField whose grid is used (OpenVDB's resampleToMatch).  transform: a 3 x 4 or 4 x 4 array that maps source space to
+        target space and places the solid; it must be a similarity (rotation, uniform scale s, reflection, translation), so that
+        distances stay distances: the values are multiplied by s.  None is the identity.  mode: SampleMode.Snap keeps every bit where
+        the grids agree by whole cells (crop and pad); Trilinear and Tetrahedral interpolate and lose the band's outermost cells.
+        background: a scalar or (inside, outside); None is this field's times s.  After an interpolating mode the result is not a
+        distance field: follow it with `redistance`.  It carries `.resample_info` (a ResampleInfo)."""
+        if isinstance(grid, BandField):
+            grid = grid.grid
+        if not isinstance(grid, Grid):
+            raise M2SPanic(_lib.ERR_BAD_ARG, "resample: grid is neither a Grid nor a BandField")
+        ro = _lib.M2SBandResampleOpts()
+        ro.struct_size, ro.mode, ro.value_scale = C.sizeof(_lib.M2SBandResampleOpts), int(mode), 1.0
+        ro.to_source[0] = ro.to_source[5] = ro.to_source[10] = 1.0
+        if transform is not None:
+            to_source, scale = _similarity(transform)
+            ro.to_source[:] = [float(v) for v in to_source]
+            ro.value_scale = float(scale)
+        q = self._side(timings)
+        fo = None
+        if background is not None:
+            bg_in, bg_out = _backgrounds(background)
+            fo = C.byref(_lib.M2SBandFieldOpts(C.sizeof(_lib.M2SBandFieldOpts), float(np.float32(bg_out)), float(np.float32(bg_in))))
+        info = _lib.M2SBandResampleInfo(C.sizeof(_lib.M2SBandResampleInfo))
+        h = C.c_void_p()
+        rc = _lib.lib().m2s_band_resample(self._handle(), C.byref(grid._g), C.byref(ro), fo, C.byref(q.opts), C.byref(h), C.byref(info))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        out = BandField._adopt(h, grid, self._dev)
+        out.resample_info = ResampleInfo(int(info.n_cells), int(info.n_partial), int(info.n_nonfinite), int(info.n_open))
         return out
 
     def smooth(self, kind, iterations: int, band, *, where: "BandField" = None) -> "BandField":

@@ -1,5 +1,5 @@
 // band_handle.h — the resident band behind include/m2s.h's `m2s_band`, shared by band_query.hip (m2s_band_create / destroy / info / sample /
-// raymarch) and band_csg.hip (m2s_band_csg / export / field_info).  Moved here from band_query.hip unchanged: the handle, its device view and
+// raymarch), band_csg.hip (m2s_band_csg / export / field_info) and the units of the later band calls.  Moved here from band_query.hip unchanged: the handle, its device view and
 // the two steps every call on a handle takes with its m2s_opts.  The device view and the helpers are in an unnamed namespace, as
 // isosurface.hip.h's are: each translation unit that includes this has its own copy.
 #pragma once
@@ -18,6 +18,7 @@ struct m2s_band {
   uint64_t n = 0, total = 0, n_words = 0;
   uint64_t device_bytes = 0;   // the arrays' sizes as include/m2s.h states them (the allocation adds alignment only)
   char* block = nullptr;       // one allocation: mask, word_off, [inside], dist
+  char* block2 = nullptr;      // m2s_band_resample's result: dist in an allocation of its own, made once the count is known
   const uint64_t* mask = nullptr;
   const uint64_t* word_off = nullptr;
   const uint64_t* inside = nullptr;
