@@ -2,21 +2,15 @@
 // handle's lists back out, gfx950.  The contract is include/m2s.h's (the rules per grid point, to the bit); tests/band_csg_model.py
 // restates it in numpy.  Nothing sized 4 bytes per grid point exists: the work is the index words of the operands plus their band cells.
 //
-// A CSG call is three launches over the mask words.  A wave owns a UNIT of 256 words and takes it in 4 steps of 64:
-// lane l loads word 64 * step + l of all four index arrays (mask and sign mask of A and B), coalesced.
+// A CSG call is three launches over the mask words, band_walk.hip.h's walk and offsets.  A lane loads its word of all
+// four index arrays (mask and sign mask of A and B), coalesced.
 //   k_csg_mask   a word with maskA | maskB == 0 (the common case: a band is O(n^2) of n^3) is settled by its own lane: result mask 0,
-//                result sign word = the op of the two sign words (B's complemented for A \ B).  The others are taken one at a time by
-//                the whole wave (a ballot finds them, v_readlane broadcasts the word's six values): lane t owns bit t, reads its operand
-//                values at word_off + popcount(mask below t) — contiguous runs —, takes the backgrounds by select and evaluates the
-//                rules; two ballots are the result's mask word and sign word.  The unit's popcount goes to unit_cnt, and by one
-//                atomic add to the sum of its GROUP of 16 units.
-//   k_scan_tiles the group sums, one workgroup (scan.hip.h); the total is the result's cell count, read by the host.
-//   k_csg_emit   the same units: the group's base plus the counts of the units before it in the group, then a wave scan of the
-//                result's popcounts, is the result's word_off; the words with active points are taken one at a time as above and
-//                lane t stores r at word_off + rank.
-// The unit is small because a word's round is a chain of dependent loads (offset, then value) that only other waves hide: at 256^3
-// units of 1024 words left three quarters of the SIMDs without a wave.  The groups are there because k_scan_tiles is one workgroup:
-// one sum per unit is half a million of them at 2048^3 and cost it 0.4 ms (profiles/band_csg.txt has both measurements).
+//                result sign word = the op of the two sign words (B's complemented for A \ B).  In the others lane t reads its operand
+//                values at their list places — contiguous runs —, takes the backgrounds by select and evaluates the rules; two ballots
+//                are the result's mask word and sign word.  The unit's popcount is published.
+//   k_scan_tiles the group sums; the total is the result's cell count, read by the host.
+//   k_csg_emit   the same units: the result's word_off, and lane t of a word with active points stores r at word_off + rank.
+// The unit is 256 words and the group 16 units (profiles/band_csg.txt has the measurements; DESIGN.md §4.16 the reasons).
 // r is computed twice rather than kept: where it would go is known only after the scan, and a buffer of candidates would be the size
 // of the result.  All stores are plain vector stores.
 // Export: k_csg_cells (L = 64 w + bit at word_off + rank, the word taken by the wave as above), a copy of dist, and k_csg_unsign, the
@@ -24,12 +18,12 @@
 // where a row starts mid-word).
 #include "../../include/m2s.h"
 #include "band_handle.h"
+#include "band_walk.hip.h"
 #include "capi_internal.h"
 #include "common.h"
 #include "isosurface.hip.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 
 #pragma clang fp contract(off)
@@ -37,11 +31,7 @@
 namespace m2s {
 namespace {
 
-constexpr int kCsgThreads = 256;
-constexpr int kCsgWaves = kCsgThreads / 64;
-constexpr int kCsgSteps = 4;                                // steps of 64 words per wave
-constexpr uint64_t kCsgUnit = 64 * kCsgSteps;               // 256 words per wave
-constexpr int kCsgGroup = 16;                               // units per scanned sum (at most 64: one lane each in k_csg_emit)
+constexpr int kCsgGroup = 16;                               // units per scanned sum
 
 // D'_X at bit t of one mask word: the value, whether the band supplies it, and the sign s_X of the definition.  NEG: the same of -X.
 struct CsgPoint {
@@ -55,8 +45,7 @@ __device__ __forceinline__ CsgPoint csg_point(const BandDev& X, float bg_out, fl
   CsgPoint p;
   p.act = (m >> t) & 1ull;
   const bool ins = (in >> t) & 1ull;
-  uint64_t at = wo + (uint64_t)__popcll(m & ((1ull << t) - 1ull));
-  at = at < X.n ? at : 0;   // at < n whenever the index is sound; the guard keeps a broken invariant in bounds
+  const uint64_t at = walk_rank(m, wo, t, X.n);
   float x = ins ? bg_in_neg : bg_out;
   if (p.act) x = X.dist[at];
   if (NEG) {
@@ -96,33 +85,20 @@ __device__ __forceinline__ CsgWord csg_load(const BandDev& A, const BandDev& B, 
   }
   return x;
 }
-// Lane j's value in every lane, j wave-uniform (it comes out of a ballot): two v_readlane into scalar registers, no trip through the LDS
-// crossbar as a shuffle would take.
-__device__ __forceinline__ uint64_t csg_lane(uint64_t v, int j) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
-  return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ CsgWord csg_broadcast(const CsgWord& x, int j) {
-  return CsgWord{csg_lane(x.mA, j), csg_lane(x.mB, j), csg_lane(x.iA, j), csg_lane(x.iB, j), csg_lane(x.woA, j), csg_lane(x.woB, j)};
+  return CsgWord{walk_lane(x.mA, j), walk_lane(x.mB, j), walk_lane(x.iA, j), walk_lane(x.iB, j), walk_lane(x.woA, j), walk_lane(x.woB, j)};
 }
 
 template <int OP, bool NEG>
-__global__ void __launch_bounds__(kCsgThreads) k_csg_mask(BandDev A, BandDev B, float a_out, float a_in_neg, float b_out, float b_in_neg, uint64_t n_words, uint64_t total, uint64_t* __restrict__ out_mask,
+__global__ void __launch_bounds__(kWalkThreads) k_csg_mask(BandDev A, BandDev B, float a_out, float a_in_neg, float b_out, float b_in_neg, uint64_t n_words, uint64_t total, uint64_t* __restrict__ out_mask,
                                                           uint64_t* __restrict__ out_inside, uint32_t* __restrict__ unit_cnt,
                                                           uint64_t* __restrict__ group_sum) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t unit = (uint64_t)blockIdx.x * kCsgWaves + (uint64_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t w0 = unit * kCsgUnit;
-  if (w0 >= n_words) return;   // the whole wave: the last workgroup's spare units
+  WALK_UNIT_HEAD(kWalkSteps, n_words)
   uint64_t cnt = 0;
-  for (int i = 0; i < kCsgSteps; ++i) {
-    const uint64_t wb = w0 + (uint64_t)i * 64;   // wave-uniform
-    if (wb >= n_words) break;
-    const uint64_t w = wb + lane;
-    const bool in_range = w < n_words;
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD(n_words)
     const CsgWord x = csg_load(A, B, w, in_range);
-    const uint64_t left = in_range ? total - (w << 6) : 0;
-    const uint64_t valid = left >= 64 ? ~0ull : ((1ull << left) - 1ull);   // the last word's points
+    const uint64_t valid = walk_valid(w, in_range, total);
     const uint64_t iBs = NEG ? ~x.iB : x.iB;
     uint64_t rm = 0;
     uint64_t ri = (OP == 0 ? (x.iA | iBs) : (x.iA & iBs)) & valid;
@@ -148,44 +124,21 @@ __global__ void __launch_bounds__(kCsgThreads) k_csg_mask(BandDev A, BandDev B, 
     }
     cnt += (uint64_t)__popcll(rm);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if (lane == 0) {
-    unit_cnt[unit] = (uint32_t)cnt;   // at most 64 * 256
-    if (cnt) atomicAdd((unsigned long long*)(group_sum + unit / kCsgGroup), (unsigned long long)cnt);   // zeroed by the launcher
-  }
+  walk_publish<kCsgGroup>(cnt, lane, unit, unit_cnt, group_sum);
 }
 
 // group_base: the scanned group sums.  cap: the floats out_dist holds.
 template <int OP, bool NEG>
-__global__ void __launch_bounds__(kCsgThreads) k_csg_emit(BandDev A, BandDev B, float a_out, float a_in_neg, float b_out, float b_in_neg, uint64_t n_words, const uint64_t* __restrict__ out_mask,
+__global__ void __launch_bounds__(kWalkThreads) k_csg_emit(BandDev A, BandDev B, float a_out, float a_in_neg, float b_out, float b_in_neg, uint64_t n_words, const uint64_t* __restrict__ out_mask,
                                                           const uint32_t* __restrict__ unit_cnt, const uint64_t* __restrict__ group_base,
                                                           uint64_t* __restrict__ out_word_off,
                                                           float* __restrict__ out_dist, uint64_t cap) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t unit = (uint64_t)blockIdx.x * kCsgWaves + (uint64_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t w0 = unit * kCsgUnit;
-  if (w0 >= n_words) return;   // the whole wave
-  const uint64_t first = unit - unit % kCsgGroup;   // the group's first unit: every unit from there to this one exists
-  uint64_t before = first + lane < unit ? unit_cnt[first + lane] : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
-  uint64_t base = group_base[unit / kCsgGroup] + before;
-  for (int i = 0; i < kCsgSteps; ++i) {
-    const uint64_t wb = w0 + (uint64_t)i * 64;   // wave-uniform
-    if (wb >= n_words) break;
-    const uint64_t w = wb + lane;
-    const bool in_range = w < n_words;
+  WALK_UNIT_HEAD(kWalkSteps, n_words)
+  uint64_t base = walk_unit_base<kCsgGroup>(lane, unit, unit_cnt, group_base);
+  for (int step = 0; step < kWalkSteps; ++step) {
+    WALK_STEP_HEAD(n_words)
     const uint64_t rm = in_range ? out_mask[w] : 0;
-    const uint64_t c = (uint64_t)__popcll(rm);
-    uint64_t incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t y = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += y;
-    }
-    const uint64_t off = base + incl - c;
-    base += csg_lane(incl, 63);
+    const uint64_t off = walk_word_off((uint64_t)__popcll(rm), lane, base);
     if (in_range) out_word_off[w] = off;
     const CsgWord x = csg_load(A, B, w, rm != 0);
     uint64_t todo = __ballot(rm != 0);
@@ -193,24 +146,24 @@ __global__ void __launch_bounds__(kCsgThreads) k_csg_emit(BandDev A, BandDev B, 
       const int j = __ffsll((unsigned long long)todo) - 1;
       todo &= todo - 1;
       const CsgWord y = csg_broadcast(x, j);
-      const uint64_t rmj = csg_lane(rm, j), offj = csg_lane(off, j);
+      const uint64_t rmj = walk_lane(rm, j), offj = walk_lane(off, j);
       const CsgPoint a = csg_point<false>(A, a_out, a_in_neg, y.mA, y.iA, y.woA, lane);
       const CsgPoint b = csg_point<NEG>(B, b_out, b_in_neg, y.mB, y.iB, y.woB, lane);
       float r;
       bool active, s;
       csg_rule<OP>(a, b, &r, &active, &s);
-      const uint64_t pos = offj + (uint64_t)__popcll(rmj & ((1ull << lane) - 1ull));
+      const uint64_t pos = offj + (uint64_t)__popcll(rmj & walk_below(lane));
       if (((rmj >> lane) & 1ull) && pos < cap) out_dist[pos] = r;
     }
   }
 }
 
 // Export: the cells of a handle from its mask, 64 words per wave and step.
-__global__ void __launch_bounds__(kCsgThreads) k_csg_cells(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ word_off, uint64_t n_words,
+__global__ void __launch_bounds__(kWalkThreads) k_csg_cells(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ word_off, uint64_t n_words,
                                                            uint64_t n, uint64_t* __restrict__ cells) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (uint64_t wb = ((uint64_t)blockIdx.x * (kCsgThreads / 64) + wave) * 64; wb < n_words; wb += (uint64_t)gridDim.x * kCsgThreads) {
+  for (uint64_t wb = ((uint64_t)blockIdx.x * kWalkWaves + wave) * 64; wb < n_words; wb += (uint64_t)gridDim.x * kWalkThreads) {
     const uint64_t w = wb + lane;
     const uint64_t m = w < n_words ? mask[w] : 0;
     const uint64_t wo = m ? word_off[w] : 0;
@@ -218,8 +171,8 @@ __global__ void __launch_bounds__(kCsgThreads) k_csg_cells(const uint64_t* __res
     while (todo) {   // wave-uniform
       const int j = __ffsll((unsigned long long)todo) - 1;
       todo &= todo - 1;
-      const uint64_t mj = csg_lane(m, j), oj = csg_lane(wo, j);
-      const uint64_t pos = oj + (uint64_t)__popcll(mj & ((1ull << lane) - 1ull));
+      const uint64_t mj = walk_lane(m, j), oj = walk_lane(wo, j);
+      const uint64_t pos = oj + (uint64_t)__popcll(mj & walk_below(lane));
       if (((mj >> lane) & 1ull) && pos < n) cells[pos] = ((wb + (uint64_t)j) << 6) + (uint64_t)lane;
     }
   }
@@ -245,22 +198,17 @@ __global__ void __launch_bounds__(256) k_csg_unsign(const uint64_t* __restrict__
   }
 }
 
-constexpr uint64_t kMaxBlocks = 1u << 20;   // beyond that the grid-stride loops take over
-unsigned blocks_for(uint64_t n) { return (unsigned)std::min<uint64_t>(kMaxBlocks, (n + 255) / 256); }
-
 template <int OP, bool NEG>
-void launch_csg_as(hipStream_t st, const BandDev& A, const BandDev& B, uint64_t n_words, uint64_t total, uint64_t n_units, uint64_t* mask,
-                   uint64_t* inside, uint64_t* word_off, float* dist, uint64_t cap, uint32_t* unit_cnt, uint64_t* group_sum, uint64_t* d_total) {
-  const unsigned blocks = (unsigned)((n_units + kCsgWaves - 1) / kCsgWaves);
+void launch_csg_as(hipStream_t st, const BandDev& A, const BandDev& B, uint64_t n_words, uint64_t total, uint64_t n_units, const BandBlock& res,
+                   uint64_t cap, uint32_t* unit_cnt, uint64_t* group_sum, uint64_t* d_total) {
+  const unsigned blocks = (unsigned)((n_units + kWalkWaves - 1) / kWalkWaves);
   const uint64_t n_groups = (n_units + kCsgGroup - 1) / kCsgGroup;
-  hipLaunchKernelGGL((k_csg_mask<OP, NEG>), dim3(blocks), dim3(kCsgThreads), 0, st, A, B, A.bg_out, A.bg_in_neg, B.bg_out, B.bg_in_neg, n_words, total,
-                     mask, inside, unit_cnt, group_sum);
+  hipLaunchKernelGGL((k_csg_mask<OP, NEG>), dim3(blocks), dim3(kWalkThreads), 0, st, A, B, A.bg_out, A.bg_in_neg, B.bg_out, B.bg_in_neg, n_words, total,
+                     res.mask, res.inside, unit_cnt, group_sum);
   hipLaunchKernelGGL((k_scan_tiles<kScanThreads, uint64_t>), dim3(1), dim3(kScanThreads), 0, st, group_sum, n_groups, d_total);
-  hipLaunchKernelGGL((k_csg_emit<OP, NEG>), dim3(blocks), dim3(kCsgThreads), 0, st, A, B, A.bg_out, A.bg_in_neg, B.bg_out, B.bg_in_neg, n_words,
-                     (const uint64_t*)mask, (const uint32_t*)unit_cnt, (const uint64_t*)group_sum, word_off, dist, cap);
+  hipLaunchKernelGGL((k_csg_emit<OP, NEG>), dim3(blocks), dim3(kWalkThreads), 0, st, A, B, A.bg_out, A.bg_in_neg, B.bg_out, B.bg_in_neg, n_words,
+                     (const uint64_t*)res.mask, (const uint32_t*)unit_cnt, (const uint64_t*)group_sum, res.word_off, res.dist, cap);
 }
-
-bool good_background(float v) { return v >= 0.0f && std::isfinite(v); }
 
 }  // namespace
 
@@ -281,17 +229,11 @@ int m2s_band_csg(const m2s_band* a, const m2s_band* b, int op, const m2s_band_fi
   if (op != M2S_CSG_UNION && op != M2S_CSG_INTERSECTION && op != M2S_CSG_DIFFERENCE) return fail(M2S_ERR_BAD_ARG, "bad m2s_csg_op %d", op);
   if (!a || !b) return fail(M2S_ERR_BAD_ARG, "band is NULL");
   if (a->device != b->device) return fail(M2S_ERR_BAD_ARG, "the bands live on devices %d and %d", a->device, b->device);
-  if (memcmp(a->grid.first_cell, b->grid.first_cell, sizeof(a->grid.first_cell)) != 0 ||
-      memcmp(a->grid.cell_size, b->grid.cell_size, sizeof(a->grid.cell_size)) != 0 ||
-      memcmp(a->grid.cell_count, b->grid.cell_count, sizeof(a->grid.cell_count)) != 0)
+  if (!band_same_grid(a->grid, b->grid))
     return fail(M2S_ERR_BAD_ARG, "the bands' grids differ (first_cell, cell_size and cell_count must agree in every bit)");
-  if (fopts) {
-    if (fopts->struct_size != sizeof(m2s_band_field_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_band_field_opts.struct_size is not sizeof(m2s_band_field_opts)");
-    if (!good_background(fopts->background_outside) || !good_background(fopts->background_inside))
-      return fail(M2S_ERR_BAD_ARG, "the backgrounds (%g outside, %g inside) must be >= 0 and finite", (double)fopts->background_outside,
-                  (double)fopts->background_inside);
-  }
-  int rc = band_opts_args(opts, "m2s_band_csg");
+  int rc = band_field_opts_args(fopts);
+  if (rc) return rc;
+  rc = band_opts_args(opts, "m2s_band_csg");
   if (rc) return rc;
   m2s_opts o;
   rc = band_call_opts(a, opts, &o);
@@ -307,15 +249,10 @@ int m2s_band_csg(const m2s_band* a, const m2s_band* b, int op, const m2s_band_fi
   const float bg_in = fopts ? fopts->background_inside : std::min(a->bg_in, bs_in);
   const uint64_t total = a->total, n_words = a->n_words;
   const uint64_t cap = std::max<uint64_t>(1, std::min(a->n + b->n, total));   // the bound of the result's cells: at least one float
-  const uint64_t n_units = (n_words + kCsgUnit - 1) / kCsgUnit;               // below 2^22: a grid has fewer than 2^36 cells
-  const size_t b_words = align_up(n_words * 8), b_dist = align_up(cap * 4);
-  char* block = nullptr;
-  M2S_HIP_CHECK(hipMalloc((void**)&block, 3 * b_words + b_dist));
-  auto drop = [&](int code) { (void)hipFree(block); return code; };
-  uint64_t* mask = reinterpret_cast<uint64_t*>(block);
-  uint64_t* word_off = reinterpret_cast<uint64_t*>(block + b_words);
-  uint64_t* inside = reinterpret_cast<uint64_t*>(block + 2 * b_words);
-  float* dist = reinterpret_cast<float*>(block + 3 * b_words);
+  const uint64_t n_units = (n_words + kWalkUnit - 1) / kWalkUnit;               // below 2^22: a grid has fewer than 2^36 cells
+  BandBlock res;
+  M2S_HIP_CHECK(res.alloc(n_words, cap));
+  auto drop = [&](int code) { res.free(); return code; };
   const uint64_t n_groups = (n_units + kCsgGroup - 1) / kCsgGroup;
   rc = ensure_capacity(*st, 4096 + 256 + align_up((size_t)n_units * 4) + align_up((size_t)n_groups * 8));
   if (rc) return drop(rc);
@@ -327,12 +264,12 @@ int m2s_band_csg(const m2s_band* a, const m2s_band* b, int op, const m2s_band_fi
   const BandDev A = dev_of(a), B = dev_of(b);
   hipError_t e = hipSuccess;
   if (c.timings) e = hipEventRecord(st->ev[0], c.stream);
-  if (e == hipSuccess) e = hipMemsetAsync(dist, 0, 4, c.stream);   // an empty result still has one defined float
+  if (e == hipSuccess) e = hipMemsetAsync(res.dist, 0, 4, c.stream);   // an empty result still has one defined float
   if (e == hipSuccess) e = hipMemsetAsync(group_sum, 0, n_groups * 8, c.stream);
   if (e != hipSuccess) return drop(fail(M2S_ERR_HIP, "HIP error: %s", hipGetErrorString(e)));
-  if (op == M2S_CSG_UNION) launch_csg_as<0, false>(c.stream, A, B, n_words, total, n_units, mask, inside, word_off, dist, cap, unit_cnt, group_sum, d_total);
-  else if (op == M2S_CSG_INTERSECTION) launch_csg_as<1, false>(c.stream, A, B, n_words, total, n_units, mask, inside, word_off, dist, cap, unit_cnt, group_sum, d_total);
-  else launch_csg_as<1, true>(c.stream, A, B, n_words, total, n_units, mask, inside, word_off, dist, cap, unit_cnt, group_sum, d_total);
+  if (op == M2S_CSG_UNION) launch_csg_as<0, false>(c.stream, A, B, n_words, total, n_units, res, cap, unit_cnt, group_sum, d_total);
+  else if (op == M2S_CSG_INTERSECTION) launch_csg_as<1, false>(c.stream, A, B, n_words, total, n_units, res, cap, unit_cnt, group_sum, d_total);
+  else launch_csg_as<1, true>(c.stream, A, B, n_words, total, n_units, res, cap, unit_cnt, group_sum, d_total);
   e = hipGetLastError();
   if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[1], c.stream);
   uint64_t n = 0;
@@ -348,21 +285,7 @@ int m2s_band_csg(const m2s_band* a, const m2s_band* b, int op, const m2s_band_fi
     c.timings->total_ms = ms;
     c.timings->n_units = n;
   }
-  m2s_band* h = new m2s_band();
-  h->device = a->device;
-  h->grid = a->grid;
-  h->n = n;
-  h->total = total;
-  h->n_words = n_words;
-  h->device_bytes = n_words * 24 + n * 4;
-  h->block = block;
-  h->mask = mask;
-  h->word_off = word_off;
-  h->inside = inside;
-  h->dist = dist;
-  h->bg_out = bg_out;
-  h->bg_in = bg_in;
-  *out = h;
+  *out = band_adopt(res, a->device, a->grid, n, total, n_words, bg_out, bg_in);
   return M2S_OK;
 }
 
@@ -385,7 +308,7 @@ int m2s_band_export(const m2s_band* band, uint64_t* cells_out, float* distances_
                    {inside_bits_out, inside_bits_out ? sign_words * 4 : 0, true}};
   return run_query(&o, io, 3, n, [&](hipStream_t s) {
     if (cells_out && n)
-      hipLaunchKernelGGL(k_csg_cells, dim3(blocks_for(n_words)), dim3(kCsgThreads), 0, s, band->mask, band->word_off, n_words, n,
+      hipLaunchKernelGGL(k_csg_cells, dim3(blocks_for(n_words)), dim3(kWalkThreads), 0, s, band->mask, band->word_off, n_words, n,
                          reinterpret_cast<uint64_t*>(io[0].dev));
     if (distances_out && n) M2S_HIP_CHECK(hipMemcpyAsync(io[1].dev, band->dist, n * 4, hipMemcpyDeviceToDevice, s));
     if (inside_bits_out)

@@ -2,9 +2,7 @@
 // band or inside a region, gfx950.  The contract is include/m2s.h's (per grid point, to the bit); tests/band_filter_model.py restates it in
 // numpy.  Nothing sized 4 bytes per grid point exists: the arrays are per mask word (the result's sign word) or per active cell.
 //
-// The two kernels that walk the mask words use band_walk.hip.h, band_redistance.hip's form: a wave owns 256 words; a
-// word with no active point is settled by its own lane, the others are taken one at a time by the whole wave and lane t owns the point
-// L = 64 w + t.
+// The two kernels that walk the mask words are band_walk.hip.h's walk, units of 256 words.
 //   k_bf_table   per active cell, once: the list places of its 6 or 18 clamped neighbours as 32-bit slots (a rank look-up each: mask word,
 //                word_off, popcount below); an inactive neighbour becomes one of the two places n and n + 1 behind the values, which hold
 //                +background_outside and -background_inside; the cell's `where` bit; its value into the first value buffer.
@@ -58,7 +56,7 @@ __device__ __forceinline__ uint32_t bf_slot(const BandDev& X, uint64_t M) {
 template <int NSLOT>
 __global__ void __launch_bounds__(kWalkThreads) k_bf_table(BandDev X, BandDev Wh, int has_where, WalkGrid g, uint32_t* __restrict__ slots,
                                                          uint8_t* __restrict__ in_region, float* __restrict__ v0, float* __restrict__ v1) {
-  WALK_UNIT_HEAD
+  WALK_UNIT_HEAD(kWalkSteps, g.n_words)
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     v0[X.n] = X.bg_out;
     v0[X.n + 1] = X.bg_in_neg;
@@ -66,7 +64,7 @@ __global__ void __launch_bounds__(kWalkThreads) k_bf_table(BandDev X, BandDev Wh
     v1[X.n + 1] = X.bg_in_neg;
   }
   for (int step = 0; step < kWalkSteps; ++step) {
-    WALK_STEP_HEAD
+    WALK_STEP_HEAD(g.n_words)
     const uint64_t m = in_range ? X.mask[w] : 0;
     const uint64_t wo = m ? X.word_off[w] : 0;
     const uint64_t wm = (m && has_where) ? Wh.mask[w] : 0;
@@ -106,9 +104,7 @@ __global__ void __launch_bounds__(kWalkThreads) k_bf_table(BandDev X, BandDev Wh
         if (has_where) {
           in = (winj >> lane) & 1ull;
           if ((wmj >> lane) & 1ull) {
-            uint64_t at = wwoj + (uint64_t)__popcll(wmj & walk_below(lane));
-            at = at < Wh.n ? at : 0;
-            in = Wh.dist[at] < 0.0f;
+            in = Wh.dist[walk_rank(wmj, wwoj, lane, Wh.n)] < 0.0f;
           }
         }
         in_region[r] = in ? 1 : 0;
@@ -169,10 +165,10 @@ __global__ void __launch_bounds__(256) k_bf_pass(const uint32_t* __restrict__ sl
 // counters[1] += n_changed, counters[2] += n_sign_flips, counters[3] = max(the bits of fabsf(r - x)): non-negative floats order as their bits.
 __global__ void __launch_bounds__(kWalkThreads) k_bf_final(BandDev X, WalkGrid g, const float* __restrict__ v, uint64_t* __restrict__ S, float* __restrict__ out,
                                                          uint64_t* __restrict__ counters) {
-  WALK_UNIT_HEAD
+  WALK_UNIT_HEAD(kWalkSteps, g.n_words)
   uint32_t n_changed = 0, n_flips = 0, top = 0;
   for (int step = 0; step < kWalkSteps; ++step) {
-    WALK_STEP_HEAD
+    WALK_STEP_HEAD(g.n_words)
     const uint64_t m = in_range ? X.mask[w] : 0;
     const uint64_t in = in_range && X.inside ? X.inside[w] : 0;
     const uint64_t wo = m ? X.word_off[w] : 0;
@@ -213,8 +209,6 @@ __global__ void __launch_bounds__(kWalkThreads) k_bf_final(BandDev X, WalkGrid g
   }
 }
 
-bool good_background(float v) { return v >= 0.0f && std::isfinite(v); }
-
 template <int KIND, int AXIS>
 void launch_pass(hipStream_t st, unsigned blocks, const uint32_t* slots, const uint8_t* in_region, const float* v_in, float* v_out, uint64_t n,
                  const BfConst& k, uint64_t* counters) {
@@ -246,21 +240,15 @@ int m2s_band_filter(const m2s_band* band, const m2s_band* where, const m2s_band_
     return fail(M2S_ERR_BAD_ARG, "bad m2s_filter_kind %d", fl->kind);
   if (fl->iterations == 0 || fl->iterations > 65536) return fail(M2S_ERR_BAD_ARG, "iterations = %u: must be 1 .. 65536", fl->iterations);
   if (fl->width != 1) return fail(M2S_ERR_BAD_ARG, "width = %u: must be 1", fl->width);
-  if (fopts) {
-    if (fopts->struct_size != sizeof(m2s_band_field_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_band_field_opts.struct_size is not sizeof(m2s_band_field_opts)");
-    if (!good_background(fopts->background_outside) || !good_background(fopts->background_inside))
-      return fail(M2S_ERR_BAD_ARG, "the backgrounds (%g outside, %g inside) must be >= 0 and finite", (double)fopts->background_outside,
-                  (double)fopts->background_inside);
-  }
+  int rc = band_field_opts_args(fopts);
+  if (rc) return rc;
   if (info_out && info_out->struct_size != sizeof(m2s_band_filter_info))
     return fail(M2S_ERR_BAD_ARG, "m2s_band_filter_info.struct_size is not sizeof(m2s_band_filter_info)");
-  int rc = band_opts_args(opts, "m2s_band_filter");
+  rc = band_opts_args(opts, "m2s_band_filter");
   if (rc) return rc;
   if (where) {
     if (where->device != band->device) return fail(M2S_ERR_BAD_ARG, "the band and the region live on devices %d and %d", band->device, where->device);
-    if (memcmp(band->grid.first_cell, where->grid.first_cell, sizeof(band->grid.first_cell)) != 0 ||
-        memcmp(band->grid.cell_size, where->grid.cell_size, sizeof(band->grid.cell_size)) != 0 ||
-        memcmp(band->grid.cell_count, where->grid.cell_count, sizeof(band->grid.cell_count)) != 0)
+    if (!band_same_grid(band->grid, where->grid))
       return fail(M2S_ERR_BAD_ARG, "the band's and the region's grids differ (first_cell, cell_size and cell_count must agree in every bit)");
   }
   const uint64_t n = band->n;
@@ -288,26 +276,18 @@ int m2s_band_filter(const m2s_band* band, const m2s_band* where, const m2s_band_
   k.xs[1] = 0.25f * (r[0] * r[2]);
   k.xs[2] = 0.25f * (r[1] * r[2]);
   k.dt = 1.0f / (2.0f * ((k.w[0] + k.w[1]) + k.w[2]));
-  WalkGrid g;
-  g.total = band->total;
-  g.n_words = band->n_words;
-  g.nx = band->grid.cell_count[0];
-  g.ny = band->grid.cell_count[1];
-  g.nz = band->grid.cell_count[2];
-  g.sj = g.nz;
-  g.si = g.ny * g.nz;
+  const WalkGrid g = walk_grid_of(band->grid.cell_count, band->total, band->n_words);
 
   const uint64_t n_words = g.n_words;
   const uint64_t n_units = (n_words + kWalkUnit - 1) / kWalkUnit;   // below 2^22: a grid has fewer than 2^36 cells
   const unsigned blocks = (unsigned)((n_units + kWalkWaves - 1) / kWalkWaves);
-  const size_t b_words = align_up(n_words * 8);
   const size_t b_v = align_up((n + 2) * 4), b_slots = align_up((uint64_t)n_slots * n * 4 + 4), b_region = align_up(n + 1);
   const uint64_t cap = std::max<uint64_t>(n, 1);   // at least one float
   char* tmp = nullptr;     // two value buffers, the table, the region bytes: 33 or 81 bytes per active cell
-  char* block = nullptr;   // the result
+  BandBlock res;           // the result
   auto drop = [&](int code) {
     (void)hipFree(tmp);
-    (void)hipFree(block);
+    res.free();
     return code;
   };
   auto hip_fail = [&](hipError_t e) { return drop(fail(M2S_ERR_HIP, "HIP error: %s", hipGetErrorString(e))); };
@@ -317,15 +297,11 @@ int m2s_band_filter(const m2s_band* band, const m2s_band* where, const m2s_band_
   uint64_t* d_hdr = ws.take<uint64_t>(4);   // [0] n_nonfinite, [1] n_changed, [2] n_sign_flips, [3] the bits of max_change
   if (!d_hdr) return fail(M2S_ERR_HIP, "internal: workspace");
   hipError_t e = hipMalloc((void**)&tmp, 2 * b_v + b_slots + b_region);
-  if (e == hipSuccess) e = hipMalloc((void**)&block, 3 * b_words + align_up(cap * 4));
+  if (e == hipSuccess) e = res.alloc(n_words, cap);
   if (e != hipSuccess) return hip_fail(e);
   float* v[2] = {reinterpret_cast<float*>(tmp), reinterpret_cast<float*>(tmp + b_v)};
   uint32_t* slots = reinterpret_cast<uint32_t*>(tmp + 2 * b_v);
   uint8_t* in_region = reinterpret_cast<uint8_t*>(tmp + 2 * b_v + b_slots);
-  uint64_t* mask = reinterpret_cast<uint64_t*>(block);
-  uint64_t* word_off = reinterpret_cast<uint64_t*>(block + b_words);
-  uint64_t* inside = reinterpret_cast<uint64_t*>(block + 2 * b_words);
-  float* dist = reinterpret_cast<float*>(block + 3 * b_words);
   const BandDev X = dev_of(band);
   const BandDev Wh = where ? dev_of(where) : X;
   hipStream_t s = c.stream;
@@ -333,9 +309,9 @@ int m2s_band_filter(const m2s_band* band, const m2s_band* where, const m2s_band_
   // ---- the table ----
   if (c.timings) e = hipEventRecord(st->ev[0], s);
   if (e == hipSuccess) e = hipMemsetAsync(d_hdr, 0, 32, s);
-  if (e == hipSuccess) e = hipMemsetAsync(dist, 0, 4, s);   // an empty result still has one defined float
-  if (e == hipSuccess) e = hipMemcpyAsync(mask, band->mask, n_words * 8, hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(word_off, band->word_off, n_words * 8, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(res.dist, 0, 4, s);   // an empty result still has one defined float
+  if (e == hipSuccess) e = hipMemcpyAsync(res.mask, band->mask, n_words * 8, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(res.word_off, band->word_off, n_words * 8, hipMemcpyDeviceToDevice, s);
   if (e != hipSuccess) return hip_fail(e);
   if (n_slots == kBfAllSlots)
     hipLaunchKernelGGL((k_bf_table<kBfAllSlots>), dim3(blocks), dim3(kWalkThreads), 0, s, X, Wh, where ? 1 : 0, g, slots, in_region, v[0], v[1]);
@@ -346,7 +322,7 @@ int m2s_band_filter(const m2s_band* band, const m2s_band* where, const m2s_band_
   if (e != hipSuccess) return hip_fail(e);
 
   // ---- the passes, back to back: pass p reads v[p & 1] and writes the other buffer ----
-  const unsigned pass_blocks = (unsigned)std::min<uint64_t>(1u << 20, (n + 255) / 256);
+  const unsigned pass_blocks = blocks_for(n);
   if (n) {
     for (uint64_t p = 0; p < passes; ++p) {
       const float* v_in = v[p & 1];
@@ -363,7 +339,7 @@ int m2s_band_filter(const m2s_band* band, const m2s_band* where, const m2s_band_
   if (e != hipSuccess) return hip_fail(e);
 
   // ---- the result ----
-  hipLaunchKernelGGL(k_bf_final, dim3(blocks), dim3(kWalkThreads), 0, s, X, g, (const float*)v[passes & 1], inside, dist, d_hdr);
+  hipLaunchKernelGGL(k_bf_final, dim3(blocks), dim3(kWalkThreads), 0, s, X, g, (const float*)v[passes & 1], res.inside, res.dist, d_hdr);
   e = hipGetLastError();
   uint64_t hdr[4] = {0, 0, 0, 0};
   if (e == hipSuccess) e = hipMemcpyAsync(hdr, d_hdr, 32, hipMemcpyDeviceToHost, s);
@@ -392,21 +368,8 @@ int m2s_band_filter(const m2s_band* band, const m2s_band* where, const m2s_band_
     info_out->n_sign_flips = hdr[2];
     info_out->n_nonfinite = hdr[0];
   }
-  m2s_band* h = new m2s_band();
-  h->device = band->device;
-  h->grid = band->grid;
-  h->n = n;
-  h->total = g.total;
-  h->n_words = n_words;
-  h->device_bytes = n_words * 24 + n * 4;
-  h->block = block;
-  h->mask = mask;
-  h->word_off = word_off;
-  h->inside = inside;
-  h->dist = dist;
-  h->bg_out = fopts ? fopts->background_outside : band->bg_out;
-  h->bg_in = fopts ? fopts->background_inside : band->bg_in;
-  *out = h;
+  *out = band_adopt(res, band->device, band->grid, n, g.total, n_words, fopts ? fopts->background_outside : band->bg_out,
+                    fopts ? fopts->background_inside : band->bg_in);
   return M2S_OK;
 }
 

@@ -3,7 +3,7 @@
 // for (its values on the band's cells, a signed background elsewhere), bit for bit, and no array sized by 4 bytes per grid point exists.
 // tests/band_query_model.py restates it in numpy.
 //
-// The handle (band_handle.h, shared with band_csg.hip) owns, in device memory:
+// The handle (band_handle.h, shared with the other band calls) owns, in device memory:
 //   mask      1 bit per grid point, word L >> 6, bit L & 63            k_biso_mask (isosurface.hip.h: the index m2s_band_isosurface builds)
 //   word_off  per mask word: the list place of its first active point  k_biso_mask; zeroed first, so every word is defined
 //   dist      the band's distances, in list order                      a copy
@@ -170,9 +170,6 @@ __global__ __launch_bounds__(256) void k_band_raymarch(GridQuery q, BandDev b, c
   }
 }
 
-constexpr uint64_t kMaxBlocks = 1u << 20;   // beyond 2^28 lanes the grid-stride loop takes over
-unsigned blocks_for(uint64_t n) { return (unsigned)std::min<uint64_t>(kMaxBlocks, (n + 255) / 256); }
-
 template <int MODE, bool SIGN, int FORM>
 void launch_sample_as(hipStream_t st, const GridQuery& q, const BandDev& b, const float* pts, uint64_t n, float* value_out, float* normal_out,
                       uint8_t* support_out) {
@@ -245,23 +242,19 @@ int m2s_band_create(const m2s_grid* grid, const uint64_t* cells, const float* di
   *out = nullptr;
   if (!grid) return fail(M2S_ERR_BAD_ARG, "grid is NULL");
   if (!fopts) return fail(M2S_ERR_BAD_ARG, "m2s_band_field_opts is NULL: the backgrounds have no default");
-  if (fopts->struct_size != sizeof(m2s_band_field_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_band_field_opts.struct_size is not sizeof(m2s_band_field_opts)");
-  if (!(fopts->background_outside >= 0.0f) || !std::isfinite(fopts->background_outside) || !(fopts->background_inside >= 0.0f) ||
-      !std::isfinite(fopts->background_inside))
-    return fail(M2S_ERR_BAD_ARG, "the backgrounds (%g outside, %g inside) must be >= 0 and finite", (double)fopts->background_outside,
-                (double)fopts->background_inside);
+  int rc = band_field_opts_args(fopts);
+  if (rc) return rc;
   if (n_cells && (!cells || !distances)) return fail(M2S_ERR_BAD_ARG, "cells / distances is NULL with n_cells > 0");
-  int rc = band_opts_args(opts, "m2s_band_create");
+  rc = band_opts_args(opts, "m2s_band_create");
   if (rc) return rc;
   GridQuery q;
   int mode = 0;
   rc = grid_query_args(grid, nullptr, false, nullptr, &q, &mode);   // what m2s_sample_grid rejects of a grid
   if (rc) return rc;
   const uint64_t nx = grid->cell_count[0], ny = grid->cell_count[1], nz = grid->cell_count[2];
-  const uint64_t nyz = ny * nz;
-  if (nyz / ny != nz) return fail(M2S_ERR_BAD_ARG, "the grid has 2^36 or more cells");
-  const uint64_t total = nyz * nx;
-  if (total / nx != nyz || total >= ((uint64_t)1 << 36)) return fail(M2S_ERR_BAD_ARG, "the grid has 2^36 or more cells");
+  uint64_t total = 0, n_words = 0;
+  rc = band_grid_cells(grid, "grid", &total, &n_words);
+  if (rc) return rc;
   if (n_cells > total) return fail(M2S_ERR_BAD_ARG, "n_cells = %llu above the grid's %llu cells", (unsigned long long)n_cells, (unsigned long long)total);
   const bool host = !opts || opts->mem_kind == M2S_MEM_HOST;
   if (host) {   // host memory: the list and its values are judged here, before any device work
@@ -276,17 +269,12 @@ int m2s_band_create(const m2s_grid* grid, const uint64_t* cells, const float* di
   DeviceState* st = nullptr;
   rc = resolve_ctx(opts, &c, &st);
   if (rc) return rc;
-  const uint64_t n = n_cells, n_words = (total + 63) / 64;
+  const uint64_t n = n_cells;
   const uint64_t sign_words = (nz + 31) / 32 * nx * ny;
-  // the handle's block: mask, word_off, [inside], dist (at least one float: a lane's guarded read needs an address)
-  const size_t b_mask = align_up(n_words * 8), b_sign = inside_bits ? align_up(n_words * 8) : 0, b_dist = align_up((n ? n : 1) * 4);
-  char* block = nullptr;
-  M2S_HIP_CHECK(hipMalloc((void**)&block, 2 * b_mask + b_sign + b_dist));
-  auto drop = [&](int code) { (void)hipFree(block); return code; };
-  uint64_t* mask = reinterpret_cast<uint64_t*>(block);
-  uint64_t* word_off = reinterpret_cast<uint64_t*>(block + b_mask);
-  uint64_t* inside = inside_bits ? reinterpret_cast<uint64_t*>(block + 2 * b_mask) : nullptr;
-  float* dist = reinterpret_cast<float*>(block + 2 * b_mask + b_sign);
+  // the handle's block: mask, word_off, [inside], dist (at least one float)
+  BandBlock res;
+  M2S_HIP_CHECK(res.alloc(n_words, n ? n : 1, inside_bits != nullptr));
+  auto drop = [&](int code) { res.free(); return code; };
   // the workspace: the flag and, for host memory, the staged list and sign mask
   size_t need = 4096 + 256;
   if (host) need += align_up(n * 8) + (inside_bits ? align_up(sign_words * 4) : 0);
@@ -302,7 +290,7 @@ int m2s_band_create(const m2s_grid* grid, const uint64_t* cells, const float* di
       char* sc = ws.take<char>(n * 8);
       if (!sc) return drop(fail(M2S_ERR_HIP, "internal: workspace"));
       if ((rc = staged_h2d(*st, c.stream, sc, reinterpret_cast<const char*>(cells), n * 8))) return drop(rc);
-      if ((rc = staged_h2d(*st, c.stream, reinterpret_cast<char*>(dist), reinterpret_cast<const char*>(distances), n * 4))) return drop(rc);
+      if ((rc = staged_h2d(*st, c.stream, reinterpret_cast<char*>(res.dist), reinterpret_cast<const char*>(distances), n * 4))) return drop(rc);
       dc = reinterpret_cast<const uint64_t*>(sc);
     }
     if (inside_bits) {
@@ -312,19 +300,19 @@ int m2s_band_create(const m2s_grid* grid, const uint64_t* cells, const float* di
       db = reinterpret_cast<const uint32_t*>(sb);
     }
   } else if (n) {
-    if (hipMemcpyAsync(dist, distances, n * 4, hipMemcpyDeviceToDevice, c.stream) != hipSuccess) return drop(fail(M2S_ERR_HIP, "hipMemcpyAsync failed"));
+    if (hipMemcpyAsync(res.dist, distances, n * 4, hipMemcpyDeviceToDevice, c.stream) != hipSuccess) return drop(fail(M2S_ERR_HIP, "hipMemcpyAsync failed"));
   }
   hipError_t e = hipSuccess;
   if (c.timings) e = hipEventRecord(st->ev[0], c.stream);
   if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 32, c.stream);
-  if (e == hipSuccess) e = hipMemsetAsync(mask, 0, b_mask * 2, c.stream);   // the mask and every word's offset
-  if (e == hipSuccess && n == 0) e = hipMemsetAsync(dist, 0, 4, c.stream);
+  if (e == hipSuccess) e = hipMemsetAsync(res.mask, 0, align_up(n_words * 8) * 2, c.stream);   // the mask and every word's offset
+  if (e == hipSuccess && n == 0) e = hipMemsetAsync(res.dist, 0, 4, c.stream);
   if (e != hipSuccess) return drop(fail(M2S_ERR_HIP, "HIP error: %s", hipGetErrorString(e)));
   if (n)
     hipLaunchKernelGGL(k_biso_mask, dim3((unsigned)((n + kMaskThreads - 1) / kMaskThreads)), dim3(kMaskThreads), 0, c.stream, total, dc,
-                       (const float*)dist, n, mask, word_off, d_flag);
+                       (const float*)res.dist, n, res.mask, res.word_off, d_flag);
   if (inside_bits)
-    hipLaunchKernelGGL(k_bq_sign, dim3(blocks_for(n_words)), dim3(256), 0, c.stream, total, nz, n_words, db, inside);
+    hipLaunchKernelGGL(k_bq_sign, dim3(blocks_for(n_words)), dim3(256), 0, c.stream, total, nz, n_words, db, res.inside);
   e = hipGetLastError();
   if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[1], c.stream);
   uint32_t raised[2] = {0, 0};
@@ -341,21 +329,7 @@ int m2s_band_create(const m2s_grid* grid, const uint64_t* cells, const float* di
     c.timings->total_ms = ms;
     c.timings->n_units = n_cells;
   }
-  m2s_band* h = new m2s_band();
-  h->device = c.device;
-  h->grid = *grid;
-  h->n = n;
-  h->total = total;
-  h->n_words = n_words;
-  h->device_bytes = n_words * 16 + n * 4 + (inside_bits ? n_words * 8 : 0);
-  h->block = block;
-  h->mask = mask;
-  h->word_off = word_off;
-  h->inside = inside;
-  h->dist = dist;
-  h->bg_out = fopts->background_outside;
-  h->bg_in = fopts->background_inside;
-  *out = h;
+  *out = band_adopt(res, c.device, *grid, n, total, n_words, fopts->background_outside, fopts->background_inside);
   return M2S_OK;
 }
 

@@ -2,16 +2,13 @@
 // the caller asks for, gfx950.  The contract is include/m2s.h's (per grid point, to the bit); tests/band_redistance_model.py restates it
 // in numpy.  Nothing sized 4 bytes per grid point exists: the arrays are per mask word (8 bytes per 64 points) or per candidate cell.
 //
-// Every kernel that walks the mask words has band_csg.hip's form: a wave owns a UNIT of 256 words and takes it in
-// 4 steps of 64, lane l loading word 64 * step + l; a word with nothing to do is settled by its own lane, the others are taken one at a
-// time by the whole wave (a ballot finds them, v_readlane broadcasts the word's values) and lane t owns bit t, the point L = 64 w + t.
-// A word's base L is decomposed into (i, j, k) once, by the lane that loaded it, and stepped per bit.
+// Every kernel that walks the mask words is band_walk.hip.h's walk, units of 256 words.
 //   k_rd_sign     s on every grid point (the result's sign mask): the source's sign word where no point is active, else the values' signs.
 //   k_rd_frozen   F: per active point the six neighbours' act and s bits; n_frozen, n_open.
 //   k_rd_dilate   one axis of the box dilation, a gather: a word first ORs the 2K + 1 shifted windows of its source (a superset: it
 //                 ignores the row ends); only words where that is not zero are taken by the wave, lane t testing its own clipped range.
 //   k_rd_select   C = s ? dilation by the interior K : by the exterior K.
-//   k_rd_count / k_scan_tiles / k_rd_offsets   a mask's word_off (used for C and for the result): per unit counts, group sums, scan.
+//   k_rd_count / k_scan_tiles / k_rd_offsets   a mask's word_off (used for C and for the result): band_walk.hip.h's offsets, groups of 16.
 //   k_rd_table    per candidate, once: the places in C of its six neighbours (a rank look-up each: C word, word_off, popcount below),
 //                 with the in-grid, same-sign and in-C tests folded into an empty slot; meta (frozen, s); u = |x| on F, +inf on the rest
 //                 of C, into both value buffers.
@@ -38,7 +35,7 @@
 namespace m2s {
 namespace {
 
-constexpr int kRdGroup = 16;                               // units per scanned sum (at most 64: one lane each in k_rd_offsets)
+constexpr int kRdGroup = 16;                               // units per scanned sum
 constexpr int kRdScanThreads = 1024;
 constexpr int kRdBatch = 4;                                // sweeps between two reads of the change flags
 
@@ -46,9 +43,9 @@ __device__ __forceinline__ bool rd_bit(const uint64_t* __restrict__ a, uint64_t 
 
 // s on every grid point, bits past the grid zero.
 __global__ void __launch_bounds__(kWalkThreads) k_rd_sign(BandDev X, WalkGrid g, uint64_t* __restrict__ S) {
-  WALK_UNIT_HEAD
+  WALK_UNIT_HEAD(kWalkSteps, g.n_words)
   for (int step = 0; step < kWalkSteps; ++step) {
-    WALK_STEP_HEAD
+    WALK_STEP_HEAD(g.n_words)
     const uint64_t m = in_range ? X.mask[w] : 0;
     const uint64_t in = in_range && X.inside ? X.inside[w] : 0;
     const uint64_t wo = m ? X.word_off[w] : 0;
@@ -74,10 +71,10 @@ __global__ void __launch_bounds__(kWalkThreads) k_rd_sign(BandDev X, WalkGrid g,
 // F, and counters[0] += n_frozen, counters[1] += n_open.
 __global__ void __launch_bounds__(kWalkThreads) k_rd_frozen(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ S, WalkGrid g,
                                                           uint64_t* __restrict__ Fm, uint64_t* __restrict__ counters) {
-  WALK_UNIT_HEAD
+  WALK_UNIT_HEAD(kWalkSteps, g.n_words)
   uint64_t n_frozen = 0, n_open = 0;
   for (int step = 0; step < kWalkSteps; ++step) {
-    WALK_STEP_HEAD
+    WALK_STEP_HEAD(g.n_words)
     const uint64_t m = in_range ? mask[w] : 0;
     const uint64_t sw = m ? S[w] : 0;
     WalkIjk base{0, 0, 0};
@@ -142,11 +139,11 @@ __device__ __forceinline__ uint64_t rd_window(const uint64_t* __restrict__ src, 
 // dilation by K.
 template <int AXIS>
 __global__ void __launch_bounds__(kWalkThreads) k_rd_dilate(const uint64_t* __restrict__ src, WalkGrid g, int64_t K, int64_t hop, uint64_t* __restrict__ dst) {
-  WALK_UNIT_HEAD
+  WALK_UNIT_HEAD(kWalkSteps, g.n_words)
   const int64_t stride = (AXIS == 0 ? (int64_t)g.si : AXIS == 1 ? (int64_t)g.sj : 1) * hop;
   const int64_t n_axis = (int64_t)(AXIS == 0 ? g.nx : AXIS == 1 ? g.ny : g.nz);
   for (int step = 0; step < kWalkSteps; ++step) {
-    WALK_STEP_HEAD
+    WALK_STEP_HEAD(g.n_words)
     uint64_t any = 0;
     if (in_range) {
       if (AXIS == 2 && hop == 1 && K < 64) {   // the windows overlap: the word, the K bits before it and the K bits after it
@@ -191,48 +188,30 @@ __global__ void __launch_bounds__(256) k_rd_select(const uint64_t* DE, const uin
 // A mask's popcounts per unit, and by one atomic add per unit the sum of its group (zeroed by the launcher).
 __global__ void __launch_bounds__(kWalkThreads) k_rd_count(const uint64_t* __restrict__ mask, WalkGrid g, uint32_t* __restrict__ unit_cnt,
                                                          uint64_t* __restrict__ group_sum) {
-  WALK_UNIT_HEAD
+  WALK_UNIT_HEAD(kWalkSteps, g.n_words)
   uint64_t cnt = 0;
   for (int step = 0; step < kWalkSteps; ++step) {
-    WALK_STEP_HEAD
+    WALK_STEP_HEAD(g.n_words)
     cnt += in_range ? (uint64_t)__popcll(mask[w]) : 0;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if (lane == 0) {
-    unit_cnt[unit] = (uint32_t)cnt;   // at most 64 * 256
-    if (cnt) atomicAdd((unsigned long long*)(group_sum + unit / kRdGroup), (unsigned long long)cnt);
-  }
+  walk_publish<kRdGroup>(cnt, lane, unit, unit_cnt, group_sum);
 }
 
 // word_off of a mask from the scanned group sums and the unit counts.
 __global__ void __launch_bounds__(kWalkThreads) k_rd_offsets(const uint64_t* __restrict__ mask, WalkGrid g, const uint32_t* __restrict__ unit_cnt,
                                                            const uint64_t* __restrict__ group_base, uint64_t* __restrict__ word_off) {
-  WALK_UNIT_HEAD
-  const uint64_t first = unit - unit % kRdGroup;   // the group's first unit: every unit from there to this one exists
-  uint64_t before = first + lane < unit ? unit_cnt[first + lane] : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
-  uint64_t base = group_base[unit / kRdGroup] + before;
+  WALK_UNIT_HEAD(kWalkSteps, g.n_words)
+  uint64_t base = walk_unit_base<kRdGroup>(lane, unit, unit_cnt, group_base);
   for (int step = 0; step < kWalkSteps; ++step) {
-    WALK_STEP_HEAD
-    const uint64_t c = in_range ? (uint64_t)__popcll(mask[w]) : 0;
-    uint64_t incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t y = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += y;
-    }
-    if (in_range) word_off[w] = base + incl - c;
-    base += walk_lane(incl, 63);
+    WALK_STEP_HEAD(g.n_words)
+    const uint64_t off = walk_word_off(in_range ? (uint64_t)__popcll(mask[w]) : 0, lane, base);
+    if (in_range) word_off[w] = off;
   }
 }
 
 // x of an active point of X: bit t of word w.
 __device__ __forceinline__ float rd_x(const BandDev& X, uint64_t mX, uint64_t woX, int t) {
-  uint64_t at = woX + (uint64_t)__popcll(mX & walk_below(t));
-  at = at < X.n ? at : 0;   // at < n whenever the index is sound
-  return X.dist[at];
+  return X.dist[walk_rank(mX, woX, t, X.n)];
 }
 
 struct RdField {
@@ -263,9 +242,9 @@ __device__ __forceinline__ uint32_t rd_slot(const RdField& p, uint64_t M, bool s
 // fold into kRdNone, so a sweep needs no index word and no coordinate.
 __global__ void __launch_bounds__(kWalkThreads) k_rd_table(BandDev X, WalkGrid g, const uint64_t* __restrict__ Fm, RdField fld, uint32_t* __restrict__ slots,
                                                          uint8_t* __restrict__ meta, float* __restrict__ u0, float* __restrict__ u1) {
-  WALK_UNIT_HEAD
+  WALK_UNIT_HEAD(kWalkSteps, g.n_words)
   for (int step = 0; step < kWalkSteps; ++step) {
-    WALK_STEP_HEAD
+    WALK_STEP_HEAD(g.n_words)
     const uint64_t c = in_range ? fld.C[w] : 0;
     const uint64_t co = c ? fld.Coff[w] : 0;
     const uint64_t f = c ? Fm[w] : 0;
@@ -380,9 +359,9 @@ __global__ void __launch_bounds__(256) k_rd_sweep(const uint32_t* __restrict__ s
 // The result's mask: F, or in C with u <= W.
 __global__ void __launch_bounds__(kWalkThreads) k_rd_final(WalkGrid g, const uint64_t* __restrict__ Fm, RdField fld, float w_out, float w_in,
                                                          uint64_t* __restrict__ R) {
-  WALK_UNIT_HEAD
+  WALK_UNIT_HEAD(kWalkSteps, g.n_words)
   for (int step = 0; step < kWalkSteps; ++step) {
-    WALK_STEP_HEAD
+    WALK_STEP_HEAD(g.n_words)
     const uint64_t c = in_range ? fld.C[w] : 0;
     const uint64_t f = c ? Fm[w] : 0;
     const uint64_t co = c ? fld.Coff[w] : 0;
@@ -407,9 +386,9 @@ __global__ void __launch_bounds__(kWalkThreads) k_rd_final(WalkGrid g, const uin
 // The result's values at Roff + rank: x on F, else -u or +u by s.  cap: the floats out holds.
 __global__ void __launch_bounds__(kWalkThreads) k_rd_emit(BandDev X, WalkGrid g, const uint64_t* __restrict__ Fm, RdField fld, const uint64_t* __restrict__ R,
                                                         const uint64_t* __restrict__ Roff, float* __restrict__ out, uint64_t cap) {
-  WALK_UNIT_HEAD
+  WALK_UNIT_HEAD(kWalkSteps, g.n_words)
   for (int step = 0; step < kWalkSteps; ++step) {
-    WALK_STEP_HEAD
+    WALK_STEP_HEAD(g.n_words)
     const uint64_t rm = in_range ? R[w] : 0;
     const uint64_t ro = rm ? Roff[w] : 0;
     const uint64_t c = rm ? fld.C[w] : 0;
@@ -440,8 +419,6 @@ __global__ void __launch_bounds__(kWalkThreads) k_rd_emit(BandDev X, WalkGrid g,
     }
   }
 }
-
-bool good_width(float v) { return v >= 0.0f && std::isfinite(v); }
 
 // K_a = min(ceil(W / h_a) + 1, n_a), the division and the ceil in binary32.
 int64_t reach(float width, float h, uint64_t n) {
@@ -502,17 +479,13 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   if (!ropts) return fail(M2S_ERR_BAD_ARG, "m2s_band_redistance_opts is NULL");
   if (ropts->struct_size != sizeof(m2s_band_redistance_opts))
     return fail(M2S_ERR_BAD_ARG, "m2s_band_redistance_opts.struct_size is not sizeof(m2s_band_redistance_opts)");
-  if (!good_width(ropts->exterior) || !good_width(ropts->interior))
+  if (!good_background(ropts->exterior) || !good_background(ropts->interior))   // a width is judged as a background is
     return fail(M2S_ERR_BAD_ARG, "the widths (%g exterior, %g interior) must be >= 0 and finite", (double)ropts->exterior, (double)ropts->interior);
-  if (fopts) {
-    if (fopts->struct_size != sizeof(m2s_band_field_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_band_field_opts.struct_size is not sizeof(m2s_band_field_opts)");
-    if (!good_width(fopts->background_outside) || !good_width(fopts->background_inside))
-      return fail(M2S_ERR_BAD_ARG, "the backgrounds (%g outside, %g inside) must be >= 0 and finite", (double)fopts->background_outside,
-                  (double)fopts->background_inside);
-  }
+  int rc = band_field_opts_args(fopts);
+  if (rc) return rc;
   if (info_out && info_out->struct_size != sizeof(m2s_band_redistance_info))
     return fail(M2S_ERR_BAD_ARG, "m2s_band_redistance_info.struct_size is not sizeof(m2s_band_redistance_info)");
-  int rc = band_opts_args(opts, "m2s_band_redistance");
+  rc = band_opts_args(opts, "m2s_band_redistance");
   if (rc) return rc;
   m2s_opts o;
   rc = band_call_opts(band, opts, &o);
@@ -525,14 +498,7 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   const float w_out = ropts->exterior, w_in = ropts->interior;
   const float hx = band->grid.cell_size[0], hy = band->grid.cell_size[1], hz = band->grid.cell_size[2];
   const float wx = 1.0f / (hx * hx), wy = 1.0f / (hy * hy), wz = 1.0f / (hz * hz);
-  WalkGrid g;
-  g.total = band->total;
-  g.n_words = band->n_words;
-  g.nx = band->grid.cell_count[0];
-  g.ny = band->grid.cell_count[1];
-  g.nz = band->grid.cell_count[2];
-  g.sj = g.nz;
-  g.si = g.ny * g.nz;
+  const WalkGrid g = walk_grid_of(band->grid.cell_count, band->total, band->n_words);
   const float hs[3] = {hx, hy, hz};
   const uint64_t ns[3] = {g.nx, g.ny, g.nz};
   int64_t k_out[3], k_in[3];
@@ -553,12 +519,12 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   const int n_arrays = one_reach ? 6 : 7;   // S, F, T1, T2, DE (then C), Coff[, DI]
   char* tmp = nullptr;
   char* ubuf = nullptr;
-  char* block = nullptr;
+  BandBlock res;
   M2S_HIP_CHECK(hipMalloc((void**)&tmp, (size_t)n_arrays * b_words));
   auto drop = [&](int code) {
     (void)hipFree(tmp);
     (void)hipFree(ubuf);
-    (void)hipFree(block);
+    res.free();
     return code;
   };
   auto hip_fail = [&](hipError_t e) { return drop(fail(M2S_ERR_HIP, "HIP error: %s", hipGetErrorString(e))); };
@@ -597,7 +563,7 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   hipLaunchKernelGGL(k_rd_frozen, dim3(blocks), dim3(kWalkThreads), 0, s, X.mask, (const uint64_t*)S, g, Fm, d_hdr);
   dilate(s, blocks, g, k_out, Fm, T1, T2, Cm);
   if (!one_reach) dilate(s, blocks, g, k_in, Fm, T1, T2, DI);
-  hipLaunchKernelGGL(k_rd_select, dim3((unsigned)std::min<uint64_t>(1u << 20, (n_words + 255) / 256)), dim3(256), 0, s, (const uint64_t*)Cm,
+  hipLaunchKernelGGL(k_rd_select, dim3(blocks_for(n_words)), dim3(256), 0, s, (const uint64_t*)Cm,
                      (const uint64_t*)DI, (const uint64_t*)S, n_words, Cm);
   e = hipGetLastError();
   if (e == hipSuccess) e = count_and_scan(Cm);
@@ -626,7 +592,7 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   // ---- the sweeps, kRdBatch of them between two reads of their flags ----
   uint64_t run = 0, sweeps = 0;
   uint32_t converged = n_cand == 0 ? 1u : 0u;   // nothing to sweep: the first sweep changes nothing
-  const unsigned sweep_blocks = (unsigned)std::min<uint64_t>(1u << 20, (n_cand + 255) / 256);
+  const unsigned sweep_blocks = blocks_for(n_cand);
   while (!converged && run < max_sweeps) {
     const int batch = (int)std::min<uint64_t>(kRdBatch, max_sweeps - run);
     e = hipMemsetAsync(d_flags, 0, kRdBatch * 4, s);
@@ -661,18 +627,14 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
   if (e != hipSuccess) return hip_fail(e);
   if (n > n_cand) return drop(fail(M2S_ERR_HIP, "internal: the result has %llu cells of %llu candidates", (unsigned long long)n, (unsigned long long)n_cand));
   const uint64_t cap = std::max<uint64_t>(n, 1);   // at least one float
-  e = hipMalloc((void**)&block, 3 * b_words + align_up(cap * 4));
+  e = res.alloc(n_words, cap);
   if (e != hipSuccess) return hip_fail(e);
-  uint64_t* mask = reinterpret_cast<uint64_t*>(block);
-  uint64_t* word_off = reinterpret_cast<uint64_t*>(block + b_words);
-  uint64_t* inside = reinterpret_cast<uint64_t*>(block + 2 * b_words);
-  float* dist = reinterpret_cast<float*>(block + 3 * b_words);
-  e = hipMemsetAsync(dist, 0, 4, s);   // an empty result still has one defined float
-  if (e == hipSuccess) e = hipMemcpyAsync(mask, R, n_words * 8, hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(inside, S, n_words * 8, hipMemcpyDeviceToDevice, s);
+  e = hipMemsetAsync(res.dist, 0, 4, s);   // an empty result still has one defined float
+  if (e == hipSuccess) e = hipMemcpyAsync(res.mask, R, n_words * 8, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(res.inside, S, n_words * 8, hipMemcpyDeviceToDevice, s);
   if (e != hipSuccess) return hip_fail(e);
-  hipLaunchKernelGGL(k_rd_offsets, dim3(blocks), dim3(kWalkThreads), 0, s, (const uint64_t*)R, g, (const uint32_t*)unit_cnt, (const uint64_t*)group_sum, word_off);
-  hipLaunchKernelGGL(k_rd_emit, dim3(blocks), dim3(kWalkThreads), 0, s, X, g, (const uint64_t*)Fm, fld, (const uint64_t*)R, (const uint64_t*)word_off, dist, cap);
+  hipLaunchKernelGGL(k_rd_offsets, dim3(blocks), dim3(kWalkThreads), 0, s, (const uint64_t*)R, g, (const uint32_t*)unit_cnt, (const uint64_t*)group_sum, res.word_off);
+  hipLaunchKernelGGL(k_rd_emit, dim3(blocks), dim3(kWalkThreads), 0, s, X, g, (const uint64_t*)Fm, fld, (const uint64_t*)R, (const uint64_t*)res.word_off, res.dist, cap);
   e = hipGetLastError();
   if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[3], s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -699,21 +661,7 @@ int m2s_band_redistance(const m2s_band* band, const m2s_band_redistance_opts* ro
     info_out->n_open = n_open;
     info_out->n_candidates = n_cand;
   }
-  m2s_band* h = new m2s_band();
-  h->device = band->device;
-  h->grid = band->grid;
-  h->n = n;
-  h->total = g.total;
-  h->n_words = n_words;
-  h->device_bytes = n_words * 24 + n * 4;
-  h->block = block;
-  h->mask = mask;
-  h->word_off = word_off;
-  h->inside = inside;
-  h->dist = dist;
-  h->bg_out = fopts ? fopts->background_outside : w_out;
-  h->bg_in = fopts ? fopts->background_inside : w_in;
-  *out = h;
+  *out = band_adopt(res, band->device, band->grid, n, g.total, n_words, fopts ? fopts->background_outside : w_out, fopts ? fopts->background_inside : w_in);
   return M2S_OK;
 }
 

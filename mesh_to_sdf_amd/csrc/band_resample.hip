@@ -3,24 +3,24 @@
 // tests/band_resample_model.py restates it in numpy.  Nothing sized 4 bytes per point of either grid exists: per 64 target points the
 // result's three index words and the unit counts, per result cell its value.
 //
-// The two passes are band_csg.hip's with one difference: here EVERY target word has work, not one in a few
-// hundred, so a word is not "settled by its own lane" but taken by the whole wave, one after the other: lane t owns bit t, the point
-// L = 64 w + t.  Lane l of a step decomposes the base of word 64 * step + l into (i, j, k) once (band_walk.hip.h); the round of word j
-// takes that base by v_readlane and steps it by t.
+// The two passes are band_csg.hip's on band_walk.hip.h's walk and offsets with one difference: here EVERY target
+// word has work, not one in a few hundred, so a word is not "settled by its own lane" but taken by the whole wave, one after the other.
 //   k_rs_mask    per point: the centre p, the source point q, and whether q is on the source box.  A word whose 64 points are all off the
 //                box (one ballot) is settled as 0 / 0 with no memory read.  Otherwise prepare<MODE> and the K source mask bits; only a
 //                lane with full support fetches its values (band_fetch.hip.h) for the isfinite rule; an inactive lane on the box reads
-//                sX at its SNAP cell.  Two ballots are the result's mask word and sign word.  The unit's popcount goes to unit_cnt and,
-//                by one atomic add, to the sum of its GROUP of units; n_partial and n_nonfinite by one atomic add per wave.
-//   k_scan_tiles the group sums, one workgroup (scan.hip.h); the total is the result's cell count, read by the host with the call's one
-//                synchronisation inside it; the values are then allocated at their true size.
-//   k_rs_emit    the same units: the group's base plus the counts of the units before it in the group, then a wave scan of the result's
-//                popcounts, is the result's word_off; the words with active points are taken as above and lane t computes r again and
-//                stores it at word_off + rank.  r is computed twice rather than kept: where it goes is known only after the scan.
+//                sX at its SNAP cell.  Two ballots are the result's mask word and sign word.  The unit's popcount is published;
+//                n_partial and n_nonfinite go by one atomic add per wave.
+//   k_scan_tiles the group sums; the total is the result's cell count, read by the host with the call's one synchronisation inside it;
+//                the values are then allocated at their true size.
+//   k_rs_emit    the same units: the result's word_off, and lane t of a word with active points computes r again and stores it at
+//                word_off + rank.  r is computed twice rather than kept: where it goes is known only after the scan.
 //   k_rs_open    n_open: band_redistance.hip's neighbour look-ups on the result's mask and sign words, units of 256 words (most are empty).
 // A unit is kRsSteps * 64 words.  With every word at work a wave's unit is a chain of that many rounds of dependent loads, so it is one
 // step: at 256^3 (262 144 words) units of 256 words are one wave per SIMD of the chip.  The groups hold 64 units, so that k_scan_tiles
-// sees as many sums as in a CSG call.  All stores are plain vector stores; the ballot loops are wave-uniform; no LDS but the scan's.
+// sees as many sums as in a CSG call.  The unit and step heads are band_walk.hip.h's; its three offsets helpers (walk_publish,
+// walk_unit_base, walk_word_off) are written out in k_rs_mask and k_rs_emit: hipcc orders the inlined helpers' instructions otherwise,
+// k_rs_mask came out 6 - 7 instructions longer and the TRILINEAR k_rs_emit measured 0.5 - 2 % slower (profiles/band_walk_isa_check.txt).
+// A change to a helper is made here too.  All stores are plain vector stores; the ballot loops are wave-uniform; no LDS but the scan's.
 #include "../../include/m2s.h"
 #include "band_fetch.hip.h"
 #include "band_handle.h"
@@ -39,8 +39,6 @@
 namespace m2s {
 namespace {
 
-constexpr int kRsThreads = 256;
-constexpr int kRsWaves = kRsThreads / 64;
 #ifndef M2S_RS_STEPS   // tools/exp_band_resample.py measures a build with -DM2S_RS_STEPS=4 -DM2S_RS_GROUP=16 (band_csg.hip's units) beside this one
 #define M2S_RS_STEPS 1
 #define M2S_RS_GROUP 64
@@ -114,26 +112,17 @@ __device__ __forceinline__ float rs_value(const GridQuery& q, const BandDev& X, 
   return combine<MODE>(q, p, v[0]) * scale;
 }
 
-#define RS_UNIT_HEAD                                                                                                      \
-  const int lane = threadIdx.x & 63;                                                                                      \
-  const uint64_t unit = (uint64_t)blockIdx.x * kRsWaves + (uint64_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     \
-  const uint64_t w0 = unit * kRsUnit;                                                                                     \
-  if (w0 >= g.n_words) return; /* the whole wave: the last workgroup's spare units */
-
 // q, X: the source grid (iso 0) and handle; t, g: the target.  counters[1] += n_partial, counters[2] += n_nonfinite.
 template <int MODE, bool SIGN>
-__global__ void __launch_bounds__(kRsThreads) k_rs_mask(GridQuery q, BandDev X, RsTarget t, WalkGrid g, uint64_t* __restrict__ out_mask,
+__global__ void __launch_bounds__(kWalkThreads) k_rs_mask(GridQuery q, BandDev X, RsTarget t, WalkGrid g, uint64_t* __restrict__ out_mask,
                                                         uint64_t* __restrict__ out_inside, uint32_t* __restrict__ unit_cnt,
                                                         uint64_t* __restrict__ group_sum, uint64_t* __restrict__ counters) {
   constexpr int K = Corners<MODE>::K;
-  RS_UNIT_HEAD
+  WALK_UNIT_HEAD(kRsSteps, g.n_words)
   uint64_t cnt = 0;
   uint32_t n_partial = 0, n_nonfinite = 0;
   for (int step = 0; step < kRsSteps; ++step) {
-    const uint64_t wb = w0 + (uint64_t)step * 64;   // wave-uniform
-    if (wb >= g.n_words) break;
-    const uint64_t w = wb + lane;
-    const bool in_range = w < g.n_words;
+    WALK_STEP_HEAD(g.n_words)
     WalkIjk base{0, 0, 0};
     if (in_range) base = walk_base(w << 6, g);
     uint64_t rm = 0, ri = 0;
@@ -172,7 +161,7 @@ __global__ void __launch_bounds__(kRsThreads) k_rs_mask(GridQuery q, BandDev X, 
     cnt += (uint64_t)__popcll(rm);
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {   // walk_publish written out: one reduction and one lane-0 block with the two counters
     cnt += __shfl_xor(cnt, o, 64);
     n_partial += __shfl_xor(n_partial, o, 64);
     n_nonfinite += __shfl_xor(n_nonfinite, o, 64);
@@ -187,20 +176,18 @@ __global__ void __launch_bounds__(kRsThreads) k_rs_mask(GridQuery q, BandDev X, 
 
 // group_base: the scanned group sums.  cap: the floats out_dist holds.
 template <int MODE>
-__global__ void __launch_bounds__(kRsThreads) k_rs_emit(GridQuery q, BandDev X, RsTarget t, WalkGrid g, const uint64_t* __restrict__ out_mask,
+__global__ void __launch_bounds__(kWalkThreads) k_rs_emit(GridQuery q, BandDev X, RsTarget t, WalkGrid g, const uint64_t* __restrict__ out_mask,
                                                         const uint32_t* __restrict__ unit_cnt, const uint64_t* __restrict__ group_base,
                                                         uint64_t* __restrict__ out_word_off, float* __restrict__ out_dist, uint64_t cap) {
-  RS_UNIT_HEAD
+  WALK_UNIT_HEAD(kRsSteps, g.n_words)
+  // walk_unit_base and walk_word_off written out (see the head of the file)
   const uint64_t first = unit - unit % kRsGroup;   // the group's first unit: every unit from there to this one exists
   uint64_t before = first + lane < unit ? unit_cnt[first + lane] : 0;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
   uint64_t run = group_base[unit / kRsGroup] + before;
   for (int step = 0; step < kRsSteps; ++step) {
-    const uint64_t wb = w0 + (uint64_t)step * 64;   // wave-uniform
-    if (wb >= g.n_words) break;
-    const uint64_t w = wb + lane;
-    const bool in_range = w < g.n_words;
+    WALK_STEP_HEAD(g.n_words)
     const uint64_t rm = in_range ? out_mask[w] : 0;
     const uint64_t c = (uint64_t)__popcll(rm);
     uint64_t incl = c;
@@ -236,10 +223,10 @@ __device__ __forceinline__ bool rs_bit(const uint64_t* __restrict__ a, uint64_t 
 // counters[3] += the ordered pairs (L active, M an inactive axis neighbour inside the grid, s[M] != s[L]): k_rd_frozen's look-ups.
 __global__ void __launch_bounds__(kWalkThreads) k_rs_open(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ S, WalkGrid g,
                                                         uint64_t* __restrict__ counters) {
-  WALK_UNIT_HEAD
+  WALK_UNIT_HEAD(kWalkSteps, g.n_words)
   uint64_t n_open = 0;
   for (int step = 0; step < kWalkSteps; ++step) {
-    WALK_STEP_HEAD
+    WALK_STEP_HEAD(g.n_words)
     const uint64_t m = in_range ? mask[w] : 0;
     const uint64_t sw = m ? S[w] : 0;
     WalkIjk base{0, 0, 0};
@@ -276,17 +263,15 @@ __global__ void __launch_bounds__(kWalkThreads) k_rs_open(const uint64_t* __rest
 template <int MODE>
 void launch_mask_as(hipStream_t st, unsigned blocks, bool sign, const GridQuery& q, const BandDev& X, const RsTarget& t, const WalkGrid& g,
                     uint64_t* mask, uint64_t* inside, uint32_t* unit_cnt, uint64_t* group_sum, uint64_t* counters) {
-  if (sign) hipLaunchKernelGGL((k_rs_mask<MODE, true>), dim3(blocks), dim3(kRsThreads), 0, st, q, X, t, g, mask, inside, unit_cnt, group_sum, counters);
-  else hipLaunchKernelGGL((k_rs_mask<MODE, false>), dim3(blocks), dim3(kRsThreads), 0, st, q, X, t, g, mask, inside, unit_cnt, group_sum, counters);
+  if (sign) hipLaunchKernelGGL((k_rs_mask<MODE, true>), dim3(blocks), dim3(kWalkThreads), 0, st, q, X, t, g, mask, inside, unit_cnt, group_sum, counters);
+  else hipLaunchKernelGGL((k_rs_mask<MODE, false>), dim3(blocks), dim3(kWalkThreads), 0, st, q, X, t, g, mask, inside, unit_cnt, group_sum, counters);
 }
 
 template <int MODE>
 void launch_emit_as(hipStream_t st, unsigned blocks, const GridQuery& q, const BandDev& X, const RsTarget& t, const WalkGrid& g, const uint64_t* mask,
                     const uint32_t* unit_cnt, const uint64_t* group_base, uint64_t* word_off, float* dist, uint64_t cap) {
-  hipLaunchKernelGGL((k_rs_emit<MODE>), dim3(blocks), dim3(kRsThreads), 0, st, q, X, t, g, mask, unit_cnt, group_base, word_off, dist, cap);
+  hipLaunchKernelGGL((k_rs_emit<MODE>), dim3(blocks), dim3(kWalkThreads), 0, st, q, X, t, g, mask, unit_cnt, group_base, word_off, dist, cap);
 }
-
-bool good_background(float v) { return v >= 0.0f && std::isfinite(v); }
 
 }  // namespace
 
@@ -324,30 +309,20 @@ int m2s_band_resample(const m2s_band* band, const m2s_grid* target, const m2s_ba
       return fail(M2S_ERR_BAD_ARG, "value_scale = %g must be > 0 and finite", (double)ropts->value_scale);
     t.scale = ropts->value_scale;
   }
-  if (fopts) {
-    if (fopts->struct_size != sizeof(m2s_band_field_opts)) return fail(M2S_ERR_BAD_ARG, "m2s_band_field_opts.struct_size is not sizeof(m2s_band_field_opts)");
-    if (!good_background(fopts->background_outside) || !good_background(fopts->background_inside))
-      return fail(M2S_ERR_BAD_ARG, "the backgrounds (%g outside, %g inside) must be >= 0 and finite", (double)fopts->background_outside,
-                  (double)fopts->background_inside);
-  }
+  int rc = band_field_opts_args(fopts);
+  if (rc) return rc;
   if (info_out && info_out->struct_size != sizeof(m2s_band_resample_info))
     return fail(M2S_ERR_BAD_ARG, "m2s_band_resample_info.struct_size is not sizeof(m2s_band_resample_info)");
-  int rc = band_opts_args(opts, "m2s_band_resample");
+  rc = band_opts_args(opts, "m2s_band_resample");
   if (rc) return rc;
   GridQuery qt;
   int ignored = 0;
   rc = grid_query_args(target, nullptr, false, nullptr, &qt, &ignored);   // what m2s_band_create rejects of a grid
   if (rc) return rc;
-  WalkGrid g;
-  g.nx = target->cell_count[0];
-  g.ny = target->cell_count[1];
-  g.nz = target->cell_count[2];
-  g.sj = g.nz;
-  g.si = g.ny * g.nz;
-  if (g.si / g.ny != g.nz) return fail(M2S_ERR_BAD_ARG, "the target grid has 2^36 or more cells");
-  g.total = g.si * g.nx;
-  if (g.total / g.nx != g.si || g.total >= ((uint64_t)1 << 36)) return fail(M2S_ERR_BAD_ARG, "the target grid has 2^36 or more cells");
-  g.n_words = (g.total + 63) / 64;
+  uint64_t total = 0, n_words = 0;
+  rc = band_grid_cells(target, "target grid", &total, &n_words);
+  if (rc) return rc;
+  const WalkGrid g = walk_grid_of(target->cell_count, total, n_words);
   for (int a = 0; a < 3; ++a) {
     t.first[a] = target->first_cell[a];
     t.cs[a] = target->cell_size[a];
@@ -371,18 +346,14 @@ int m2s_band_resample(const m2s_band* band, const m2s_grid* target, const m2s_ba
   rc = resolve_ctx(&o, &c, &st);
   if (rc) return rc;
 
-  const uint64_t n_words = g.n_words;
   const uint64_t n_units = (n_words + kRsUnit - 1) / kRsUnit;          // below 2^24: a grid has fewer than 2^36 cells
   const uint64_t n_groups = (n_units + kRsGroup - 1) / kRsGroup;
-  const unsigned blocks = (unsigned)((n_units + kRsWaves - 1) / kRsWaves);
+  const unsigned blocks = (unsigned)((n_units + kWalkWaves - 1) / kWalkWaves);
   const uint64_t open_units = (n_words + kWalkUnit - 1) / kWalkUnit;
   const unsigned open_blocks = (unsigned)((open_units + kWalkWaves - 1) / kWalkWaves);
-  const size_t b_words = align_up(n_words * 8);
-  char* block = nullptr;    // the result's three index arrays
-  char* values = nullptr;   // the result's values, allocated once the count is known
+  BandBlock res;   // the result: its three index arrays now, its values once the count is known
   auto drop = [&](int code) {
-    (void)hipFree(values);
-    (void)hipFree(block);
+    res.free();
     return code;
   };
   auto hip_fail = [&](hipError_t e) { return drop(fail(M2S_ERR_HIP, "HIP error: %s", hipGetErrorString(e))); };
@@ -393,11 +364,8 @@ int m2s_band_resample(const m2s_band* band, const m2s_grid* target, const m2s_ba
   uint32_t* unit_cnt = ws.take<uint32_t>(n_units);
   uint64_t* group_sum = ws.take<uint64_t>(n_groups);
   if (!d_hdr || !unit_cnt || !group_sum) return fail(M2S_ERR_HIP, "internal: workspace");
-  hipError_t e = hipMalloc((void**)&block, 3 * b_words);
+  hipError_t e = res.alloc_index(n_words);
   if (e != hipSuccess) return hip_fail(e);
-  uint64_t* mask = reinterpret_cast<uint64_t*>(block);
-  uint64_t* word_off = reinterpret_cast<uint64_t*>(block + b_words);
-  uint64_t* inside = reinterpret_cast<uint64_t*>(block + 2 * b_words);
   const BandDev X = dev_of(band);
   hipStream_t s = c.stream;
 
@@ -407,9 +375,9 @@ int m2s_band_resample(const m2s_band* band, const m2s_grid* target, const m2s_ba
   if (e == hipSuccess) e = hipMemsetAsync(group_sum, 0, n_groups * 8, s);
   if (e != hipSuccess) return hip_fail(e);
   const bool sign = X.inside != nullptr;
-  if (mode == M2S_SAMPLE_SNAP) launch_mask_as<M2S_SAMPLE_SNAP>(s, blocks, sign, q, X, t, g, mask, inside, unit_cnt, group_sum, d_hdr);
-  else if (mode == M2S_SAMPLE_TRILINEAR) launch_mask_as<M2S_SAMPLE_TRILINEAR>(s, blocks, sign, q, X, t, g, mask, inside, unit_cnt, group_sum, d_hdr);
-  else launch_mask_as<M2S_SAMPLE_TETRAHEDRAL>(s, blocks, sign, q, X, t, g, mask, inside, unit_cnt, group_sum, d_hdr);
+  if (mode == M2S_SAMPLE_SNAP) launch_mask_as<M2S_SAMPLE_SNAP>(s, blocks, sign, q, X, t, g, res.mask, res.inside, unit_cnt, group_sum, d_hdr);
+  else if (mode == M2S_SAMPLE_TRILINEAR) launch_mask_as<M2S_SAMPLE_TRILINEAR>(s, blocks, sign, q, X, t, g, res.mask, res.inside, unit_cnt, group_sum, d_hdr);
+  else launch_mask_as<M2S_SAMPLE_TETRAHEDRAL>(s, blocks, sign, q, X, t, g, res.mask, res.inside, unit_cnt, group_sum, d_hdr);
   hipLaunchKernelGGL((k_scan_tiles<kScanThreads, uint64_t>), dim3(1), dim3(kScanThreads), 0, s, group_sum, n_groups, d_hdr);
   e = hipGetLastError();
   if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[1], s);
@@ -420,21 +388,20 @@ int m2s_band_resample(const m2s_band* band, const m2s_grid* target, const m2s_ba
   const uint64_t n = hdr[0];
   if (n > g.total) return drop(fail(M2S_ERR_HIP, "internal: the result has %llu cells, the grid %llu", (unsigned long long)n, (unsigned long long)g.total));
   const uint64_t cap = std::max<uint64_t>(n, 1);   // at least one float: a lane's guarded read needs an address
-  e = hipMalloc((void**)&values, align_up(cap * 4));
+  e = res.alloc_values(cap);
   if (e != hipSuccess) return hip_fail(e);
-  float* dist = reinterpret_cast<float*>(values);
 
   // ---- the value pass, then n_open ----
   if (c.timings) e = hipEventRecord(st->ev[2], s);
-  if (e == hipSuccess) e = hipMemsetAsync(dist, 0, 4, s);   // an empty result still has one defined float
+  if (e == hipSuccess) e = hipMemsetAsync(res.dist, 0, 4, s);   // an empty result still has one defined float
   if (e != hipSuccess) return hip_fail(e);
-  if (mode == M2S_SAMPLE_SNAP) launch_emit_as<M2S_SAMPLE_SNAP>(s, blocks, q, X, t, g, mask, unit_cnt, group_sum, word_off, dist, cap);
-  else if (mode == M2S_SAMPLE_TRILINEAR) launch_emit_as<M2S_SAMPLE_TRILINEAR>(s, blocks, q, X, t, g, mask, unit_cnt, group_sum, word_off, dist, cap);
-  else launch_emit_as<M2S_SAMPLE_TETRAHEDRAL>(s, blocks, q, X, t, g, mask, unit_cnt, group_sum, word_off, dist, cap);
+  if (mode == M2S_SAMPLE_SNAP) launch_emit_as<M2S_SAMPLE_SNAP>(s, blocks, q, X, t, g, res.mask, unit_cnt, group_sum, res.word_off, res.dist, cap);
+  else if (mode == M2S_SAMPLE_TRILINEAR) launch_emit_as<M2S_SAMPLE_TRILINEAR>(s, blocks, q, X, t, g, res.mask, unit_cnt, group_sum, res.word_off, res.dist, cap);
+  else launch_emit_as<M2S_SAMPLE_TETRAHEDRAL>(s, blocks, q, X, t, g, res.mask, unit_cnt, group_sum, res.word_off, res.dist, cap);
   e = hipGetLastError();
   if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[3], s);
   if (e != hipSuccess) return hip_fail(e);
-  hipLaunchKernelGGL(k_rs_open, dim3(open_blocks), dim3(kWalkThreads), 0, s, (const uint64_t*)mask, (const uint64_t*)inside, g, d_hdr);
+  hipLaunchKernelGGL(k_rs_open, dim3(open_blocks), dim3(kWalkThreads), 0, s, (const uint64_t*)res.mask, (const uint64_t*)res.inside, g, d_hdr);
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(&hdr[3], d_hdr + 3, 8, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && c.timings) e = hipEventRecord(st->ev[4], s);
@@ -458,22 +425,7 @@ int m2s_band_resample(const m2s_band* band, const m2s_grid* target, const m2s_ba
     info_out->n_nonfinite = hdr[2];
     info_out->n_open = hdr[3];
   }
-  m2s_band* h = new m2s_band();
-  h->device = band->device;
-  h->grid = *target;
-  h->n = n;
-  h->total = g.total;
-  h->n_words = n_words;
-  h->device_bytes = n_words * 24 + n * 4;
-  h->block = block;
-  h->block2 = values;
-  h->mask = mask;
-  h->word_off = word_off;
-  h->inside = inside;
-  h->dist = dist;
-  h->bg_out = bg_out;
-  h->bg_in = bg_in;
-  *out = h;
+  *out = band_adopt(res, band->device, *target, n, g.total, n_words, bg_out, bg_in);
   return M2S_OK;
 }
 
