@@ -19,8 +19,12 @@ struct alignas(32) TriRec {
   uint32_t index;      // triangle index in Topology::get_triangles order (tie-break for Rtree)
   float cx, cy, cz;
   float pad0;
-  // edge vectors exactly as geo.rs computes them per call (b.sub(a), c.sub(a), c.sub(b)): they are
-  // the same for all 64 lanes, so they are formed once at build time instead of on the VALU
+  // edge vectors exactly as geo.rs computes them per call (b.sub(a), c.sub(a), c.sub(b)): where a wave tests ONE triangle — the seed
+  // evaluation, the wave-wide leaf evaluation (walk.hip.h eval_triangle_leaf: DEFER 0, the direct half of DEFER 2), the lane walk, the brute
+  // force — they are the same for all 64 lanes and arrive as scalar operands, so they are formed once at build time instead of on the VALU.
+  // The queued pairs of the packet walk (distance.hip defer_flush), every lane its own triangle, do NOT read them for the unsigned distance:
+  // a row is a 64-lane gather there, and the lanes form the edges from the vertices (geo.hip.h point_triangle_pair_dist2, the same bits);
+  // the Normal fold's and nearest-with-normal's queued pairs still gather the rows, for their fourth components:
   // the 4th components carry the raw normal ab x ac (geo.rs:60-64), same arithmetic as the reference, formed once
   float abx, aby, abz, nrx;
   float acx, acy, acz, nry;

@@ -334,6 +334,25 @@ __device__ __forceinline__ DeferQueue defer_begin(unsigned long long* lds) {
   }
   return dq;
 }
+// What the unsigned evaluation of a queued pair reads of its triangle: bytes [0, 48) of the TriRec, the three vertices and the class.  Every
+// lane has its own triangle here, so each 16-byte row of the record is a 64-lane gather; the stored edge rows, which the wave-wide forms get
+// as scalar operands for nothing, would be three more of them, and the compiler used to sink two of the six into the regions that use them,
+// each behind a wait of its own: up to three L2 round trips in a row per batch.  pair_verts_request issues the three loads together, ordinary
+// cached loads; pair_verts_arrive, placed behind the owner fetches, is an empty statement that takes the ten words as operands: no load can
+// be moved past it, and the one wait in front of it covers the batch.  The edges are formed on the VALU (geo.hip.h point_triangle_pair_dist2).
+// The Normal fold and nearest-with-normal need the edge rows' fourth components (the raw normal) and keep gathering the whole record.
+struct PairVerts {
+  f3 a, b, c;
+  uint32_t cls;
+};
+__device__ __forceinline__ PairVerts pair_verts_request(const TriRec* tris, uint32_t t) {
+  static_assert(offsetof(TriRec, cls) == 12 && offsetof(TriRec, bx) == 16 && offsetof(TriRec, cx) == 32, "a | cls, b, c in the first three rows");
+  const TriRec& r = tris[t];   // a | cls as one dwordx4, b and c as dwordx3: no register for the words nobody reads
+  return {mk3(r.ax, r.ay, r.az), mk3(r.bx, r.by, r.bz), mk3(r.cx, r.cy, r.cz), r.cls};
+}
+__device__ __forceinline__ void pair_verts_arrive(PairVerts& pr) {
+  asm volatile("" : "+v"(pr.a.x), "+v"(pr.a.y), "+v"(pr.a.z), "+v"(pr.cls), "+v"(pr.b.x), "+v"(pr.b.y), "+v"(pr.b.z), "+v"(pr.c.x), "+v"(pr.c.y), "+v"(pr.c.z));
+}
 // Evaluates up to 64 queued pairs (all of them when fewer are left) and refreshes the lanes' results from their slots.
 template <int MODE>
 __device__ __forceinline__ void defer_flush(const DeviceMesh& mesh, f3 p, DeferQueue& dq, Best<MODE>& best) {
@@ -343,9 +362,14 @@ __device__ __forceinline__ void defer_flush(const DeviceMesh& mesh, f3 p, DeferQ
   const bool valid = lane < take;
   const uint32_t e = valid ? dq.q[(dq.head + lane) & 127u] : 0u;
   const uint32_t v = e & 63u, t = e >> 6, va = owner_addr(e);
+  PairVerts pr = {};
+  if (MODE == MODE_UNSIGNED) pr = pair_verts_request(mesh.tris, t);
   const f3 pv = mk3(owner_fetch(va, p.x), owner_fetch(va, p.y), owner_fetch(va, p.z));
+  if (MODE == MODE_UNSIGNED) pair_verts_arrive(pr);
   Best<MODE> one;
-  eval_triangle<MODE>(one, pv, mesh.tris[t]);
+  // (a NaN d2 goes to the LDS minimum as it is: its bits lie above +inf's, with either sign, and never win — what fminf made of it before)
+  if (MODE == MODE_UNSIGNED) one.d2 = point_triangle_pair_dist2(pv, pr.a, pr.b, pr.c, pr.cls);
+  else eval_triangle<MODE>(one, pv, mesh.tris[t]);
   if (valid) {
     if (MODE == MODE_NEAREST_NORMAL) atomicMin(&reinterpret_cast<unsigned long long*>(dq.slot)[v], defer_key<MODE>(one));
     else {

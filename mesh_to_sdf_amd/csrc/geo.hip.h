@@ -145,6 +145,31 @@ M2S_HD float point_triangle_dist2(f3 p, f3 a, f3 b, f3 c, const TriEdges& e, uin
   return dot3(d, d);
 }
 
+// The same d2 for a (point, triangle) PAIR per lane — the packet walk's queued evaluations (distance.hip defer_flush), where every lane holds
+// its own triangle and `cls` is NOT wave-uniform.  From the vertices alone: ab = b - a, ac = c - a, bc = c - b are formed here, the three f32
+// subtractions tri_edges makes at build time, so the bits are those of point_triangle_dist2 with the stored edges (a gathered edge row is a
+// 1 KiB fetch per wave to spare three v_sub_f32).  The regular body runs for every lane, unmasked; only if some lane of the wave holds a
+// degenerate triangle does the cold block behind it run, for all lanes select-style, and its result replaces the regular one in the lanes
+// that are degenerate (what the regular body made of them — 0 / 0 — is dropped unread).  The hot path pays one compare and one branch.
+M2S_HD bool pair_any_lane(bool x) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return __ballot(x) != 0ull;
+#else
+  return x;
+#endif
+}
+M2S_HD float point_triangle_pair_dist2(f3 p, f3 a, f3 b, f3 c, uint32_t cls) {
+  const f3 ab = sub3(b, a), ac = sub3(c, a);
+  f3 q = closest_point_regular_tail(closest_point_regular_head(p, a, b, c, ab, ac), a, b, c, ab, ac, sub3(c, b));
+  if (pair_any_lane(cls != TRI_REGULAR)) {
+    const f3 qs = closest_point_segment(p, a, sel3(cls == TRI_SEG_AC, ac, ab));   // geo.rs:77-85
+    const f3 qd = sel3(cls == TRI_POINT, a, qs);                                   // geo.rs:74-76
+    q = sel3(cls != TRI_REGULAR, qd, q);
+  }
+  const f3 d = sub3(p, q);
+  return dot3(d, d);
+}
+
 // geo.rs:43-56 — returns d2 and whether the reference's signed distance is positive
 // (direction . ((b-a) x (c-a)) > 0, normal not normalised; == 0 counts as negative).
 M2S_HD float point_triangle_dist2_signed(f3 p, f3 a, f3 b, f3 c, const TriEdges& e, uint32_t cls, bool* positive) {

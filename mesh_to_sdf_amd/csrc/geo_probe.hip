@@ -1,5 +1,5 @@
 // geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h, sample.hip.h, voxel.hip.h, band.hip.h and cut_size.hip.h, for CPU unit tests only
-// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py, tests/test_narrow_band_cpu.py, tests/test_cut_size_cpu.py, tests/test_walk_leaf_count_cpu.py).  Not linked into libm2s_hip.so.
+// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py, tests/test_narrow_band_cpu.py, tests/test_cut_size_cpu.py, tests/test_walk_leaf_count_cpu.py, tests/test_pair_eval_cpu.py).  Not linked into libm2s_hip.so.
 #include "geo.hip.h"
 #include "ray.hip.h"
 #include "sample.hip.h"
@@ -13,6 +13,17 @@ extern "C" {
 float probe_dist2(const float* p, const float* a, const float* b, const float* c) {
   f3 A = mk3(a[0], a[1], a[2]), B = mk3(b[0], b[1], b[2]), Cc = mk3(c[0], c[1], c[2]);
   return point_triangle_dist2(mk3(p[0], p[1], p[2]), A, B, Cc, tri_edges(A, B, Cc), tri_class(A, B, Cc));
+}
+// n cases of 3 floats each: want[i] = point_triangle_dist2 with the edges of tri_edges (what the records store), got[i] = the queued pairs'
+// evaluation from the vertices alone
+void probe_pair_dist2_n(size_t n, const float* p, const float* a, const float* b, const float* c, float* want, float* got) {
+  for (size_t i = 0; i < n; ++i) {
+    const f3 P = mk3(p[3 * i], p[3 * i + 1], p[3 * i + 2]), A = mk3(a[3 * i], a[3 * i + 1], a[3 * i + 2]);
+    const f3 B = mk3(b[3 * i], b[3 * i + 1], b[3 * i + 2]), Cc = mk3(c[3 * i], c[3 * i + 1], c[3 * i + 2]);
+    const uint32_t cls = tri_class(A, B, Cc);
+    want[i] = point_triangle_dist2(P, A, B, Cc, tri_edges(A, B, Cc), cls);
+    got[i] = point_triangle_pair_dist2(P, A, B, Cc, cls);
+  }
 }
 float probe_dist2_signed(const float* p, const float* a, const float* b, const float* c, int* positive) {
   f3 A = mk3(a[0], a[1], a[2]), B = mk3(b[0], b[1], b[2]), Cc = mk3(c[0], c[1], c[2]);
