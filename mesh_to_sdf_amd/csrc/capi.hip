@@ -350,6 +350,9 @@ static int stats_end(hipStream_t stream, const unsigned long long* d_stats) {
   if (h[0] && h[1] && h[2])
     fprintf(stderr, "[m2s stats]   lanes served: %.1f of 64 want the node per node test, %.1f reach the leaf per pre-test, %.1f reach the triangle per exact evaluation (queued pairs per packet: %.0f)\n",
             (double)h[75] / h[0], (double)h[76] / h[1], (double)h[77] / h[2], (double)h[77] / w);
+  if (h[120])   // (M2S_SEED_SKIP=0: the pre-test is run and counted; otherwise the walk passes over the seed and the last figure is 0)
+    fprintf(stderr, "[m2s stats]   the packet's seed triangle met again by the walk: %.2f times per packet, %.1f lanes per packet want its leaf then ((lane, seed) pairs a queueing walk would form), %.1f of them pass the pre-test and are evaluated a second time\n",
+            h[120] / w, h[78] / w, h[79] / w);
   {  // work units (node tests + pre-tests + 4 x exact evaluations) per packet, in octaves
     char line[512] = "";
     for (int o = 0; o < 24; ++o)
@@ -1904,6 +1907,9 @@ int m2s_debug_grid_walk_choice_slab(const m2s_grid* grid, const m2s_opts* opts, 
 // Test hook: launches of the packet walk's gather-ahead form (k_packet's GA variants) by this process so far — tests/test_gpu_gather_ahead.py checks
 // that M2S_GATHER_AHEAD really selects the kernel it names.
 uint64_t m2s_debug_gather_ahead_launches(void) { return gather_ahead_launches(); }
+// ... and of packet walks (k_packet's plain forms, k_packet_group) told to pass over their seed triangle — tests/test_gpu_seed_skip.py checks that
+// M2S_SEED_SKIP reaches the launches.
+uint64_t m2s_debug_seed_skip_launches(void) { return seed_skip_launches(); }
 int m2s_debug_grid_walk_choice(const m2s_grid* grid, size_t n_tris, size_t n_nodes, uint32_t leaf_max, int algorithm, uint32_t out[8]) {
   return m2s_debug_grid_walk_choice_slab(grid, nullptr, n_tris, n_nodes, leaf_max, algorithm, out);
 }

@@ -284,6 +284,7 @@ hipError_t select_flagged_indices(void* tmp, size_t& bytes, const uint8_t* flags
 void warm_bvh(hipStream_t st);
 void warm_sign(hipStream_t st);
 void warm_distance(hipStream_t st);
+uint64_t seed_skip_launches();     // test hook: launches of packet walks that pass over their seed so far (distance.hip, M2S_SEED_SKIP)
 uint64_t gather_ahead_launches();   // test hook: launches of k_packet's gather-ahead form so far (distance.hip)
 void warm_seeds(hipStream_t st);
 void warm_cut(hipStream_t st);
@@ -340,7 +341,13 @@ struct SplitCtl {
   uint32_t* acc = nullptr;          // per slot: 64 x d2 bits, then (Normal fold) 64 x d2pos bits — merged with atomic minima
   uint4* items = nullptr;           // lists of the follow-up rounds, cap_items each: (packet, first byte, end byte, slot)
   uint32_t cap_slots = 0, cap_items = 0;
-  uint32_t grace = 0;               // work units a walk does before it first looks at the flag (rounds: and between flag and suspension)
+  union {
+    uint32_t grace = 0;             // work units a walk does before it first looks at the flag (rounds: and between flag and suspension)
+    // A launch of k_packet that does NOT split (cnt == nullptr; nothing else of this struct is read then) carries its one launch word in the
+    // same four bytes under its own name: what is ORed into the seed's slot, 0 or 0xffffffff = "none" (M2S_SEED_SKIP; distance.hip plain_ctl).
+    // The plain forms share their argument list with the split forms, whose symbols and descriptors stay what they were: no new argument.
+    uint32_t plain_seed_none;
+  };
   uint32_t patience_q8 = 0;         // k_packet: (ordinary packet times a walk may outlast the flag) / (rounds before the flag), in 1/256
   uint32_t idle_below = 0;          // 1: forced — the stamps are all time 0 (flags up, no patience)
   uint32_t emit_min = 0, emit_max = 0;   // bytes of records: a suspended walk hands over the surviving subtrees of this size range

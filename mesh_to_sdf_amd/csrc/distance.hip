@@ -127,6 +127,11 @@ __device__ __forceinline__ uint32_t stab_count_dense(const DeviceMesh& mesh, f3 
 struct WalkStats {
   uint32_t box = 0, ext = 0, leaf = 0, pruned = 0, slab = 0, sphere = 0, pairs = 0;
   uint32_t node_lanes = 0, pre_lanes = 0;   // lanes whose bound reaches the node / that take part in a leaf's pre-test by that measure
+  // the packet's seed triangle as the walk meets it again (walk_span SEEDED): its slot — set by k_packet whether or not the walk passes over
+  // it —, how often the walk met it, the lanes whose bound reached its leaf then (the (lane, seed) pairs the DEFER 3 walk would queue) and,
+  // where it was not passed over, how many of those passed the pre-test (and were evaluated a second time)
+  uint32_t seed = 0xffffffffu, seed_met = 0, seed_lanes = 0, seed_passed = 0;
+  bool seed_inside = false;   // on the way down inside the seed's collapsed leaf
 };
 
 // ---- split walk -------------------------------------------------------------------------------
@@ -167,6 +172,10 @@ struct WalkStats {
 // from the scalar to the vector unit, "may be clobbered", behind the cut list's cold miss: + 20 %).  Every string starts with
 // s_nop 4: the compiler does not see into it, and an address that has just come out of a spill lane (a VALU write of an SGPR) needs
 // five wait states before a memory instruction may read it — without them a follow-up round loaded its flag from garbage addresses.
+// The SplitCtl of a launch that does not split: no counters (split_arm arms nothing, and only the split forms call it), and the plain forms' one
+// launch word under its own name (common.h SplitCtl::plain_seed_none, the bytes of `grace`, which a plain form must never read as such).
+static_assert(offsetof(SplitCtl, plain_seed_none) == offsetof(SplitCtl, grace) && sizeof(SplitCtl) == 64, "the word shares grace's bytes: the split forms' argument list is unchanged");
+inline SplitCtl plain_ctl(uint32_t seed_none) { SplitCtl ctl{}; ctl.plain_seed_none = seed_none; return ctl; }
 constexpr uint32_t SPLIT_CHECK_EVERY = 64;
 constexpr uint32_t SPLIT_CONTINUATION = 0x80000000u;   // item tag (with the slot): a suspended packet, not a subtree
 struct SplitState {
@@ -482,10 +491,17 @@ __device__ __forceinline__ bool pretest_consume(const DeviceMesh& mesh, f3 p, fl
 // records and pre-test planes through scalar loads, a subtree left when no lane's bound reaches it.  BUDGET: the walk may stop
 // early (sp.suspended, off = the first record not yet looked at).  EMIT: a suspended walk — surviving subtrees of em.min_bytes ..
 // em.max_bytes are written to the next round's list instead of being entered.
-template <int MODE, bool STATS, bool BUDGET, bool EMIT = false, bool HANDOVER = false, int DEFER = 0, bool GA = false>
+// SEEDED: `seed` is the triangle slot (the index space of nr.tri) that the caller has ALREADY evaluated for every lane, ungated — the packet's
+// seed; 0xffffffff: none.  The walk passes over that leaf triangle: every fold of Best<MODE> is an idempotent minimum (fminf; two fminf and
+// an OR of `nan`; the lexicographic minimum of (d2, index)), so evaluating the seed's arithmetic a second time cannot change a bit, and it
+// was what the lanes whose nearest triangle IS the seed did — the pre-test passes for exactly those.  The tree comes from the cut list and
+// the seed is k_cut's witness, so the walk always reaches the seed's leaf.  `seed` is wave-uniform (an SGPR).  The split forms (BUDGET, EMIT)
+// start from handed-over minima, sit at the SGPR cap and are instantiated without it: their code is what it was.
+template <int MODE, bool STATS, bool BUDGET, bool EMIT = false, bool HANDOVER = false, int DEFER = 0, bool GA = false, bool SEEDED = false>
 __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float slack, Best<MODE>& best, float& thr, uint32_t& off,
                                           uint32_t end, WalkStats& st, SplitState& sp, EmitState* emp = nullptr, DeferQueue* dqp = nullptr,
-                                          PretestAhead* gap = nullptr) {
+                                          PretestAhead* gap = nullptr, uint32_t seed = 0xffffffffu) {
+  static_assert(!(SEEDED && (BUDGET || EMIT)), "the split forms pass no seed");
   // The walk addresses NodeExt by BYTE offset (its skip links are stored that way): the scalar loads then take
   // the offset operand directly and the loop carries no address arithmetic.
   // `off` is wave-uniform at every caller (a v_readlane / v_readfirstlane result) and stays so: it only ever takes nr.skip or off + NB.
@@ -523,6 +539,19 @@ __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float sl
       // first time always: leaf_cursor_steps of geo.hip.h, held against cnt = (nr.skip - off + NB) / (2 NB) by
       // tests/test_walk_leaf_count_cpu.py.  No division, no count and no guard in front of the loop.
       uint32_t tri = (uint32_t)nr.tri, cur = below;
+      // The seed's leaf (SEEDED).  ONE test per leaf — seed_in_leaf of geo.hip.h: a subtraction, a multiplication, a subtraction, a compare and
+      // a branch — is all the node loop pays; the leaf loops below are the same instructions as without a seed.  Where the seed IS one of this
+      // leaf's triangles: a single-triangle leaf is passed over; a collapsed leaf is entered like an interior node — the records below it are a
+      // tree of their own, every one marked as the (smaller) leaf it would be (bvh.hip: tri = first wherever cnt <= leaf_max) —, so its other
+      // triangles are met as leaves of their own and the seed alone is left out.  That costs the node tests on the seed's path, two for a leaf of
+      // two triangles, and saves the seed's queued pairs, pre-tests and second evaluations.  Either way the next record is `below`.
+      if (SEEDED && seed_in_leaf(seed, tri, below, nr.skip, NB)) {
+        // (counted where the walk meets the seed's leaf as the tree has it, not again on the way down inside it)
+        if (STATS && !st.seed_inside) { ++st.seed_met; st.seed_lanes += (uint32_t)__popcll(__ballot(!(ed2 > thr))); }
+        if (STATS) st.seed_inside = below != nr.skip;
+        off = below;
+        continue;
+      }
       if (DEFER == 3) {
         // GA: the batch pending from an earlier leaf is taken first — one scalar branch per leaf is all the node loop pays —, one issued by
         // this leaf when the ring fills again inside it (long leaves; rare); the ring never holds 128 pairs.
@@ -563,6 +592,12 @@ __device__ __forceinline__ void walk_span(const DeviceMesh& mesh, f3 p, float sl
         } while (cur <= nr.skip);
       } else
       do {
+        if (STATS && tri == st.seed) {   // (the walk has not passed over the seed — M2S_SEED_SKIP=0: what becomes of it)
+          const bool want = !(ed2 > thr);
+          ++st.seed_met;
+          st.seed_lanes += (uint32_t)__popcll(__ballot(want));
+          st.seed_passed += (uint32_t)__popcll(__ballot(want & !(planes_dist2(p, record_at(mesh.planes, tri)) > thr)));
+        }
         if (STATS) { ++st.ext; st.pre_lanes += (uint32_t)__popcll(__ballot(!(ed2 > thr))); }
         if (BUDGET) ++sp.units;
         const TriPlanes tp = record_at(mesh.planes, tri);   // scalar: small, needed for every leaf triangle
@@ -730,7 +765,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     // Among 3, 7 and 10 s_nop nothing is measured to matter (the headline is level; blob-1M's 0.04 ms between 3 and 10 is one series of four
     // runs, two of its spreads): what IS measured is that the load must not stand in the first bytes of a line.  Ten are seven issue slots per
     // packet more than three; the position the parent had was kept so that the A/B against it compares the loop and not its placement.
-    if (GRID && MODE == MODE_UNSIGNED && SIGN == SIGN_GRID_PLANE && DEFER == 3 && GA) asm volatile(".rept 10\n s_nop 0\n .endr");
+    if (GRID && MODE == MODE_UNSIGNED && SIGN == SIGN_GRID_PLANE && DEFER == 3 && GA) asm volatile(".rept 5\n s_nop 0\n .endr");
     const float scale = fmaxf(mesh_scale(mesh), fmaxf(fabsf(p.x), fmaxf(fabsf(p.y), fabsf(p.z))));
     const float slack = 4.0e-6f * scale + (MODE == MODE_NORMAL_FOLD ? 2.5e-6f : 0.0f);
     SplitState sp;
@@ -760,6 +795,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       // The whole 64-byte record with ONE vector load — lane l takes word l.
       cw = cut.lists[(size_t)cb * CUT_WORDS + ((uint32_t)lane & 15u)];
     }
+    // The slot of the triangle evaluated here for every lane: the walk passes over it (walk_span SEEDED).  The launch's word (SplitCtl::plain_seed_none)
+    // is 0xffffffff where it shall not (M2S_SEED_SKIP=0) — ORed in, the slot becomes "none", the parent's walk — and 0 where it shall.
+    uint32_t seed_slot = 0xffffffffu;
     if (seed_in != nullptr) {
       // seed: a triangle near this packet's centre, from the seed pass
       uint32_t sidx = packet;
@@ -777,6 +815,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       const uint32_t slot = __builtin_amdgcn_readfirstlane(min(seed_in[sidx], mesh.n_tris - 1));
       const TriRec tr = record_at(mesh.tris, slot);
       eval_triangle<MODE>(best, p, tr);
+      seed_slot = slot;
     } else {
       // seed: greedy descent towards the packet's first point, evaluate that leaf for every lane
       const f3 c = {__shfl(p.x, 0), __shfl(p.y, 0), __shfl(p.z, 0)};
@@ -795,7 +834,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       }
       const TriRec tr = mesh.tris[nr.tri];
       eval_triangle<MODE>(best, p, tr);
+      seed_slot = (uint32_t)__builtin_amdgcn_readfirstlane(nr.tri);   // (the descent is wave-uniform: towards lane 0's point)
     }
+    if (STATS) st.seed = seed_slot;
+    if (!SPLIT) seed_slot |= split.plain_seed_none;
     if (cut.lists != nullptr) {
       // The list word's first use.  Lanes 1..15 decode their range side by side (eight VALU instructions for the whole list), and the
       // range loop below fetches (start, end) of range k from lane 1 + k with two v_readlane: no load and no scalar arithmetic per range.
@@ -824,7 +866,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         off = (uint32_t)__builtin_amdgcn_readlane((int)cut_off_v, (int)(1u + range));
         const uint32_t end = (uint32_t)__builtin_amdgcn_readlane((int)cut_end_v, (int)(1u + range));
         if (STATS) st_rbytes += end - off;
-        walk_span<MODE, STATS, SPLIT, false, SPLIT, DEFER, GA>(mesh, p, slack, best, thr, off, end, st, sp, nullptr, &dq, &ga);
+        walk_span<MODE, STATS, SPLIT, false, SPLIT, DEFER, GA, !SPLIT>(mesh, p, slack, best, thr, off, end, st, sp, nullptr, &dq, &ga, seed_slot);
       }
       // (a batch still pending: with the bound the walk ended on, as defer_drain's own)
       if (GA && ga.pending) pretest_consume<MODE>(mesh, p, prune_bound(best.d2, slack), dq, best, ga);
@@ -851,6 +893,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     atomicAdd(&mesh.stats[75], (unsigned long long)st.node_lanes);
     atomicAdd(&mesh.stats[76], (unsigned long long)st.pre_lanes);
     atomicAdd(&mesh.stats[77], (unsigned long long)st.pairs);
+    atomicAdd(&mesh.stats[78], (unsigned long long)st.seed_lanes);
+    atomicAdd(&mesh.stats[79], (unsigned long long)st.seed_passed);
+    atomicAdd(&mesh.stats[120], (unsigned long long)st.seed_met);
     unsigned long long* q = mesh.stats + 8 + 8 * st_band;
     atomicAdd(&q[0], (unsigned long long)st.box);
     atomicAdd(&q[1], (unsigned long long)st.ext);
@@ -920,7 +965,8 @@ __global__ __launch_bounds__(TOP_SUBTREES) void k_tree_top(DeviceMesh mesh, uint
 template <int MODE, int SIGN>
 __global__ __launch_bounds__(64 * GROUP_MAX_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_packet_group(
     DeviceMesh mesh, GridParams g, const uint32_t* __restrict__ plane, float* __restrict__ out, int* __restrict__ err, uint32_t n_packets,
-    const uint32_t* __restrict__ seed_in, uint32_t seed_shift, uint32_t seed_ny, uint32_t seed_nz, uint32_t bx_off, const uint2* __restrict__ top, PeerOut peers) {
+    const uint32_t* __restrict__ seed_in, uint32_t seed_shift, uint32_t seed_ny, uint32_t seed_nz, uint32_t bx_off, const uint2* __restrict__ top, PeerOut peers,
+    uint32_t seed_none) {   // 0: the walks pass over the seed's leaf triangle, 0xffffffff: they evaluate it again (k_packet)
   static_assert(MODE == MODE_UNSIGNED || MODE == MODE_NORMAL_FOLD, "grid modes");
   const int lane = threadIdx.x & 63;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -958,7 +1004,7 @@ __global__ __launch_bounds__(64 * GROUP_MAX_WAVES) __attribute__((amdgpu_waves_p
       uint32_t off = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.x);
       const uint32_t end = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.y);
       if (off >= end) continue;
-      walk_span<MODE, false, false, false, false, 3>(mesh, p, slack, best, thr, off, end, st, sp, nullptr, &dq);
+      walk_span<MODE, false, false, false, false, 3, false, true>(mesh, p, slack, best, thr, off, end, st, sp, nullptr, &dq, nullptr, slot | seed_none);
     }
     defer_drain<MODE>(mesh, p, slack, dq, best);
     // this wave's minima (the seed's among them) join the group's
@@ -1385,6 +1431,17 @@ struct PacketArgs {
 // It is taken where it is asked for (1) and, left to the automatic setting (-1), by the forms it was measured to win on: the grid walk of the
 // unsigned distance (the headline, configs 2 and 4) and the queries' walk with the three-ray sign (config 3; Bvh(Raycast) and RtreeBvh both run
 // it).  The Normal fold and the nearest-with-normal walk keep the plain form until they are measured (profiles/gather_ahead_ab.txt).
+// M2S_SEED_SKIP: what the packet kernels OR into their seed's slot (k_packet `seed_none`): 0 — the walk passes over the seed's leaf triangle,
+// which the prologue has evaluated for every lane — where the knob says 1 or is left to the automatic setting (-1: every packet form,
+// profiles/seed_skip_ab.txt), 0xffffffff ("none": the walk evaluates it again, the same bits) where it says 0.
+std::atomic<uint64_t> g_seed_skip_launches{0};   // test hook (m2s_debug_seed_skip_launches): launches whose walks pass over their seed so far
+static uint32_t seed_none_word() { return tuning().seed_skip != 0 ? 0u : 0xffffffffu; }
+// ... for a launch of a plain k_packet form or of the packet groups (counted: the split forms never pass over it)
+static uint32_t seed_none_word_counted() {
+  const uint32_t w = seed_none_word();
+  if (w == 0u) g_seed_skip_launches.fetch_add(1, std::memory_order_relaxed);
+  return w;
+}
 std::atomic<uint64_t> g_gather_ahead_launches{0};   // test hook (m2s_debug_gather_ahead_launches): launches of a GA form so far
 template <bool GRID, int MODE, int SIGN>
 void launch_packet(hipStream_t st, const PacketArgs& a, int defer, int gather_ahead_knob) {
@@ -1395,7 +1452,7 @@ void launch_packet(hipStream_t st, const PacketArgs& a, int defer, int gather_ah
   const auto launch = [&](auto stats, auto split, auto form, auto ahead) {
     hipLaunchKernelGGL((k_packet<GRID, MODE, SIGN, decltype(stats)::value, decltype(split)::value, decltype(form)::value, decltype(ahead)::value>), dim3(grid_blocks), dim3(64), 0, st,
                        a.mesh, a.g, a.qsorted, a.perm, a.n_q, a.plane, a.out, a.err, a.n_packets, a.seed_in, a.seed_shift, a.seed_ny, a.seed_nz, a.seed_lattice,
-                       a.cut, a.peers, a.split);
+                       a.cut, a.peers, decltype(split)::value ? a.split : plain_ctl(seed_none_word_counted()));
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
@@ -1438,6 +1495,7 @@ void launch_split_rounds(hipStream_t st, const DeviceMesh& mesh, const GridParam
 
 }  // namespace
 uint64_t gather_ahead_launches() { return g_gather_ahead_launches.load(std::memory_order_relaxed); }
+uint64_t seed_skip_launches() { return g_seed_skip_launches.load(std::memory_order_relaxed); }
 namespace {
 uint32_t host_brick_count(const GridParams& g) { return brick_counts(g).padded; }
 
@@ -1684,7 +1742,7 @@ int launch_grid_walk(hipStream_t st, const DeviceMesh& mesh, const GridParams& g
         const uint32_t per = 8u << XCD_RUN_LOG, grid_blocks = ((packets + per - 1) / per) * per;        // as launch_packet: whole runs per XCD (xcd_remap)
         const size_t lds = ((size_t)ch.group_waves * 256u + DeferLayout<MODE>::SLOT_WORDS) * 4u;
         hipLaunchKernelGGL((k_packet_group<MODE, SIGN>), dim3(grid_blocks), dim3(64 * ch.group_waves), lds, st, mesh, g, plane, d_out, d_err, packets,
-                           a.seed_in, a.seed_shift, a.seed_ny, a.seed_nz, bx_off, plan.group_top, pz);
+                           a.seed_in, a.seed_shift, a.seed_ny, a.seed_nz, bx_off, plan.group_top, pz, seed_none_word_counted());
         break;
       }
       case GridWalkChoice::PACKET:

@@ -276,4 +276,15 @@ M2S_HD uint32_t leaf_cursor_steps(uint32_t off, uint32_t skip, uint32_t nb) {
   return n;
 }
 
+// The packet walk's seed test (distance.hip walk_span, SEEDED): is triangle slot `seed` one of the leaf's triangles tri, tri + 1, ...?  `below`
+// is the record behind the leaf's own and `skip` the end of its subtree, so the leaf loop's cursor (leaf_cursor_steps) stands at
+// below + 2 nb k for its k-th triangle and the leaf holds (skip - below) / (2 nb) + 1 of them.  In 32-bit arithmetic that wraps, without a
+// range check in front: a seed below `tri`, or "none" (0xffffffff), gives 2^32 - 2 nb m with m = tri - seed or tri + 1, which stays far above
+// any leaf's span as long as 2 nb m < 2^32 - 2 nb 16 — triangle slots below 2^25 and nb = 48, both checked by the build (walk.hip.h
+// record_at_bytes) — and a seed behind the leaf gives its true distance, which is too large.  tests/test_seed_skip_cpu.py, through the CPU
+// probe library.
+M2S_HD bool seed_in_leaf(uint32_t seed, uint32_t tri, uint32_t below, uint32_t skip, uint32_t nb) {
+  return (seed - tri) * (2u * nb) <= skip - below;
+}
+
 }  // namespace m2s

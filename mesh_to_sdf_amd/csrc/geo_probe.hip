@@ -51,6 +51,10 @@ void probe_cut_small_enough_n(size_t n, const float* R, const float* half, const
 void probe_leaf_cursor_steps_n(size_t n, const uint32_t* off, const uint32_t* skip, uint32_t nb, uint32_t* out) {
   for (size_t i = 0; i < n; ++i) out[i] = leaf_cursor_steps(off[i], skip[i], nb);
 }
+// geo.hip.h: the packet walk's seed test for n (seed, tri, below, skip) quadruples of records of nb bytes (out: one byte each)
+void probe_seed_in_leaf_n(size_t n, const uint32_t* seed, const uint32_t* tri, const uint32_t* below, const uint32_t* skip, uint32_t nb, unsigned char* out) {
+  for (size_t i = 0; i < n; ++i) out[i] = seed_in_leaf(seed[i], tri[i], below[i], skip[i], nb) ? 1 : 0;
+}
 float probe_normal_fold_result(float d2_all, float d2_pos) { return normal_fold_result(d2_all, d2_pos); }
 int probe_approx_eq_abs(float a, float b) { return approx_eq_abs(a, b) ? 1 : 0; }
 void probe_tri_box(const float* a, const float* b, const float* c, float* mn, float* mx) {

@@ -51,6 +51,7 @@ const Entry TABLE[] = {
     M2S_KNOB("M2S_SPLIT_REPORT", K_INT, split_report),
     M2S_KNOB("M2S_DEFER", K_INT, defer),
     M2S_KNOB("M2S_GATHER_AHEAD", K_INT, gather_ahead),
+    M2S_KNOB("M2S_SEED_SKIP", K_INT, seed_skip),
     M2S_KNOB("M2S_BAND_CHUNK", K_U32, band_chunk),
     M2S_KNOB("M2S_BAND_FETCH", K_INT, band_fetch),
     M2S_KNOB("M2S_HOST_PIECE_MB", K_U32, host_piece_mb),
@@ -90,6 +91,8 @@ void sanitise(Tuning& t) {
   if (t.band_chunk > (1u << 30)) t.band_chunk = 1u << 30;
   if (t.gather_ahead > 1) t.gather_ahead = 1;     // -1, 0, 1 and nothing else
   if (t.gather_ahead < -1) t.gather_ahead = -1;
+  if (t.seed_skip > 1) t.seed_skip = 1;           // -1, 0, 1 and nothing else
+  if (t.seed_skip < -1) t.seed_skip = -1;
   if (t.band_fetch > 2) t.band_fetch = 2;
   if (t.band_fetch < -1) t.band_fetch = -1;
   if (t.cut_wave_cap > 99999) t.cut_wave_cap = 99999;   // k_cut's visit caps stay below the per-brick budget of 100 000 opened nodes the kernel

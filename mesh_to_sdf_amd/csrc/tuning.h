@@ -46,6 +46,7 @@ struct Tuning {
   int split_report = 0;             // M2S_SPLIT_REPORT 1: suspended packets and items per round of every grid walk, on stderr (synchronises)
   int defer = -1;                   // M2S_DEFER        the packet walk's leaf work: -1 automatic (by triangles per brick: 2 / 1 / 3), 0 wave-wide at once, 1 exact evaluations queued as (voxel, triangle) pairs and run 64 at a time, 2 + wave-wide where >= 48 lanes are reached, 3 the pre-tests queued too
   int gather_ahead = -1;            // M2S_GATHER_AHEAD the DEFER 3 walk's pre-test gathers: 0 issued where they are used, 1 issued a leaf ahead of their use (k_packet's GA form; the split walk, the packet groups and the other DEFER forms have none), -1 automatic: ahead for the grid walk of the unsigned distance and the queries' walk with the three-ray sign, where it is measured to win; other values are clamped to -1 .. 1
+  int seed_skip = -1;               // M2S_SEED_SKIP    the packet walks (k_packet's plain forms, the packet groups) and their seed triangle, which the prologue has evaluated for every lane: 1 the walk passes over it where it meets it again as a leaf triangle, 0 it is queued, pre-tested and evaluated a second time (idempotent minima: the same bits either way; the split walk's kernels and the lane walks always do), -1 automatic: passed over in every packet form (profiles/seed_skip_ab.txt); other values are clamped to -1 .. 1
   // ---- narrow bands (band.hip)
   uint32_t band_chunk = 1u << 24;   // M2S_BAND_CHUNK      candidates per pass of the query walk in a narrow-band call (1 .. 2^30); every chunk pays the query path's sort and seed passes again (DESIGN.md section 4.13 has the sweep), and the workspace grows by about 100 bytes per candidate of a chunk
   // ---- band queries (band_query.hip)
