@@ -1,11 +1,12 @@
-// geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h, sample.hip.h, voxel.hip.h, band.hip.h and cut_size.hip.h, for CPU unit tests only
-// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py, tests/test_narrow_band_cpu.py, tests/test_cut_size_cpu.py, tests/test_walk_leaf_count_cpu.py, tests/test_pair_eval_cpu.py).  Not linked into libm2s_hip.so.
+// geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h, sample.hip.h, voxel.hip.h, band.hip.h, cut_size.hip.h and sign.hip.h, for CPU unit tests only
+// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py, tests/test_narrow_band_cpu.py, tests/test_cut_size_cpu.py, tests/test_walk_leaf_count_cpu.py, tests/test_pair_eval_cpu.py, tests/test_sign_planes_cpu.py).  Not linked into libm2s_hip.so.
 #include "geo.hip.h"
 #include "ray.hip.h"
 #include "sample.hip.h"
 #include "voxel.hip.h"
 #include "band.hip.h"
 #include "cut_size.hip.h"
+#include "sign.hip.h"
 
 using namespace m2s;
 
@@ -181,5 +182,60 @@ void probe_band_candidates(uint64_t n_tris, const float* tris, const float* firs
         for (uint32_t k = klo; k < khi; ++k) occ[((size_t)i * n[1] + j) * n[2] + k] = 1;
       }
   }
+}
+// sign.hip.h
+static GridParams probe_sign_grid(const float* first, const float* size, const uint32_t* n) {
+  GridParams g = {};
+  for (int m = 0; m < 3; ++m) { g.first[m] = first[m]; g.size[m] = size[m]; g.n[m] = n[m]; }
+  g.nzw = (n[2] + 31u) / 32u;
+  return g;
+}
+// the f32 centre the marking kernels give cell idx of a line's free axis
+float probe_sign_centre(float first, float size, uint32_t idx) { return cell_center(first, size, idx); }
+// ... of m cells at once
+void probe_sign_centres_n(float first, float size, size_t m, const uint32_t* idx, float* out) {
+  for (size_t i = 0; i < m; ++i) out[i] = cell_center(first, size, idx[i]);
+}
+// lo_hi = the inclusive range (lo > hi: empty)
+void probe_sign_axis_range(float bmn, float bmx, float first, float cs, uint32_t n, uint32_t* lo_hi) {
+  axis_range(bmn, bmx, first, cs, n, &lo_hi[0], &lo_hi[1]);
+}
+// ... for m quintuples at once (lo_hi: 2 m words)
+void probe_sign_axis_range_n(size_t m, const float* bmn, const float* bmx, const float* first, const float* cs, const uint32_t* n, uint32_t* lo_hi) {
+  for (size_t i = 0; i < m; ++i) axis_range(bmn[i], bmx[i], first[i], cs[i], n[i], &lo_hi[2 * i], &lo_hi[2 * i + 1]);
+}
+// tri: 9 floats (a, b, c); slab: lo, hi, chunk_log, period, all; out = ulo, uhi, wlo, whi of the window of the lines along `axis`.
+// Returns window_count.
+uint32_t probe_sign_window(const float* tri, const float* first, const float* size, const uint32_t* n, const uint32_t* slab, int axis, uint32_t* out) {
+  const GridParams g = probe_sign_grid(first, size, n);
+  const SlabX sx = {slab[0], slab[1], slab[2], slab[3], slab[4] != 0u};
+  f3 mn, mx;
+  triangle_bounding_box(mk3(tri[0], tri[1], tri[2]), mk3(tri[3], tri[4], tri[5]), mk3(tri[6], tri[7], tri[8]), &mn, &mx);
+  const Window w = axis == 0 ? make_window<0>(mn, mx, g, sx) : axis == 1 ? make_window<1>(mn, mx, g, sx) : make_window<2>(mn, mx, g, sx);
+  out[0] = w.ulo; out[1] = w.uhi; out[2] = w.wlo; out[3] = w.whi;
+  return window_count(w);
+}
+// the largest window_count of n_tris triangles (9 floats each) per axis: out[3]
+void probe_sign_max_window(size_t n_tris, const float* tris, const float* first, const float* size, const uint32_t* n, const uint32_t* slab, uint32_t* out) {
+  uint32_t w[4];
+  out[0] = out[1] = out[2] = 0;
+  for (size_t i = 0; i < n_tris; ++i)
+    for (int axis = 0; axis < 3; ++axis) {
+      const uint32_t c = probe_sign_window(tris + 9 * i, first, size, n, slab, axis, w);
+      if (c > out[axis]) out[axis] = c;
+    }
+}
+// slab: lo, hi, chunk_log, period, all; out[x] = x_in_slab for x < nx
+void probe_sign_x_in_slab(const uint32_t* slab, uint32_t nx, uint8_t* out) {
+  const SlabX sx = {slab[0], slab[1], slab[2], slab[3], slab[4] != 0u};
+  for (uint32_t x = 0; x < nx; ++x) out[x] = x_in_slab(sx, x) ? 1 : 0;
+}
+uint32_t probe_sign_bucket(float t, float cell_size, uint32_t n) { return ray_bucket(t, cell_size, n); }
+// out = lanes per triangle, list flag, rows form of the z combine; consts = SMALL_WINDOW, RAY_MARK_SHARED_BELOW, LIST_ABOVE_LINES, BIG_CHUNK
+void probe_sign_path(uint32_t n_tris, const uint32_t* n, uint32_t* out, uint64_t* consts) {
+  const float zero[3] = {0.0f, 0.0f, 0.0f};
+  const SignPath p = sign_path(n_tris, probe_sign_grid(zero, zero, n));
+  out[0] = p.lanes; out[1] = p.list ? 1u : 0u; out[2] = p.rows ? 1u : 0u;
+  consts[0] = SMALL_WINDOW; consts[1] = RAY_MARK_SHARED_BELOW; consts[2] = LIST_ABOVE_LINES; consts[3] = BIG_CHUNK;
 }
 }

@@ -12,78 +12,13 @@
 //   k_scan_xy  : suffix XOR of the markers along x / y  ==  parity of "increment cells 0..=k" (both planes in one launch).
 //   k_scan_z_combine : suffix XOR along z inside the words, then majority of the three planes.
 // Work is O(T * lines-per-triangle + N^3 / 32) instead of O(N^2 log T + hits * N) atomics.
-#include <algorithm>
-
 #include "common.h"
 #include "geo.hip.h"
+#include "sign.hip.h"
 
 namespace m2s {
 
 namespace {
-
-constexpr uint32_t SMALL_WINDOW = 64;  // lines a lane handles alone; larger windows are spread over the wave
-#ifndef M2S_RAY_SHARED_BELOW
-#define M2S_RAY_SHARED_BELOW 16384
-#endif
-constexpr uint32_t RAY_MARK_SHARED_BELOW = M2S_RAY_SHARED_BELOW;   // meshes of up to this many triangles: sixteen lanes per triangle (k_ray_mark<16>)
-
-struct Window {
-  uint32_t ulo, uhi, wlo, whi;  // inclusive index ranges on the two free axes; empty if ulo > uhi
-};
-
-__device__ __forceinline__ void axis_range(float bmn, float bmx, float first, float cs, uint32_t n, uint32_t* lo,
-                                           uint32_t* hi) {
-  // conservative index range of cells whose centre first + i*cs can lie in [bmn, bmx]
-  float i0 = (bmn - first) / cs, i1 = (bmx - first) / cs;
-  if (i0 > i1) { float t = i0; i0 = i1; i1 = t; }
-  const bool bad = !(i0 == i0) || !(i1 == i1) || !(fabsf(i0) < 3.0e38f) || !(fabsf(i1) < 3.0e38f);
-  if (bad) { *lo = 0; *hi = n - 1; return; }
-  // cells whose centre index lies in [i0, i1], widened by a tolerance that covers the f32 rounding of
-  // the index computation (the exact closed-interval test on the true centres decides membership)
-  const float tol = 1.0e-3f + 4.0e-6f * fmaxf(fabsf(i0), fabsf(i1)) + 1.0e-6f * (fabsf(bmn) + fabsf(bmx) + fabsf(first)) / fabsf(cs);
-  const float l = ceilf(i0 - tol), h = floorf(i1 + tol);
-  if (h < 0.0f || l > (float)(n - 1) || h < l) { *lo = 1; *hi = 0; return; }
-  *lo = l < 0.0f ? 0u : (uint32_t)l;
-  *hi = h >= (float)(n - 1) ? n - 1 : (uint32_t)h;
-}
-
-template <int AXIS>
-struct FreeAxes {
-  static constexpr int U = AXIS == 0 ? 1 : 0;
-  static constexpr int W = AXIS == 2 ? 1 : 2;
-};
-
-// A call that computes an x-slab only needs the planes of the slab's layers: Y- and Z-lines lie inside one x-layer,
-// so a line outside the slab is never looked at (its markers would only be read by cells the call does not compute); X-lines cross
-// all layers and are all traced — their hits are slab-independent, t is measured from cell 0 — but the suffix scan along x stops
-// at the slab's first layer.  SlabX: the real x-layers of the slab ([lo, hi) is their hull; an interleaved slab owns the chunks
-// [lo + j * period, + 2^chunk_log) inside it); all == true: the whole grid (persistent meshes keep their planes per grid, not per slab).
-struct SlabX {
-  uint32_t lo, hi, chunk_log, period;
-  bool all;
-};
-__device__ __forceinline__ bool x_in_slab(const SlabX& sx, uint32_t x) {
-  if (sx.all) return true;
-  if (x < sx.lo || x >= sx.hi) return false;
-  return sx.chunk_log >= 31u || ((x - sx.lo) % sx.period) < (1u << sx.chunk_log);
-}
-template <int AXIS>
-__device__ __forceinline__ Window make_window(f3 mn, f3 mx, const GridParams& g, const SlabX& sx) {
-  constexpr int U = FreeAxes<AXIS>::U, W = FreeAxes<AXIS>::W;
-  const float bmn[3] = {mn.x, mn.y, mn.z}, bmx[3] = {mx.x, mx.y, mx.z};
-  Window w;
-  axis_range(bmn[U], bmx[U], g.first[U], g.size[U], g.n[U], &w.ulo, &w.uhi);
-  axis_range(bmn[W], bmx[W], g.first[W], g.size[W], g.n[W], &w.wlo, &w.whi);
-  if (AXIS != 0 && !sx.all && w.ulo <= w.uhi) {      // U is x for the Y- and Z-lines: only the slab's layers
-    w.ulo = max(w.ulo, sx.lo);
-    w.uhi = min(w.uhi, sx.hi - 1u);
-  }
-  if (w.wlo > w.whi) { w.ulo = 1; w.uhi = 0; }
-  return w;
-}
-__device__ __forceinline__ uint32_t window_count(const Window& w) {
-  return w.ulo > w.uhi ? 0u : (w.uhi - w.ulo + 1u) * (w.whi - w.wlo + 1u);
-}
 
 // One grid line (free-axis cell iu, iw) against one triangle.
 template <int AXIS>
@@ -98,16 +33,11 @@ __device__ __forceinline__ void mark_line(f3 a, f3 b, f3 c, f3 mn, f3 mx, const 
   if (!ray_meets_box<AXIS>(o, mn, mx)) return;                                   // bvh.traverse candidate rule
   float t;
   if (!ray_triangle_aligned<AXIS>(o, a, b, c, &t)) return;                       // grid.rs:601-603
-  const float f = floorf(t / g.size[AXIS]);                                      // grid.rs:605-606
-  const uint32_t n = g.n[AXIS];
-  uint32_t k = 0;                                                                // `as usize` saturates, NaN -> 0
-  if (f == f && f > 0.0f) k = f >= (float)n ? n - 1 : min((uint32_t)f, n - 1);   // .min(n - 1), grid.rs:607
-  cell[AXIS] = k;
+  cell[AXIS] = ray_bucket(t, g.size[AXIS], g.n[AXIS]);                           // grid.rs:605-607
   const size_t word = ((size_t)cell[0] * g.n[1] + cell[1]) * g.nzw + (cell[2] >> 5);
   atomicXor(&plane[word], 1u << (cell[2] & 31u));
 }
 
-constexpr uint32_t BIG_CHUNK = 2048;   // lines of a big window one workgroup pass handles (256 threads x 8)
 struct BigList {
   unsigned long long* counter;   // (items << 32) | chunks
   uint2* items;                  // x = triangle | axis << 30, y = first chunk;  nullptr: no list (small grids)
@@ -308,13 +238,6 @@ __global__ __launch_bounds__(256) void k_scan_z_combine_rows(const uint32_t* __r
 
 }  // namespace
 
-// Grids whose largest possible window (a whole face of the grid) exceeds this use the work list for big windows.
-constexpr uint64_t LIST_ABOVE_LINES = 4096;
-static bool use_big_list(const GridParams& g) {
-  const uint64_t a = (uint64_t)g.n[1] * g.n[2], b = (uint64_t)g.n[0] * g.n[2], c = (uint64_t)g.n[0] * g.n[1];
-  return std::max(a, std::max(b, c)) > LIST_ABOVE_LINES;
-}
-
 size_t sign_workspace_bytes(const GridParams& g, size_t n_tris) {
   return 3 * ((size_t)g.n[0] * g.n[1] * g.nzw * 4 + 256) + 2048 + (use_big_list(g) ? 3 * n_tris * sizeof(uint2) + 512 : 0);
 }
@@ -336,8 +259,9 @@ int build_grid_sign_plane(Arena& ws, hipStream_t st, const DeviceMesh& mesh, con
   M2S_HIP_CHECK(hipMemsetAsync(block, 0, (3 * wpad + 16) * 4, st));
   const unsigned B = 256;
   if (mesh.n_tris) {
+    const SignPath path = sign_path(mesh.n_tris, g);
     BigList list{nullptr, nullptr};
-    if (use_big_list(g)) {
+    if (path.list) {
       list.counter = reinterpret_cast<unsigned long long*>(block + 3 * wpad);
       list.items = ws.take<uint2>(3 * (size_t)mesh.n_tris);
       if (!list.items) {
@@ -357,7 +281,7 @@ int build_grid_sign_plane(Arena& ws, hipStream_t st, const DeviceMesh& mesh, con
       sx.period = g.period ? g.period : 1u;
     }
     const uint32_t layers = whole ? g.n[0] : vlayers;
-    if (mesh.n_tris <= RAY_MARK_SHARED_BELOW) hipLaunchKernelGGL(k_ray_mark<16>, dim3((mesh.n_tris * 16u + B - 1) / B), dim3(B), 0, st, mesh, g, sx, px, py, pz, list);
+    if (path.lanes == 16u) hipLaunchKernelGGL(k_ray_mark<16>, dim3((mesh.n_tris * 16u + B - 1) / B), dim3(B), 0, st, mesh, g, sx, px, py, pz, list);
     else hipLaunchKernelGGL(k_ray_mark<1>, dim3((mesh.n_tris + B - 1) / B), dim3(B), 0, st, mesh, g, sx, px, py, pz, list);
     if (list.items) hipLaunchKernelGGL(k_ray_mark_big, dim3(2048), dim3(B), 0, st, mesh, g, sx, px, py, pz, list);
     const size_t row_words = (size_t)g.n[1] * g.nzw;
@@ -365,7 +289,7 @@ int build_grid_sign_plane(Arena& ws, hipStream_t st, const DeviceMesh& mesh, con
     const unsigned x_blocks = (unsigned)((row_words + B - 1) / B), y_blocks = (unsigned)((ycols + B - 1) / B);
     hipLaunchKernelGGL(k_scan_xy, dim3(x_blocks + y_blocks), dim3(B), 0, st, px, py, g, layers, whole, row_words, whole ? 0u : sx.lo, x_blocks);
     const size_t rows = (size_t)layers * g.n[1], slab_words = rows * g.nzw;
-    if (g.nzw <= 64 && (g.nzw & (g.nzw - 1)) == 0)
+    if (path.rows)
       hipLaunchKernelGGL(k_scan_z_combine_rows, dim3((unsigned)((slab_words + B - 1) / B)), dim3(B), 0, st, px, py, pz, g, whole, slab_words, g.nzw);
     else
       hipLaunchKernelGGL(k_scan_z_combine, dim3((unsigned)((rows + B - 1) / B)), dim3(B), 0, st, px, py, pz, g, whole, rows, g.nzw);
