@@ -1084,6 +1084,76 @@ int m2s_band_resample(const m2s_band* band, const m2s_grid* target, const m2s_ba
                       const m2s_band_field_opts* fopts /* NULL = the input's backgrounds times value_scale */, const m2s_opts* opts,
                       m2s_band** out, m2s_band_resample_info* info_out /* may be NULL */);
 
+/* ---- Connected components of a narrow band: label, measure, select ------------------------------------------------------------------------
+ * m2s_band_components labels the connected components of a resident band's active cells and measures each; m2s_band_select returns the
+ * band with some of them erased: what segmentActiveVoxels / segmentSDF and "keep the largest component" / "drop islands below N voxels"
+ * are in OpenVDB, split() in trimesh and ndimage.label in scipy.  They take apart what the other band calls produce: the slivers and
+ * floating debris m2s_band_csg leaves where two surfaces nearly coincide, the loose parts of a voxelised scan, the two halves of a part
+ * that a difference cut in two.  Both are DEFINED to the bit (tests/band_components_model.py restates them in numpy).
+ *
+ * m2s_band_components.  The graph's nodes are the band's active cells.  Two cells are joined when their (i, j, k) differ by at most 1 on
+ *   every axis and by 1 on at most 1, 2 or 3 axes: connectivity 6 (faces), 18 (faces and edges) or 26 (faces, edges and corners).  There
+ *   is NO clamping: a step off the grid finds no neighbour, unlike the filters' clamped step.  The values play no part.
+ *   Numbering: the components are numbered 0 .. C-1 in ascending order of their smallest linear cell index L = k + j*nz + i*ny*nz, the
+ *   raster numbering of scipy.ndimage.label.  labels_out[r] is the component of list place r (the r-th active cell in ascending L,
+ *   the order of m2s_band_export), n_cells entries.  M2S_LABEL_NONE is never written; it is a value for callers to mark cells with.
+ *   Per component, components_out[c] holds: first_cell = its smallest L; n_cells; n_negative = its cells whose value is < 0 (-0.0 is
+ *   not), a volume proxy for a band that holds a solid's skin; lo / hi = the inclusive bounding box of its (i, j, k).  Everything
+ *   reported is an integer, so the atomics that gather it give the same bits in any order.
+ *   Protocol: *n_components_out = C is written whenever the arguments are valid.  labels_out == components_out == NULL only counts
+ *   (either may be NULL alone).  A `capacity` below C with components_out given is M2S_ERR_BAD_ARG with C written and components_out
+ *   untouched: call again with room.  Always synchronous.  m2s_opts.mem_kind covers labels_out and components_out.  An empty band
+ *   gives 0 components and M2S_OK.
+ *   M2S_ERR_BAD_ARG before any device work: a NULL band or count pointer; a copts->struct_size other than sizeof; a connectivity other
+ *   than 6, 18 or 26 (copts == NULL means 6); an m2s_opts.device that is not the handle's (-1 means its own); algorithm, x_begin,
+ *   x_end, x_period or peer_out not zero; a bad mem_kind; 2^32 - 1 or more active cells: labels and parents are 32-bit, the limit
+ *   m2s_band_redistance puts on its candidates.  m2s_opts: device, stream / stream_mode, lane.  timings: distance_ms = total_ms = the
+ *   whole call, n_units = the band's cells.
+ *   Method: a lock-free union-find over the list places with parent[r] <= r; each cell is united with the active cells of the backward
+ *   half of its stencil, the larger root hooked under the smaller by compare-and-swap.  A component's root is its smallest place in any
+ *   order of execution, so the result is deterministic without sweeps.  (Label propagation in Jacobi sweeps would need as many sweeps
+ *   as the cell graph's diameter, thousands at 2048^3.)
+ *   Memory during the call: 4 bytes per active cell beside the outputs (twice that when labels_out is host memory, or NULL with
+ *   components_out given), and 8 bytes per 4096 cells of scan partials.  Nothing is sized per grid point or per mask word.
+ *
+ * m2s_band_select.  Cell r (list place) is KEPT iff labels[r] < n_keep && keep[labels[r]] != 0; every other cell is DROPPED.
+ *   M2S_LABEL_NONE and any label from elsewhere therefore drop the cell, and no validation pass exists.  labels has n_cells entries,
+ *   keep n_keep bytes; the labels need not come from m2s_band_components.
+ *   Result: a new immutable m2s_band on the same grid and device.  Its cells are the kept cells, ascending, with every bit of their
+ *   values.  A dropped cell becomes inactive and outside.  Backgrounds: fopts', or the input's by default.  Sign mask, on EVERY grid
+ *   point as for every derived handle:
+ *     a kept cell              v < 0
+ *     a dropped cell           0
+ *     an inactive point of the input whose inside bit is clear    0
+ *     an inactive point of the input whose inside bit is set      CLEARED iff, in its own k-row (same i, j), the nearest active cell
+ *                              of the input towards +k and the nearest towards -k are dropped cells, for every side that has one, and
+ *                              at least one side has one; otherwise it keeps its bit.
+ *   An input without a sign mask has no such points.  This is a scan-line flood like OpenVDB's signedFloodFill, restricted to what an
+ *   erased component owned: without it m2s_band_sample and m2s_band_raymarch would still see the solid interior of an erased island.
+ *   THE LIMIT: the rule knows rows, not solids.  Erasing the band around a CAVITY (the inner skin of a hollow part) turns the cavity
+ *   into outside, which it already was, and leaves the row segments of solid that ended on it bracketed on one side only by a kept
+ *   cell: they keep their bit, but the cavity's skin is gone, so the field steps from -background_inside to +background_outside with
+ *   no band cell between.  A row segment of solid between two erased cavities is cleared.  Erase islands, not voids.
+ *   info_out (may be NULL; set struct_size): n_cells = the result's cells, n_dropped = the input's cells minus those, n_sign_cleared
+ *   = the inactive points whose inside bit was cleared.  m2s_band_info of the result: device_bytes by the formula for a handle with a
+ *   sign mask.
+ *   Always synchronous.  *out = NULL on every failure.  m2s_opts.mem_kind covers labels and keep.  M2S_ERR_BAD_ARG before any device
+ *   work: a NULL band, labels or out; keep == NULL with n_keep > 0; a struct_size other than sizeof (fopts, info_out); a negative or
+ *   non-finite background; the m2s_opts fields as above.  timings: seed_ms = total_ms = the three launches, n_units = the result's cells.
+ *   Memory during the call: the result, 4 bytes per 256 mask words and 8 per 4096 of counts, and a host caller's labels and keep.  The
+ *   row search loads at most nz / 64 + 1 mask words per direction, and only for words that have inactive-inside bits. */
+enum m2s_connectivity { M2S_CONNECT_6 = 6, M2S_CONNECT_18 = 18, M2S_CONNECT_26 = 26 };
+typedef struct m2s_band_components_opts { uint32_t struct_size; int32_t connectivity; } m2s_band_components_opts;   /* 8 bytes */
+typedef struct m2s_band_component { uint64_t first_cell, n_cells, n_negative; uint32_t lo[3], hi[3]; } m2s_band_component;   /* 48 bytes */
+typedef struct m2s_band_select_info { uint32_t struct_size, reserved; uint64_t n_cells, n_dropped, n_sign_cleared; } m2s_band_select_info;   /* 32 bytes */
+#define M2S_LABEL_NONE 0xffffffffu
+int m2s_band_components(const m2s_band* band, const m2s_band_components_opts* copts /* NULL = 6 */, const m2s_opts* opts,
+                        uint32_t* labels_out /* n_cells, list order; may be NULL */, m2s_band_component* components_out /* may be NULL */,
+                        uint64_t capacity, uint64_t* n_components_out /* host */);
+int m2s_band_select(const m2s_band* band, const uint32_t* labels /* n_cells */, const uint8_t* keep, uint64_t n_keep,
+                    const m2s_band_field_opts* fopts /* NULL = the input's backgrounds */, const m2s_opts* opts,
+                    m2s_band** out, m2s_band_select_info* info_out /* may be NULL */);
+
 /* glTF 2.0 / GLB ingestion (host side) — what the reference client extracts from a file before the merge:
  * mesh_to_sdf_client/src/gltf/mod.rs:56-174 (models keyed by mesh index, one primitive per mesh survives;
  * POSITION + indices, sparse accessors and byteStride honoured; missing indices = 0..n, pbr/model.rs:29-32),

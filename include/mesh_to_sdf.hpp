@@ -27,6 +27,7 @@
 // V is any point type with x(), y(), z() | .x .y .z | operator[] (the reference's `Point` trait adapters,
 // point/impl_*.rs: [f32;3], glam, cgmath, nalgebra, mint all reduce to three f32).  Header only; link -lm2s_hip.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -626,6 +627,29 @@ struct FilterInfo {
 struct ResampleInfo {
   uint64_t n_cells = 0, n_partial = 0, n_nonfinite = 0, n_open = 0;
 };
+// Which cells of a band count as joined (m2s_connectivity): faces, faces and edges, faces, edges and corners.
+enum class Connectivity : int { Faces = M2S_CONNECT_6, Edges = M2S_CONNECT_18, Corners = M2S_CONNECT_26 };
+// What BandField::components returns (m2s_band_components): the components numbered in ascending order of their smallest cell index (the
+// raster numbering of scipy.ndimage.label); labels[r] is the component of the r-th cell of export_band().cells; components[c] holds its
+// first cell, cell count, negative-cell count (a volume proxy) and inclusive (i, j, k) bounding box.
+struct Components {
+  std::vector<uint32_t> labels;
+  std::vector<m2s_band_component> components;
+  uint64_t count() const { return components.size(); }
+  // The numbers of the k components with the most cells, largest first; a tie goes to the lower number.
+  std::vector<uint32_t> largest(size_t k = 1) const {
+    std::vector<uint32_t> order(components.size());
+    for (size_t c = 0; c < order.size(); ++c) order[c] = (uint32_t)c;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return components[a].n_cells > components[b].n_cells; });
+    order.resize(std::min(k, order.size()));
+    return order;
+  }
+};
+// What BandField::select reports (m2s_band_select_info): the result's cells, the cells erased, the inactive points whose inside bit was
+// cleared because erased cells bracketed them.
+struct SelectInfo {
+  uint64_t n_cells = 0, n_dropped = 0, n_sign_cleared = 0;
+};
 template <class V>
 class BandField {
  public:
@@ -766,6 +790,51 @@ class BandField {
       info->n_open = ri.n_open;
     }
     return BandField(target, h);
+  }
+  // The connected components of the field's cells (m2s_band_components: a lock-free union-find on the device, to the bit).  One
+  // labelling, with room for 256 components; a second only when there are more (the call then reports the count and fills nothing).
+  Components components(Connectivity connectivity = Connectivity::Faces) const {
+    m2s_band_components_opts co{};
+    co.struct_size = sizeof(co);
+    co.connectivity = (int32_t)connectivity;
+    Components r;
+    r.labels.resize(count());
+    r.components.resize(256);
+    uint64_t n = 0;
+    const int rc = m2s_band_components(h_, &co, nullptr, r.labels.data(), r.components.data(), r.components.size(), &n);
+    if (rc == M2S_ERR_BAD_ARG && n > r.components.size()) {
+      r.components.resize(n);
+      detail::check(m2s_band_components(h_, &co, nullptr, r.labels.data(), r.components.data(), n, &n));
+    } else {
+      detail::check(rc);
+    }
+    r.components.resize(n);
+    return r;
+  }
+  // The field with some components erased, as a new resident field (m2s_band_select): a cell is kept iff keep[labels[r]] != 0 (a label
+  // beyond keep, M2S_LABEL_NONE included, erases it).  The kept cells keep every bit; an erased cell becomes inactive and outside, and so
+  // does the solid interior that only erased cells bracketed along k.  Erase islands, not voids: erasing the band around a cavity
+  // leaves the solid around it without a band cell on that side.  The backgrounds are kept.
+  BandField select(const std::vector<uint32_t>& labels, const std::vector<uint8_t>& keep, SelectInfo* info = nullptr) const {
+    if (labels.size() != count()) throw Panic(M2S_ERR_BAD_ARG, "select: one label per cell");
+    static const uint32_t none = M2S_LABEL_NONE;
+    m2s_band_select_info si{};
+    si.struct_size = sizeof(si);
+    m2s_band* h = nullptr;
+    detail::check(m2s_band_select(h_, labels.empty() ? &none : labels.data(), keep.empty() ? nullptr : keep.data(), keep.size(), nullptr, nullptr, &h, &si));
+    if (info) {
+      info->n_cells = si.n_cells;
+      info->n_dropped = si.n_dropped;
+      info->n_sign_cleared = si.n_sign_cleared;
+    }
+    return BandField(grid_, h);
+  }
+  // The field with all but its k largest components erased.
+  BandField keep_largest(size_t k = 1, Connectivity connectivity = Connectivity::Faces, SelectInfo* info = nullptr) const {
+    const Components c = components(connectivity);
+    std::vector<uint8_t> keep(c.count(), 0);
+    for (uint32_t id : c.largest(k)) keep[id] = 1;
+    return select(c.labels, keep, info);
   }
   // The field's lists back out (m2s_band_export): cells ascending, distances bit for bit, and `bits` the sign mask in the layout of
   // Voxels::bits (all zero for a field made without one).  band_isosurface(grid, b.cells, b.distances) meshes it.

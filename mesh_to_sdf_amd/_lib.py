@@ -165,6 +165,22 @@ class M2SBandResampleInfo(C.Structure):
                 ("n_nonfinite", C.c_uint64), ("n_open", C.c_uint64)]
 
 
+class M2SBandComponentsOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("connectivity", C.c_int32)]
+
+
+class M2SBandComponent(C.Structure):
+    _fields_ = [("first_cell", C.c_uint64), ("n_cells", C.c_uint64), ("n_negative", C.c_uint64), ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3)]
+
+
+class M2SBandSelectInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_cells", C.c_uint64), ("n_dropped", C.c_uint64),
+                ("n_sign_cleared", C.c_uint64)]
+
+
+LABEL_NONE = 0xffffffff
+
+
 class M2SSampleOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("iso", C.c_float), ("outside", C.c_float), ("max_steps", C.c_uint32)]
 
@@ -230,6 +246,8 @@ EXPORTS = [
     "m2s_band_redistance",
     "m2s_band_filter",
     "m2s_band_resample",
+    "m2s_band_components",
+    "m2s_band_select",
     "m2s_merge_instances",
     "m2s_gltf_open",
     "m2s_gltf_instances",
@@ -339,6 +357,10 @@ def _prototypes():
                                       C.POINTER(C.c_void_p), C.POINTER(M2SBandFilterInfo)]),
         "m2s_band_resample": (C.c_int, [C.c_void_p, C.POINTER(M2SGrid), C.POINTER(M2SBandResampleOpts), C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
                                         C.POINTER(C.c_void_p), C.POINTER(M2SBandResampleInfo)]),
+        "m2s_band_components": (C.c_int, [C.c_void_p, C.POINTER(M2SBandComponentsOpts), C.POINTER(M2SOpts), C.c_void_p, C.c_void_p, C.c_uint64,
+                                          C.POINTER(C.c_uint64)]),
+        "m2s_band_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
+                                      C.POINTER(C.c_void_p), C.POINTER(M2SBandSelectInfo)]),
         "m2s_merge_instances": (C.c_int, [C.POINTER(M2SInstance), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(M2SOpts)]),
         "m2s_gltf_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(M2SGltfInfo)]),
         "m2s_gltf_instances": (C.c_int, [C.c_void_p, C.POINTER(M2SInstance), C.c_size_t]),

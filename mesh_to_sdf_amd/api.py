@@ -993,40 +993,52 @@ def isosurface_band(grid: Grid, iso: float = 0.0):
     return _f32_up(max(0.0, w - iso)), _f32_up(max(0.0, iso + w))
 
 
-def _remesh(band: "NarrowBand", iso):
-    verts, idx, n_open = band.isosurface(iso)
+def _remesh(band: "NarrowBand", iso, keep_largest: int = 0):
+    if keep_largest > 0:
+        with band.field() as whole, whole.keep_largest(keep_largest) as kept:
+            verts, idx, n_open = kept.isosurface(iso)
+    else:
+        verts, idx, n_open = band.isosurface(iso)
     if n_open != 0:
         raise M2SError(_lib.ERR_BAD_ARG, f"remesh: the band is too narrow for iso = {iso}: {n_open} cells are cut but incomplete")
     return verts, idx
 
 
-def remesh(vertices, indices: Topology, grid: Grid, *, iso: float = 0.0, sign_method: SignMethod = SignMethod.Raycast):
+def remesh(vertices, indices: Topology, grid: Grid, *, iso: float = 0.0, sign_method: SignMethod = SignMethod.Raycast, keep_largest: int = 0):
     """Mesh -> level set -> mesh without a dense grid: narrow_band_sdf with the band of isosurface_band(grid, iso), then its isosurface at
     `iso`.  The sparse voxel remesh (iso = 0) / offset surface (iso != 0) of the mesh on `grid`; where the distance field is exact the
     result is grid_isosurface(grid, generate_grid_sdf(...), iso) bit for bit.  Returns (vertices, indices); raises M2SError if the band
-    turns out too narrow (n_open != 0)."""
-    return _remesh(narrow_band_sdf(vertices, indices, grid, isosurface_band(grid, iso), sign_method), iso)
+    turns out too narrow (n_open != 0).  keep_largest = k > 0 erases all but the band's k largest connected components first
+    (BandField.keep_largest): loose parts and debris do not reach the mesh."""
+    return _remesh(narrow_band_sdf(vertices, indices, grid, isosurface_band(grid, iso), sign_method), iso, int(keep_largest))
 
 
-def _boolean(mesh_a: "Mesh", mesh_b: "Mesh", op, grid: Grid, sign_method):
+def _boolean(mesh_a: "Mesh", mesh_b: "Mesh", op, grid: Grid, sign_method, keep_largest: int = 0):
     op = _csg_op(op)
     w = isosurface_band(grid, 0.0)                    # (interior, exterior): the same width w on both sides at iso = 0
     with mesh_a.narrow_band_field(grid, w, sign_method, True, background=w) as fa, \
             mesh_b.narrow_band_field(grid, w, sign_method, True, background=w) as fb, fa.csg(fb, op) as fr:
-        verts, idx, n_open = fr.isosurface(0.0)
+        if keep_largest > 0:
+            with fr.keep_largest(keep_largest) as kept:
+                verts, idx, n_open = kept.isosurface(0.0)
+        else:
+            verts, idx, n_open = fr.isosurface(0.0)
     if n_open != 0:
         raise M2SError(_lib.ERR_BAD_ARG, f"boolean: the bands are too narrow: {n_open} cells are cut but incomplete")
     return verts, idx
 
 
-def boolean(vertices_a, indices_a: Topology, vertices_b, indices_b: Topology, op, grid: Grid, *, sign_method: SignMethod = SignMethod.Raycast):
+def boolean(vertices_a, indices_a: Topology, vertices_b, indices_b: Topology, op, grid: Grid, *, sign_method: SignMethod = SignMethod.Raycast,
+            keep_largest: int = 0):
     """A mesh boolean through level sets, without a dense grid: both meshes to narrow band fields on `grid` (the widths of
     isosurface_band(grid, 0), both backgrounds that width, the Raycast sign beyond the band), BandField.csg with `op` (a CsgOp or its
     name: union, intersection, difference = a minus b), then the isosurface at 0.  Where the distance fields are exact the result is
     grid_isosurface of min / max of the two dense grids clamped to the band width, bit for bit.  Returns (vertices, indices); raises
-    M2SError if a band turns out too narrow (n_open != 0).  The surface is that of the grid's resolution: features below a cell are lost."""
+    M2SError if a band turns out too narrow (n_open != 0).  The surface is that of the grid's resolution: features below a cell are lost.
+    keep_largest = k > 0 erases all but the result's k largest connected components before meshing (BandField.keep_largest): the
+    slivers and floating debris a boolean leaves where two surfaces nearly coincide."""
     with Mesh(vertices_a, indices_a) as ma, Mesh(vertices_b, indices_b) as mb:
-        return _boolean(ma, mb, op, grid, sign_method)
+        return _boolean(ma, mb, op, grid, sign_method, int(keep_largest))
 
 
 def default_background(distances):
@@ -1122,6 +1134,51 @@ class ResampleInfo(NamedTuple):
     n_partial: int
     n_nonfinite: int
     n_open: int
+
+
+class Connectivity(enum.IntEnum):
+    """include/m2s.h `m2s_connectivity`: which cells of a band count as joined.  Faces (6), faces and edges (18), faces, edges and
+    corners (26)."""
+    Faces = 6
+    Edges = 18
+    Corners = 26
+
+
+def _connectivity(c) -> Connectivity:
+    try:
+        return Connectivity(int(c))
+    except (ValueError, TypeError):
+        raise M2SPanic(_lib.ERR_BAD_ARG, f"connectivity = {c!r} is not 6, 18 or 26") from None
+
+
+class SelectInfo(NamedTuple):
+    """include/m2s.h `m2s_band_select_info`: the result's cells, the cells erased, and the inactive points whose inside bit was
+    cleared because the erased cells bracketed them."""
+    n_cells: int
+    n_dropped: int
+    n_sign_cleared: int
+
+
+class Components:
+    """The connected components of a BandField's cells (include/m2s.h m2s_band_components), numbered 0 .. count - 1 in ascending order of
+    their smallest cell index, the raster numbering of scipy.ndimage.label.  labels: one uint32 per cell in list order (the order of
+    `to_band().cells`), a device tensor for a field made from device tensors, a host array otherwise.  Per component, as host arrays:
+    first_cell (its smallest L), n_cells, n_negative (cells with a value < 0: a volume proxy), box_lo / box_hi (the inclusive
+    (i, j, k) bounding box, uint32[count, 3])."""
+
+    def __init__(self, labels, connectivity, first_cell, n_cells, n_negative, box_lo, box_hi):
+        self.labels, self.connectivity = labels, connectivity
+        self.first_cell, self.n_cells, self.n_negative, self.box_lo, self.box_hi = first_cell, n_cells, n_negative, box_lo, box_hi
+        self.count = int(n_cells.size)
+
+    def largest(self, k: int = 1):
+        """The numbers of the k components with the most cells, largest first; a tie goes to the lower number."""
+        order = np.argsort(-self.n_cells.astype(np.int64), kind="stable")
+        return order[:max(int(k), 0)].astype(np.int64)
+
+    def at_least(self, min_cells: int):
+        """The numbers of the components with min_cells cells or more, ascending."""
+        return np.flatnonzero(self.n_cells >= int(min_cells)).astype(np.int64)
 
 
 def _similarity(transform):
@@ -1402,6 +1459,102 @@ class BandField:
         out = BandField._adopt(h, grid, self._dev)
         out.resample_info = ResampleInfo(int(info.n_cells), int(info.n_partial), int(info.n_nonfinite), int(info.n_open))
         return out
+
+    def components(self, connectivity=6, *, timings: M2STimings = None) -> "Components":
+        """The connected components of the field's cells (include/m2s.h m2s_band_components; connectivity 6, 18 or 26 or a
+        Connectivity): a Components with the labels in list order and each component's first cell, cell count, negative-cell count
+        and bounding box.  One labelling; a second call only when there are more components than the first had room for."""
+        conn = _connectivity(connectivity)
+        h = self._handle()
+        q = self._side(timings)
+        n = self.count
+        co = _lib.M2SBandComponentsOpts(C.sizeof(_lib.M2SBandComponentsOpts), int(conn))
+        labels, p_l = q.empty(n, np.uint32)
+        count = C.c_uint64(0)
+        cap = 256
+        while True:
+            stats, p_s = q.empty((cap, 6), np.uint64)
+            rc = _lib.lib().m2s_band_components(h, C.byref(co), C.byref(q.opts), p_l, p_s, cap, C.byref(count))
+            if rc == _lib.M2S_OK:
+                break
+            if rc != _lib.ERR_BAD_ARG or count.value <= cap:
+                _raise(rc)
+            cap = int(count.value)
+        c = int(count.value)
+        stats = (stats.cpu().numpy() if q.device else stats)[:c].view(np.uint64).reshape(c, 6)
+        box = np.ascontiguousarray(stats[:, 3:]).view(np.uint32).reshape(c, 6)
+        if q.device and hasattr(q.torch, "uint32"):
+            labels = labels.view(q.torch.uint32)
+        return Components(labels, conn, stats[:, 0].copy(), stats[:, 1].copy(), stats[:, 2].copy(), box[:, :3].copy(), box[:, 3:].copy())
+
+    def select(self, components, keep, background=None, *, timings: M2STimings = None) -> "BandField":
+        """This field with some components erased, as a new resident BandField (include/m2s.h m2s_band_select).  components: a
+        Components of this field, or a labels array with one entry per cell.  keep: the numbers of the components to keep, or a
+        boolean mask over them.  The kept cells keep every bit; an erased cell becomes inactive and outside, and so does the solid
+        interior that only erased cells bracketed along k, so that `sample` and `raymarch` no longer see an erased island.  Erase
+        islands, not voids: erasing the band around a cavity leaves the solid around it without a band cell on that side.
+        background: a scalar or (inside, outside); None keeps this field's.  The result carries `.select_info` (a SelectInfo)."""
+        h = self._handle()
+        q = self._side(timings)
+        labels = components.labels if isinstance(components, Components) else components
+        keep = np.asarray(keep.detach().cpu().numpy() if _is_torch(keep) else keep)
+        if keep.dtype == bool:
+            mask = keep.reshape(-1).astype(np.uint8)
+        else:
+            ids = keep.reshape(-1).astype(np.int64)
+            size = components.count if isinstance(components, Components) else (int(ids.max()) + 1 if ids.size else 0)
+            if ids.size and (ids.min() < 0 or ids.max() >= size):
+                raise M2SPanic(_lib.ERR_BAD_ARG, f"select: component numbers must be 0 .. {size - 1}")
+            mask = np.zeros(size, np.uint8)
+            mask[ids] = 1
+        if q.device:
+            t = q.torch
+            lab = labels if _is_torch(labels) else t.as_tensor(np.ascontiguousarray(np.asarray(labels)).astype(np.uint32).view(np.int32))
+            lab = lab.detach()
+            if lab.dtype != t.int32:
+                lab = lab.view(t.int32) if lab.dtype == getattr(t, "uint32", None) else lab.to(t.int32)
+            lab = lab.to(device=q.dev).contiguous().reshape(-1)
+            have = lab.numel()
+            if have == 0:
+                lab = t.zeros(1, dtype=t.int32, device=q.dev)
+            kp = t.as_tensor(mask, device=q.dev)
+        else:
+            lab = labels.detach().cpu().numpy() if _is_torch(labels) else np.asarray(labels)
+            lab = np.ascontiguousarray(lab.reshape(-1))
+            lab = lab.view(np.uint32) if lab.dtype in (np.uint32, np.int32) else lab.astype(np.uint32)
+            have = lab.size
+            if have == 0:
+                lab = np.zeros(1, np.uint32)
+            kp = mask
+        if have != self.count:
+            raise M2SPanic(_lib.ERR_BAD_ARG, f"select: {have} labels, the field has {self.count} cells")
+        fo = None
+        if background is not None:
+            bg_in, bg_out = _backgrounds(background)
+            fo = C.byref(_lib.M2SBandFieldOpts(C.sizeof(_lib.M2SBandFieldOpts), float(np.float32(bg_out)), float(np.float32(bg_in))))
+        info = _lib.M2SBandSelectInfo(C.sizeof(_lib.M2SBandSelectInfo))
+        out = C.c_void_p()
+        rc = _lib.lib().m2s_band_select(h, q.ptr(lab), q.ptr(kp), int(mask.size), fo, C.byref(q.opts), C.byref(out), C.byref(info))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        res = BandField._adopt(out, self.grid, self._dev)
+        res.select_info = SelectInfo(int(info.n_cells), int(info.n_dropped), int(info.n_sign_cleared))
+        return res
+
+    def keep_largest(self, k: int = 1, connectivity=6) -> "BandField":
+        """The field with all but its k largest components (by cell count; a tie goes to the lower number) erased."""
+        comps = self.components(connectivity)
+        return self.select(comps, comps.largest(k))
+
+    def remove_islands(self, min_cells: int, connectivity=6) -> "BandField":
+        """The field with every component of fewer than min_cells cells erased."""
+        comps = self.components(connectivity)
+        return self.select(comps, comps.at_least(min_cells))
+
+    def split(self, connectivity=6):
+        """One field per component, in the components' order, each with that component alone kept."""
+        comps = self.components(connectivity)
+        return [self.select(comps, [c]) for c in range(comps.count)]
 
     def smooth(self, kind, iterations: int, band, *, where: "BandField" = None) -> "BandField":
         """`filter(kind, iterations, where=where)` followed by `redistance(band)`: a smoothed field that is a distance field again.
@@ -1962,13 +2115,13 @@ class Mesh:
             inside = self.voxelize(grid, solid=True, bits=True, occupancy=False, count=False)
         return nb.field(background, inside)
 
-    def remesh(self, grid: Grid, *, iso: float = 0.0, sign_method: SignMethod = SignMethod.Raycast):
+    def remesh(self, grid: Grid, *, iso: float = 0.0, sign_method: SignMethod = SignMethod.Raycast, keep_largest: int = 0):
         """remesh on the resident mesh: the same bits as the one-shot function."""
-        return _remesh(self.narrow_band_sdf(grid, isosurface_band(grid, iso), sign_method), iso)
+        return _remesh(self.narrow_band_sdf(grid, isosurface_band(grid, iso), sign_method), iso, int(keep_largest))
 
-    def boolean(self, other: "Mesh", op, grid: Grid, *, sign_method: SignMethod = SignMethod.Raycast):
+    def boolean(self, other: "Mesh", op, grid: Grid, *, sign_method: SignMethod = SignMethod.Raycast, keep_largest: int = 0):
         """boolean on two resident meshes: the same bits as the one-shot function."""
-        return _boolean(self, other, op, grid, sign_method)
+        return _boolean(self, other, op, grid, sign_method, int(keep_largest))
 
     def sample_sdf_near_surface(self, n: int, sigmas=None, uniform_fraction: float = 0.05, sign: str = "winding", seed: int = 0):
         """sample_sdf_near_surface on this mesh."""
