@@ -1154,6 +1154,69 @@ int m2s_band_select(const m2s_band* band, const uint32_t* labels /* n_cells */, 
                     const m2s_band_field_opts* fopts /* NULL = the input's backgrounds */, const m2s_opts* opts,
                     m2s_band** out, m2s_band_select_info* info_out /* may be NULL */);
 
+/* ---- Measures of a narrow band: area, volume, centroid, per component ----------------------------------------------------------------------
+ * m2s_band_measure measures the level set d = iso of a resident band field as m2s_band_isosurface would mesh it, without building that
+ * mesh: what LevelSetMeasure is in OpenVDB and area / volume / center_mass in trimesh.  It answers "what is the interference volume of
+ * these two parts" after m2s_band_csg, "how big was the debris" after m2s_band_select, "how much material did that add" after an
+ * offset.  Nothing is sized by the grid, the band or the triangle count: the workspace is one record of raw sums per group.
+ *
+ * Groups.  labels == NULL: one group, measures_out[0].  Otherwise labels has n_cells entries in list order (what m2s_band_components
+ *   returns; device or host memory as m2s_opts.mem_kind says) and measures_out n_groups entries.  A complete cell belongs to the group
+ *   labels[r] of its base corner's list place r; a counted vertex, and an open cell, to the group of the point that owns the edge or
+ *   the cell.  Places with labels[r] >= n_groups are skipped (their cell, their vertices) and counted in n_skipped; M2S_LABEL_NONE is
+ *   the way to leave cells out, so n_groups is at most 2^32 - 1.  Nothing validates labels.  The VALUES of skipped places still serve
+ *   as corners of their neighbours' cells.
+ *
+ * THE DEFINITION (tests/band_measure_model.py restates it in numpy; the device equals it in every bit of every integer field).
+ *   The cells, cases, triangles and their order are m2s_band_isosurface's: the cells whose 8 corners are all active, the case from
+ *   d < iso, the table of isosurface_table.h.  A vertex on the edge from corner point p along axis a has the mesh vertex's
+ *   t = (iso - d0) / (d1 - d0) in float32.  Its local coordinate u in its cell is the edge's corner offset (0 or 1 per axis) with
+ *   u[a] = t; its index coordinate is U = (double)(i, j, k) + (double)u, (i, j, k) the cell's base corner.  No operation is fused;
+ *   float64 is only added, subtracted, multiplied and rounded to the nearest even integer (llrint), which numpy reproduces.  Per triangle
+ *   (U0, U1, U2) of a group:
+ *   Area, in world scale (cell sizes may differ per axis): in float32, q = u * cell_size per axis, A2 = |(q1 - q0) x (q2 - q0)| as
+ *     m2s_sample_surface's triangle weight (the squares summed left to right, sqrt; a non-finite A2 counts as 0); E =
+ *     floor(log2(cmax * cmax)) with cmax the largest cell size and the product in float32 (info_out->area_exponent);
+ *     w = (uint64) floor((double)A2 * 2^(24 - E)).  area_q = the sum of w; area = ldexp((double)area_q, E - 25).  A2 < 2^(E + 3), so
+ *     w < 2^27; 5 triangles per cell and fewer than 2^32 cells keep the sum below 2^62.
+ *   Volume, in index space (it is affine-covariant; the cell sizes come in once at the end): in float64, a = U1 - U0, b = U2 - U0,
+ *     nz = a.x * b.y - a.y * b.x, sz = (U0.z + U1.z) + U2.z.  volume_q = the sum of llrint((nz * sz) * 2^20): six times the enclosed
+ *     index volume (the divergence theorem along z) at a scale of 2^-20.  volume = volume_q * 2^-20 / 6 * cs_x * cs_y * cs_z.  The mesh
+ *     is wound outwards: a solid's volume is positive, a cavity's negative.
+ *   First moments: n = a x b; per axis c, s = ((x0*x0 + x1*x1) + x2*x2) + ((x0*x1 + x1*x2) + x2*x0) over the three U[c].  moment_q[c] =
+ *     the sum of llrint((n[c] * s) * 2^8): 24 times the first moment at a scale of 2^-8.  centroid[c] = first_cell[c] + (moment_q[c] *
+ *     2^-8 / 24) / (volume_q * 2^-20 / 6) * cell_size[c], NaN where volume_q == 0 (an empty band's, too).
+ *   A float64 term that is not finite (values so large that d1 - d0 overflows) counts as 0.
+ *   The sums are 64-bit integer adds: every order of execution gives the same bits, and two's-complement wrap-around of partial sums
+ *   is harmless as long as the true sum fits.  For a closed surface 6 V * 2^20 < 2^59 (a grid has fewer than 2^36 cells) and
+ *   24 M * 2^8 < 2^63 whenever total_cells * max(cell_count) < 2^50, THE MOMENT LIMIT: larger grids are refused.  2048^3 is 2^44.
+ *   Counts: n_triangles as above.  n_vertices = the crossing edges with both ends active, counted at the point that owns the edge (its
+ *     lower end).  n_open = the cells cut inside the band but incomplete, m2s_band_isosurface's n_open.  n_border = the counted
+ *     vertices whose edge lies in a boundary face of the grid: for an axis other than the edge's own, the owner's index is 0 or
+ *     cell_count - 1.
+ *   CLOSED: the surface of a group is closed exactly when n_open == 0 && n_border == 0.  Only then are volume and centroid a volume
+ *   and a centre of mass; otherwise they are still the sums defined above and depend on the grid's origin.  For a closed group
+ *   n_vertices - n_triangles / 2 is its Euler characteristic.  Label with connectivity 26 to have it per mesh component: the 8 corners
+ *   of a cell are mutually 26-adjacent, so a mesh component never straddles two labels.
+ *   The raw sums do not depend on first_cell, and on cell_size only through the area.
+ * measures_out is HOST memory whatever mem_kind says (as area_out of m2s_sample_surface).  Always synchronous.  An empty band gives
+ *   zeros (and NaN centroids) and M2S_OK.  M2S_ERR_BAD_ARG before any device work: a NULL band or measures_out; a struct_size other than
+ *   sizeof (mopts, info_out); a non-finite iso; labels with n_groups == 0 or n_groups >= 2^32; an m2s_opts.device that is not the
+ *   handle's (-1 means its own); algorithm, x_begin, x_end, x_period or peer_out not zero; a bad mem_kind; a grid past the moment limit.
+ *   m2s_opts: device, stream / stream_mode, lane; mem_kind covers labels.  timings (the argument; m2s_opts.timings serves when it is
+ *   NULL): distance_ms = total_ms = the one kernel and the clearing of its records, n_units = the band's cells.
+ *   Memory during the call: 72 bytes per group, and a host caller's labels. */
+typedef struct m2s_band_measure_opts { uint32_t struct_size; float iso; } m2s_band_measure_opts;          /* NULL = iso 0 */
+typedef struct m2s_band_measure_record {
+  uint64_t n_triangles, n_vertices, n_open, n_border;   /* integers, as counted above */
+  uint64_t area_q;  int64_t volume_q;  int64_t moment_q[3];   /* the raw sums the definition fixes to the bit */
+  double area, volume, centroid[3];                     /* world units, derived on the host from the raw sums */
+} m2s_band_measure_record;   /* 112 bytes; a typedef cannot share the call's name */
+typedef struct m2s_band_measure_info { uint32_t struct_size; int32_t area_exponent; uint64_t n_groups, n_skipped; } m2s_band_measure_info;   /* 24 bytes */
+int m2s_band_measure(const m2s_band* band, const m2s_band_measure_opts* mopts, const uint32_t* labels /* n_cells, list order; NULL = one group */,
+                     uint64_t n_groups, const m2s_opts* opts, m2s_band_measure_record* measures_out /* HOST, n_groups entries (1 if labels is NULL) */,
+                     m2s_band_measure_info* info_out /* may be NULL */, m2s_timings* timings /* may be NULL */);
+
 /* glTF 2.0 / GLB ingestion (host side) — what the reference client extracts from a file before the merge:
  * mesh_to_sdf_client/src/gltf/mod.rs:56-174 (models keyed by mesh index, one primitive per mesh survives;
  * POSITION + indices, sparse accessors and byteStride honoured; missing indices = 0..n, pbr/model.rs:29-32),

@@ -650,6 +650,14 @@ struct Components {
 struct SelectInfo {
   uint64_t n_cells = 0, n_dropped = 0, n_sign_cleared = 0;
 };
+// What BandField::measure returns (m2s_band_measure_record): the level set measured as band_isosurface would mesh it.  The counts, the
+// raw integer sums the C header defines to the bit, and area, volume and centroid in world units.
+struct Measure : m2s_band_measure_record {
+  // Only a closed surface has a volume and a centre of mass; otherwise volume and centroid are the defined sums and depend on the origin.
+  bool closed() const { return n_open == 0 && n_border == 0; }
+  // The Euler characteristic of a closed surface: 2 for a sphere, 0 for a torus.
+  int64_t euler() const { return (int64_t)n_vertices - (int64_t)(n_triangles / 2); }
+};
 template <class V>
 class BandField {
  public:
@@ -836,6 +844,29 @@ class BandField {
     for (uint32_t id : c.largest(k)) keep[id] = 1;
     return select(c.labels, keep, info);
   }
+  // The level set d = iso measured without a mesh (m2s_band_measure): triangle and vertex counts, area, enclosed volume, centroid.
+  Measure measure(float iso = 0.0f) const {
+    m2s_band_measure_opts mo{};
+    mo.struct_size = sizeof(mo);
+    mo.iso = iso;
+    Measure r{};
+    detail::check(m2s_band_measure(h_, &mo, nullptr, 0, nullptr, &r, nullptr, nullptr));
+    return r;
+  }
+  // One Measure per group: a cell belongs to the group labels[r] of its base corner (Components::labels with count() groups; label with
+  // Connectivity::Corners to measure per mesh component); a label of n_groups or more, M2S_LABEL_NONE included, leaves the cell out.
+  std::vector<Measure> measure(const std::vector<uint32_t>& labels, uint64_t n_groups, float iso = 0.0f) const {
+    if (labels.size() != count()) throw Panic(M2S_ERR_BAD_ARG, "measure: one label per cell");
+    static const uint32_t none = M2S_LABEL_NONE;
+    m2s_band_measure_opts mo{};
+    mo.struct_size = sizeof(mo);
+    mo.iso = iso;
+    std::vector<Measure> r(n_groups);
+    static_assert(sizeof(Measure) == sizeof(m2s_band_measure_record), "Measure adds no data to the record");
+    detail::check(m2s_band_measure(h_, &mo, labels.empty() ? &none : labels.data(), n_groups, nullptr, r.data(), nullptr, nullptr));
+    return r;
+  }
+  std::vector<Measure> measure(const Components& c, float iso = 0.0f) const { return measure(c.labels, c.count(), iso); }
   // The field's lists back out (m2s_band_export): cells ascending, distances bit for bit, and `bits` the sign mask in the layout of
   // Voxels::bits (all zero for a field made without one).  band_isosurface(grid, b.cells, b.distances) meshes it.
   NarrowBand export_band() const {

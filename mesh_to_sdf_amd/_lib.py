@@ -181,6 +181,19 @@ class M2SBandSelectInfo(C.Structure):
 LABEL_NONE = 0xffffffff
 
 
+class M2SBandMeasureOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iso", C.c_float)]
+
+
+class M2SBandMeasureRecord(C.Structure):
+    _fields_ = [("n_triangles", C.c_uint64), ("n_vertices", C.c_uint64), ("n_open", C.c_uint64), ("n_border", C.c_uint64), ("area_q", C.c_uint64),
+                ("volume_q", C.c_int64), ("moment_q", C.c_int64 * 3), ("area", C.c_double), ("volume", C.c_double), ("centroid", C.c_double * 3)]
+
+
+class M2SBandMeasureInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("area_exponent", C.c_int32), ("n_groups", C.c_uint64), ("n_skipped", C.c_uint64)]
+
+
 class M2SSampleOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("iso", C.c_float), ("outside", C.c_float), ("max_steps", C.c_uint32)]
 
@@ -248,6 +261,7 @@ EXPORTS = [
     "m2s_band_resample",
     "m2s_band_components",
     "m2s_band_select",
+    "m2s_band_measure",
     "m2s_merge_instances",
     "m2s_gltf_open",
     "m2s_gltf_instances",
@@ -361,6 +375,8 @@ def _prototypes():
                                           C.POINTER(C.c_uint64)]),
         "m2s_band_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
                                       C.POINTER(C.c_void_p), C.POINTER(M2SBandSelectInfo)]),
+        "m2s_band_measure": (C.c_int, [C.c_void_p, C.POINTER(M2SBandMeasureOpts), C.c_void_p, C.c_uint64, C.POINTER(M2SOpts),
+                                       C.POINTER(M2SBandMeasureRecord), C.POINTER(M2SBandMeasureInfo), C.POINTER(M2STimings)]),
         "m2s_merge_instances": (C.c_int, [C.POINTER(M2SInstance), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(M2SOpts)]),
         "m2s_gltf_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(M2SGltfInfo)]),
         "m2s_gltf_instances": (C.c_int, [C.c_void_p, C.POINTER(M2SInstance), C.c_size_t]),

@@ -1180,6 +1180,30 @@ class Components:
         """The numbers of the components with min_cells cells or more, ascending."""
         return np.flatnonzero(self.n_cells >= int(min_cells)).astype(np.int64)
 
+    def measure(self, field: "BandField", iso: float = 0.0):
+        """`field.measure(iso, self)`: one Measure per component of the level set d = iso of `field`, whose labelling this is."""
+        return field.measure(iso, self)
+
+
+class Measure(NamedTuple):
+    """include/m2s.h `m2s_band_measure_record`: the level set d = iso of a BandField, or of one group of its cells, measured as
+    `isosurface` would mesh it.  n_triangles, n_vertices, n_open (cells cut inside the band but incomplete) and n_border (vertices on a
+    boundary face of the grid) are counts; area_q, volume_q and moment_q are the raw integer sums the header defines to the bit; area,
+    volume and centroid are world units.  closed: n_open == 0 and n_border == 0; only then are volume and centroid a volume and a
+    centre of mass.  euler: n_vertices - n_triangles / 2, the Euler characteristic of a closed surface."""
+    n_triangles: int
+    n_vertices: int
+    n_open: int
+    n_border: int
+    area_q: int
+    volume_q: int
+    moment_q: tuple
+    area: float
+    volume: float
+    centroid: tuple
+    closed: bool
+    euler: int
+
 
 def _similarity(transform):
     """A 3 x 4 or 4 x 4 map p = A q + t from source space to target space -> (to_source float32[12], value_scale float32): checked in
@@ -1487,6 +1511,73 @@ class BandField:
             labels = labels.view(q.torch.uint32)
         return Components(labels, conn, stats[:, 0].copy(), stats[:, 1].copy(), stats[:, 2].copy(), box[:, :3].copy(), box[:, 3:].copy())
 
+    def _labels_arg(self, q, labels, what):
+        """One label per cell, a device tensor or a host array, as the 32-bit array a call on q's side reads (one entry at least)."""
+        if q.device:
+            t = q.torch
+            lab = labels if _is_torch(labels) else t.as_tensor(np.ascontiguousarray(np.asarray(labels)).astype(np.uint32).view(np.int32))
+            lab = lab.detach()
+            if lab.dtype != t.int32:
+                lab = lab.view(t.int32) if lab.dtype == getattr(t, "uint32", None) else lab.to(t.int32)
+            lab = lab.to(device=q.dev).contiguous().reshape(-1)
+            have = lab.numel()
+            if have == 0:
+                lab = t.zeros(1, dtype=t.int32, device=q.dev)
+        else:
+            lab = labels.detach().cpu().numpy() if _is_torch(labels) else np.asarray(labels)
+            lab = np.ascontiguousarray(lab.reshape(-1))
+            lab = lab.view(np.uint32) if lab.dtype in (np.uint32, np.int32) else lab.astype(np.uint32)
+            have = lab.size
+            if have == 0:
+                lab = np.zeros(1, np.uint32)
+        if have != self.count:
+            raise M2SPanic(_lib.ERR_BAD_ARG, f"{what}: {have} labels, the field has {self.count} cells")
+        return lab
+
+    def measure(self, iso: float = 0.0, components=None, *, n_groups: int = None, timings: M2STimings = None):
+        """The level set d = iso of this field measured as `isosurface` would mesh it, without building the mesh (include/m2s.h
+        m2s_band_measure): a Measure with the triangle and vertex counts, area, enclosed volume and centroid.  components: a Components
+        of this field (a list of Measures, one per component), or a labels array with one entry per cell and n_groups (cells whose
+        label is n_groups or more, LABEL_NONE among them, are left out).  Label with connectivity 26 to measure per mesh component.
+        The last call's `m2s_band_measure_info` is kept as `.measure_info` = (area_exponent, n_groups, n_skipped)."""
+        h = self._handle()
+        q = self._side(timings)
+        mo = _lib.M2SBandMeasureOpts(C.sizeof(_lib.M2SBandMeasureOpts), float(np.float32(iso)))
+        p_l, groups = None, 1
+        if components is not None:
+            if isinstance(components, Components):
+                labels, groups = components.labels, components.count
+            else:
+                if n_groups is None:
+                    raise M2SPanic(_lib.ERR_BAD_ARG, "measure: labels need n_groups")
+                labels, groups = components, int(n_groups)
+            if groups == 0 and self.count == 0:
+                return []
+            lab = self._labels_arg(q, labels, "measure")
+            p_l = q.ptr(lab)
+        out = (_lib.M2SBandMeasureRecord * max(groups, 1))()
+        info = _lib.M2SBandMeasureInfo(C.sizeof(_lib.M2SBandMeasureInfo))
+        rc = _lib.lib().m2s_band_measure(h, C.byref(mo), p_l, groups, C.byref(q.opts), out, C.byref(info), None)
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        self.measure_info = (int(info.area_exponent), int(info.n_groups), int(info.n_skipped))
+        res = [Measure(int(m.n_triangles), int(m.n_vertices), int(m.n_open), int(m.n_border), int(m.area_q), int(m.volume_q), tuple(int(v) for v in m.moment_q),
+                       float(m.area), float(m.volume), tuple(float(v) for v in m.centroid), m.n_open == 0 and m.n_border == 0,
+                       int(m.n_vertices) - int(m.n_triangles) // 2) for m in out[:groups]]
+        return res[0] if components is None else res
+
+    def area(self, iso: float = 0.0) -> float:
+        """The area of the level set d = iso (`measure(iso).area`)."""
+        return self.measure(iso).area
+
+    def volume(self, iso: float = 0.0) -> float:
+        """The volume the level set d = iso encloses (`measure(iso).volume`; a volume only where the surface is closed)."""
+        return self.measure(iso).volume
+
+    def centroid(self, iso: float = 0.0):
+        """The centre of mass of the solid the level set d = iso bounds (`measure(iso).centroid`; only where the surface is closed)."""
+        return self.measure(iso).centroid
+
     def select(self, components, keep, background=None, *, timings: M2STimings = None) -> "BandField":
         """This field with some components erased, as a new resident BandField (include/m2s.h m2s_band_select).  components: a
         Components of this field, or a labels array with one entry per cell.  keep: the numbers of the components to keep, or a
@@ -1507,27 +1598,8 @@ class BandField:
                 raise M2SPanic(_lib.ERR_BAD_ARG, f"select: component numbers must be 0 .. {size - 1}")
             mask = np.zeros(size, np.uint8)
             mask[ids] = 1
-        if q.device:
-            t = q.torch
-            lab = labels if _is_torch(labels) else t.as_tensor(np.ascontiguousarray(np.asarray(labels)).astype(np.uint32).view(np.int32))
-            lab = lab.detach()
-            if lab.dtype != t.int32:
-                lab = lab.view(t.int32) if lab.dtype == getattr(t, "uint32", None) else lab.to(t.int32)
-            lab = lab.to(device=q.dev).contiguous().reshape(-1)
-            have = lab.numel()
-            if have == 0:
-                lab = t.zeros(1, dtype=t.int32, device=q.dev)
-            kp = t.as_tensor(mask, device=q.dev)
-        else:
-            lab = labels.detach().cpu().numpy() if _is_torch(labels) else np.asarray(labels)
-            lab = np.ascontiguousarray(lab.reshape(-1))
-            lab = lab.view(np.uint32) if lab.dtype in (np.uint32, np.int32) else lab.astype(np.uint32)
-            have = lab.size
-            if have == 0:
-                lab = np.zeros(1, np.uint32)
-            kp = mask
-        if have != self.count:
-            raise M2SPanic(_lib.ERR_BAD_ARG, f"select: {have} labels, the field has {self.count} cells")
+        lab = self._labels_arg(q, labels, "select")
+        kp = q.torch.as_tensor(mask, device=q.dev) if q.device else mask
         fo = None
         if background is not None:
             bg_in, bg_out = _backgrounds(background)
