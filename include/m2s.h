@@ -1217,6 +1217,56 @@ int m2s_band_measure(const m2s_band* band, const m2s_band_measure_opts* mopts, c
                      uint64_t n_groups, const m2s_opts* opts, m2s_band_measure_record* measures_out /* HOST, n_groups entries (1 if labels is NULL) */,
                      m2s_band_measure_info* info_out /* may be NULL */, m2s_timings* timings /* may be NULL */);
 
+/* ---- Band fields from spheres and capsules: points, particles, struts ----------------------------------------------------------------------
+ * m2s_band_from_capsules makes a resident band field of a union of capsules without a mesh: what ParticlesToLevelSet,
+ * createLevelSetSphere and createLevelSetCapsule are in OpenVDB.  A capsule is a segment a-b with a radius r; a sphere is the capsule
+ * with a == b (b == NULL makes every shape one).  A particle set becomes a surface (this, a filter, m2s_band_isosurface), a graph of
+ * edges a strut lattice, `field - capsule` (m2s_band_csg) a drilled hole.  Nothing is sized 4 bytes per grid point: the result's three
+ * bit planes, its values, and 72 bytes per shape of workspace.
+ *
+ * THE DEFINITION (mesh_to_sdf_amd/csrc/shape.hip.h states it with its error bound; tests/band_shapes_model.py restates it in numpy; the
+ * device equals it in every bit).  A shape is SOUND when its coordinates are finite and its radius is finite and >= 0; the others are
+ * counted in n_skipped and take no part.  For a grid point with centre c = first_cell + (float)index * cell_size per axis and a sound
+ * shape s, in binary32 with no operation fused and sums left to right:
+ *     ab = b - a;  ap = c - a;  den = (ab.x*ab.x + ab.y*ab.y) + ab.z*ab.z
+ *     t  = den > 0 ? clamp(((ap.x*ab.x + ap.y*ab.y) + ap.z*ab.z) / den, 0, 1) : 0
+ *     e  = ap - t*ab                    (per component: one product, one subtraction)
+ *     d_s = sqrtf((e.x*e.x + e.y*e.y) + e.z*e.z) - r
+ *   D(c) = the minimum of d_s over the sound shapes (+inf when there is none; a d_s that is NaN takes no part).  A point is ACTIVE iff
+ *   -interior <= D <= exterior, and its value is D.  The sign bit is D < 0 at EVERY grid point, active or not.  So a point buried deeper
+ *   than `interior` in one shape is inactive even where another shape's surface passes through it, and a small ball inside a large one
+ *   adds no cells.  A minimum is the same in any order: the result does not depend on the order of the shapes or of execution.
+ *   Outside the union D is the Euclidean distance to it up to 96 * 2^-24 * the largest |coordinate| (shape.hip.h derives it); inside it
+ *   is a lower bound of the depth, as after every level-set CSG: m2s_band_redistance makes distances of it again.
+ * sopts: the half-widths (both >= 0 and finite) and the radius every shape takes when `radius` is NULL (>= 0 and finite).  fopts: the
+ *   result's backgrounds; NULL = (exterior, interior), the widths.  a, b, radius: host or device memory as m2s_opts.mem_kind says.
+ * info: n_cells = the result's cells; n_inside = the set bits of its sign mask; n_skipped = the shapes that are not sound;
+ *   n_off_grid = the sound shapes with no grid point at d_s <= exterior.
+ * The result is an ordinary handle with a sign mask (m2s_band_info's device_bytes by the formula for one; the values are an allocation
+ *   of their own, sized by the count).  n == 0, or no shape that reaches the grid, gives an empty field and M2S_OK.
+ * M2S_ERR_BAD_ARG before any device work: a NULL out, grid or sopts; a struct_size other than sizeof (sopts, fopts); a width or
+ *   sopts->radius that is negative or not finite; a NULL `a` with n > 0; n >= 2^32; a cell_size that is not > 0 and finite, a grid box
+ *   that is not finite, a cell_count of 0, or of 2^32 or more on one axis; a grid of 2^36 or more points; algorithm, x_begin, x_end,
+ *   x_period or peer_out not zero; a bad mem_kind.  m2s_opts: device, stream / stream_mode, lane, mem_kind.  Always synchronous.
+ *   timings (the argument; m2s_opts.timings serves when it is NULL): seed_ms = the shapes' boxes, the three bit planes, the mask and
+ *   its offsets; distance_ms = the values; total_ms = the whole call; n_units = the result's cells; n_triangles = the sound shapes. */
+typedef struct m2s_band_shapes_opts {
+  uint32_t struct_size;
+  float exterior, interior;   /* half-widths: active iff -interior <= D <= exterior; both >= 0 and finite */
+  float radius;               /* used by every shape when `radius` (the array) is NULL; >= 0 and finite */
+} m2s_band_shapes_opts;
+typedef struct m2s_band_shapes_info {
+  uint64_t n_cells;      /* active cells of the result */
+  uint64_t n_inside;     /* grid points with D < 0 (set bits of the sign mask) */
+  uint64_t n_skipped;    /* shapes with a non-finite coordinate or a radius that is negative or non-finite */
+  uint64_t n_off_grid;   /* sound shapes that reach no grid point within `exterior` */
+} m2s_band_shapes_info;
+int m2s_band_from_capsules(const m2s_grid* grid, const float* a /* n x 3 */, const float* b /* n x 3, or NULL: spheres, b = a */,
+                           const float* radius /* n, or NULL: sopts->radius for all */, uint64_t n /* < 2^32; 0 gives an empty field */,
+                           const m2s_band_shapes_opts* sopts, const m2s_band_field_opts* fopts /* NULL = the widths */,
+                           const m2s_opts* opts, m2s_band** out, m2s_band_shapes_info* info /* may be NULL */,
+                           m2s_timings* timings /* may be NULL */);
+
 /* glTF 2.0 / GLB ingestion (host side) — what the reference client extracts from a file before the merge:
  * mesh_to_sdf_client/src/gltf/mod.rs:56-174 (models keyed by mesh index, one primitive per mesh survives;
  * POSITION + indices, sparse accessors and byteStride honoured; missing indices = 0..n, pbr/model.rs:29-32),

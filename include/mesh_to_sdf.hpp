@@ -658,6 +658,9 @@ struct Measure : m2s_band_measure_record {
   // The Euler characteristic of a closed surface: 2 for a sphere, 0 for a torus.
   int64_t euler() const { return (int64_t)n_vertices - (int64_t)(n_triangles / 2); }
 };
+// What BandField::from_capsules reports (m2s_band_shapes_info): the result's cells, the grid points inside the union, the shapes left out
+// (a non-finite coordinate or radius, a negative radius) and the sound shapes that reach no grid point within the exterior width.
+struct ShapesInfo : m2s_band_shapes_info {};
 template <class V>
 class BandField {
  public:
@@ -878,6 +881,32 @@ class BandField {
     r.bits.resize(n[0] * n[1] * ((n[2] + 31) / 32));
     detail::check(m2s_band_export(h_, r.count ? r.cells.data() : nullptr, r.count ? r.distances.data() : nullptr, r.count, r.bits.data(), nullptr));
     return r;
+  }
+  // The union of the capsules a[n]-b[n] with the radii radius[n] as a resident field, with no mesh (m2s_band_from_capsules: the smallest
+  // distance to a capsule's surface per grid point and to the bit, active within the half-widths, a sign mask on every point).  b empty:
+  // spheres.  radius: one per shape, or a single value for all.  The backgrounds are the two widths.  Inside the union the values are a
+  // lower bound of the depth: redistance makes distances of them.
+  static BandField from_capsules(const Grid<V>& grid, const std::vector<V>& a, const std::vector<V>& b, const std::vector<float>& radius, float exterior,
+                                 float interior, ShapesInfo* info = nullptr) {
+    if (!b.empty() && b.size() != a.size()) throw Panic(M2S_ERR_BAD_ARG, "from_capsules: a and b differ in length");
+    if (radius.size() != a.size() && radius.size() != 1) throw Panic(M2S_ERR_BAD_ARG, "from_capsules: one radius per shape, or one for all");
+    detail::Packed<V> pa(a.data(), a.size()), pb(b.data(), b.size());
+    m2s_band_shapes_opts so{};
+    so.struct_size = sizeof(so);
+    so.exterior = exterior;
+    so.interior = interior;
+    const bool one = radius.size() == 1 && a.size() != 1;
+    so.radius = one ? radius[0] : 0.0f;
+    ShapesInfo si{};
+    m2s_band* h = nullptr;
+    detail::check(m2s_band_from_capsules(&grid.raw(), pa.ptr, b.empty() ? nullptr : pb.ptr, one ? nullptr : radius.data(), a.size(), &so, nullptr, nullptr, &h,
+                                         &si, nullptr));
+    if (info) *info = si;
+    return BandField(grid, h);
+  }
+  static BandField from_spheres(const Grid<V>& grid, const std::vector<V>& centers, const std::vector<float>& radius, float exterior, float interior,
+                                ShapesInfo* info = nullptr) {
+    return from_capsules(grid, centers, {}, radius, exterior, interior, info);
   }
   float background_outside() const { return field_info().background_outside; }
   float background_inside() const { return field_info().background_inside; }

@@ -194,6 +194,14 @@ class M2SBandMeasureInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("area_exponent", C.c_int32), ("n_groups", C.c_uint64), ("n_skipped", C.c_uint64)]
 
 
+class M2SBandShapesOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("exterior", C.c_float), ("interior", C.c_float), ("radius", C.c_float)]
+
+
+class M2SBandShapesInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_inside", C.c_uint64), ("n_skipped", C.c_uint64), ("n_off_grid", C.c_uint64)]
+
+
 class M2SSampleOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("iso", C.c_float), ("outside", C.c_float), ("max_steps", C.c_uint32)]
 
@@ -262,6 +270,7 @@ EXPORTS = [
     "m2s_band_components",
     "m2s_band_select",
     "m2s_band_measure",
+    "m2s_band_from_capsules",
     "m2s_merge_instances",
     "m2s_gltf_open",
     "m2s_gltf_instances",
@@ -377,6 +386,9 @@ def _prototypes():
                                       C.POINTER(C.c_void_p), C.POINTER(M2SBandSelectInfo)]),
         "m2s_band_measure": (C.c_int, [C.c_void_p, C.POINTER(M2SBandMeasureOpts), C.c_void_p, C.c_uint64, C.POINTER(M2SOpts),
                                        C.POINTER(M2SBandMeasureRecord), C.POINTER(M2SBandMeasureInfo), C.POINTER(M2STimings)]),
+        "m2s_band_from_capsules": (C.c_int, [C.POINTER(M2SGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(M2SBandShapesOpts),
+                                             C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts), C.POINTER(C.c_void_p), C.POINTER(M2SBandShapesInfo),
+                                             C.POINTER(M2STimings)]),
         "m2s_merge_instances": (C.c_int, [C.POINTER(M2SInstance), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(M2SOpts)]),
         "m2s_gltf_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(M2SGltfInfo)]),
         "m2s_gltf_instances": (C.c_int, [C.c_void_p, C.POINTER(M2SInstance), C.c_size_t]),

@@ -1205,6 +1205,16 @@ class Measure(NamedTuple):
     euler: int
 
 
+class ShapesInfo(NamedTuple):
+    """include/m2s.h `m2s_band_shapes_info`: the result's cells, the grid points inside the union (the set bits of its sign mask), the
+    shapes left out because a coordinate was not finite or the radius negative or not finite, and the sound shapes that reach no
+    grid point within the exterior width."""
+    n_cells: int
+    n_inside: int
+    n_skipped: int
+    n_off_grid: int
+
+
 def _similarity(transform):
     """A 3 x 4 or 4 x 4 map p = A q + t from source space to target space -> (to_source float32[12], value_scale float32): checked in
     float64 to be a similarity (A^T A = s^2 I to a relative 1e-5; reflections pass), inverted as [A^T / s^2, -A^T t / s^2]."""
@@ -1351,6 +1361,87 @@ class BandField:
         self.count, self.device_bytes = int(n.value), int(nbytes.value)
         self.background = (float(fo.background_inside), float(fo.background_outside))
         return self
+
+    @classmethod
+    def from_capsules(cls, grid: Grid, a, b, radius, band, *, background=None, timings: M2STimings = None) -> "BandField":
+        """The union of the capsules a[n]-b[n] with the radii `radius` as a resident BandField, with no mesh on the way (include/m2s.h
+        m2s_band_from_capsules states the result per grid point, to the bit): the value is the smallest distance to a capsule's
+        surface, active where it lies within the half-widths `band` (a scalar or (interior, exterior)), with a sign mask on every
+        point.  a, b: float32[n, 3], numpy arrays or device tensors (a CUDA tensor `a` keeps the call on its device); b None: spheres.
+        radius: a scalar or an array of n.  background: a scalar or (inside, outside); None is the two widths.  Shapes with a
+        non-finite coordinate or radius, or a negative radius, are left out and counted.  Inside the union the values are a lower
+        bound of the depth: follow with `redistance` before reading them as distances.  The result carries `.shapes_info` (a
+        ShapesInfo)."""
+        interior, exterior = _band_widths(band)
+        q = _GridQuery(a if _is_torch(a) and a.is_cuda else np.zeros(0, np.float32), timings)
+        p_a, n = q.points(a)
+        p_b = None
+        if b is not None:
+            p_b, n_b = q.points(b)
+            if n_b != n:
+                raise M2SPanic(_lib.ERR_BAD_ARG, f"{n} first ends but {n_b} second ends")
+        so = _lib.M2SBandShapesOpts(C.sizeof(_lib.M2SBandShapesOpts), float(np.float32(exterior)), float(np.float32(interior)), 0.0)
+        p_r = None
+        if np.isscalar(radius):
+            so.radius = float(np.float32(radius))
+        else:
+            if q.device:
+                r = radius if _is_torch(radius) else q.torch.as_tensor(np.asarray(radius, np.float32))
+                r = r.detach().to(device=q.dev, dtype=q.torch.float32).contiguous().reshape(-1)
+                n_r = r.numel()
+            else:
+                r = radius.detach().cpu().numpy() if _is_torch(radius) else radius
+                r = np.ascontiguousarray(np.asarray(r, np.float32)).reshape(-1)
+                n_r = r.size
+            if n_r != n:
+                raise M2SPanic(_lib.ERR_BAD_ARG, f"{n} shapes but {n_r} radii")
+            p_r = q.ptr(r)
+        fo = None
+        if background is not None:
+            bg_in, bg_out = _backgrounds(background)
+            fo = C.byref(_lib.M2SBandFieldOpts(C.sizeof(_lib.M2SBandFieldOpts), float(np.float32(bg_out)), float(np.float32(bg_in))))
+        info = _lib.M2SBandShapesInfo()
+        h = C.c_void_p()
+        rc = _lib.lib().m2s_band_from_capsules(C.byref(grid._g), p_a, p_b, p_r, n, C.byref(so), fo, C.byref(q.opts), C.byref(h), C.byref(info), None)
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        out = cls._adopt(h, grid, q.dev if q.device else None)
+        out.shapes_info = ShapesInfo(int(info.n_cells), int(info.n_inside), int(info.n_skipped), int(info.n_off_grid))
+        return out
+
+    @classmethod
+    def from_spheres(cls, grid: Grid, centers, radius, band, *, background=None, timings: M2STimings = None) -> "BandField":
+        """The union of the balls around centers[n] with the radii `radius` (a scalar or an array): `from_capsules` with b = a.  A
+        particle set becomes a surface with `from_spheres(...).smooth(...).isosurface()`."""
+        return cls.from_capsules(grid, centers, None, radius, band, background=background, timings=timings)
+
+    @classmethod
+    def from_points(cls, grid: Grid, points, radius: float, band, *, background=None, timings: M2STimings = None) -> "BandField":
+        """`from_spheres` with one radius for every point: a point cloud dilated by `radius`."""
+        return cls.from_spheres(grid, points, float(radius), band, background=background, timings=timings)
+
+    @classmethod
+    def from_edges(cls, grid: Grid, vertices, edges, radius, band, *, background=None, timings: M2STimings = None) -> "BandField":
+        """The union of the capsules along the edges[m] = (i, j) of the graph on vertices[n]: a strut lattice, a dilated wireframe.
+        radius: a scalar, or one per edge.  The two ends are gathered on the side of `vertices` and go to `from_capsules`."""
+        if _is_torch(vertices) and vertices.is_cuda:
+            import torch
+
+            v = vertices.detach().to(torch.float32).reshape(-1, 3)
+            e = edges if _is_torch(edges) else torch.as_tensor(np.asarray(edges).astype(np.int64))
+            e = e.detach().to(device=v.device, dtype=torch.int64).reshape(-1, 2)
+            if e.numel() and (int(e.min()) < 0 or int(e.max()) >= v.shape[0]):
+                raise M2SPanic(_lib.ERR_BAD_ARG, f"edges name a vertex outside [0, {v.shape[0]})")
+            a, b = v[e[:, 0]].contiguous(), v[e[:, 1]].contiguous()
+        else:
+            v = vertices.detach().cpu().numpy() if _is_torch(vertices) else vertices
+            v = np.asarray(v, np.float32).reshape(-1, 3)
+            e = edges.detach().cpu().numpy() if _is_torch(edges) else edges
+            e = np.asarray(e).astype(np.int64).reshape(-1, 2)
+            if e.size and (int(e.min()) < 0 or int(e.max()) >= v.shape[0]):
+                raise M2SPanic(_lib.ERR_BAD_ARG, f"edges name a vertex outside [0, {v.shape[0]})")
+            a, b = v[e[:, 0]], v[e[:, 1]]
+        return cls.from_capsules(grid, a, b, radius, band, background=background, timings=timings)
 
     def _side(self, timings=None) -> "_GridQuery":
         """The options and buffers of a call with no input array, on the side this field's lists came from."""

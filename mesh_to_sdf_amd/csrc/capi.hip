@@ -1314,6 +1314,7 @@ int m2s_warmup(int device, size_t workspace_bytes, size_t host_ring_bytes) {
   warm_band_resample(c.stream);
   warm_band_components(c.stream);
   warm_band_measure(c.stream);
+  warm_band_shapes(c.stream);
   warm_sortlib(c.stream);                                        // (the rocPRIM sorts of large meshes and of the query path: units of their own,
   warm_sortlib_query(c.stream);                                  // which a grid call over a mesh of <= 229 376 triangles never loads)
   M2S_HIP_CHECK(hipGetLastError());

@@ -307,6 +307,7 @@ void warm_band_filter(hipStream_t st);
 void warm_band_resample(hipStream_t st);
 void warm_band_components(hipStream_t st);
 void warm_band_measure(hipStream_t st);
+void warm_band_shapes(hipStream_t st);
 // bvh.hip: flatten topology, build triangle records + LBVH in pre-order layout.
 size_t bvh_workspace_bytes(size_t n_tris);
 // `after_setup` (optional) is called twice with the input-order centroid array and triangle records: with phase 0 once the kernels that fill

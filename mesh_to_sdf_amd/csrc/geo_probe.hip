@@ -1,5 +1,5 @@
-// geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h, sample.hip.h, voxel.hip.h, band.hip.h, cut_size.hip.h and sign.hip.h, for CPU unit tests only
-// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py, tests/test_narrow_band_cpu.py, tests/test_cut_size_cpu.py, tests/test_walk_leaf_count_cpu.py, tests/test_pair_eval_cpu.py, tests/test_sign_planes_cpu.py).  Not linked into libm2s_hip.so.
+// geo_probe.hip — HOST build of the device math in geo.hip.h, ray.hip.h, sample.hip.h, voxel.hip.h, band.hip.h, cut_size.hip.h, sign.hip.h and shape.hip.h, for CPU unit tests only
+// (tests/test_device_math_host.py, tests/test_rays_cpu.py, tests/test_sample_cpu.py, tests/test_voxelize_cpu.py, tests/test_narrow_band_cpu.py, tests/test_cut_size_cpu.py, tests/test_walk_leaf_count_cpu.py, tests/test_pair_eval_cpu.py, tests/test_sign_planes_cpu.py, tests/test_band_shapes_cpu.py).  Not linked into libm2s_hip.so.
 #include "geo.hip.h"
 #include "ray.hip.h"
 #include "sample.hip.h"
@@ -7,6 +7,7 @@
 #include "band.hip.h"
 #include "cut_size.hip.h"
 #include "sign.hip.h"
+#include "shape.hip.h"
 
 using namespace m2s;
 
@@ -238,4 +239,24 @@ void probe_sign_path(uint32_t n_tris, const uint32_t* n, uint32_t* out, uint64_t
   out[0] = p.lanes; out[1] = p.list ? 1u : 0u; out[2] = p.rows ? 1u : 0u;
   consts[0] = SMALL_WINDOW; consts[1] = RAY_MARK_SHARED_BELOW; consts[2] = LIST_ABOVE_LINES; consts[3] = BIG_CHUNK;
 }
+// shape.hip.h
+static Capsule probe_capsule(const float* s) { return Capsule{{s[0], s[1], s[2]}, {s[3], s[4], s[5]}, s[6]}; }
+// n (shape, point) pairs: shapes 7 floats each (a, b, r), points 3 floats each; out[i] = d_s
+void probe_shape_dist_n(uint64_t n, const float* shapes, const float* points, float* out) {
+  for (uint64_t i = 0; i < n; ++i) out[i] = shape_dist(probe_capsule(shapes + 7 * i), points[3 * i], points[3 * i + 1], points[3 * i + 2]);
+}
+// lo_hi = lo[3], hi[3] of the shape's index box on the grid; returns shape_sound (0: lo_hi untouched)
+int probe_shape_box(const float* shape, const float* first, const float* size, const uint32_t* n, float exterior, uint32_t* lo_hi) {
+  const Capsule s = probe_capsule(shape);
+  if (!shape_sound(s)) return 0;
+  const float f[3] = {first[0], first[1], first[2]}, sz[3] = {size[0], size[1], size[2]};
+  const uint32_t cnt[3] = {n[0], n[1], n[2]};
+  uint32_t lo[3], hi[3];
+  shape_box(s, f, sz, cnt, exterior, shape_grid_scale(f, sz, cnt), lo, hi);
+  for (int m = 0; m < 3; ++m) { lo_hi[m] = lo[m]; lo_hi[3 + m] = hi[m]; }
+  return 1;
+}
+uint32_t probe_shape_key(float x) { return shape_key(x); }
+float probe_shape_unkey(uint32_t k) { return shape_unkey(k); }
+float probe_shape_err_u(void) { return SHAPE_ERR_U; }
 }
