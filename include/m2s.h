@@ -49,7 +49,7 @@ extern "C" {
 #endif
 
 #define M2S_VERSION_MAJOR 0
-#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface, m2s_band_create / destroy / info / sample / raymarch, m2s_band_csg, m2s_band_export, m2s_band_field_info, m2s_band_redistance); additive within 0.5 too: m2s_band_filter, m2s_band_resample; 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
+#define M2S_VERSION_MINOR 5   /* 0.5: + m2s_tuning_set, m2s_tuning_describe (and, additive within 0.5: m2s_sample_surface, m2s_mesh_sample_surface, m2s_voxelize, m2s_mesh_voxelize, m2s_narrow_band_sdf, m2s_mesh_narrow_band_sdf, m2s_band_isosurface, m2s_band_create / destroy / info / sample / raymarch, m2s_band_csg, m2s_band_export, m2s_band_field_info, m2s_band_redistance); additive within 0.5 too: m2s_band_filter, m2s_band_resample, m2s_band_advect; 0.4: + m2s_warmup, m2s_peer_bandwidth, m2s_balanced_slabs, M2S_PART_ADAPTIVE, m2s_multi_opts.partition_used / slabs (additive) */
 
 /* Return codes.  The reference panics where this ABI returns a negative code; the Rust shim
  * turns a negative code back into panic!(m2s_last_error()). */
@@ -1024,6 +1024,73 @@ typedef struct m2s_band_filter_info { uint32_t struct_size, passes; float max_ch
 int m2s_band_filter(const m2s_band* band, const m2s_band* where /* may be NULL = everywhere */, const m2s_band_filter_opts* fl,
                     const m2s_band_field_opts* fopts /* NULL = the input's backgrounds */, const m2s_opts* opts,
                     m2s_band** out, m2s_band_filter_info* info_out /* may be NULL */);
+
+/* ---- Moving a narrow band: advection by a velocity, propagation along the normal by a speed ----------------------------------------------
+ * m2s_band_advect takes a resident band and a field with one entry per cell, and returns a resident band on the same cells whose
+ * values have taken `steps` explicit first-order upwind steps of dt: what LevelSetAdvect, and the step under LevelSetMorph, are in
+ * OpenVDB with FIRST_BIAS.  A particle surface is carried by a flow, a part thickened by an amount that varies over its surface, a
+ * front propagated at a given speed, one shape morphed into another (speed = minus the target's value), with no dense grid and nothing
+ * leaving the device.  The result is DEFINED per grid point, to the bit (tests/band_advect_model.py restates it in numpy).
+ * Input: a handle X, a kind, steps, dt and the field.  act, x = D'_X[L], s, the clamped neighbour reads N(+a), N(-a) and c = N(0,0,0)
+ *   are exactly those of m2s_band_filter's definition above: v[L] is the current value where L is active and D'_X[L] elsewhere (X's own
+ *   backgrounds, not the result's).  Inactive points never change.  h = (h_i, h_j, h_k) is the grid's cell_size.
+ *   All arithmetic is IEEE binary32 with no FMA, each operation in the order written; sqrtf is correctly rounded.
+ * Host constants, computed in binary32 and handed to the kernels as values: r_a = 1 / h_a.
+ * field: host or device memory as m2s_opts.mem_kind says, n_cells x 3 floats (M2S_ADVECT_VELOCITY: u_i, u_j, u_k of a cell side by
+ *   side) or n_cells floats (M2S_ADVECT_NORMAL: F), in list order: entry n belongs to the band's n-th cell in ascending order, the
+ *   order of m2s_band_export.  One field and one dt serve the whole call.
+ * Moving cells: an active cell is MOVING when any of its three velocity components != 0 (M2S_ADVECT_VELOCITY), or its speed != 0
+ *   (M2S_ADVECT_NORMAL); -0.0 is 0 and a NaN counts as moving.  A cell that is not moving evaluates no candidate and keeps every bit
+ *   through every step.
+ * One step, for a moving L:  Dm_a = (c - N(-a)) * r_a,  Dp_a = (N(+a) - c) * r_a, and
+ *   M2S_ADVECT_VELOCITY  phi_t + u . grad phi = 0, each axis differenced against the wind:
+ *                        t_a = u_a > 0 ? u_a * Dm_a : u_a * Dp_a
+ *                        cand = c - dt * ((t_i + t_j) + t_k)
+ *   M2S_ADVECT_NORMAL    phi_t + F |grad phi| = 0, Godunov's scheme; F > 0 moves the surface outward.
+ *                        With pos(v) = v > 0 ? v : 0 and neg(v) = v < 0 ? v : 0:
+ *                        A_a = F > 0 ? pos(Dm_a) : neg(Dm_a)
+ *                        B_a = F > 0 ? neg(Dp_a) : pos(Dp_a)
+ *                        qa = A_a * A_a, qb = B_a * B_a, q_a = qb > qa ? qb : qa
+ *                        g = sqrtf((q_i + q_j) + q_k)
+ *                        cand = c - dt * (F * g)
+ *   next[L] = isfinite(cand) ? cand : c.  A non-finite cand of a moving cell keeps c and counts once, per cell and step, in
+ *   n_nonfinite; non-finite entries of `field` are accepted and end there, and so do values of +-f32::MAX in a band.
+ * IT MUST BE JACOBI.  Every step reads the previous step's values only; the library keeps two value buffers, as for redistancing.
+ *   An in-place step ends in different bits, and so does a tile that runs several steps in local memory.
+ * Result: a new immutable m2s_band on the same grid and device.  The active set is X's.  The values r are those after the last
+ *   step.  Sign mask: on EVERY grid point, act ? (r < 0) : s.  Backgrounds: fopts', or X's by default.  m2s_band_info's device_bytes
+ *   follows the formula for a handle with a sign mask.  An empty band gives an empty band with the sign mask; `field` may then be NULL.
+ * info_out (may be NULL; set struct_size): steps; n_moving = the moving cells; n_changed = the active cells whose final bits differ
+ *   from x; n_sign_flips = the active cells with (r < 0) != (x < 0); max_change = the largest fabsf(r - x) over the active cells (0 for
+ *   an empty band; it may be +inf); n_nonfinite as above; max_cfl = the largest over the active cells of
+ *   dt * ((|u_i|*r_i + |u_j|*r_j) + |u_k|*r_k) (M2S_ADVECT_VELOCITY) or dt * (|F| * ((r_i + r_j) + r_k)) (M2S_ADVECT_NORMAL), taken as a
+ *   maximum of the bit patterns of the values that are not NaN; +inf is possible; 0 for an empty band.  All are deterministic: integer
+ *   sums and maxima.
+ * What the definition does NOT promise: the result is not a distance field.  Cells at the band's rim read the backgrounds, that is
+ *   the clamped field, so error enters from the upwind rim and travels at the flow's speed.  A caller moves the surface by less than
+ *   the half-width minus two cells and then calls m2s_band_redistance, which keeps the cells next to the zero set in every bit and
+ *   re-grows the band around it.  Stability needs max_cfl <= 1: the call reports the figure and does not enforce it, and the
+ *   definition holds above 1 too.  First-order upwind is diffusive; `scheme` must be 0 and exists so that a higher order can follow.
+ * Accuracy (measured with the numpy model): a sphere carried a few cells by a constant velocity, or grown or shrunk
+ *   along its normal, keeps its zero set within about a quarter of a cell; a quarter turn about an off-centre axis within about a cell.
+ * Always synchronous: one synchronisation at the end, for the info, none between steps.  *out = NULL on every failure.
+ *   M2S_ERR_BAD_ARG before any device work: a NULL band, aopts or out; a struct_size other than sizeof (aopts, fopts, info_out); a bad
+ *   kind; scheme != 0; steps == 0 or above 65 536; a dt that is not finite or not > 0; a NULL field with n_cells > 0; a negative or
+ *   non-finite background; n_cells + 2 >= 2^32; an m2s_opts.device that is not the handle's (-1
+ *   means its own); algorithm, x_begin, x_end, x_period or peer_out not zero; a bad mem_kind.
+ *   m2s_opts: device, stream / stream_mode, lane, mem_kind (where `field` lives).  timings: seed_ms = the neighbour table and the
+ *   moving bytes, distance_ms = the steps, total_ms = the whole call, n_units = the cell count.
+ * Memory during the call: per active cell two values, 24 bytes of 32-bit neighbour places and a byte, 33 bytes, plus the copy of a
+ *   host caller's field, 12 or 4 bytes (a device caller's field is read where it lies); per 64 grid points the result's sign word
+ *   (with the copies of the mask and its offsets, the result itself).  Nothing sized 4 bytes per grid point is allocated.  An inactive
+ *   neighbour is one of two extra places behind the values, which is why n_cells + 2 must stay below 2^32. */
+enum m2s_advect_kind { M2S_ADVECT_VELOCITY = 0, M2S_ADVECT_NORMAL = 1 };
+typedef struct m2s_band_advect_opts { uint32_t struct_size; int32_t kind; uint32_t steps; uint32_t scheme /* must be 0 */; float dt; } m2s_band_advect_opts;
+typedef struct m2s_band_advect_info { uint32_t struct_size, steps; float max_change, max_cfl;
+                                      uint64_t n_moving, n_changed, n_sign_flips, n_nonfinite; } m2s_band_advect_info;
+int m2s_band_advect(const m2s_band* band, const float* field /* list order: n_cells x 3 (VELOCITY) or n_cells (NORMAL) */,
+                    const m2s_band_advect_opts* aopts, const m2s_band_field_opts* fopts /* NULL = the input's backgrounds */,
+                    const m2s_opts* opts, m2s_band** out, m2s_band_advect_info* info_out /* may be NULL */);
 
 /* ---- Resampling a narrow band onto another grid under a similarity: crop, pad, move, turn, scale, refine --------------------------------
  * m2s_band_resample evaluates a resident band at the cell centres of another grid, under an optional map from target space to source

@@ -621,6 +621,17 @@ struct FilterInfo {
   float max_change = 0.0f;
   uint64_t n_changed = 0, n_sign_flips = 0, n_nonfinite = 0;
 };
+// What BandField::advect steps (m2s_advect_kind): the field carried along a velocity per cell (phi_t + u . grad phi = 0), or the surface moved
+// along its normal by a speed per cell (phi_t + F |grad phi| = 0).
+enum class AdvectKind : int { Velocity = M2S_ADVECT_VELOCITY, Normal = M2S_ADVECT_NORMAL };
+// What BandField::advect reports (m2s_band_advect_info): the steps run, the largest |result - input| over the cells, the largest CFL number
+// of a cell (stable up to 1; reported, not enforced), the cells with a field entry other than zero, the cells whose bits changed, the cells
+// whose sign changed, the candidates that were not finite and were dropped (per cell and step).
+struct AdvectInfo {
+  uint32_t steps = 0;
+  float max_change = 0.0f, max_cfl = 0.0f;
+  uint64_t n_moving = 0, n_changed = 0, n_sign_flips = 0, n_nonfinite = 0;
+};
 // What BandField::resample reports (m2s_band_resample_info): the result's cells, the points on the source box with some but not all of
 // their reads in the band (the rim the interpolation loses), the points whose value came out non-finite and were dropped, the sign changes
 // towards an inactive cell (> 0: the result does not bracket its zero set there).
@@ -776,6 +787,33 @@ class BandField {
       info->n_changed = fi.n_changed;
       info->n_sign_flips = fi.n_sign_flips;
       info->n_nonfinite = fi.n_nonfinite;
+    }
+    return BandField(grid_, h);
+  }
+  // The field on the same cells after `steps` first-order upwind steps of dt, as a new resident field (m2s_band_advect: Jacobi steps over
+  // the band's cells, per grid point and to the bit; no dense grid).  field: one entry per cell in the order of export_band().cells, three
+  // floats (AdvectKind::Velocity) or one (AdvectKind::Normal); a cell whose entry is zero keeps every bit.  The backgrounds are kept.  The
+  // result is not a distance field and the band does not follow the surface: move it by less than the half-width minus two cells, then
+  // redistance.  info->max_cfl should stay at or below 1.
+  BandField advect(AdvectKind kind, const std::vector<float>& field, float dt, uint32_t steps = 1, AdvectInfo* info = nullptr) const {
+    if (field.size() != count() * (kind == AdvectKind::Velocity ? 3 : 1)) throw Panic(M2S_ERR_BAD_ARG, "advect: field does not hold one entry per cell");
+    m2s_band_advect_opts ao{};
+    ao.struct_size = sizeof(ao);
+    ao.kind = (int32_t)kind;
+    ao.steps = steps;
+    ao.dt = dt;
+    m2s_band_advect_info ai{};
+    ai.struct_size = sizeof(ai);
+    m2s_band* h = nullptr;
+    detail::check(m2s_band_advect(h_, field.empty() ? nullptr : field.data(), &ao, nullptr, nullptr, &h, &ai));
+    if (info) {
+      info->steps = ai.steps;
+      info->max_change = ai.max_change;
+      info->max_cfl = ai.max_cfl;
+      info->n_moving = ai.n_moving;
+      info->n_changed = ai.n_changed;
+      info->n_sign_flips = ai.n_sign_flips;
+      info->n_nonfinite = ai.n_nonfinite;
     }
     return BandField(grid_, h);
   }

@@ -11,6 +11,6 @@ from .api import (AccelerationMethod, Exchange, Grid, M2SError, M2SPanic, Mesh, 
                   RayHits, cast_rays, count_intersections, test_occlusions, SurfaceSamples, sample_surface, surface_area,
                   sample_sdf_near_surface, Voxels, voxelize, NarrowBand, narrow_band_sdf,
                   band_isosurface, isosurface_band, remesh, BandField, default_background, CsgOp, boolean, RedistanceInfo,
-                  FilterKind, FilterInfo, ResampleInfo, Connectivity, Components, SelectInfo, Measure, ShapesInfo)
+                  FilterKind, FilterInfo, AdvectKind, AdvectInfo, FlowInfo, flow_round, ResampleInfo, Connectivity, Components, SelectInfo, Measure, ShapesInfo)
 from ._lib import M2STimings  # noqa: F401
 from . import serde  # noqa: F401,E402  (mesh_to_sdf::serde, serde.rs)

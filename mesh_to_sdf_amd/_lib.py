@@ -156,6 +156,15 @@ class M2SBandFilterInfo(C.Structure):
                 ("n_changed", C.c_uint64), ("n_sign_flips", C.c_uint64), ("n_nonfinite", C.c_uint64)]
 
 
+class M2SBandAdvectOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("steps", C.c_uint32), ("scheme", C.c_uint32), ("dt", C.c_float)]
+
+
+class M2SBandAdvectInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("steps", C.c_uint32), ("max_change", C.c_float), ("max_cfl", C.c_float),
+                ("n_moving", C.c_uint64), ("n_changed", C.c_uint64), ("n_sign_flips", C.c_uint64), ("n_nonfinite", C.c_uint64)]
+
+
 class M2SBandResampleOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("to_source", C.c_float * 12), ("value_scale", C.c_float)]
 
@@ -266,6 +275,7 @@ EXPORTS = [
     "m2s_band_field_info",
     "m2s_band_redistance",
     "m2s_band_filter",
+    "m2s_band_advect",
     "m2s_band_resample",
     "m2s_band_components",
     "m2s_band_select",
@@ -378,6 +388,8 @@ def _prototypes():
                                           C.POINTER(C.c_void_p), C.POINTER(M2SBandRedistanceInfo)]),
         "m2s_band_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(M2SBandFilterOpts), C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
                                       C.POINTER(C.c_void_p), C.POINTER(M2SBandFilterInfo)]),
+        "m2s_band_advect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(M2SBandAdvectOpts), C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
+                                      C.POINTER(C.c_void_p), C.POINTER(M2SBandAdvectInfo)]),
         "m2s_band_resample": (C.c_int, [C.c_void_p, C.POINTER(M2SGrid), C.POINTER(M2SBandResampleOpts), C.POINTER(M2SBandFieldOpts), C.POINTER(M2SOpts),
                                         C.POINTER(C.c_void_p), C.POINTER(M2SBandResampleInfo)]),
         "m2s_band_components": (C.c_int, [C.c_void_p, C.POINTER(M2SBandComponentsOpts), C.POINTER(M2SOpts), C.c_void_p, C.c_void_p, C.c_uint64,

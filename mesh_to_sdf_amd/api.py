@@ -14,6 +14,7 @@ stream, nothing crosses PCIe).  Where the reference panics this raises M2SPanic.
 """
 import ctypes as C
 import enum
+import math
 from dataclasses import dataclass
 from typing import NamedTuple, Optional, Sequence
 
@@ -1126,6 +1127,84 @@ class FilterInfo(NamedTuple):
     n_nonfinite: int
 
 
+class AdvectKind(enum.IntEnum):
+    """include/m2s.h `m2s_advect_kind`: what BandField.advect steps.  Velocity carries the field along a velocity per cell
+    (phi_t + u . grad phi = 0), Normal moves the surface along its normal by a speed per cell (phi_t + F |grad phi| = 0)."""
+    Velocity = 0
+    Normal = 1
+
+
+class AdvectInfo(NamedTuple):
+    """include/m2s.h `m2s_band_advect_info`: the steps run, the largest |result - input| over the cells, the largest CFL number of a
+    cell (stable up to 1; reported, not enforced), the cells with a field entry other than zero, the cells whose bits changed, the
+    cells whose sign changed, and the candidates that were not finite and were therefore dropped (per cell and step)."""
+    steps: int
+    max_change: float
+    max_cfl: float
+    n_moving: int
+    n_changed: int
+    n_sign_flips: int
+    n_nonfinite: int
+
+
+class FlowInfo(NamedTuple):
+    """What BandField.flow ran: the rounds (each an advect followed by a redistance), the steps over all rounds, and the time reached."""
+    rounds: int
+    steps: int
+    time: float
+
+
+def flow_round(field, kind, cell_size, left: float, cfl: float = 0.5, reach: float = 1.0):
+    """The schedule of one round of BandField.flow -> (steps, dt, time taken).  field: the round's float32[n, 3] velocities or
+    float32[n] speeds (a device tensor or a host array); left: the time that remains.  In float64, from the binary32 entries:
+    rate = the largest |u_i| r_i + |u_j| r_j + |u_k| r_k (or |F| (r_i + r_j + r_k)) with r_a = 1 / h_a in binary32, fastest = the
+    largest |u| (or |F|).  The round lasts reach * min(h) / fastest, or `left` where that is no more than it (to a millionth), in steps = ceil(that * rate / cfl) steps (65 536 at the
+    most, a shorter round then) of dt = the round's time / steps rounded to binary32, one float down where the rounding would lift
+    dt * rate above cfl.  (0, 0.0, left) when nothing moves; raises on a non-finite field."""
+    h = np.asarray(cell_size, np.float32)
+    r = (np.float32(1) / h).astype(np.float64)
+    velocity = int(kind) == int(AdvectKind.Velocity)
+    if _is_torch(field):
+        import torch as t
+
+        a = field.detach().to(t.float64).abs()
+        if a.numel() == 0:
+            return 0, 0.0, float(left)
+        if velocity:
+            a = a.reshape(-1, 3)
+            rate = float(((a[:, 0] * float(r[0]) + a[:, 1] * float(r[1])) + a[:, 2] * float(r[2])).max())
+            fastest = math.sqrt(float(((a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2]).max()))
+        else:
+            fastest = float(a.max())
+            rate = fastest * float((r[0] + r[1]) + r[2])
+    else:
+        a = np.abs(np.asarray(field, np.float32).astype(np.float64))
+        if a.size == 0:
+            return 0, 0.0, float(left)
+        if velocity:
+            a = a.reshape(-1, 3)
+            rate = float(((a[:, 0] * r[0] + a[:, 1] * r[1]) + a[:, 2] * r[2]).max())
+            fastest = math.sqrt(float(((a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2]).max()))
+        else:
+            fastest = float(a.max())
+            rate = fastest * float((r[0] + r[1]) + r[2])
+    if not (np.isfinite(rate) and np.isfinite(fastest)):
+        raise M2SPanic(_lib.ERR_BAD_ARG, "flow: the velocity or speed is not finite")
+    if rate == 0.0:
+        return 0, 0.0, float(left)
+    took = float(reach) * float(h.min()) / fastest
+    if left <= took * (1 + 1e-6):                                    # no round for a remainder of rounding's size
+        took = float(left)
+    steps = max(1, int(np.ceil(took * rate / float(cfl))))
+    if steps > 65536:
+        steps = 65536
+        took = steps * float(cfl) / rate
+    dt = np.float32(took / steps)
+    if float(dt) * rate > float(cfl):
+        dt = np.nextafter(dt, np.float32(0))
+    return steps, float(dt), took
+
+
 class ResampleInfo(NamedTuple):
     """include/m2s.h `m2s_band_resample_info`: the result's cells, the points on the source box that had some but not all of their
     reads in the band (the rim the interpolation loses), the points whose value came out non-finite and were dropped, and the sign
@@ -1539,6 +1618,125 @@ class BandField:
         out = BandField._adopt(h, self.grid, self._dev)
         out.filter_info = FilterInfo(int(info.passes), float(info.max_change), int(info.n_changed), int(info.n_sign_flips), int(info.n_nonfinite))
         return out
+
+    def centers(self):
+        """The centres of the field's cells, float32[n, 3] in list order, as m2s_grid_cell_center gives them (first_cell +
+        (float)idx * cell_size per axis): where a velocity or a speed for `advect` is evaluated.  A device tensor for a field made from
+        device tensors, a host array otherwise, like `to_band`."""
+        cells = self.to_band().cells
+        first, size = self.grid.get_first_cell(), self.grid.get_cell_size()
+        _, ny, nz = self.grid.get_cell_count()
+        if _is_torch(cells):
+            import torch as t
+
+            L = cells.to(t.int64)
+            idx = (L // (ny * nz), (L // nz) % ny, L % nz)
+            return t.stack([idx[a].to(t.float32) * float(size[a]) + float(first[a]) for a in range(3)], 1)
+        L = np.asarray(cells).astype(np.int64)
+        idx = (L // (ny * nz), (L // nz) % ny, L % nz)
+        return np.stack([first[a] + idx[a].astype(np.float32) * size[a] for a in range(3)], 1).astype(np.float32)
+
+    def _cell_field(self, q, value, width, what):
+        """`value` (an array with one entry per cell, or a scalar / a vector of `width` broadcast to the cells) as the float32 array
+        [n, width] or [n] a call on q's side reads."""
+        shape = (self.count, width) if width > 1 else (self.count,)
+        if q.device:
+            t = q.torch
+            f = value if _is_torch(value) else t.as_tensor(np.asarray(value, np.float32))
+            f = f.detach().to(device=q.dev, dtype=t.float32)
+            if f.numel() == (width if width > 1 else 1):
+                f = f.reshape(-1).expand(shape) if width > 1 else f.reshape(()).expand(shape)
+            have = f.numel()
+            f = f.contiguous()
+        else:
+            f = np.asarray(value.detach().cpu().numpy() if _is_torch(value) else value, np.float32)
+            if f.size == (width if width > 1 else 1):
+                f = np.broadcast_to(f.reshape(-1) if width > 1 else f.reshape(()), shape)
+            have = f.size
+            f = np.ascontiguousarray(f)
+        if have != self.count * width:
+            raise M2SPanic(_lib.ERR_BAD_ARG, f"{what} holds {have} values, the field's {self.count} cells need {self.count * width}")
+        return f.reshape(shape)
+
+    def advect(self, dt: float, steps: int = 1, *, velocity=None, speed=None, background=None, timings: M2STimings = None) -> "BandField":
+        """A new resident BandField on the same cells whose values have taken `steps` first-order upwind steps of `dt` (include/m2s.h
+        m2s_band_advect states the result per grid point, to the bit).  Exactly one of velocity (phi_t + u . grad phi = 0: the field
+        is carried along u) and speed (phi_t + F |grad phi| = 0: the surface moves outward along its normal by F) is given: an array
+        with one entry per cell in list order (float32[n, 3] / float32[n], as `centers` orders them; a device tensor or a host
+        array), or a 3-vector / a scalar for every cell.  A cell whose entry is zero keeps every bit.  background: a scalar or
+        (inside, outside); None keeps this field's.  The result is not a distance field and the band does not follow the surface:
+        move it by less than the half-width minus two cells, then `redistance`, or call `flow`.  It carries `.advect_info` (an
+        AdvectInfo), whose max_cfl should stay at or below 1."""
+        if (velocity is None) == (speed is None):
+            raise M2SPanic(_lib.ERR_BAD_ARG, "advect: give exactly one of velocity and speed")
+        kind = AdvectKind.Velocity if speed is None else AdvectKind.Normal
+        q = self._side(timings)
+        h = self._handle()
+        f = self._cell_field(q, velocity if speed is None else speed, 3 if speed is None else 1, "velocity" if speed is None else "speed")
+        ao = _lib.M2SBandAdvectOpts(C.sizeof(_lib.M2SBandAdvectOpts), int(kind), int(steps), 0, float(np.float32(dt)))
+        fo = None
+        if background is not None:
+            bg_in, bg_out = _backgrounds(background)
+            fo = C.byref(_lib.M2SBandFieldOpts(C.sizeof(_lib.M2SBandFieldOpts), float(np.float32(bg_out)), float(np.float32(bg_in))))
+        info = _lib.M2SBandAdvectInfo(C.sizeof(_lib.M2SBandAdvectInfo))
+        out = C.c_void_p()
+        rc = _lib.lib().m2s_band_advect(h, q.ptr(f), C.byref(ao), fo, C.byref(q.opts), C.byref(out), C.byref(info))
+        if rc != _lib.M2S_OK:
+            _raise(rc)
+        res = BandField._adopt(out, self.grid, self._dev)
+        res.advect_info = AdvectInfo(int(info.steps), float(info.max_change), float(info.max_cfl), int(info.n_moving), int(info.n_changed),
+                                     int(info.n_sign_flips), int(info.n_nonfinite))
+        return res
+
+    def flow(self, time: float, band, *, velocity=None, speed=None, cfl: float = 0.5, reach: float = 1.0) -> "BandField":
+        """The field moved over `time` by a velocity or a normal speed, as a new BandField of half-widths `band` that is a distance
+        field again: the tracker around `advect`.  velocity / speed: as for `advect`, or a callable f(centers) that is evaluated on
+        the cells' centres at the start of every round.  A round takes the largest steps with max_cfl <= cfl until the fastest cell
+        has moved `reach` of the smallest cell edge or `time` is used up (`flow_round` is the schedule), then `redistance(band)`
+        re-grows the band around the moved zero set.  Raises if a round's zero set leaves what the band brackets (n_open > 0):
+        lower `reach` or widen `band`.  The result carries `.flow_info` (a FlowInfo), and the last round's `.advect_info` and
+        `.redistance_info`."""
+        if (velocity is None) == (speed is None):
+            raise M2SPanic(_lib.ERR_BAD_ARG, "flow: give exactly one of velocity and speed")
+        given, kind = (velocity, AdvectKind.Velocity) if speed is None else (speed, AdvectKind.Normal)
+        if not (np.isfinite(time) and time >= 0 and cfl > 0 and reach > 0):
+            raise M2SPanic(_lib.ERR_BAD_ARG, f"flow: time = {time}, cfl = {cfl}, reach = {reach}")
+        width = 3 if kind == AdvectKind.Velocity else 1
+        cur, left, rounds, steps, reached, last = self, float(time), 0, 0, 0.0, None
+        try:
+            while left > 0 and cur.count:
+                f = cur._cell_field(cur._side(), given(cur.centers()) if callable(given) else given, width, "the field")
+                n_steps, dt, took = flow_round(f, kind, self.grid.get_cell_size(), left, cfl, reach)
+                if n_steps == 0:                                     # nothing moves any more
+                    break
+                with cur.advect(dt, n_steps, **{"velocity" if kind == AdvectKind.Velocity else "speed": f}) as moved:
+                    nxt = moved.redistance(band)
+                    nxt.advect_info = last = moved.advect_info
+                if cur is not self:
+                    cur.close()
+                cur = nxt
+                if cur.redistance_info.n_open:
+                    raise M2SError(_lib.ERR_BAD_ARG, f"flow: round {rounds + 1} leaves the band at {cur.redistance_info.n_open} cell faces; "
+                                                     "lower reach or widen the band")
+                rounds, steps, reached = rounds + 1, steps + n_steps, reached + float(dt) * n_steps
+                left = 0.0 if took >= left else left - took
+            out = cur.redistance(band) if cur is self else cur
+        except Exception:
+            if cur is not self:
+                cur.close()
+            raise
+        if last is not None:
+            out.advect_info = last
+        out.flow_info = FlowInfo(rounds, steps, reached)
+        return out
+
+    def morph(self, target: "BandField", time: float, band, **flow) -> "BandField":
+        """This field morphed towards `target` over `time`: `flow` with the speed -target.sample(centers, mode=Trilinear), which moves
+        the surface outward where it lies inside the target and inward where it lies outside, and rests on the target's zero set
+        (OpenVDB's LevelSetMorph).  flow: `cfl`, `reach`."""
+        if not isinstance(target, BandField):
+            raise M2SPanic(_lib.ERR_BAD_ARG, "morph: target is not a BandField")
+        return self.flow(time, band, speed=lambda centers: -target.sample(centers, mode=SampleMode.Trilinear), **flow)
 
     def resample(self, grid, transform=None, *, mode: SampleMode = SampleMode.Trilinear, background=None,
                  timings: M2STimings = None) -> "BandField":

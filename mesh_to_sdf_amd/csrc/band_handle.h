@@ -1,6 +1,6 @@
 // band_handle.h — the resident band behind include/m2s.h's `m2s_band`, and the host steps the calls on one share: band_query.hip
 // (m2s_band_create / destroy / info / sample / raymarch), band_csg.hip (m2s_band_csg / export / field_info), band_redistance.hip,
-// band_filter.hip, band_resample.hip and band_components.hip.  Here are the handle and its device view; the argument checks on m2s_opts, m2s_band_field_opts
+// band_filter.hip, band_advect.hip, band_resample.hip and band_components.hip.  Here are the handle and its device view; the argument checks on m2s_opts, m2s_band_field_opts
 // and two grids; a grid's cell and word counts; blocks_for; and BandBlock / band_adopt, a result's device arrays while a call fills them
 // and the one place that makes them a handle.  Each is a small function a call takes where it has that step: the calls differ in their
 // allocations and synchronisations, so nothing here runs a call.  The device view and the helpers are in an unnamed namespace, as

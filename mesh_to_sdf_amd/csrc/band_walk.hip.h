@@ -1,5 +1,5 @@
 // band_walk.hip.h — the walk over mask words that every band call shares: band_csg.hip, band_redistance.hip,
-// band_filter.hip, band_resample.hip and band_components.hip.  A wave owns a UNIT of STEPS * 64 words and takes it in steps of 64, lane l loading word
+// band_filter.hip and band_advect.hip (through band_stencil.hip.h), band_resample.hip and band_components.hip.  A wave owns a UNIT of STEPS * 64 words and takes it in steps of 64, lane l loading word
 // 64 * step + l; a word with nothing to do is settled by its own lane, the others are taken one at a time by the whole wave (a ballot finds
 // them, v_readlane broadcasts the word's values) and lane t owns bit t, the point L = 64 w + t.  A word's base L is decomposed into (i, j, k)
 // once, by the lane that loaded it, and stepped per bit.  A mask's word_off comes from three pieces: walk_publish (a unit's count, and by one

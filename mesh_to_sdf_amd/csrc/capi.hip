@@ -1311,6 +1311,7 @@ int m2s_warmup(int device, size_t workspace_bytes, size_t host_ring_bytes) {
   warm_band_csg(c.stream);
   warm_band_redistance(c.stream);
   warm_band_filter(c.stream);
+  warm_band_advect(c.stream);
   warm_band_resample(c.stream);
   warm_band_components(c.stream);
   warm_band_measure(c.stream);

@@ -304,6 +304,7 @@ void warm_band_query(hipStream_t st);
 void warm_band_csg(hipStream_t st);
 void warm_band_redistance(hipStream_t st);
 void warm_band_filter(hipStream_t st);
+void warm_band_advect(hipStream_t st);
 void warm_band_resample(hipStream_t st);
 void warm_band_components(hipStream_t st);
 void warm_band_measure(hipStream_t st);
