@@ -10,12 +10,19 @@ A chain lives on a PAIR of grids that differ in first cell, cell size and cell c
 POOL of four start bands, which are also the partners of `csg` and the regions of `filter`.  `plan(seed, pair)` is plain data (tuples,
 numbers, names), a pure function of its arguments; what a step needs of the grid it happens to run on (widths in world units, the map
 between the two grids, the keep mask over however many components there are) is resolved at replay by `widths`, `forward_of` and
-`keep_of`, which both sides call."""
+`keep_of`, which both sides call.
+
+There are two families of chains.  The first (`OPS`, `SALT`, `SEEDS`, `draw`, `plan`, `chain`) is the one the suite began with and
+stays exactly as it was: `draw` picks OPS[rng.integers(len(OPS))], so a sixth op in OPS would change every chain.  The second
+(`OPS_B`, `SALT_B`, `SEEDS_B`, `draw_b`, `plan_b`, `chain_b`) has a generator stream of its own and `advect` as a sixth op
+(band_advect_model.band_advect); its five old ops draw their arguments as in the first.  An advect step's velocities or speeds and its
+time step depend on the cells it meets, so they too are resolved at replay, by `field_of` and `dt_of`."""
 import functools
 from typing import NamedTuple
 
 import numpy as np
 
+import band_advect_model as am
 import band_components_model as ccm
 import band_csg_model as cm
 import band_filter_model as fm
@@ -29,6 +36,12 @@ SALT = 3            # of the generator's streams, one whose 36 chains meet every
 SEEDS = tuple(range(12))
 OPS = ("csg", "filter", "redistance", "resample", "select")
 CSG_NAMES = ("union", "intersection", "difference")
+# the second family: the same pairs and pools, the six ops, 16 seeds per pair (384 steps) so that each op still meets 40 non-empty inputs
+OPS_B = OPS + ("advect",)
+SALT_B = 4          # of the streams default_rng([salt, seed, pair, 6]) with salt 0 .. 7, the one whose 48 chains meet every condition of
+#                     tests/test_band_chain_cpu.py with the widest margin: every op on 48 non-empty inputs or more, every rare branch 7 times or more
+SEEDS_B = tuple(range(16))
+ADVECT_NAMES = ("velocity", "normal speed")
 
 
 def _around(centre, cell, shape):
@@ -89,30 +102,45 @@ def _floats(x):
     return tuple(float(v) for v in x)
 
 
+def _draw_step(rng, ops):
+    """One step with its op drawn from `ops`; the five ops of OPS take the same numbers from the generator in both families."""
+    op = ops[int(rng.integers(len(ops)))]
+    if op == "csg":
+        return (op, ("partner", int(rng.integers(4))), ("swap", bool(rng.integers(2))), ("kind", int(rng.integers(3))))
+    if op == "filter":
+        where = int(rng.integers(5))
+        bg = _floats(rng.uniform(0.1, 2.0, 2)) if rng.integers(2) else None
+        return (op, ("kind", int(rng.integers(3))), ("iterations", int(rng.integers(1, 4))), ("where", None if where == 4 else where),
+                ("background", bg))
+    if op == "redistance":
+        return (op, ("exterior", float(rng.uniform(1, 3))), ("interior", float(rng.uniform(1, 3))))
+    if op == "resample":
+        return (op, ("target", int(rng.integers(2))), ("scale", float(rng.uniform(0.9, 1.1))), ("axis", _floats(rng.normal(size=3))),
+                ("angle", float(rng.uniform(-0.3, 0.3))), ("jitter", _floats(rng.uniform(-0.5, 0.5, 3))), ("mode", int(rng.integers(3))))
+    if op == "select":
+        return (op, ("connectivity", int(ccm.CONNECTIVITIES[int(rng.integers(3))])), ("keep_u", _floats(rng.random(32))))
+    # advect: 9 frequencies and 3 phases of `field_of`, the share of cells at rest, the CFL fraction of `dt_of`
+    coef = _floats(rng.uniform(0.2, 0.9, 9)) + _floats(rng.uniform(0, 6, 3))
+    bg = _floats(rng.uniform(0.1, 2.0, 2)) if rng.integers(2) else None
+    return (op, ("kind", int(rng.integers(2))), ("steps", int(rng.integers(1, 4))), ("cfl", float(rng.uniform(0.2, 0.9))), ("coef", coef),
+            ("still", float(rng.uniform(0, 0.5))), ("background", bg))
+
+
+def _draw(rng, ops):
+    start = (int(rng.integers(2)), int(rng.integers(4)))
+    return start, tuple(_draw_step(rng, ops) for _ in range(STEPS))
+
+
 @functools.lru_cache(maxsize=None)
 def draw(seed, pair):
     """-> ((start grid, start pool band), the 8 steps), from default_rng([SALT, seed, pair]) alone."""
-    rng = np.random.default_rng([SALT, int(seed), int(pair)])
-    start = (int(rng.integers(2)), int(rng.integers(4)))
-    steps = []
-    for _ in range(STEPS):
-        op = OPS[int(rng.integers(len(OPS)))]
-        if op == "csg":
-            step = (op, ("partner", int(rng.integers(4))), ("swap", bool(rng.integers(2))), ("kind", int(rng.integers(3))))
-        elif op == "filter":
-            where = int(rng.integers(5))
-            bg = _floats(rng.uniform(0.1, 2.0, 2)) if rng.integers(2) else None
-            step = (op, ("kind", int(rng.integers(3))), ("iterations", int(rng.integers(1, 4))), ("where", None if where == 4 else where),
-                    ("background", bg))
-        elif op == "redistance":
-            step = (op, ("exterior", float(rng.uniform(1, 3))), ("interior", float(rng.uniform(1, 3))))
-        elif op == "resample":
-            step = (op, ("target", int(rng.integers(2))), ("scale", float(rng.uniform(0.9, 1.1))), ("axis", _floats(rng.normal(size=3))),
-                    ("angle", float(rng.uniform(-0.3, 0.3))), ("jitter", _floats(rng.uniform(-0.5, 0.5, 3))), ("mode", int(rng.integers(3))))
-        else:
-            step = (op, ("connectivity", int(ccm.CONNECTIVITIES[int(rng.integers(3))])), ("keep_u", _floats(rng.random(32))))
-        steps.append(step)
-    return start, tuple(steps)
+    return _draw(np.random.default_rng([SALT, int(seed), int(pair)]), OPS)
+
+
+@functools.lru_cache(maxsize=None)
+def draw_b(seed, pair):
+    """The second family's `draw`: the six ops of OPS_B, from default_rng([SALT_B, seed, pair, 6]) alone."""
+    return _draw(np.random.default_rng([SALT_B, int(seed), int(pair), 6]), OPS_B)
 
 
 def plan(seed, pair):
@@ -125,6 +153,14 @@ def start_of(seed, pair):
     return draw(seed, pair)[0]
 
 
+def plan_b(seed, pair):
+    return list(draw_b(seed, pair)[1])
+
+
+def start_of_b(seed, pair):
+    return draw_b(seed, pair)[0]
+
+
 def args(step):
     return dict(step[1:])
 
@@ -135,6 +171,8 @@ def describe(step):
         return f"csg {CSG_NAMES[a['kind']]} with pool band {a['partner']}" + (" as the first operand" if a["swap"] else "")
     if step[0] == "select":
         return f"select connectivity {a['connectivity']}"
+    if step[0] == "advect":
+        return f"advect by a {ADVECT_NAMES[a['kind']]}, {a['steps']} steps, CFL fraction {a['cfl']:.3f}, {a['still']:.2f} at rest, background {a['background']}"
     return step[0] + " " + ", ".join(f"{k} {v}" for k, v in a.items())
 
 
@@ -163,6 +201,30 @@ def keep_of(step, n_cells):
     if count:
         keep[int(np.argmax(np.asarray(n_cells).astype(np.int64)))] = True
     return keep
+
+
+def field_of(step, band, spec):
+    """advect: the velocities float32[n, 3] (kind 0) or normal speeds float32[n] (kind 1) on the cells of `band`, in list order: one
+    sine of the cell's (i, j, k) per component, so every entry lies in [-1, 1], evaluated in float64 and rounded to binary32; the
+    cells a hash of L picks (the drawn share of them) are exactly 0 in every component, so that they are at rest.  `spec` is the grid
+    the band is on; the field depends on the indices alone."""
+    a = args(step)
+    c = np.asarray(a["coef"], np.float64)
+    _, ny, nz = band.shape
+    L = band.cells.astype(np.int64)
+    i, j, k = L // (ny * nz), (L // nz) % ny, L % nz
+    width = 3 if a["kind"] == am.VELOCITY else 1
+    f = np.stack([np.sin(c[3 * w] * i + c[3 * w + 1] * j + c[3 * w + 2] * k + c[9 + w]) for w in range(width)], 1).astype(F)
+    h = (L.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(int(c[0] * 2 ** 40))) >> np.uint64(44)
+    f[(h % np.uint64(1024)).astype(np.int64) < a["still"] * 1024] = 0
+    return f if width == 3 else f.reshape(-1)
+
+
+def dt_of(step, spec):
+    """advect: the time step, the drawn CFL fraction of the smallest cell side, in binary32.  The entries of `field_of` reach 1 per
+    component, so max_cfl goes up to that fraction times (1/h_i + 1/h_j + 1/h_k) min(h): past 1 on the cubic grids, which the call
+    reports and does not forbid."""
+    return F(args(step)["cfl"] * min(spec.cell))
 
 
 # ---- the model chain -----------------------------------------------------------------------------------------------------------------------
@@ -203,6 +265,8 @@ def model_step(pair, step, band, at):
         comps = ccm.components(band, a["connectivity"])
         keep = keep_of(step, comps.n_cells)
         out, info = ccm.select(band, comps.labels, keep)
+    elif op == "advect":
+        out, info = am.band_advect(band, spec.cell, a["kind"], field_of(step, band, spec), dt_of(step, spec), a["steps"], a["background"])
     else:
         raise ValueError(op)
     return Result(step, band, at, out, to, info, comps, keep)
@@ -223,3 +287,10 @@ def chain(seed, pair):
     """The model's side of chain `seed` on PAIRS[pair], once: -> (start grid, start pool band, [Result])."""
     g, p = start_of(seed, pair)
     return g, p, run_model(pair, plan(seed, pair), pool(pair, g)[p], g)
+
+
+@functools.lru_cache(maxsize=None)
+def chain_b(seed, pair):
+    """The second family's `chain`."""
+    g, p = start_of_b(seed, pair)
+    return g, p, run_model(pair, plan_b(seed, pair), pool(pair, g)[p], g)

@@ -10,8 +10,18 @@ big grid.  That is exact only while nothing the call reads or writes crosses the
   redistance    the candidate box reaches K_a = min(ceil(W / h_a) + 1, n_a) from a frozen point.  On every interior side K_a + 1 layers
                 hold no active point, the sign bits are uniform outside the box of the active cells, and the window's n_a exceeds K_a so
                 that the `min` picks the same branch as on the big grid.
+  advect        the filter rule as it stands: the stencil reaches +-1 with clamped reads, an inactive neighbour takes the background of
+                its sign bit; there is no `where`.  `embed_field` puts the windows' velocities or speeds into the big grid's list order,
+                `sum_advect` adds the infos up.
+  components    a step off the grid is no edge and nothing is clamped, so a face of the big grid needs no care: on every side of a
+                window that is not a face of the big grid the outermost layer holds no active point.  The windows being disjoint, no
+                cell of one is then a 26-neighbour of a cell of another, and `merge_components` renumbers the windows' components by
+                their first cell in the big grid.
+  select        the sign rule is per k-row and looks to the row's ends, so a window spans whole rows: lo[2] == 0 and shape[2] == nz of
+                the big grid, with any (i, j) extent (`row_window`).  Outside the windows no row holds an active cell and nothing is
+                cleared: the mask there is the input's with the bits at k >= nz zero.  `sum_select` adds the infos up.
 
-`check_filter` and `check_redistance` raise LayoutError when a test's layout breaks its rule; tests/test_band_window_cpu.py proves the
+`check_filter`, `check_redistance`, `check_advect`, `check_components` and `check_select` raise LayoutError when a test's layout breaks its rule; tests/test_band_window_cpu.py proves the
 rules (the dense model on a whole grid equals the window results embedded, bit for bit) on grids small enough for the dense models.
 
 Everything here is numpy on window-sized arrays plus index arithmetic in Python integers / int64; nothing is sized by the big grid except
@@ -20,6 +30,8 @@ from typing import NamedTuple
 
 import numpy as np
 
+import band_advect_model as am
+import band_components_model as ccm
 import band_csg_model as cm
 import band_filter_model as fm
 import band_query_model as bqm
@@ -167,7 +179,7 @@ def _layers(a, axis, side, count):
     return a[tuple(sl)]
 
 
-def check_filter(win, band, where=None, outside=False):
+def check_filter(win, band, where=None, outside=False, call="filter"):
     """The filter rule.  outside: the sign bit the big grid holds on the layer just beyond every interior side of the window."""
     _need(band.shape == win.shape and (where is None or where.shape == win.shape), "a band is not on its window")
     for b, name in ((band, "band"), (where, "where")):
@@ -178,8 +190,8 @@ def check_filter(win, band, where=None, outside=False):
             for side in (0, 1):
                 if win.at_face(axis, side):
                     continue
-                _need(not _layers(act, axis, side, 1).any(), f"filter: the {name}'s outermost layer on axis {axis} side {side} holds an active point")
-                _need(bool((_layers(s, axis, side, 1) == bool(outside)).all()), f"filter: the {name}'s sign bits on axis {axis} side {side} differ from the next layer out")
+                _need(not _layers(act, axis, side, 1).any(), f"{call}: the {name}'s outermost layer on axis {axis} side {side} holds an active point")
+                _need(bool((_layers(s, axis, side, 1) == bool(outside)).all()), f"{call}: the {name}'s sign bits on axis {axis} side {side} differ from the next layer out")
 
 
 def check_redistance(win, band, cell_size, exterior, interior, outside=False):
@@ -200,6 +212,95 @@ def check_redistance(win, band, cell_size, exterior, interior, outside=False):
         for side, room in ((0, lo[axis]), (1, win.shape[axis] - hi[axis])):
             if not win.at_face(axis, side):
                 _need(room >= K + 1, f"redistance: {room} layers without active points on axis {axis} side {side}, K + 1 = {K + 1} are needed")
+
+
+def check_advect(win, band, outside=False):
+    """The advect rule: the filter's, without a `where`."""
+    check_filter(win, band, None, outside, call="advect")
+
+
+def check_components(win, band):
+    """The components rule: no active point in the outermost layer of a side that is not a face of the big grid."""
+    _need(band.shape == win.shape, "the band is not on its window")
+    act = cm.dense(band)[0]
+    for axis in range(3):
+        for side in (0, 1):
+            _need(win.at_face(axis, side) or not _layers(act, axis, side, 1).any(),
+                  f"components: the band's outermost layer on axis {axis} side {side} holds an active point")
+
+
+def check_select(win, band):
+    """The select rule: the window spans whole k-rows of the big grid."""
+    _need(band.shape == win.shape, "the band is not on its window")
+    _need(win.lo[2] == 0 and win.shape[2] == win.big[2], f"select: the window covers k = {win.lo[2]} .. {win.hi[2] - 1} of rows of {win.big[2]}")
+
+
+def row_window(big, lo, shape):
+    """The window of whole k-rows over lo <= (i, j) < lo + shape."""
+    return Window(big, (lo[0], lo[1], 0), (shape[0], shape[1], big[2]))
+
+
+def rehome(band, src, dst, s=None):
+    """A Band on the window `src` as a Band on the window `dst` of the same grid, which holds every cell of it.  s: its sign bits,
+    bool[dst.shape]; None is the band's own where the windows overlap and clear elsewhere."""
+    _need(band.shape == src.shape and src.big == dst.big, "the band is not on its window")
+    if s is None:
+        s = np.zeros(dst.shape, bool)
+        lo = [max(a, b) for a, b in zip(src.lo, dst.lo)]
+        hi = [min(a, b) for a, b in zip(src.hi, dst.hi)]
+        if all(h > l for l, h in zip(lo, hi)):
+            part = cm.unpack_bits(src.shape, band.bits)[tuple(slice(l - o, h - o) for l, h, o in zip(lo, hi, src.lo))]
+            s[tuple(slice(l - o, h - o) for l, h, o in zip(lo, hi, dst.lo))] = part
+    return cm.Band(dst.shape, dst.from_big(src.to_big(band.cells)), band.distances, cm.pack_bits(dst.shape, s), band.bg_out, band.bg_in)
+
+
+def embed_field(windows, bands, fields):
+    """The windows' velocities float32[n_w, 3] or speeds float32[n_w], each in its band's list order, in the big grid's list order: the
+    order of `embed`."""
+    check_disjoint(windows)
+    for b, f in zip(bands, fields):
+        _need(len(f) == b.cells.size, "a field has not one entry per cell")
+    cells = np.concatenate([w.to_big(b.cells) for w, b in zip(windows, bands)])
+    return np.concatenate([np.asarray(f, F) for f in fields])[np.argsort(cells, kind="stable")]
+
+
+def _max_bits(values):
+    """The largest of binary32 values that are not negative, by their bit patterns (+inf above every finite one)."""
+    return np.array([F(v) for v in values], F).view(np.uint32).max().view(F)
+
+
+def sum_advect(infos):
+    """The Info of the big grid from the windows': the steps are the same, the maxima are taken on the bits, the counts add up."""
+    _need(len({i.steps for i in infos}) == 1, "the windows ran different numbers of steps")
+    return am.Info(infos[0].steps, _max_bits([i.max_change for i in infos]), _max_bits([i.max_cfl for i in infos]), sum(i.n_moving for i in infos),
+                   sum(i.n_changed for i in infos), sum(i.n_sign_flips for i in infos), sum(i.n_nonfinite for i in infos))
+
+
+def sum_select(infos):
+    return ccm.SelectInfo(sum(i.n_cells for i in infos), sum(i.n_dropped for i in infos), sum(i.n_sign_cleared for i in infos))
+
+
+def merge_components(windows, bands, comps):
+    """The Components of the big grid from the windows' (`bands` gives each window's cells): the components are numbered by ascending
+    first_cell converted to the big grid's L, the labels are renumbered so and put into the big grid's list order, lo and hi are
+    shifted by the window's corner, n_cells and n_negative are carried over.  -> (Components, per window the big grid's number of each
+    of its components)."""
+    check_disjoint(windows)
+    for w, b, c in zip(windows, bands, comps):
+        _need(b.shape == w.shape and c.labels.size == b.cells.size, "a band is not on its window, or the labels are not the band's")
+    first = np.concatenate([w.to_big(c.first_cell.astype(np.int64)) for w, c in zip(windows, comps)])
+    order = np.argsort(first, kind="stable")
+    number = np.empty(first.size, np.int64)
+    number[order] = np.arange(first.size)
+    ends = np.cumsum([0] + [c.count for c in comps])
+    maps = [number[ends[x]:ends[x + 1]] for x in range(len(comps))]
+    cells = np.concatenate([w.to_big(b.cells) for w, b in zip(windows, bands)])
+    labels = np.concatenate([m[c.labels.astype(np.int64)] for m, c in zip(maps, comps)]).astype(np.uint32)[np.argsort(cells, kind="stable")]
+    cat = lambda parts: np.concatenate(parts)[order]                                        # noqa: E731
+    lo = cat([c.lo.astype(np.int64) + np.asarray(w.lo) for w, c in zip(windows, comps)]).astype(np.uint32).reshape(-1, 3)
+    hi = cat([c.hi.astype(np.int64) + np.asarray(w.lo) for w, c in zip(windows, comps)]).astype(np.uint32).reshape(-1, 3)
+    merged = ccm.Components(labels, int(first.size), first[order].astype(np.uint64), cat([c.n_cells for c in comps]), cat([c.n_negative for c in comps]), lo, hi)
+    return merged, maps
 
 
 def sum_redistance(infos):
@@ -388,6 +489,69 @@ def layout(big, first, cell, box_los, widths, seed, box_shape=(9, 9, 11)):
     return Layout(tuple(big), tuple(first), tuple(cell), tuple(widths), sites, a, b, where, full)
 
 
+# ---- components, select and advect: bands of several components and their fields -------------------------------------------------------------
+SLABS = ((((0, 2), 0.2), ((3, 6), 0.85), ((7, 9), 0.2)),         # per site: the layers along i of the box that hold cells, and the share
+         (((0, 2), 0.2), ((3, 5), 0.25), ((6, 9), 0.5)))         # of their points that is active
+
+
+def blob_bands(lt, seed=0, slabs=SLABS):
+    """One Band per site of many components: three slabs of the box along i with an empty layer between them, so that no two slabs
+    touch under any connectivity.  A sparse slab (two points in ten active) falls into dozens of 6-components, about half as many
+    18-components and fewer 26-components.  The first site's middle slab, dense and three layers thick, is around the layer of
+    L = 2^32 on G33 and holds the largest component of all, with enough complete cells to be meshed and measured; the second site's
+    box ends with the grid.  Values uniform in [-0.8, 0.8] min(cell); sign bits random in the box and clear outside it."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for st, layers in zip(lt.sites, slabs):
+        w, lo, n = st.window, st.box_lo, st.box_shape
+        _need(all(0 <= a < b <= n[0] for (a, b), _ in layers), "a slab leaves the site's box")
+        act = np.zeros(w.shape, bool)
+        for (a, b), density in layers:
+            act[lo[0] + a:lo[0] + b, lo[1]:lo[1] + n[1], lo[2]:lo[2] + n[2]] = rng.random((b - a, n[1], n[2])) < density
+        s = np.zeros(w.shape, bool)
+        s[lo[0]:lo[0] + n[0], lo[1]:lo[1] + n[1], lo[2]:lo[2] + n[2]] = rng.random(n) < 0.5
+        cells = np.flatnonzero(act.reshape(-1))
+        out.append(cm.Band(w.shape, cells, (rng.uniform(-1, 1, cells.size) * 0.8 * min(lt.cell)).astype(F), cm.pack_bits(w.shape, s), 0.75, 0.5))
+    return tuple(out)
+
+
+def trig_field(win, band, kind, seed, still=0.25):
+    """Velocities float32[n, 3] (am.VELOCITY) or speeds float32[n] for the cells of a Band on `win`: sines of the big grid's (i, j, k),
+    in [-1, 1], with the share `still` of the cells, picked by a hash of the big grid's L, exactly zero."""
+    rng = np.random.default_rng(seed)
+    width = 3 if kind == am.VELOCITY else 1
+    c, ph = rng.uniform(0.2, 0.9, (width, 3)), rng.uniform(0, 6, width)
+    i, j, k = win.ijk(band.cells)
+    f = np.stack([np.sin(c[x, 0] * i + c[x, 1] * j + c[x, 2] * k + ph[x]) for x in range(width)], 1).astype(F)
+    h = (win.to_big(band.cells).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(44)
+    f[(h % np.uint64(1024)).astype(np.int64) < still * 1024] = 0
+    return f if width == 3 else f.reshape(-1)
+
+
+def select_windows(lt, margin=(3, 3)):
+    """Per site the window of whole rows over the box grown by `margin` layers in i and j, cut at the grid."""
+    out = []
+    for st in lt.sites:
+        lo = [max(st.window.lo[a] + st.box_lo[a] - margin[a], 0) for a in range(2)]
+        hi = [min(st.window.lo[a] + st.box_lo[a] + st.box_shape[a] + margin[a], lt.big[a]) for a in range(2)]
+        out.append(row_window(lt.big, lo, [h - l for l, h in zip(lo, hi)]))
+    check_disjoint(out)
+    return out
+
+
+def select_bands(lt, bands, runs, margin=(3, 3)):
+    """The Bands of `blob_bands` on the windows of `select_windows`, with sign masks made for select: on every row through the box the
+    bits of k in runs[site] = (from, to) are set, a long inside run whose inactive points look for their nearest active cell across
+    many mask words (on active points no call reads the bit)."""
+    out = []
+    for st, band, win, (k0, k1) in zip(lt.sites, bands, select_windows(lt, margin), runs):
+        s = np.zeros(win.shape, bool)
+        lo = [st.window.lo[a] + st.box_lo[a] - win.lo[a] for a in range(2)]
+        s[lo[0]:lo[0] + st.box_shape[0], lo[1]:lo[1] + st.box_shape[1], k0:k1] = True
+        out.append(rehome(band, st.window, win, s))
+    return out
+
+
 def box_centre(lt, i):
     """The centre of site i's box in world coordinates (float64)."""
     st = lt.sites[i]
@@ -438,6 +602,7 @@ G33 = (2048, 2048, 1100)
 G33_FIRST = (-8.0, -16.0, -2.0)
 G33_CELL = (2.0 ** -7, 2.0 ** -6, 2.0 ** -8)
 G33_WIDTHS = ((2.5 * 2.0 ** -7, 2.0 * 2.0 ** -7), (3.0 * 2.0 ** -7, 0.0))      # two-sided and one-sided, 2 to 3 cells of hx
+G33_RUNS = ((200, 1000), (300, 1100))     # `select_bands`: inside runs of 800 points, 9 mask words below the first box and 3 above it, 12 below the second
 # 4096 x 4096 x 1100 = 1.845e10 points, above 2^34: 288 358 400 mask words and 587 202 560 sign words, both above 2^28
 G34 = (4096, 4096, 1100)
 G34_FIRST = (-16.0, -32.0, -2.0)

@@ -1,10 +1,12 @@
 """tests/band_window.py proved on the CPU: on grids small enough for the dense numpy models, the model on the whole grid equals, bit for
-bit, the models on the windows embedded, for csg, redistance and filter; a layout that breaks a margin rule by one layer makes the
+bit, the models on the windows embedded (or, for components, merged), for csg, redistance, filter, advect, components and select; a layout that breaks a margin rule by one layer makes the
 helper raise; and the layouts of tests/test_gpu_band_large.py meet, with the models alone, the conditions that keep those tests from
 passing vacuously.  This is what makes the expected values of the large GPU tests trustworthy."""
 import numpy as np
 import pytest
 
+import band_advect_model as am
+import band_components_model as ccm
 import band_csg_model as cm
 import band_filter_model as fm
 import band_redistance_model as rm
@@ -164,6 +166,95 @@ def test_resample(lay, mode):
         assert want.bg_out.view(np.uint32) == got.bg_out.view(np.uint32) and want.bg_in.view(np.uint32) == got.bg_in.view(np.uint32)
 
 
+# slabs of the 5 x 5 x 6 boxes: sparse, dense, and in the second box two sparse ones
+SLABS = ((((0, 2), 0.3), ((3, 5), 0.85)), (((0, 2), 0.3), ((3, 5), 0.4)))
+
+
+def _runs(lay):
+    return ((1, lay.big[2] - 2), (2, lay.big[2]))
+
+
+@pytest.mark.parametrize("kind", am.KINDS)
+def test_advect(lay, kind):
+    w = lay.windows
+    rng = np.random.default_rng(4)
+    outside = _random_bits(rng, lay.big, w)
+    dt = F(0.5 * min(CELL))
+    fields = [bw.trig_field(win, b, kind, 10 + i) for i, (win, b) in enumerate(zip(w, lay.a))]
+    for masked in (True, False):
+        bands = lay.a if masked else [cm.Band(b.shape, b.cells, b.distances, None, b.bg_out, b.bg_in) for b in lay.a]
+        for win, b in zip(w, bands):
+            bw.check_advect(win, b)
+        A = bw.embed_band(w, bands, outside, masked)
+        for background in (None, (1.25, 0.375)):
+            got, info = am.band_advect(A, CELL, kind, bw.embed_field(w, bands, fields), dt, 3, background)
+            parts = [am.band_advect(b, CELL, kind, f, dt, 3, background) for b, f in zip(bands, fields)]
+            assert bw.same_as_embedded(got, w, [p[0] for p in parts], outside if masked else None), (kind, masked)
+            assert got.bg_out == parts[0][0].bg_out and got.bg_in == parts[0][0].bg_in
+            want = bw.sum_advect([p[1] for p in parts])
+            assert info[0] == want[0] == 3 and info[3:] == want[3:] and all(F(x).view(np.uint32) == F(y).view(np.uint32) for x, y in zip(info[1:3], want[1:3]))
+            assert all(0 < p[1].n_moving < b.cells.size and p[1].n_changed > 0 for p, b in zip(parts, bands))
+    # the maxima are the larger window's, taken on the bits: +inf is above every finite value
+    x = am.Info(3, F(0.5), F(np.inf), 1, 2, 3, 4)
+    assert bw.sum_advect([x, am.Info(3, F(0.75), F(2.0), 10, 20, 30, 40)]) == am.Info(3, F(0.75), F(np.inf), 11, 22, 33, 44)
+    with pytest.raises(bw.LayoutError):
+        bw.sum_advect([x, am.Info(2, F(0), F(0), 0, 0, 0, 0)])
+
+
+def _same_components(got, want):
+    return (got.count == want.count and all(np.array_equal(g, x) and g.dtype == x.dtype and g.shape == x.shape
+                                            for g, x in zip((got.labels,) + tuple(got[2:]), (want.labels,) + tuple(want[2:]))))
+
+
+@pytest.mark.parametrize("connectivity", ccm.CONNECTIVITIES)
+def test_components(lay, connectivity):
+    w = lay.windows
+    counts = {}
+    for name, bands in (("blobs", bw.blob_bands(lay, 1, SLABS)), ("a", lay.a)):
+        for win, b in zip(w, bands):
+            bw.check_components(win, b)
+        parts = [ccm.components(b, connectivity) for b in bands]
+        merged, maps = bw.merge_components(w, bands, parts)
+        assert _same_components(ccm.components(bw.embed_band(w, bands), connectivity), merged), (name, connectivity)
+        assert all(np.array_equal(np.sort(m), m) and m.size == p.count for m, p in zip(maps, parts)) and merged.count == sum(p.count for p in parts)
+        counts[name] = [p.count for p in parts]
+    assert all(c >= 2 for c in counts["blobs"])
+
+
+def test_select(lay):
+    w = lay.windows
+    blobs = bw.blob_bands(lay, 1, SLABS)
+    rows = bw.select_windows(lay, (2, 2))
+    bands = bw.select_bands(lay, blobs, _runs(lay), (2, 2))
+    rng = np.random.default_rng(6)
+    outside = _random_bits(rng, lay.big, rows)
+    A = bw.embed_band(rows, bands, outside)
+    for win, b in zip(rows, bands):
+        bw.check_select(win, b)
+    for connectivity in ccm.CONNECTIVITIES:
+        parts = [ccm.components(b, connectivity) for b in bands]
+        merged, maps = bw.merge_components(rows, bands, parts)
+        keep = np.arange(merged.count) % 2 == 0
+        for background in (None, (1.25, 0.375)):
+            got, info = ccm.select(A, merged.labels, keep, background)
+            res = [ccm.select(b, p.labels, keep[m], background) for b, p, m in zip(bands, parts, maps)]
+            assert bw.same_as_embedded(got, rows, [r[0] for r in res], outside), connectivity
+            assert got.bg_out == res[0][0].bg_out and got.bg_in == res[0][0].bg_in
+            assert info == bw.sum_select([r[1] for r in res]) and all(r[1].n_dropped > 0 and r[1].n_cells > 0 for r in res)
+            assert sum(r[1].n_sign_cleared for r in res) > 0
+
+
+def test_rehome_moves_a_band_between_windows():
+    lt = _layout((23, 19, 70))
+    st = lt.sites[0]
+    rows = bw.select_windows(lt, (2, 2))[0]
+    moved = bw.rehome(lt.a[0], st.window, rows)
+    assert np.array_equal(rows.to_big(moved.cells), st.window.to_big(lt.a[0].cells)) and np.array_equal(moved.distances, lt.a[0].distances)
+    assert bw.same_as_embedded(bw.embed_band([st.window], [lt.a[0]]), [rows], [moved])     # the box's bits travel, the rest is clear on both
+    with pytest.raises(bw.LayoutError):
+        bw.rehome(lt.a[0], st.window, bw.Window(lt.big, st.window.lo, (3, 3, 3)))
+
+
 def test_a_resample_window_that_cuts_the_source_box_raises():
     lt = _layout((40, 37, 21))
     spec = rsm.GridSpec(lt.first, lt.cell, lt.big)
@@ -215,6 +306,27 @@ def test_a_margin_one_layer_too_thin_raises():
     corner = bw.Window(big, (11, 7, 56), (12, 12, 14))
     bw.check_redistance(corner, _one_cell(corner, (11, 11, 13)), CELL, ext, inn)
     bw.check_filter(corner, _one_cell(corner, (11, 11, 13)))
+    # advect has the filter's rule, components needs the free layer only, select whole rows
+    bw.check_advect(win, ok)
+    bw.check_components(win, ok)
+    bw.check_advect(corner, _one_cell(corner, (11, 11, 13)))
+    bw.check_components(corner, _one_cell(corner, (11, 11, 13)))
+    for at in ((0, 5, 5), (5, 0, 5), (5, 5, 0), (11, 5, 5), (5, 11, 5), (5, 5, 13)):
+        with pytest.raises(bw.LayoutError, match="advect: .* holds an active point"):
+            bw.check_advect(win, _one_cell(win, at))
+        with pytest.raises(bw.LayoutError, match="components: .* holds an active point"):
+            bw.check_components(win, _one_cell(win, at))
+    with pytest.raises(bw.LayoutError, match="advect: .* sign bits"):
+        bw.check_advect(win, _one_cell(win, (5, 5, 5), s=s))
+    bw.check_components(win, _one_cell(win, (5, 5, 5), s=s))                                 # components reads no sign bit
+    with pytest.raises(bw.LayoutError, match="select: the window covers"):
+        bw.check_select(win, ok)
+    for lo, n in (((3, 3, 1), (4, 4, 69)), ((3, 3, 0), (4, 4, 69))):
+        cut = bw.Window(big, lo, n)
+        with pytest.raises(bw.LayoutError, match="select: the window covers"):
+            bw.check_select(cut, _one_cell(cut, (1, 1, 1)))
+    rows = bw.row_window(big, (3, 3), (4, 4))
+    bw.check_select(rows, _one_cell(rows, (0, 0, 0)))
 
 
 def test_a_margin_too_thin_changes_the_result():
@@ -235,6 +347,28 @@ def test_a_margin_too_thin_changes_the_result():
         bw.check_redistance(st.window, band, CELL, *WIDTHS[0])
     whole, cut = rm.redistance(bw.embed_band([st.window], [band]), CELL, *WIDTHS[0]), rm.redistance(band, CELL, *WIDTHS[0])
     assert whole[1].n_candidates > cut[1].n_candidates                                    # the info no longer adds up
+
+
+def test_windows_that_break_the_new_rules_change_the_result():
+    """Two windows whose bands touch across their sides are one component on the whole grid and two when merged; a select window that
+    cuts a row does not see the kept cell beyond the cut and clears what the whole row keeps."""
+    big = (23, 19, 70)
+    w = [bw.Window(big, (4, 4, 4), (3, 3, 3)), bw.Window(big, (7, 4, 4), (3, 3, 3))]
+    bands = [_one_cell(w[0], (2, 1, 1)), _one_cell(w[1], (0, 1, 1))]
+    with pytest.raises(bw.LayoutError):
+        bw.check_components(w[0], bands[0])
+    merged, _ = bw.merge_components(w, bands, [ccm.components(b, 6) for b in bands])
+    assert merged.count == 2 and ccm.components(bw.embed_band(w, bands), 6).count == 1
+    # a row with a dropped cell at k = 10, inside bits above it, and a kept cell at k = 40: nothing is cleared; cut at k = 30, all is
+    s = np.zeros(big, bool)
+    s[5, 5, 11:40] = True
+    whole = cm.Band(big, [10 + 5 * 70 + 5 * 19 * 70, 40 + 5 * 70 + 5 * 19 * 70], [0.01, 0.01], cm.pack_bits(big, s), 0.5, 0.5)
+    assert ccm.select(whole, [0, 1], [False, True])[1] == ccm.SelectInfo(1, 1, 0)
+    cut = bw.Window(big, (5, 5, 0), (1, 1, 30))
+    part = cm.Band(cut.shape, [10], [0.01], cm.pack_bits(cut.shape, s[5:6, 5:6, :30]), 0.5, 0.5)
+    with pytest.raises(bw.LayoutError):
+        bw.check_select(cut, part)
+    assert ccm.select(part, [0], [False])[1] == ccm.SelectInfo(0, 1, 19)
 
 
 # ---- the layouts of the large GPU tests, with the models alone -------------------------------------------------------------------------------
@@ -284,3 +418,44 @@ def test_the_large_layouts_meet_their_conditions(name):
             r, info = bw.resample_window(y, small, spec, win, *rsm.similarity(inv), mode)
             big = win.to_big(r.cells)
             assert info.n_cells > 50 and (i != 0 or ((big < 2 ** 32).sum() > 50 and (big >= 2 ** 32).sum() > 50)), (i, mode, info)
+
+
+def test_the_g33_layouts_of_components_select_and_advect_meet_their_conditions():
+    """What tests/test_gpu_band_large.py asserts of its components, select, advect and chain cases, with the models alone."""
+    lt = bw.layout_g33()
+    w = lt.windows
+    blobs = bw.blob_bands(lt)
+    cells = bw.embed(w, blobs)[0]
+    counts = []
+    for connectivity in ccm.CONNECTIVITIES:
+        for win, b in zip(w, blobs):
+            bw.check_components(win, b)
+        parts = [ccm.components(b, connectivity) for b in blobs]
+        merged, maps = bw.merge_components(w, blobs, parts)
+        assert all(p.count >= 3 for p in parts) and (merged.first_cell >= 2 ** 32).sum() >= 3 and (merged.first_cell < 2 ** 32).sum() >= 3
+        largest = int(np.argmax(merged.n_cells))
+        L = cells[merged.labels == largest]
+        assert (L < 2 ** 32).sum() > 50 and (L >= 2 ** 32).sum() > 50, "the largest component does not straddle L = 2^32"
+        counts.append(merged.count)
+    assert counts[0] > counts[1] > counts[2]
+    # select: whole rows, long runs, an alternating keep mask
+    rows = bw.select_windows(lt)
+    bands = bw.select_bands(lt, blobs, bw.G33_RUNS)
+    assert all(r.shape[0] * r.shape[1] * r.shape[2] <= 250000 for r in rows)
+    for win, b in zip(rows, bands):
+        bw.check_select(win, b)
+    parts = [ccm.components(b, 18) for b in bands]
+    merged, maps = bw.merge_components(rows, bands, parts)
+    keep = np.arange(merged.count) % 2 == 0
+    for b, p, m in zip(bands, parts, maps):
+        info = ccm.select(b, p.labels, keep[m])[1]
+        assert info.n_cells > 50 and info.n_dropped > 10 and info.n_sign_cleared > 64, info
+    # advect: the bands of the filter cases and the blobs, fields with cells at rest
+    dt = F(0.5 * min(lt.cell))
+    for bands in (lt.a, blobs):
+        for kind in am.KINDS:
+            for i, (win, b) in enumerate(zip(w, bands)):
+                bw.check_advect(win, b)
+                bw.check_advect(win, cm.Band(b.shape, b.cells, b.distances, None, b.bg_out, b.bg_in))
+                r, info = am.band_advect(b, lt.cell, kind, bw.trig_field(win, b, kind, 20 + i), dt, 3)
+                assert 0 < info.n_moving < b.cells.size and info.n_changed > 50 and info.n_sign_flips > 0 and r.cells.size > 50, (kind, i, info)

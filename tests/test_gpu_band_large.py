@@ -1,6 +1,7 @@
 """The band calls on grids past 2^32 points, where every cell index L = k + j * nz + i * ny * nz of the upper part needs more than 32 bits:
-m2s_band_create / m2s_band_export, m2s_band_csg, m2s_band_redistance, m2s_band_filter, m2s_band_resample, m2s_narrow_band_sdf,
-m2s_voxelize and the chain from a mesh to an isosurface on G33 = 2048 x 2048 x 1100 (4.61e9 points, 72 089 600 mask words; L = 2^32 is
+m2s_band_create / m2s_band_export, m2s_band_csg, m2s_band_redistance, m2s_band_filter, m2s_band_resample, m2s_band_components,
+m2s_band_select, m2s_band_advect, m2s_narrow_band_sdf, m2s_voxelize, the chain from a mesh to an isosurface and the chain advect ->
+select -> measure on G33 = 2048 x 2048 x 1100 (4.61e9 points, 72 089 600 mask words; L = 2^32 is
 the point (1906, 1027, 796)), and create / export / csg / redistance on G34 = 4096 x 4096 x 1100 (1.845e10 points, above 2^34:
 288 358 400 mask words and 587 202 560 sign words, both above 2^28, so every grid-stride loop behind a launch capped at 2^20
 workgroups takes a second trip).
@@ -18,9 +19,12 @@ import numpy as np
 import pytest
 import torch
 
+import band_advect_model as am
+import band_components_model as ccm
 import band_csg_model as cm
 import band_filter_model as fm
 import band_isosurface_model as bim
+import band_measure_model as mm
 import band_query_model as bqm
 import band_redistance_model as rm
 import band_resample_model as rsm
@@ -69,16 +73,18 @@ def _clear_tail(mask, nz):
         mask[:, :, -1] &= (1 << (nz % 32)) - 1
 
 
-def _mask(lt, bands, slabs=()):
+def _mask(lt, bands, slabs=(), windows=None):
     """A device sign mask: zeros, the slabs' words set to their patterns (in the last word of a row that sets bits at k >= nz too, which
-    the library must ignore), then the windows' bits.  The slabs lie outside every window."""
+    the library must ignore), then the windows' bits.  The slabs lie outside every window.  windows: those of `bands`, where they are
+    not the layout's."""
     nx, ny, nz = lt.big
+    windows = lt.windows if windows is None else windows
     m = torch.zeros((nx, ny, (nz + 31) // 32), dtype=torch.int32, device=DEV)
     for sl, pattern in slabs:
         m[sl] = pattern
-    for w in lt.windows:
+    for w in windows:
         assert not m[w.word_slices()].any(), "a slab crosses a window"
-    _patch(m, lt.windows, bands)
+    _patch(m, windows, bands)
     return m
 
 
@@ -86,18 +92,18 @@ def _grid(lt):
     return Grid(list(lt.first), list(lt.cell), list(lt.big))
 
 
-def _field(lt, grid, bands, mask):
-    cells, dist = bw.embed(lt.windows, bands)
+def _field(lt, grid, bands, mask, windows=None):
+    cells, dist = bw.embed(lt.windows if windows is None else windows, bands)
     return BandField(grid, torch.as_tensor(cells, device=DEV), torch.as_tensor(dist, device=DEV),
                      background=(float(bands[0].bg_in), float(bands[0].bg_out)), inside=mask)
 
 
-def _check(field, lt, want, want_mask, what, created=False, windows=None):
+def _check(field, lt, want, want_mask, what, created=False, windows=None, min_cells=50):
     """A handle against the window Bands embedded and the expected device sign mask (None: no mask was given, the export is zeros).
-    windows: those of `want`, where they are not the layout's."""
+    windows: those of `want`, where they are not the layout's.  min_cells: what every window must contribute (more than that)."""
     cells, dist = bw.embed(lt.windows if windows is None else windows, want)
     for b in want:
-        assert b.cells.size > 50, f"{what}: a window contributes {b.cells.size} cells"
+        assert b.cells.size > min_cells, f"{what}: a window contributes {b.cells.size} cells"
     nb = field.to_band()
     assert nb.count == field.count == cells.size, f"{what}: {nb.count} cells, the windows hold {cells.size}"
     got_cells, got_dist = _np(nb.cells).astype(np.int64), _np(nb.distances)
@@ -228,6 +234,172 @@ def test_filter(g33, kind, restricted):
             assert (fi.passes, fi.n_changed, fi.n_sign_flips, fi.n_nonfinite) == (info.passes, info.n_changed, info.n_sign_flips, info.n_nonfinite), (fi, info)
             assert F(fi.max_change).view(np.uint32) == F(info.max_change).view(np.uint32), (fi, info)
             _check(r, lt, [p[0] for p in parts], want_mask, f"G33 filter {kind.name} restricted {restricted}")
+
+
+# ---- components, select, advect ----------------------------------------------------------------------------------------------------------------
+SLABS_OUTSIDE = ((slice(100, 110), -1), ((slice(None), slice(700, 703)), 0x5A5A5A5A))     # as mask_a's: far from every window of a G33 case
+
+
+@pytest.fixture(scope="module")
+def blobs(g33):
+    """The bands of many components (band_window.blob_bands) and the device sign mask that holds their own bits and nothing else."""
+    c = Case()
+    c.bands = bw.blob_bands(g33.lt)
+    c.mask = _mask(g33.lt, c.bands)
+    yield c
+    del c.mask
+    torch.cuda.empty_cache()
+
+
+def _check_components(got, want, what):
+    """A Components of the library against the windows' merged (band_window.merge_components): labels, count and the five statistics."""
+    assert got.count == want.count, f"{what}: {got.count} components, the windows hold {want.count}"
+    labels = _np(got.labels).view(np.uint32)
+    differ = labels != want.labels
+    assert not differ.any(), f"{what}: {int(differ.sum())} labels differ, first at list place {int(np.flatnonzero(differ)[0])}"
+    for name, g, w in (("first_cell", got.first_cell, want.first_cell), ("n_cells", got.n_cells, want.n_cells), ("n_negative", got.n_negative, want.n_negative),
+                       ("box_lo", got.box_lo, want.lo), ("box_hi", got.box_hi, want.hi)):
+        assert g.shape == w.shape and np.array_equal(g, w), f"{what}: {name} differs, first at component {int(np.flatnonzero((g != w).reshape(want.count, -1).any(1))[0])}"
+
+
+@pytest.mark.parametrize("connectivity", ccm.CONNECTIVITIES)
+def test_components(g33, blobs, connectivity):
+    """Labels, count and the statistics of bands that fall into dozens of components per window, the largest with cells on both sides
+    of L = 2^32: the neighbour M = L + di * si + dj * sj + dk and its rank, first_cell as uint64, the boxes from (i, j, k)."""
+    lt = g33.lt
+    counts = {}
+    for conn in ccm.CONNECTIVITIES:
+        parts = [ccm.components(b, conn) for b in blobs.bands]
+        assert all(p.count >= 3 for p in parts), "a window holds fewer than 3 components"
+        counts[conn] = sum(p.count for p in parts)
+        if conn == connectivity:
+            for win, b in zip(lt.windows, blobs.bands):
+                bw.check_components(win, b)
+            want = bw.merge_components(lt.windows, blobs.bands, parts)[0]
+    assert counts[6] > counts[18] > counts[26], counts
+    cells = bw.embed(lt.windows, blobs.bands)[0]
+    L = cells[want.labels == int(np.argmax(want.n_cells))]
+    assert (L < 2 ** 32).sum() > 50 and (L >= 2 ** 32).sum() > 50, "no component has cells on both sides of L = 2^32"
+    assert (want.first_cell >= 2 ** 32).sum() >= 3 and (want.first_cell < 2 ** 32).sum() >= 3
+    with _field(lt, g33.grid, blobs.bands, blobs.mask) as f:
+        _check_components(f.components(connectivity), want, f"G33 components {connectivity}")
+        o = _lib.M2SOpts()
+        o.struct_size, o.device, o.mem_kind = C.sizeof(o), -1, _lib.MEM_DEVICE
+        n = C.c_uint64(0)
+        co = _lib.M2SBandComponentsOpts(C.sizeof(_lib.M2SBandComponentsOpts), connectivity)
+        assert _lib.lib().m2s_band_components(f._h, C.byref(co), C.byref(o), None, None, 0, C.byref(n)) == _lib.M2S_OK     # the count-only call
+        assert n.value == want.count
+
+
+def test_select(g33, blobs):
+    """Every other 18-component erased, on windows of whole rows.  The input mask has an inside run of 800 points on every row through
+    a box (below and above the first box, below the second, which ends with its rows), so that k_sel_mask's search for the nearest
+    active cell crosses a dozen mask words without one, and slabs far from the windows, with bits at k >= nz, that must come back
+    with those bits cleared and nothing else changed."""
+    lt = g33.lt
+    rows = bw.select_windows(lt)
+    bands = bw.select_bands(lt, blobs.bands, bw.G33_RUNS)
+    for win, b in zip(rows, bands):
+        bw.check_select(win, b)
+    parts = [ccm.components(b, 18) for b in bands]
+    merged, maps = bw.merge_components(rows, bands, parts)
+    keep = np.arange(merged.count) % 2 == 0
+    res = [ccm.select(b, p.labels, keep[m]) for b, p, m in zip(bands, parts, maps)]
+    assert all(r[1].n_dropped > 0 and r[1].n_sign_cleared > 64 and r[1].n_cells > 50 for r in res), [r[1] for r in res]
+    mask = _mask(lt, bands, SLABS_OUTSIDE, windows=rows)
+    want_mask = mask.clone()
+    _clear_tail(want_mask, lt.big[2])
+    assert not torch.equal(want_mask, mask), "the slabs set no bit at k >= nz"
+    _patch(want_mask, rows, [r[0] for r in res])
+    with _field(lt, g33.grid, bands, mask, windows=rows) as f:
+        for labels in (torch.as_tensor(merged.labels.view(np.int32), device=DEV), f.components(18)):
+            with f.select(labels, keep) as r:
+                assert tuple(r.select_info) == tuple(bw.sum_select([x[1] for x in res])), f"info {r.select_info}, the windows give {[x[1] for x in res]}"
+                _check(r, lt, [x[0] for x in res], want_mask, "G33 select", windows=rows)
+    del mask, want_mask
+
+
+def _advect_info_is(ai, info, what):
+    assert (ai.steps, ai.n_moving, ai.n_changed, ai.n_sign_flips, ai.n_nonfinite) == (info.steps, info.n_moving, info.n_changed, info.n_sign_flips, info.n_nonfinite), \
+        f"{what}: info {ai}, the windows give {info}"
+    assert F(ai.max_change).view(np.uint32) == F(info.max_change).view(np.uint32) and F(ai.max_cfl).view(np.uint32) == F(info.max_cfl).view(np.uint32), \
+        f"{what}: info {ai}, the windows give {info}"
+
+
+def _advected(lt, bands, kind, background=None):
+    """Three steps of the windows' bands by band_window.trig_field -> (the field in the big grid's list order on the device, dt, the
+    models' (Band, Info) per window)."""
+    dt = F(0.5 * min(lt.cell))
+    fields = [bw.trig_field(win, b, kind, 20 + i) for i, (win, b) in enumerate(zip(lt.windows, bands))]
+    for win, b in zip(lt.windows, bands):
+        bw.check_advect(win, b)
+    parts = [am.band_advect(b, lt.cell, kind, f, dt, 3, background) for b, f in zip(bands, fields)]
+    assert all(0 < p[1].n_moving < b.cells.size and p[1].n_changed > 50 for p, b in zip(parts, bands)), [p[1] for p in parts]
+    return torch.as_tensor(bw.embed_field(lt.windows, bands, fields), device=DEV), float(dt), parts
+
+
+@pytest.mark.parametrize("masked", [True, False], ids=["mask", "no-mask"])
+@pytest.mark.parametrize("kind", am.KINDS, ids=["velocity", "speed"])
+def test_advect(g33, kind, masked):
+    """Three Jacobi steps of both kinds: the neighbour table comes from the 64-bit walk, the field and the two value buffers are in
+    list order across L = 2^32, and the result's mask and offsets are copies of the input's."""
+    lt = g33.lt
+    bands = lt.a if masked else _unmasked(lt.a)
+    background = None if kind == am.VELOCITY else (1.25, 0.375)                  # (outside, inside)
+    given, dt, parts = _advected(lt, bands, kind, background)
+    if masked:
+        want_mask = g33.mask_a.clone()
+        _clear_tail(want_mask, lt.big[2])
+    else:
+        want_mask = torch.zeros_like(g33.mask_a)
+    _patch(want_mask, lt.windows, [p[0] for p in parts])
+    with _field(lt, g33.grid, bands, g33.mask_a if masked else None) as f:
+        with f.advect(dt, 3, background=None if background is None else (background[1], background[0]),
+                      **{"velocity" if kind == am.VELOCITY else "speed": given}) as r:
+            _advect_info_is(r.advect_info, bw.sum_advect([p[1] for p in parts]), f"G33 advect kind {kind} masked {masked}")
+            _check(r, lt, [p[0] for p in parts], want_mask, f"G33 advect kind {kind} masked {masked}")
+    del want_mask
+
+
+def test_the_chain_advect_select_measure(g33, blobs):
+    """advect -> components(26) -> select of the largest component -> measure, every handle on the device: a result made past 2^32 is
+    consumed past 2^32.  The models run on the windows: advect on the layout's, select on windows of whole rows; the component that
+    is left has cells on both sides of L = 2^32 and lies in the first window, whose box the measure model takes."""
+    lt = g33.lt
+    w, rows = lt.windows, bw.select_windows(lt)
+    given, dt, moved = _advected(lt, blobs.bands, am.VELOCITY)
+    on_rows = [bw.rehome(m[0], win, row) for m, win, row in zip(moved, w, rows)]
+    for row, b in zip(rows, on_rows):
+        bw.check_components(row, b)
+        bw.check_select(row, b)
+    parts = [ccm.components(b, 26) for b in on_rows]
+    merged, maps = bw.merge_components(rows, on_rows, parts)
+    keep = np.zeros(merged.count, bool)
+    keep[int(np.argmax(merged.n_cells))] = True                                 # the first of the largest, as Components.largest
+    res = [ccm.select(b, p.labels, keep[m]) for b, p, m in zip(on_rows, parts, maps)]
+    left = rows[0].to_big(res[0][0].cells)
+    assert res[1][1].n_cells == 0 and (left < 2 ** 32).sum() > 50 and (left >= 2 ** 32).sum() > 50 and all(r[1].n_dropped > 50 for r in res)
+    measured = mm.measure(lt.big, lt.cell, left, res[0][0].distances, box=(w[0].lo, w[0].shape))
+    assert int(measured.n_triangles[0]) > 50
+    want_mask = blobs.mask.clone()
+    _patch(want_mask, w, [m[0] for m in moved])
+    with _field(lt, g33.grid, blobs.bands, blobs.mask) as f, f.advect(dt, 3, velocity=given) as fa:
+        _advect_info_is(fa.advect_info, bw.sum_advect([m[1] for m in moved]), "the chain's advect")
+        _check(fa, lt, [m[0] for m in moved], want_mask, "the chain's advect")
+        comps = fa.components(26)
+        _check_components(comps, merged, "the chain's components")
+        assert np.array_equal(comps.largest(1), np.flatnonzero(keep))
+        with fa.select(comps, comps.largest(1)) as fs:
+            assert tuple(fs.select_info) == tuple(bw.sum_select([r[1] for r in res])), f"info {fs.select_info}, the windows give {[r[1] for r in res]}"
+            _patch(want_mask, rows, [r[0] for r in res])
+            _check(fs, lt, [r[0] for r in res], want_mask, "the chain's select", windows=rows, min_cells=-1)
+            m = fs.measure()
+            for name in mm.INT_FIELDS:
+                x = getattr(measured, name)[0]
+                x = tuple(int(v) for v in x) if name == "moment_q" else int(x)
+                assert getattr(m, name) == x, f"the chain's measure: {name} = {getattr(m, name)}, the model has {x}"
+            assert m.closed == mm.closed(measured) and m.euler == mm.euler(measured)
+    del want_mask
 
 
 # ---- resample ------------------------------------------------------------------------------------------------------------------------------
